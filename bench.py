@@ -9,7 +9,7 @@ are already resident in HBM; with N > 1 GPUs every rank solves its own 1024 trac
 collective inside the solve) and ONE RCCL all-gather collects the alpha vectors (north_star) inside the timed region.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config 3|4|5] [--batch B] [--n N_WAYPOINTS] [--io f64|f32]
-                  [--perturb-centreline] [--no-cpu-baseline] [--no-extras] [--force-collective]
+                  [--perturb-centreline] [--full] [--no-cpu-baseline] [--no-extras] [--force-collective] [--dump-outputs DIR]
 
 --gpus N with N > 1 and no launcher environment (WORLD_SIZE unset): bench.py re-launches itself as N ranks, one per GPU,
 under torch.distributed.run on 127.0.0.1 (what the driver does itself when it passes --gpus N under its own launcher).
@@ -21,10 +21,19 @@ under torch.distributed.run on 127.0.0.1 (what the driver does itself when it pa
 --config 5            BASELINE config 5: 65536 synthetic reference tracks over 8 GPUs = 8192 per GPU, float rows / float alpha
                       in HBM (fp64 arithmetic), per-track centrelines, one all-gather of float alpha.
 
-Besides the contract's fields the JSON line carries (rank 0, N = 1, unless --no-extras): `host_to_host` -- the wall SURVEY.md
-section 8d defines the metric on (inputs in pinned host memory -> alpha in host memory, mcq_solve_host); `iqp` -- config 3 is
-mincurv_iqp: the whole iqp_handler chain of the 1024 tracks (3 passes each) as one engine call; `cpu_baseline` -- CPU-A (the
-dense-faithful port of the reference's path) and CPU-B (structure-exploiting scalar solver, one problem per host core).
+A plain run sets up, warms up, times the K steps and prints the line: the headline figure and what the timed launches themselves
+report (iteration counts, kernel span, roofline fractions).  Everything that takes runs of its own comes only with --full (rank 0,
+N = 1, unless --no-extras): `host_to_host` -- the wall SURVEY.md section 8d defines the metric on (inputs in pinned host memory ->
+alpha in host memory, mcq_solve_host); `device_resident_two_streams`; `iqp` -- config 3 is mincurv_iqp: the whole iqp_handler chain
+of the 1024 tracks (3 passes each) as one engine call; `cpu_baseline` -- CPU-A (the dense-faithful port of the reference's path) and
+CPU-B (structure-exploiting scalar solver, one problem per host core); `latency_batch1`; and the power / temperature samples of the
+timed region (config.gpu_power_temp_during_timed_region, null in a plain run).
+
+--dump-outputs DIR    after the timed steps, rank 0 writes what the last timed step computed -- the arrays a caller of that path
+                      receives -- as DIR/<name>.npy in float64 (float32 where the path returns floats): configs 3 / 5 alpha,
+                      curv_error, status; config 4 lap_times.  At most 64 MB in all: beyond that, a fixed seeded sample of the
+                      tracks is written, with its row indices as sample_rows.npy.  Inputs depend on the arguments alone.
+                      With N > 1 ranks these are rank 0's own shard (its tracks / lap times), not the all-gathered result.
 
 Prints ONE JSON line on rank 0.
 """
@@ -366,6 +375,26 @@ def config4_workload(rank, world, tracks=("berlin_2018", "modena_2019", "handlin
                 axm=np.repeat(axm0[None], nvar, axis=0), tops=v_top[veh_of], tracks={t: int(g["reftrack"].shape[0]) for t, g in zip(tracks, gold)})
 
 
+DUMP_BUDGET_BYTES = 63_000_000         # --dump-outputs: under 64 MB in all, .npy headers included
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy, float32 kept, everything else as float64.  Over DUMP_BUDGET_BYTES in all, the same
+    fixed, seeded sample of rows (the leading axis, one track per row) is taken from every array and its indices go to sample_rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32 if v.dtype == np.float32 else np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET_BYTES:
+        rows = next(iter(arrays.values())).shape[0]
+        assert all(a.shape[0] == rows for a in arrays.values())
+        keep = max(1, int(rows * (DUMP_BUDGET_BYTES - 8 * rows) / total))
+        idx = np.sort(np.random.default_rng(0).choice(rows, keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["sample_rows"] = idx.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -383,8 +412,13 @@ def main():
     ap.add_argument("--c4-widths", type=int, default=64, help="config 4: vehicle widths per track")
     ap.add_argument("--c4-vehicles", type=int, default=64, help="config 4: (gg-scale, top-speed) vehicles per QP (a square number)")
     ap.add_argument("--perturb-centreline", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the host_to_host and iqp records (and the CPU baselines)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: host_to_host, device_resident_two_streams, iqp, the CPU baselines, "
+                         "latency_batch1, power / temperature samples of the timed region (a plain run: the headline line alone)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the host_to_host and iqp records (and the CPU baselines)")
     ap.add_argument("--cpu-a-sample", type=int, default=3)
     ap.add_argument("--cpu-b-sample", type=int, default=512)
     ap.add_argument("--force-collective", action="store_true",
@@ -534,7 +568,7 @@ def main():
     for _ in range(args.warmup):
         step(False)
     fence()
-    sampler = SmiSampler(local_rank) if (rank == 0 and not emulate) else None
+    sampler = SmiSampler(local_rank) if (rank == 0 and not emulate and args.full) else None
     if sampler:
         sampler.start()
     # the K steps are enqueued back to back -- no host synchronisation inside the timed region (until round 5 every step synchronised to read its
@@ -586,6 +620,8 @@ def main():
                 gathered_laps = [float(v) for v in lap_h[0]]
         if rank == 0:
             lap = lap_h[0]
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, {"lap_times": lap})
             out = {"metric": "lap-time-matrix variants/sec (BASELINE config 4: 16384 variants)", "value": wl["n_total"] * args.steps / dt,
                    "unit": "variants/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps,
                    "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
@@ -604,6 +640,8 @@ def main():
         info = eng.download(d_info, (B,), INFO_DTYPE)
         alpha_gpu = eng.download(d_alpha, (B, n), io_np).astype(np.float64)
         curv_gpu = eng.download(d_curv, (B,), np.float64)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"alpha": eng.download(d_alpha, (B, n), io_np), "curv_error": curv_gpu, "status": status})
         value = world * B * args.steps / dt
         k_ms = float(np.mean([m["solve"] for m in solve_ms]))
         wm = work_model(n, info)
@@ -667,7 +705,7 @@ def main():
                          "fp64_flops_per_launch": wm["flops"], "fp64_tflops": wm["flops"] / (k_ms * 1e-3) / 1e12,
                          "fp64_frac_of_%.1f_tflops" % FP64_PEAK_TFLOPS: wm["flops"] / (k_ms * 1e-3) / 1e12 / FP64_PEAK_TFLOPS},
         }
-        extras = world == 1 and not args.no_extras and not f32 and not emulate
+        extras = args.full and world == 1 and not args.no_extras and not f32 and not emulate
         if extras:
             # ---- the wall SURVEY.md section 8d defines: inputs in pinned host memory -> alpha in host memory ---------------------
             # blocking entry (one batch: H2D -> kernels -> D2H) and the pipelined stream of batches (mcq_solve_host_pipelined: step k's
@@ -790,7 +828,7 @@ def main():
                     out["latency_batch1"] = latency_batch1(eng)
                 except Exception as e:      # (a side record must not cost the line)
                     out["latency_batch1"] = {"error": str(e)[:300]}
-        elif world == 1 and not args.no_cpu_baseline and not args.no_extras and not emulate:
+        elif args.full and world == 1 and not args.no_cpu_baseline and not args.no_extras and not emulate:
             # f32 boundary: the baseline solves the rows the engine saw
             r32 = engine.increments_to_rows(rows32, org) if d_org is not None else ref_h.astype(np.float32).astype(np.float64)
             nv32 = np.stack([synthetic.prepared_track(r32[k, :, :2])[0] for k in range(min(B, args.cpu_b_sample))])

@@ -100,3 +100,51 @@ def test_bench_config5_f32_two_rank(emu_lib, rccl_stub):
     rec = _check_line(res.stdout, 2)
     assert rec["config"]["io"].startswith("f32 rows (ring increments + fp64 origin)")
     assert rec["config"]["centrelines"] == "perturbed per track" and rec["config"]["allgather_dtype"] == "float32"
+
+
+def test_bench_dump_outputs_are_reproducible(emu_lib, rccl_stub, tmp_path):
+    """--dump-outputs: what the last timed step computed (alpha, curv_error, status) as float64 .npy files; two runs with the same arguments
+    write the same arrays, and --steps is the number of timed steps the line reports."""
+    dumps = []
+    for k, steps in enumerate((1, 2)):
+        d = tmp_path / ("run%d" % k)
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "0", "--batch", "2",
+               "--n", "120", "--emulate", emu_lib, "--dump-outputs", str(d)]
+        res = subprocess.run(cmd, env=_env(rccl_stub), capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert res.returncode == 0, res.stderr[-2000:]
+        lines = [l for l in res.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, res.stdout
+        rec = json.loads(lines[0])
+        assert rec["steps"] == steps and rec["ms_per_step"] > 0 and rec["config"]["failed_problems"] == 0
+        assert not any(key in rec for key in ("host_to_host", "iqp", "cpu_baseline", "latency_batch1"))      # those come with --full
+        out = {name: np.load(d / (name + ".npy")) for name in ("alpha", "curv_error", "status")}
+        assert out["alpha"].shape == (2, 120) and all(a.dtype == np.float64 for a in out.values())
+        assert np.all(out["status"] == 0) and np.all(np.isfinite(out["alpha"]))
+        dumps.append(out)
+    for name in dumps[0]:
+        assert np.array_equal(dumps[0][name], dumps[1][name]), name
+
+
+def test_dump_outputs_over_budget_writes_a_seeded_sample(tmp_path, monkeypatch):
+    """bench.dump_outputs past its byte budget (the default config 5 run: 8192 x 2000 float32 alpha, ~65.5 MB): the same fixed, seeded
+    sample of rows from every array, its indices in sample_rows.npy, float32 kept as float32, everything else float64, within the budget."""
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 20_000)        # the arrays hold 26 368 bytes
+    rows, n = 64, 100
+    alpha = np.arange(rows * n, dtype=np.float32).reshape(rows, n)
+    curv, status = np.arange(rows, dtype=np.float64) * 0.5, np.arange(rows, dtype=np.int32)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), {"alpha": alpha, "curv_error": curv, "status": status})
+    out = {run: {name: np.load(tmp_path / run / (name + ".npy")) for name in ("alpha", "curv_error", "status", "sample_rows")} for run in ("a", "b")}
+    for name in out["a"]:
+        assert np.array_equal(out["a"][name], out["b"][name]), name
+    o = out["a"]
+    idx = o["sample_rows"].astype(np.int64)
+    assert o["alpha"].dtype == np.float32 and o["curv_error"].dtype == np.float64 and o["status"].dtype == np.float64
+    assert o["sample_rows"].dtype == np.float64 and 0 < idx.size < rows and np.all(np.diff(idx) > 0)
+    assert np.array_equal(o["alpha"], alpha[idx]) and np.array_equal(o["curv_error"], curv[idx]) and np.array_equal(o["status"], status[idx])
+    assert sum(a.nbytes for a in o.values()) <= bench.DUMP_BUDGET_BYTES
+    # under the budget: every row, no sample_rows.npy
+    bench.dump_outputs(str(tmp_path / "c"), {"alpha": alpha[:4], "curv_error": curv[:4], "status": status[:4]})
+    assert not (tmp_path / "c" / "sample_rows.npy").exists() and np.array_equal(np.load(tmp_path / "c" / "alpha.npy"), alpha[:4])

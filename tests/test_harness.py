@@ -1,97 +1,150 @@
 """BASELINE config 1: the reference's main_globaltraj.py runs UNTOUCHED on top of the drop-in package (harness notes:
-SURVEY.md App. C).  Needs the reference checkout (/root/reference) -> skipped on the GPU box.  The engine behind
-opt_min_curv here is the SIMT-interpreted kernel library (test infrastructure); the `-m gpu` suite covers the real one."""
+SURVEY.md App. C).  Its runs are recorded with the reference checkout (scripts/record_harness_runs.py, scripts/record_harness_calls.py)
+and replayed here from tests/golden without it.  The engine behind opt_min_curv here is the SIMT-interpreted kernel library (test
+infrastructure); the `-m gpu` suite covers the real one."""
+import io
 import os
 
 import numpy as np
 import pytest
 
-REF = "/root/reference"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+RUNS = os.path.join(ROOT, "tests", "golden", "harness_runs.npz")
 
 
-def _reference_dir():
-    """The reference checkout: /root/reference in the build container; on the GPU box only when a round script shipped a scratch
-    copy along (scratch_ft/ is git-ignored: it travels with a gpurun snapshot and is deleted afterwards, never committed)."""
-    for d in (os.environ.get("MCQ_REFERENCE_DIR"), REF, os.path.join(ROOT, "scratch_ft", "reference")):
-        if d and os.path.exists(os.path.join(d, "main_globaltraj.py")):
-            return d
-    return None
+def _replay_run(case, capsys, tol=1e-9):
+    """One recorded run of the untouched main_globaltraj.py on the drop-in package (scripts/record_harness_runs.py ->
+    tests/golden/harness_runs.npz), replayed without the reference tree: prep_track's calls on the raw imported track [REF
+    helper_funcs_glob/src/prep_track.py:39-59], the call the script made at the drop-in boundary on what they return, through the drop-in
+    package on whatever library engine.default_engine() loads, then the script's raceline / velocity-profile chain [REF
+    main_globaltraj.py:371-422, 498-511] through the drop-in's tph on the recorded vehicle parameters.  tol: how far the prepared track and
+    the (re-linearised) line the chain starts from may lie from the recorded ones.  Returns what the replay computed and what the script
+    printed and exported."""
+    import json
+    from global_racetrajectory_optimization_amd import trajectory_planning_helpers as tph
+    z = np.load(RUNS)
+    f = lambda k: z[case + "_" + k]
+    entry = str(f("entry"))
+    # ---- prep_track: smoothing / re-sampling of the imported track, its splines' normals, the crossing check ----
+    interp = tph.spline_approximation.spline_approximation(track=f("prep_track").copy(), **json.loads(str(f("prep_spline_kwargs"))))
+    assert interp.shape == f("prep_reftrack_interp").shape and np.max(np.abs(interp - f("prep_reftrack_interp"))) < tol
+    normvec0 = tph.calc_splines.calc_splines(path=np.vstack((interp[:, :2], interp[0, :2])))[3]
+    assert np.max(np.abs(normvec0 - f("prep_normvec"))) < tol
+    crossing = tph.check_normals_crossing.check_normals_crossing(track=interp, normvec_normalized=normvec0, horizon=int(f("prep_horizon")))
+    assert bool(crossing) == bool(f("prep_crossing"))
+    # the script hands exactly those to the boundary (checked when recording)
+    kw = dict(reftrack=interp.copy(), normvectors=normvec0.copy(), **json.loads(str(f("kwargs"))))
+    if case + "_A_scalings" in z.files:
+        ref = kw["reftrack"]
+        kw["A"] = tph.calc_splines.calc_splines(path=np.vstack((ref[:, :2], ref[0, :2])))[2]       # what prep_track hands the script
+        assert np.max(np.abs(tph.calc_splines.scalings_from_les_matrix(kw["A"]) - f("A_scalings"))) < 1e-13
+    mod, fn = entry.split(".")
+    capsys.readouterr()
+    res = getattr(getattr(tph, mod), fn)(**kw)
+    printed = capsys.readouterr().out
+    if entry == "iqp_handler.iqp_handler":
+        alpha, reftrack, normvec = res          # main rebinds both [REF main_globaltraj.py:274]
+    else:
+        alpha = res[0] if entry == "opt_min_curv.opt_min_curv" else res
+        reftrack, normvec = kw["reftrack"], kw["normvectors"]
+    assert np.max(np.abs(reftrack - f("reftrack_interp"))) < tol and np.max(np.abs(normvec - f("normvec"))) < tol
+    p = json.loads(str(f("pars")))
+    race, _, cx, cy, inds, tv, s_pts, spl_len, el = tph.create_raceline.create_raceline(
+        refline=reftrack[:, :2], normvectors=normvec, alpha=alpha, stepsize_interp=p["stepsize_interp_after_opt"])
+    psi, kappa = tph.calc_head_curv_an.calc_head_curv_an(coeffs_x=cx, coeffs_y=cy, ind_spls=inds, t_spls=tv)
+    vx = tph.calc_vel_profile.calc_vel_profile(ggv=f("ggv"), ax_max_machines=f("ax_max_machines"), v_max=p["v_max"], kappa=kappa, el_lengths=el,
+                                               closed=True, filt_window=p["filt_window"], dyn_model_exp=p["dyn_model_exp"],
+                                               drag_coeff=p["dragcoeff"], m_veh=p["mass"])
+    ax = tph.calc_ax_profile.calc_ax_profile(vx_profile=np.append(vx, vx[0]), el_lengths=el, eq_length_output=False)
+    t = tph.calc_t_profile.calc_t_profile(vx_profile=vx, ax_profile=ax, el_lengths=el)
+    traj = np.column_stack((s_pts, race, psi, kappa, vx, ax))
+    traj = np.vstack((traj, traj[0]))
+    traj[-1, 0] = np.sum(spl_len)
+    return dict(alpha=alpha, printed=printed, lap_time=float(t[-1]), traj_race_cl=traj, script_alpha=f("alpha_opt"),
+                script_traj_race_cl=f("traj_race_cl"), script_stdout=json.loads(str(f("stdout"))), csv=str(f("csv")),
+                ggv=f("ggv"), ax_max_machines=f("ax_max_machines"), pars=p, reftrack_interp=interp)
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF, "main_globaltraj.py")), reason="reference checkout not present")
-@pytest.mark.parametrize("opt_type", ["mincurv", "mincurv_iqp", "shortest_path"])
-def test_main_globaltraj_untouched(emu_lib, tmp_path, monkeypatch, opt_type):
-    from global_racetrajectory_optimization_amd import engine, harness
-    monkeypatch.setenv("MCQ_LIB", emu_lib)
-    monkeypatch.setattr(engine, "_DEFAULT_ENGINE", None)
-    res = harness.run(REF, opt_type=opt_type, track_name="rounded_rectangle", scratch=str(tmp_path), quiet=True)
-    monkeypatch.setattr(engine, "_DEFAULT_ENGINE", None)
-    assert "INFO: Estimated laptime:" in res["stdout"]
-    marker = {"mincurv": "Solver runtime opt_min_curv", "mincurv_iqp": "Minimum curvature IQP: iteration 3",
-              "shortest_path": "Solver runtime opt_shortest_path"}[opt_type]
-    assert marker in res["stdout"]
-    csv = res["outputs"]
-    assert os.path.exists(csv)
-    lines = open(csv).read().splitlines()
+def _check_exported_run(r, tol=1e-8):
+    """What the script printed and exported, against the replay: the lap-time line digit for digit, the race trajectory it held (within
+    tol), and outputs/traj_race_cl.csv as written (header, 7 columns, closed: the last row repeats the first point; values to the file's 7
+    decimals)."""
+    assert "INFO: Estimated laptime: %.2fs" % r["lap_time"] in r["script_stdout"], (r["lap_time"], r["script_stdout"])
+    assert r["traj_race_cl"].shape == r["script_traj_race_cl"].shape
+    assert np.max(np.abs(r["traj_race_cl"] - r["script_traj_race_cl"])) < tol
+    lines = r["csv"].splitlines()
     assert lines[2].replace(" ", "") == "#s_m;x_m;y_m;psi_rad;kappa_radpm;vx_mps;ax_mps2"
-    data = np.loadtxt(csv, comments="#", delimiter=";")
+    data = np.loadtxt(io.StringIO(r["csv"]), comments="#", delimiter=";")
     assert data.shape[1] == 7 and data.shape[0] > 100
     assert np.allclose(data[0, 1:3], data[-1, 1:3])          # closed: last row repeats the first point
+    assert data.shape == r["traj_race_cl"].shape and np.max(np.abs(data - r["traj_race_cl"])) < 1e-6
+
+
+@pytest.mark.parametrize("opt_type", ["mincurv", "mincurv_iqp", "shortest_path"])
+def test_main_globaltraj_untouched(emu_lib, monkeypatch, capsys, opt_type):
+    """BASELINE config 1 on rounded_rectangle, one run per opt_type of the untouched script, replayed from its recording (_replay_run)."""
+    from global_racetrajectory_optimization_amd import engine
+    monkeypatch.setenv("MCQ_LIB", emu_lib)
+    monkeypatch.setattr(engine, "_DEFAULT_ENGINE", None)
+    r = _replay_run("rr_" + opt_type, capsys)
+    monkeypatch.setattr(engine, "_DEFAULT_ENGINE", None)
+    marker = {"mincurv": "Solver runtime opt_min_curv", "mincurv_iqp": "Minimum curvature IQP: iteration 3",
+              "shortest_path": "Solver runtime opt_shortest_path"}[opt_type]
+    assert marker in r["printed"] and any(l.startswith(marker) for l in r["script_stdout"])
+    assert np.max(np.abs(r["alpha"] - r["script_alpha"])) < 1e-9
+    _check_exported_run(r)
     # the alpha the script got from the drop-in equals the golden single-shot solution
     if opt_type == "mincurv":
         g = np.load(os.path.join(os.path.dirname(__file__), "golden", "rounded_rectangle.npz"))
-        assert np.max(np.abs(res["globals"]["alpha_opt"] - g["alpha"])) < 1e-8
+        assert np.max(np.abs(r["alpha"] - g["alpha"])) < 1e-8
     elif opt_type == "mincurv_iqp":
         g = np.load(os.path.join(os.path.dirname(__file__), "golden", "rounded_rectangle.npz"))
-        assert np.max(np.abs(res["globals"]["alpha_opt"] - g["iqp_alpha"])) < 1e-7
+        assert np.max(np.abs(r["alpha"] - g["iqp_alpha"])) < 1e-7
     else:
         z = np.load(os.path.join(os.path.dirname(__file__), "golden", "shortest_path.npz"))
-        assert np.max(np.abs(res["globals"]["alpha_opt"] - z["rounded_rectangle_alpha"])) < 1e-8
+        assert np.max(np.abs(r["alpha"] - z["rounded_rectangle_alpha"])) < 1e-8
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF, "main_globaltraj.py")), reason="reference checkout not present")
-def test_main_globaltraj_untouched_on_the_goldfarb_idnani_path(emu_lib, tmp_path, monkeypatch):
-    """$MCQ_ALGORITHM=gi: the untouched script with EVERY QP of its mincurv_iqp flow solved by the engine's Goldfarb-Idnani path -- the algorithm of
-    the quadprog it replaces -- ends in the golden IQP state of the default path."""
-    from global_racetrajectory_optimization_amd import engine, harness
+def test_main_globaltraj_untouched_on_the_goldfarb_idnani_path(emu_lib, monkeypatch, capsys):
+    """$MCQ_ALGORITHM=gi: the untouched script's mincurv_iqp run (recorded with EVERY QP of its flow solved by the engine's Goldfarb-Idnani
+    path -- the algorithm of the quadprog it replaces), replayed on that path, ends in the golden IQP state of the default path."""
+    from global_racetrajectory_optimization_amd import engine
     monkeypatch.setenv("MCQ_LIB", emu_lib)
     monkeypatch.setenv("MCQ_ALGORITHM", "gi")
     monkeypatch.setattr(engine, "_DEFAULT_ENGINE", None)
-    res = harness.run(REF, opt_type="mincurv_iqp", track_name="rounded_rectangle", scratch=str(tmp_path), quiet=True)
+    r = _replay_run("rr_mincurv_iqp_gi", capsys)
     monkeypatch.setattr(engine, "_DEFAULT_ENGINE", None)
-    assert "INFO: Estimated laptime:" in res["stdout"] and "Minimum curvature IQP: iteration 3" in res["stdout"]
+    assert "Minimum curvature IQP: iteration 3" in r["printed"] and "Minimum curvature IQP: iteration 3" in r["script_stdout"][2]
+    assert np.max(np.abs(r["alpha"] - r["script_alpha"])) < 1e-9
+    _check_exported_run(r)
     g = np.load(os.path.join(os.path.dirname(__file__), "golden", "rounded_rectangle.npz"))
-    assert np.max(np.abs(res["globals"]["alpha_opt"] - g["iqp_alpha"])) < 1e-7
+    assert np.max(np.abs(r["alpha"] - g["iqp_alpha"])) < 1e-7
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF, "main_globaltraj.py")), reason="reference checkout not present")
-def test_main_globaltraj_untouched_berlin_config1(emu_lib, tmp_path, monkeypatch):
-    """BASELINE config 1 as specified: berlin_2018 (N = 776 at the ini defaults), opt_type = 'mincurv', the untouched script end to
-    end -- import_track, prep_track, opt_min_curv behind the boundary, create_raceline, velocity profile, lap time, export."""
-    from global_racetrajectory_optimization_amd import engine, harness
+def test_main_globaltraj_untouched_berlin_config1(emu_lib, monkeypatch, capsys):
+    """BASELINE config 1 as specified: berlin_2018 (N = 776 at the ini defaults), opt_type = 'mincurv', the untouched script's run end to
+    end -- import_track, prep_track, opt_min_curv behind the boundary, create_raceline, velocity profile, lap time, export -- replayed from
+    its recording (_replay_run)."""
+    from global_racetrajectory_optimization_amd import engine
     monkeypatch.setenv("MCQ_LIB", emu_lib)
     monkeypatch.setattr(engine, "_DEFAULT_ENGINE", None)
-    res = harness.run(REF, opt_type="mincurv", track_name="berlin_2018", scratch=str(tmp_path), quiet=True)
+    r = _replay_run("berlin_mincurv", capsys)
     monkeypatch.setattr(engine, "_DEFAULT_ENGINE", None)
-    assert "Solver runtime opt_min_curv" in res["stdout"] and "INFO: Estimated laptime:" in res["stdout"]
+    assert "Solver runtime opt_min_curv" in r["printed"] and any(l.startswith("INFO: Estimated laptime:") for l in r["script_stdout"])
     g = np.load(os.path.join(os.path.dirname(__file__), "golden", "berlin_2018.npz"))
-    assert res["globals"]["reftrack_interp"].shape == (776, 4)
-    assert np.max(np.abs(res["globals"]["reftrack_interp"] - g["reftrack"])) < 1e-9      # same prep as the golden inputs
-    assert np.max(np.abs(res["globals"]["alpha_opt"] - g["alpha"])) < 1e-6
-    data = np.loadtxt(res["outputs"], comments="#", delimiter=";")
-    assert data.shape[1] == 7 and np.allclose(data[0, 1:3], data[-1, 1:3])
-    lap = float([l for l in res["stdout"].splitlines() if "Estimated laptime" in l][0].split(":")[-1].strip().rstrip("s"))
+    assert r["reftrack_interp"].shape == (776, 4)
+    assert np.max(np.abs(r["reftrack_interp"] - g["reftrack"])) < 1e-9      # the drop-in's prep of the raw track = the golden inputs
+    assert np.max(np.abs(r["alpha"] - g["alpha"])) < 1e-6 and np.max(np.abs(r["script_alpha"] - g["alpha"])) < 1e-6
+    _check_exported_run(r)
+    lap = float([l for l in r["script_stdout"] if "Estimated laptime" in l][0].split(":")[-1].strip().rstrip("s"))
     # the lap time of the golden raceline through the ORACLE's velocity-profile chain (oracle/vel_ref.py)
     from oracle import tph_ref, vel_ref
     from global_racetrajectory_optimization_amd.trajectory_planning_helpers import calc_head_curv_an as ch
     out = tph_ref.create_raceline(g["reftrack"][:, :2], g["normvec"], g["alpha"], 2.0)
     _, kappa = ch.calc_head_curv_an(coeffs_x=out[2], coeffs_y=out[3], ind_spls=out[4], t_spls=out[5])
-    gl = res["globals"]
-    vx = vel_ref.calc_vel_profile(ax_max_machines=gl["ax_max_machines"], kappa=kappa, el_lengths=out[8], closed=True,
-                                  drag_coeff=gl["pars"]["veh_params"]["dragcoeff"], m_veh=gl["pars"]["veh_params"]["mass"],
-                                  ggv=gl["ggv"], v_max=gl["pars"]["veh_params"]["v_max"],
-                                  dyn_model_exp=gl["pars"]["vel_calc_opts"]["dyn_model_exp"])
+    p = r["pars"]
+    vx = vel_ref.calc_vel_profile(ax_max_machines=r["ax_max_machines"], kappa=kappa, el_lengths=out[8], closed=True,
+                                  drag_coeff=p["dragcoeff"], m_veh=p["mass"], ggv=r["ggv"], v_max=p["v_max"], dyn_model_exp=p["dyn_model_exp"])
     assert abs(lap - vel_ref.lap_time_stable(vx, out[8])) < 0.02          # the script prints two decimals
 
 
@@ -191,29 +244,27 @@ def test_replay_of_the_recorded_calls_on_the_gpu(monkeypatch, capsys):
         print("replay of main_globaltraj.py's recorded calls on libmcq.so: max |alpha - oracle| [m] = %s" % {k: "%.1e" % v for k, v in d.items()})
 
 
-def _untouched_on_the_gpu(tmp_path, monkeypatch, opt_type):
-    """Config 1 on the REAL library: the untouched main_globaltraj.py drives libmcq.so on the MI355X (Berlin, ini defaults).  Needs the
-    reference tree next to the repo snapshot (scripts/gpu_with_reference.sh ships a scratch copy).  The test exists only where that tree does
-    (round 6: on the driver's GPU box it was two SKIPS per round; what that box can verify is test_replay_of_the_recorded_calls_on_the_gpu)."""
-    ref = _reference_dir()
-    from global_racetrajectory_optimization_amd import engine, harness
+@pytest.mark.gpu
+@pytest.mark.parametrize("opt_type", ["mincurv", "mincurv_iqp"])
+def test_main_globaltraj_untouched_on_the_gpu(monkeypatch, capsys, opt_type):
+    """Config 1 on the REAL library: the untouched main_globaltraj.py's runs on Berlin (ini defaults), replayed from their recording
+    (_replay_run) through the drop-in package -> ctypes -> C ABI -> libmcq.so on the MI355X.  The recording was made on the SIMT
+    interpreter: alpha, the prepared and re-linearised lines and the race trajectory agree with it within north_star's fp64 tolerance
+    (1e-6 m), the lap-time line digit for digit."""
+    from global_racetrajectory_optimization_amd import engine
     monkeypatch.delenv("MCQ_LIB", raising=False)
     monkeypatch.setattr(engine, "_DEFAULT_ENGINE", None)
-    res = harness.run(ref, opt_type=opt_type, track_name="berlin_2018", scratch=str(tmp_path), quiet=True)
+    r = _replay_run("berlin_" + opt_type, capsys, tol=1e-6)
     monkeypatch.setattr(engine, "_DEFAULT_ENGINE", None)
-    out = res["stdout"]
-    print(out)
-    assert "INFO: Estimated laptime:" in out
-    g = np.load(os.path.join(os.path.dirname(__file__), "golden", "berlin_2018.npz"))
+    assert any(l.startswith("INFO: Estimated laptime:") for l in r["script_stdout"])
+    assert np.max(np.abs(r["alpha"] - r["script_alpha"])) < 1e-6
     if opt_type == "mincurv":
-        assert "Solver runtime opt_min_curv" in out
-        assert np.max(np.abs(res["globals"]["alpha_opt"] - g["alpha"])) < 1e-6
+        assert "Solver runtime opt_min_curv" in r["printed"]
+        g = np.load(os.path.join(os.path.dirname(__file__), "golden", "berlin_2018.npz"))
+        assert np.max(np.abs(r["alpha"] - g["alpha"])) < 1e-6
     else:
-        assert "Minimum curvature IQP: iteration 3" in out and "Finished IQP!" in out
-        assert res["globals"]["alpha_opt"].shape[0] == res["globals"]["reftrack_interp"].shape[0]     # main rebinds both [REF :274]
-    data = np.loadtxt(res["outputs"], comments="#", delimiter=";")
-    assert data.shape[1] == 7 and data.shape[0] > 1000 and np.allclose(data[0, 1:3], data[-1, 1:3])
-
-
-if _reference_dir() is not None:
-    test_main_globaltraj_untouched_on_the_gpu = pytest.mark.gpu(pytest.mark.parametrize("opt_type", ["mincurv", "mincurv_iqp"])(_untouched_on_the_gpu))
+        assert "Minimum curvature IQP: iteration 3" in r["printed"] and "Finished IQP!" in r["printed"]
+        g = np.load(os.path.join(os.path.dirname(__file__), "golden", "berlin_2018_iqp.npz"))
+        assert r["alpha"].shape == g["iqp_alpha"].shape and np.max(np.abs(r["alpha"] - g["iqp_alpha"])) < 1e-6
+    _check_exported_run(r, tol=1e-6)
+    assert r["traj_race_cl"].shape[0] > 1000
