@@ -107,6 +107,8 @@ struct mcq_handle {
     double *p_ref = nullptr, *p_nv = nullptr, *p_sc = nullptr, *p_alpha = nullptr, *p_curv = nullptr;
     int* p_status = nullptr;
     size_t pipe_elems = 0, pipe_batch = 0;
+    mcq_ends* d_ends = nullptr;         // per-problem ring / open-chain records of mcq_solve_batch_ends (device), ends_cap of them
+    size_t ends_cap = 0;
 };
 
 extern "C" const char* mcq_last_error(void) { return g_err.c_str(); }
@@ -231,6 +233,8 @@ extern "C" void mcq_destroy(mcq_handle* h)
     free_alt(h);
     free_stage(h);
     free_pipe(h);
+    (void)hipFree(h->d_ends);
+    h->d_ends = nullptr;
     if (h->stream2) (void)hipStreamDestroy(h->stream2);
     for (int k = 0; k < 2; ++k) {
         if (h->ev_up[k]) (void)hipEventDestroy(h->ev_up[k]);
@@ -1070,6 +1074,66 @@ extern "C" int mcq_les_scalings(const double* A, int n, double* s_out, int check
     return 0;
 }
 
+// ---- the same for the open system through n waypoints: [4(n-1)][4(n-1)], 12 n - 15 non-zeros (include/mcq.h) -----------------------------
+extern "C" int mcq_les_scalings_open(const double* A, int n, double* s_out, int check)
+{
+    if (!A || !s_out || n < 3) { g_err = "mcq_les_scalings_open: bad argument"; return MCQ_E_ARG; }
+    const int ns = n - 1;                       // splines
+    const size_t m = (size_t)4 * ns;
+    for (int i = 0; i + 1 < ns; ++i) s_out[i] = -A[((size_t)4 * i + 2) * m + 4 * i + 5];
+    s_out[n - 2] = s_out[n - 1] = 1.0;
+    if (!check) return 0;
+    int nthreads = (int)std::min<size_t>(32, std::max<size_t>(1, (m * m * sizeof(double)) >> 24));
+    if (const char* e = getenv("MCQ_PACK_THREADS")) nthreads = atoi(e);
+    const int hw = (int)std::thread::hardware_concurrency();
+    if (hw > 0 && nthreads > hw) nthreads = hw;
+    if (nthreads > ns) nthreads = ns;
+    if (nthreads < 1) nthreads = 1;
+    std::vector<long long> bad((size_t)nthreads, -1);
+    auto rel = [](double a, double b) { return fabs(a - b) <= 1e-12 * fabs(b); };
+    auto scan = [&](int t) {
+        const int i0 = (int)((long long)ns * t / nthreads), i1 = (int)((long long)ns * (t + 1) / nthreads);
+        for (int i = i0; i < i1 && bad[t] < 0; ++i) {
+            const size_t j = (size_t)4 * i;
+            const bool last = i == ns - 1;
+            const double s = last ? 1.0 : s_out[i];
+            if (!(s > 0.0) || !std::isfinite(s)) { bad[t] = (long long)((j + 2) * m + j + 5); break; }
+            for (int r = 0; r < 4; ++r) {
+                const double* row = A + (j + r) * m;
+                size_t nz = 0;
+                for (size_t c = 0; c < m; ++c) nz += row[c] != 0.0;
+                bool ok;
+                if (r == 0) ok = nz == 1 && row[j] == 1.0;
+                else if (r == 1) ok = nz == 4 && row[j] == 1.0 && row[j + 1] == 1.0 && row[j + 2] == 1.0 && row[j + 3] == 1.0;
+                else if (r == 2) ok = last ? (nz == 1 && row[1] == 1.0)                                     // heading at the start
+                                           : (nz == 4 && row[j + 1] == 1.0 && row[j + 2] == 2.0 && row[j + 3] == 3.0 && row[j + 5] == -s);
+                else ok = last ? (nz == 3 && row[j + 1] == 1.0 && row[j + 2] == 2.0 && row[j + 3] == 3.0)   // ... at the end
+                               : (nz == 3 && row[j + 2] == 2.0 && row[j + 3] == 6.0 && rel(-row[j + 6], 2.0 * s * s));
+                if (!ok) { bad[t] = (long long)((j + r) * m); break; }
+            }
+        }
+    };
+    if (nthreads > 1) {
+        std::vector<std::thread> th;
+        int taken = 1;
+        try {
+            for (; taken < nthreads; ++taken) th.emplace_back(scan, taken);
+        } catch (...) {}
+        scan(0);
+        for (int t = taken; t < nthreads; ++t) scan(t);
+        for (auto& t : th) t.join();
+    } else scan(0);
+    for (int t = 0; t < nthreads; ++t) {
+        if (bad[t] >= 0) {
+            char buf[160];
+            snprintf(buf, sizeof buf, "mcq_les_scalings_open: row %lld of A does not have the structure of calc_splines' open-spline system", bad[t] / (long long)m);
+            g_err = buf;
+            return MCQ_E_ARG;
+        }
+    }
+    return 0;
+}
+
 extern "C" int mcq_host_alloc(mcq_handle* h, size_t bytes, void** out)
 {
     if (!h || !out || bytes == 0) { g_err = "mcq_host_alloc: bad argument"; return MCQ_E_ARG; }
@@ -1750,8 +1814,9 @@ static int pack_and_upload(mcq_handle* h, const mcq_problem* probs, int batch, s
     return 0;
 }
 
-extern "C" int mcq_solve_batch(mcq_handle* h, const mcq_problem* probs, int batch, const mcq_opts* opts,
-                               double* alpha_out, double* curv_err_out, int* status_out, mcq_info* info_out)
+// mcq_solve_batch and mcq_solve_batch_ends: d_ends = the device copy of the per-problem mcq_ends records, or nullptr (all rings)
+static int solve_batch_impl(mcq_handle* h, const mcq_problem* probs, const mcq_ends* d_ends, int batch, const mcq_opts* opts,
+                            double* alpha_out, double* curv_err_out, int* status_out, mcq_info* info_out)
 {
     if (!h || !probs || batch <= 0 || !alpha_out || !curv_err_out || !status_out) {
         g_err = "mcq_solve_batch: bad argument";
@@ -1789,6 +1854,7 @@ extern "C" int mcq_solve_batch(mcq_handle* h, const mcq_problem* probs, int batc
     B.info = h->d_info;
     B.kappa_bound_list = h->d_kb;
     B.w_veh_list = h->d_wv;
+    B.ends = d_ends;
     const int nsl = host_slices(batch, o);
     if (nsl > 1) {
         // in slices, as mcq_solve_host (see there): chunk k's kernel is queued behind its uploads while chunk k + 1 is packed; the padded alpha
@@ -1850,6 +1916,42 @@ extern "C" int mcq_solve_batch(mcq_handle* h, const mcq_problem* probs, int batc
         if (info_out) info_out[b] = P.info[b];
     }
     return 0;
+}
+
+extern "C" int mcq_solve_batch(mcq_handle* h, const mcq_problem* probs, int batch, const mcq_opts* opts,
+                               double* alpha_out, double* curv_err_out, int* status_out, mcq_info* info_out)
+{
+    return solve_batch_impl(h, probs, nullptr, batch, opts, alpha_out, curv_err_out, status_out, info_out);
+}
+
+// ---- rings and open chains in one batch (include/mcq.h): the records go up once, the solver kernel reads its problem's -----------------------
+extern "C" int mcq_solve_batch_ends(mcq_handle* h, const mcq_problem* probs, const mcq_ends* ends, int batch, const mcq_opts* opts,
+                                    double* alpha_out, double* curv_err_out, int* status_out, mcq_info* info_out)
+{
+    if (!ends) return mcq_solve_batch(h, probs, batch, opts, alpha_out, curv_err_out, status_out, info_out);
+    if (!h || !probs || batch <= 0 || !alpha_out || !curv_err_out || !status_out) {
+        g_err = "mcq_solve_batch_ends: bad argument";
+        return MCQ_E_ARG;
+    }
+    const mcq_opts o = resolve_opts(opts);
+    for (int b = 0; b < batch; ++b) {
+        if (ends[b].closed) continue;
+        if (!probs[b].normvec) { g_err = "mcq_solve_batch_ends: an open chain needs normvec"; return MCQ_E_ARG; }
+        if (o.objective != MCQ_OBJ_MIN_CURV) { g_err = "mcq_solve_batch_ends: open chains have the minimum-curvature objective only"; return MCQ_E_ARG; }
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    if (h->ends_cap < (size_t)batch) {
+        HIP_TRY(hipStreamSynchronize(h->stream));       // (the previous records may still be read by a launch in flight)
+        (void)hipFree(h->d_ends);
+        h->d_ends = nullptr;
+        h->ends_cap = 0;
+        HIP_TRY(hipMalloc((void**)&h->d_ends, (size_t)batch * sizeof(mcq_ends)));
+        h->ends_cap = (size_t)batch;
+    }
+    // ordered before every launch of the solve (and the copy streams of its slices) by the synchronisation: the caller's array is pageable
+    HIP_TRY(hipMemcpyAsync(h->d_ends, ends, (size_t)batch * sizeof(mcq_ends), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return solve_batch_impl(h, probs, h->d_ends, batch, opts, alpha_out, curv_err_out, status_out, info_out);
 }
 
 // ---- a stream of RESIDENT uniform batches on the handle's two compute streams (include/mcq.h) ---------------------------------------------

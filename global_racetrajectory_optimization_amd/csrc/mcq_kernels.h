@@ -109,7 +109,9 @@ struct McqBatch {
     double* gis;            // SMALL slots (round 6; MCQ_ALG_GI: one per resident workgroup), working sets of up to gis_qcap < nmax constraints --
     int gis_slots, gis_qcap; // what the observed working sets need; a problem that outgrows its small slot moves into a full one in place (gi_grow).
                             // Flags: slot_flags[kbig_slots + MCQ_GI_FULL_MAX + s]
+    const mcq_ends* ends;   // [batch] (device) per-problem ring / open-chain records (include/mcq.h), or nullptr: every problem is a ring
 };
+static_assert(MCQ_CHAIN_MAXN == MCQ_TRI_MAXN, "open chains run the tridiagonal sweeps through LDS only");
 
 __global__ void mcq_assemble_kernel(McqBatch B);
 __global__ void mcq_assemble_sp_kernel(McqBatch B);

@@ -210,6 +210,11 @@ struct SolveCtx {
     mutable int kkt_f32;            // ... its records are stored as floats (mcq_kkt.inc, KRec): set by factor(), read by the solves that follow
     mutable int out_iters, out_nk;  // results of ipm / ipm_box / active_set besides their status (uniform: every thread writes the same)
     mutable double out_kkt;
+    // open chain (mcq_ends.closed == 0; DESIGN.md "Open chains"): the couplings between waypoint n - 1 and waypoint 0 are gone, rows 0 and
+    // n - 1 of the spline system are the heading rows.  Every use is a branch that is uniform over the workgroup (or a select on the
+    // first / last waypoint that never fires for a ring): rings take the same arithmetic as before.
+    int chain, fix_s, fix_e;
+    double psi_s, psi_e;
 };
 typedef __attribute__((address_space(3))) SolveCtx LCtx;
 __shared__ SolveCtx g_ctx;
@@ -248,10 +253,16 @@ __device__ __noinline__ int assemble_problem(const LCtx& c, double wveh, gdouble
     gdouble* NX = VEC(w, nm, V_NX);
     gdouble* NY = VEC(w, nm, V_NY);
     const bool derive = w.nv == nullptr;      // normals and scalings from the distance-scaled spline through the line itself
+    const bool chain = c.chain != 0;
+    // open chain: unit heading vectors of the two ends (MCQ_HEADING_SCALE), the chain's own limits.  S[n-2] = S[n-1] = 1: the last spline
+    // has no joint to its right (s_(n-2) := 1 of the spline rows), and with s_(n-1) = 1 the ring formulas of the rows next to the ends
+    // (waypoints 1 and n-2) are the chain's own.
+    if (chain && (n > MCQ_CHAIN_MAXN || derive || !(isfinite(c.psi_s) && isfinite(c.psi_e)))) flag_bad = 1.0;
     for (int i = tid; i < n; i += MCQ_NT) {
         const double x = w.ref[4 * i], y = w.ref[4 * i + 1], wr = w.ref[4 * i + 2], wl = w.ref[4 * i + 3];
         const double nx = derive ? 0.0 : w.nv[2 * i], ny = derive ? 1.0 : w.nv[2 * i + 1];
         double s = w.sc ? w.sc[i] : 1.0;
+        if (chain && i >= n - 2) s = 1.0;
         if (derive) {
             // s_i = l_i / l_{i+1},  l_i = |p_{i+1} - p_i|  (tph.calc_splines, use_dist_scaling=True, closed)
             const int i1 = i + 1 >= n ? i + 1 - n : i + 1, i2 = i1 + 1 >= n ? i1 + 1 - n : i1 + 1;
@@ -265,7 +276,8 @@ __device__ __noinline__ int assemble_problem(const LCtx& c, double wveh, gdouble
         if (!(isfinite(x) && isfinite(y) && isfinite(wr) && isfinite(wl) && isfinite(nx) && isfinite(ny) && isfinite(s)
               && s > 0.0))
             flag_bad = 1.0;
-        const double lo = -(wl - 0.5 * wveh), hi = wr - 0.5 * wveh;
+        double lo = -(wl - 0.5 * wveh), hi = wr - 0.5 * wveh;
+        if ((c.fix_s && i == 0) || (c.fix_e && i == n - 1)) { lo = -MCQ_FIX_HALF_WIDTH; hi = MCQ_FIX_HALF_WIDTH; }    // (chains only: before the check, as tph)
         if (hi < lo) flag_inf = 1.0;
         LO[i] = lo;
         HI[i] = hi;
@@ -307,6 +319,21 @@ __device__ __noinline__ int assemble_problem(const LCtx& c, double wveh, gdouble
         RX[m] = 3.0 * (sm1 * (w.ref[4 * mp] - w.ref[4 * m]) - (w.ref[4 * m] - w.ref[4 * mm]));
         RY[m] = 3.0 * (sm1 * (w.ref[4 * mp + 1] - w.ref[4 * m + 1]) - (w.ref[4 * m + 1] - w.ref[4 * mm + 1]));
     }
+    // open chain: the heading rows overwrite rows 0 and n - 1 (blocks of their own here and below: the rings' arithmetic stays what it was)
+    double hsx = 0.0, hsy = 0.0, hex = 0.0, hey = 0.0;
+    if (chain) {
+        hsx = MCQ_HEADING_SCALE * cos(c.psi_s + 0.5 * M_PI);
+        hsy = MCQ_HEADING_SCALE * sin(c.psi_s + 0.5 * M_PI);
+        hex = MCQ_HEADING_SCALE * cos(c.psi_e + 0.5 * M_PI);
+        hey = MCQ_HEADING_SCALE * sin(c.psi_e + 0.5 * M_PI);
+        __syncthreads();
+    }
+    if (chain && tid == 0) {        // 2 c_0 + s_0^2 c_1 = 3 (D_0 - h_s),  c_(n-2) + 2 c_(n-1) = 3 (h_e - D_(n-2))
+        RX[0] = 3.0 * ((w.ref[4] - w.ref[0]) - hsx);
+        RY[0] = 3.0 * ((w.ref[5] - w.ref[1]) - hsy);
+        RX[n - 1] = 3.0 * (hex - (w.ref[4 * (n - 1)] - w.ref[4 * (n - 2)]));
+        RY[n - 1] = 3.0 * (hey - (w.ref[4 * (n - 1) + 1] - w.ref[4 * (n - 2) + 1]));
+    }
     tri_solve_T(c, RX, XPP);
     tri_solve_T(c, RY, YPP);
     for (int i = tid; i < n; i += MCQ_NT) { XPP[i] *= 2.0; YPP[i] *= 2.0; }     // x''(0), y''(0) of spline i
@@ -336,6 +363,18 @@ __device__ __noinline__ int assemble_problem(const LCtx& c, double wveh, gdouble
         }
         if (sc_out) sc_out[i] = S[i];
     }
+    if (chain) {                    // x'(1) of the last spline is the end heading
+        __syncthreads();
+        if (tid == 0) {
+            const int i = n - 1;
+            const double den = pow(hex * hex + hey * hey, 1.5);
+            const double cp = den != 0.0 ? 1.0 / den : 0.0;
+            XP[i] = hex;
+            YP[i] = hey;
+            CP[i] = cp;
+            KRF[i] = cp * (hex * YPP[i] - hey * XPP[i]);
+        }
+    }
     __syncthreads();
     return MCQ_OK;
 }
@@ -349,6 +388,12 @@ __device__ __forceinline__ void ctx_set_problem(const McqBatch& B, const McqSet&
         g_ctx.w = w;
         g_ctx.nm = B.nmax;
         g_ctx.d = mcq_dims(n);
+        const mcq_ends* e = B.ends ? B.ends + pb : nullptr;
+        g_ctx.chain = (e && !e->closed) ? 1 : 0;
+        g_ctx.fix_s = g_ctx.chain && e->fix_s;
+        g_ctx.fix_e = g_ctx.chain && e->fix_e;
+        g_ctx.psi_s = g_ctx.chain ? e->psi_s : 0.0;
+        g_ctx.psi_e = g_ctx.chain ? e->psi_e : 0.0;
     }
     __syncthreads();
 }
@@ -1633,8 +1678,9 @@ MCQ_FN_PROLOGUE void write_outputs(const LCtx& c, const McqOutcome& r)
         const int ip = cyc(i + 1, n);
         const double s = VEC(c.w, nm, V_SC)[i];
         const double s2 = s * s;
-        const double xpt = XP[i] + (T1[ip] - T1[i]) - (T0[i] + 0.5 * s2 * T0[ip]) / 3.0;
-        const double ypt = YP[i] + (T2[ip] - T2[i]) - (T3[i] + 0.5 * s2 * T3[ip]) / 3.0;
+        double xpt = XP[i] + (T1[ip] - T1[i]) - (T0[i] + 0.5 * s2 * T0[ip]) / 3.0;
+        double ypt = YP[i] + (T2[ip] - T2[i]) - (T3[i] + 0.5 * s2 * T3[ip]) / 3.0;
+        if (c.chain && i == n - 1) { xpt = XP[i]; ypt = YP[i]; }      // open chain: x~'_(n-1) = h_e, whatever alpha is
         const double xpp = XPP[i] + T0[i], ypp = YPP[i] + T3[i];
         const double xp = XP[i], yp = YP[i];
         const double k0 = (xp * ypp - yp * xpp) / pow(xp * xp + yp * yp, 1.5);

@@ -177,12 +177,33 @@ __device__ __forceinline__ void kkt_point_make(const KktRaw& r, double* rec)
     rec[18] = 0.0;
     rec[19] = 1.0;
 }
+// Open chain (DESIGN.md "Open chains"; with S[n-2] = S[n-1] = 1 every other waypoint's record is the ring formula): the records of waypoints 0
+// and n - 1 after kkt_point_make.  R[0, .] = 3 (q_1 - q_0), R[n-1, .] = -3 (q_(n-1) - q_(n-2)): d03, d04 = 3 n (= -rec[15], -rec[16] of the ring
+// formula, exactly); T[0, 0] = T[n-1, n-1] = 2.  Lo_0 = 0 (nothing couples waypoint 0 to waypoint n - 1), and so is Up_(n-1) = Lo_0', the 1 of
+// T[0, n-1] (rec[19] as an Up entry) included.  (Waypoint 0 is always separator 0 and waypoint n - 1 is never a segment's first step, so rec[19]
+// is not needed as the 1 of a Lo there.)  Called only for chains: the rings' records are kkt_point_make's, instruction for instruction.
+__device__ __forceinline__ void kkt_chain_ends(double* rec, int m, int n)
+{
+    if (m == 0) {
+        rec[1] = -rec[15];
+        rec[2] = -rec[16];
+        rec[6] = 2.0;
+        rec[7] = rec[8] = rec[9] = rec[10] = rec[11] = 0.0;
+    } else if (m == n - 1) {
+        rec[1] = -rec[15];
+        rec[2] = -rec[16];
+        rec[6] = 2.0;
+        rec[12] = rec[13] = rec[14] = rec[15] = rec[16] = 0.0;
+        rec[19] = 0.0;
+    }
+}
 __device__ __forceinline__ int kkt_rec_point(int m, int s1, int n) { m = m < s1 ? m : s1 - 1; return m < n ? m : n - 1; }
 __device__ __forceinline__ void kkt_point_record(const LCtx& c, const gdouble* sig, const gschar* mk, const gdouble* wgt, const gdouble* fv, int m, double* rec)
 {
     KktRaw r;
     kkt_point_load(c, sig, mk, wgt, fv, m, r);
     kkt_point_make(r, rec);
+    if (c.chain) kkt_chain_ends(rec, m, c.d.n);
 }
 
 // t = Lo s  for the sparse coupling block given by lo[0..4]
@@ -326,6 +347,7 @@ KKT_FN int factor_kkt(const LCtx& c, const gdouble* sig, const gschar* mk, const
     RG* AD = (RG*)K_AD(c);
     RG* AS = (RG*)K_AS(c);
     RG* AY = (RG*)K_AY(c);
+    const bool chain = c.chain != 0;
     bool bad = false;
     long long kt_last = KKT_TIMERS ? (long long)wall_clock64() : 0;
 
@@ -400,6 +422,7 @@ KKT_FN int factor_kkt(const LCtx& c, const gdouble* sig, const gschar* mk, const
 #pragma unroll
                 for (int q = 0; q < KCOEF; ++q) coef[cl * KCOEF + q] = rec[q];
             }
+            if (chain) kkt_chain_ends(coef + cl * KCOEF, KKT_REC_POINT(k0), n);      // (on the staged record: nothing more stays live in the loop)
             __builtin_amdgcn_wave_barrier();
             if (k0 + KCKF < Lmax) kkt_point_load(c, sig, mk, wgt, fv, KKT_REC_POINT(k0 + KCKF), raw);
         }
@@ -607,6 +630,10 @@ KKT_FN int factor_kkt(const LCtx& c, const gdouble* sig, const gschar* mk, const
         const double u_xl0 = KKT_SEL5(t, r);
         KKT_UP_APPLY(up, xr0, t);
         const double u_xr0 = KKT_SEL5(t, r);
+        if (c.chain && j == 0) {           // open chain: Lo_0 = 0 (KKT_LO_APPLY has the 1s of T built in: its operands are zeroed instead --
+#pragma unroll                              //  a select on its result would stop the compiler from fusing the products into the differences below,
+            for (int q = 0; q < 5; ++q) xll[q] = xrl[q] = 0.0;       //  and rings would round differently)
+        }
         KKT_LO_APPLY(lo, xll, t);
         const double l_xll = KKT_SEL5(t, r);
         KKT_LO_APPLY(lo, xrl, t);
@@ -934,6 +961,10 @@ KKT_FN void solve_kkt(const LCtx& c, gdouble* vv, bool fwd_done)
             double xf[5], xl[5], t[5], u[5];
 #pragma unroll
             for (int q = 0; q < 5; ++q) { xf[q] = per[KP_X0 + j * 10 + q]; xl[q] = per[KP_X0 + jp * 10 + 5 + q]; }
+            if (c.chain && j == 0) {                    // open chain: Lo_0 = 0 (zero operand, as in factor_kkt)
+#pragma unroll
+                for (int q = 0; q < 5; ++q) xl[q] = 0.0;
+            }
             KKT_UP_APPLY(up, xf, u);
             KKT_LO_APPLY(lo, xl, t);
             rr[j * 5 + 0] = vv[KSEP(j, n, nseg)] - u[0] - t[0];
@@ -1030,8 +1061,12 @@ KKT_FN void solve_kkt(const LCtx& c, gdouble* vv, bool fwd_done)
             const double* sr = per + KP_SEP + gn * 10;
             xa[1] = fma((double)adf[18], xa[0], xa[1]);
             xa[2] = fma((double)adf[19], xa[0], xa[2]);
-            xb[1] = fma(sr[0] / sr[2], xb[0], xb[1]);
-            xb[2] = fma(sr[1] / sr[2], xb[0], xb[2]);
+            // (open chain, last segment: the right separator is waypoint 0, whose Lo is 0 -- 0 / 0 here.  X^R of that segment is identically
+            //  zero (Up_(n-1) = 0 starts its recursion), so there is nothing to fold)
+            if (!(c.chain && gn == 0)) {
+                xb[1] = fma(sr[0] / sr[2], xb[0], xb[1]);
+                xb[2] = fma(sr[1] / sr[2], xb[0], xb[2]);
+            }
         }
         for (int k = cl; k < L; k += 16) {
             const int m = lo_pt + k;

@@ -40,6 +40,12 @@ static_assert(TRI_MAXN == 8 * MCQ_NT && TRI_PE(TRI_MAXN + 2 * TRI_H - 1) < TRI_L
 static_assert(3 * TRI_LD <= OVL_SIZE, "right-hand side, 1 / delta and u of the tridiagonal solves must fit the LDS overlay");
 
 
+// Open chains (SolveCtx.chain; n <= TRI_MAXN): T loses its corners, row 0 is  2 c_0 + s_0^2 c_1  and row n - 1 is  c_(n-2) + 2 c_(n-1)
+// (d = 2, u_(n-1) = 0).  The pivots are then the chain's own, from delta_0 = 2: a thread's pivot sweep starts at waypoint max(0, m0 - TRI_W),
+// exactly at the chain's first row where it reaches it.  The solves keep their code: the halo of every LDS array -- right-hand side, 1 / delta
+// and u at the extended indices outside [0, n) -- is zero instead of a copy of the ring's other end.  A forward step into waypoint 0 then
+// multiplies by 1 / delta_(-1) = 0 (y_0 = r_0, the chain's first step), a backward step into waypoint n - 1 starts from x_n = y_n / delta_n = 0,
+// and the warm-up sweeps of the threads further in are the same contraction as on a ring.
 // 1 / delta_m and u_m into V_IDL, V_TUC (once per problem)
 __device__ void tri_prepare(const LCtx& c)
 {
@@ -48,6 +54,23 @@ __device__ void tri_prepare(const LCtx& c)
     gdouble* IDL = VEC(c.w, c.nm, V_IDL);
     gdouble* TUC = VEC(c.w, c.nm, V_TUC);
     __syncthreads();
+    if (c.chain) {
+        for (int m0 = 8 * tid; m0 < n; m0 += 8 * MCQ_NT) {
+            const int mb = m0 >= TRI_W ? m0 - TRI_W : 0;
+            double idl = 0.0, uprev = 0.0;
+            for (int m = mb; m < m0 + 8 && m < n; ++m) {
+                const double sp = m > 0 ? SC[m - 1] : 1.0, sm = SC[m];        // (S[n-2] = 1: u_(n-2) = s_(n-3))
+                const double d = (m == 0 || m == n - 1) ? 2.0 : 2.0 * sp * sp + 2.0 * sp;
+                const double u = m == n - 1 ? 0.0 : sp * sm * sm;
+                const double delta = d - uprev * idl;
+                idl = 1.0 / delta;
+                uprev = u;
+                if (m >= m0) { IDL[m] = idl; TUC[m] = u; }
+            }
+        }
+        __syncthreads();
+        return;
+    }
     for (int base = 0; base < n; base += 8 * MCQ_NT) {
         const int m0 = base + 8 * tid;
         if (m0 < n) {
@@ -88,10 +111,12 @@ __device__ __forceinline__ TriLds tri_lds()
 // Staging is thread-contiguous: a thread loads what its own eight waypoints (8 tid ..) need -- every load issued before the first use, ONE
 // memory latency per staged vector (a strided loop over the ring paid one per trip, nine trips per vector) -- and writes each value to the
 // ring's own range and to the halo copies it has.
-__device__ __forceinline__ void tri_put(double* arr, int n, int i, double v)
+__device__ __forceinline__ void tri_put(double* arr, int n, int i, double v, bool chain)
 {
     const int e = i + TRI_H;
-    if (n >= TRI_H) {
+    if (chain) {
+        arr[TRI_PE(e)] = v;                                  // (open chain: the halo stays zero, tri_stage_factors)
+    } else if (n >= TRI_H) {
         arr[TRI_PE(e)] = v;
         if (e >= n) arr[TRI_PE(e - n)] = v;                  // upstream halo: the ring's last TRI_H waypoints
         if (i < TRI_H) arr[TRI_PE(e + n)] = v;               // downstream halo: its first TRI_H
@@ -105,26 +130,35 @@ __device__ __forceinline__ int tri_win(int m0, int k, int n)
     const int j = m0 + k;
     return j < 0 ? n - 1 : j < n ? j : 0;
 }
-// 1 / delta and u into LDS (once per call of tri_apply_*)
+// 1 / delta and u into LDS (once per call of tri_apply_*); open chain: the halos of all three arrays to zero
 __device__ __forceinline__ void tri_stage_factors(const LCtx& c, const TriLds& L)
 {
     const int n = c.d.n, m0 = 8 * threadIdx.x;
     const gdouble* IDL = VEC(c.w, c.nm, V_IDL);
     const gdouble* TUC = VEC(c.w, c.nm, V_TUC);
+    const bool chain = c.chain != 0;
+    if (chain) {
+        for (int q = threadIdx.x; q < 2 * TRI_H; q += MCQ_NT) {
+            const int e = q < TRI_H ? q : n + q;             // [0, TRI_H) and [n + TRI_H, n + 2 TRI_H)
+            L.ry[TRI_PE(e)] = 0.0;
+            L.idl[TRI_PE(e)] = 0.0;
+            L.tu[TRI_PE(e)] = 0.0;
+        }
+    }
     if (m0 >= n) return;
     double a[8], b[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) { a[k] = IDL[tri_win(m0, k, n)]; b[k] = TUC[tri_win(m0, k, n)]; }
 #pragma unroll
     for (int k = 0; k < 8; ++k)
-        if (m0 + k < n) { tri_put(L.idl, n, m0 + k, a[k]); tri_put(L.tu, n, m0 + k, b[k]); }
+        if (m0 + k < n) { tri_put(L.idl, n, m0 + k, a[k], chain); tri_put(L.tu, n, m0 + k, b[k], chain); }
 }
 
 // Solves  T c = r  (TRANS = false)  or  T' x = q  (TRANS = true)  for the right-hand side in L.ry (all n + 2 TRI_H extended entries written,
 // barrier passed); returns this thread's eight entries (waypoints 8 tid ..) in own[]; L.ry holds y afterwards (the ring's own range and the
 // halo downstream of it).  Uniform over the block.  n <= TRI_MAXN.
 template <bool TRANS>
-__device__ __forceinline__ void tri_solve_chunk(const TriLds& L, int n, double (&own)[8])
+__device__ __forceinline__ void tri_solve_chunk(const TriLds& L, int n, double (&own)[8], bool chain)
 {
     const int tid = threadIdx.x, m0 = 8 * tid;
     const bool valid = m0 < n;
@@ -155,7 +189,7 @@ __device__ __forceinline__ void tri_solve_chunk(const TriLds& L, int n, double (
     if (valid)
         for (int k = 0; k < 8; ++k)
             if (m0 + k < n)
-                for (int e = m0 + k + TRI_H; e < n + 2 * TRI_H; e += n) L.ry[TRI_PE(e)] = own[k];      // (the copy downstream of the ring as well)
+                for (int e = m0 + k + TRI_H; e < (chain ? m0 + k + TRI_H + 1 : n + 2 * TRI_H); e += n) L.ry[TRI_PE(e)] = own[k];      // (the copy downstream of the ring as well; a chain has none)
     __syncthreads();
     // ---- backward sweep: warm-up downstream of the own entries (from waypoint m0 + 7 + TRI_W)
     double x = 0.0;
@@ -233,10 +267,10 @@ __device__ __noinline__ void tri_solve_T(const LCtx& c, const gdouble* rhs, gdou
         for (int k = 0; k < 8; ++k) own[k] = rhs[tri_win(m0, k, n)];
 #pragma unroll
         for (int k = 0; k < 8; ++k)
-            if (m0 + k < n) tri_put(L.ry, n, m0 + k, own[k]);
+            if (m0 + k < n) tri_put(L.ry, n, m0 + k, own[k], c.chain != 0);
     }
     __syncthreads();
-    tri_solve_chunk<false>(L, n, own);
+    tri_solve_chunk<false>(L, n, own, c.chain != 0);
     if (m0 < n) {
 #pragma unroll
         for (int k = 0; k < 8; ++k)
@@ -258,6 +292,7 @@ __device__ __noinline__ void tri_apply_E_lds(const LCtx& c, const gdouble* src, 
     const gdouble* YP = VEC(c.w, c.nm, V_YP);
     const gdouble* CP = VEC(c.w, c.nm, V_CP);
     const TriLds L = tri_lds();
+    const bool chain = c.chain != 0;
     __syncthreads();
     tri_stage_factors(c, L);
     double c1[8], c2[8];
@@ -282,11 +317,19 @@ __device__ __noinline__ void tri_apply_E_lds(const LCtx& c, const gdouble* src, 
             for (int k = -1; k <= 8; ++k) q[k + 1] = NV[tri_win(m0, k, n)] * sv[k + 1];
 #pragma unroll
             for (int k = 0; k < 8; ++k)
-                if (m0 + k < n) tri_put(L.ry, n, m0 + k, 3.0 * q[k] - 3.0 * (sc[k] + 1.0) * q[k + 1] + 3.0 * sc[k] * q[k + 2]);
+                if (m0 + k < n) tri_put(L.ry, n, m0 + k, 3.0 * q[k] - 3.0 * (sc[k] + 1.0) * q[k + 1] + 3.0 * sc[k] * q[k + 2], chain);
+            // open chain, the heading rows: 3 (q_1 - q_0) and -3 (q_(n-1) - q_(n-2)) overwrite the ring formula's values (a block of its own
+            // after the ring's stores: the ring's arithmetic stays what it was, contractions included)
+            if (chain) {
+                if (m0 == 0) L.ry[TRI_X(0)] = 3.0 * (q[2] - q[1]);
+#pragma unroll
+                for (int k = 0; k < 8; ++k)
+                    if (m0 + k == n - 1) L.ry[TRI_X(n - 1)] = 3.0 * (q[k] - q[k + 1]);
+            }
         }
         __syncthreads();
-        if (pass == 0) tri_solve_chunk<false>(L, n, c1);
-        else tri_solve_chunk<false>(L, n, c2);
+        if (pass == 0) tri_solve_chunk<false>(L, n, c1, chain);
+        else tri_solve_chunk<false>(L, n, c2, chain);
     }
     if (mine) {
         double cp[8], xp[8], yp[8], ad[8];
@@ -360,9 +403,10 @@ __device__ __noinline__ void tri_apply_Et_lds(const LCtx& c, const gdouble* src,
     const gdouble* YP = VEC(c.w, c.nm, V_YP);
     const gdouble* CP = VEC(c.w, c.nm, V_CP);
     const TriLds L = tri_lds();
+    const bool chain = c.chain != 0;
     __syncthreads();
     tri_stage_factors(c, L);
-    double acc[8];
+    double acc[8], ce0 = 0.0, cen = 0.0;
 #pragma unroll
     for (int k = 0; k < 8; ++k) acc[k] = 0.0;
     const int m0 = 8 * tid;
@@ -389,11 +433,11 @@ __device__ __noinline__ void tri_apply_Et_lds(const LCtx& c, const gdouble* src,
         if (mine) {
 #pragma unroll
             for (int k = 0; k < 8; ++k)
-                if (m0 + k < n) tri_put(L.ry, n, m0 + k, pass == 0 ? wy[k] : wx[k]);
+                if (m0 + k < n) tri_put(L.ry, n, m0 + k, pass == 0 ? wy[k] : wx[k], chain);
         }
         __syncthreads();
         double u[8];
-        tri_solve_chunk<true>(L, n, u);
+        tri_solve_chunk<true>(L, n, u, chain);
         __syncthreads();
         double nv[8];
         if (mine) {
@@ -419,6 +463,13 @@ __device__ __noinline__ void tri_apply_Et_lds(const LCtx& c, const gdouble* src,
                     acc[k] += nv[k] * rt;
                 }
             }
+            // open chain: the columns of R' at the ends, (R'u)_0 = 3 (u_1 - u_0) and (R'u)_(n-1) = 3 s_(n-3) u_(n-2) - 3 u_(n-1) (waypoint 1
+            // is the ring formula: s_(-1) = S[n-1] = 1) -- by thread 0 from the u in LDS, accumulated apart and stored over the ring formula's
+            // values at the end: the ring's arithmetic and registers stay what they were
+            if (chain && tid == 0) {
+                ce0 += NV[0] * (3.0 * (L.ry[TRI_X(1)] - L.ry[TRI_X(0)]));
+                cen += NV[n - 1] * (3.0 * (SC[n - 3] * L.ry[TRI_X(n - 2)] - L.ry[TRI_X(n - 1)]));
+            }
         }
     }
     if (mine) {
@@ -427,6 +478,10 @@ __device__ __noinline__ void tri_apply_Et_lds(const LCtx& c, const gdouble* src,
             if (m0 + k < n) dst[m0 + k] = acc[k];
     }
     __syncthreads();
+    if (chain) {                     // open chain: the two end entries (above), over what the owners of waypoints 0 and n - 1 stored
+        if (tid == 0) { dst[0] = ce0; dst[n - 1] = cen; }
+        __syncthreads();
+    }
 }
 // (Round 4, measured and NOT kept: E then E' as ONE function -- one batch of loads, factors staged once, E x in registers between the
 //  halves: 34 us per gradient instead of 40, bench +0.5 %.  Same mathematics, other rounding order -- and the block-pivoting phase of the

@@ -29,6 +29,16 @@ class McqProblem(ctypes.Structure):
                 ("kappa_bound", ctypes.c_double), ("w_veh", ctypes.c_double)]
 
 
+class McqEnds(ctypes.Structure):
+    """mcq_ends: per-problem ring / open-chain record of mcq_solve_batch_ends (include/mcq.h)."""
+    _fields_ = [("closed", ctypes.c_int), ("fix_s", ctypes.c_int), ("fix_e", ctypes.c_int), ("psi_s", ctypes.c_double),
+                ("psi_e", ctypes.c_double)]
+
+
+FIX_HALF_WIDTH = 0.05       # MCQ_FIX_HALF_WIDTH
+CHAIN_MAXN = 2048           # MCQ_CHAIN_MAXN
+
+
 # the same record as a numpy structured type (field offsets taken from the ctypes layout): a batch's records are filled column by
 # column -- one ctypes attribute store per field and track, as the per-track loop did it, costs 12 ms for 1024 tracks
 _PROBLEM_DTYPE = np.dtype({"names": ["n", "reftrack", "normvec", "scaling", "kappa_bound", "w_veh"],
@@ -102,7 +112,7 @@ EXPORTED_SYMBOLS = ("mcq_create", "mcq_destroy", "mcq_last_error", "mcq_default_
                     "mcq_device_free", "mcq_copy_to_device", "mcq_copy_to_host", "mcq_sync", "mcq_stream",
                     "mcq_last_timing", "mcq_timing_begin", "mcq_timing_end", "mcq_workspace_bytes",
                     "mcq_comm_unique_id", "mcq_comm_init", "mcq_comm_allgather", "mcq_comm_wait", "mcq_comm_world", "mcq_comm_destroy",
-                    "mcq_les_scalings", "mcq_last_upload_was_direct")
+                    "mcq_les_scalings", "mcq_last_upload_was_direct", "mcq_solve_batch_ends", "mcq_les_scalings_open")
 
 
 IQP_ROUND_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int))
@@ -150,6 +160,11 @@ def load_library(path=None):
     lib.mcq_last_upload_was_direct.restype = ctypes.c_int
     lib.mcq_les_scalings.argtypes = [vp, ctypes.c_int, vp, ctypes.c_int]
     lib.mcq_les_scalings.restype = ctypes.c_int
+    lib.mcq_les_scalings_open.argtypes = [vp, ctypes.c_int, vp, ctypes.c_int]
+    lib.mcq_les_scalings_open.restype = ctypes.c_int
+    lib.mcq_solve_batch_ends.argtypes = [vp, ctypes.POINTER(McqProblem), ctypes.POINTER(McqEnds), ctypes.c_int, ctypes.POINTER(McqOpts), _dp,
+                                         _dp, _ip, ctypes.POINTER(McqInfo)]
+    lib.mcq_solve_batch_ends.restype = ctypes.c_int
     lib.mcq_host_alloc.argtypes = [vp, ctypes.c_size_t, ctypes.POINTER(vp)]
     lib.mcq_host_alloc.restype = ctypes.c_int
     lib.mcq_host_free.argtypes = [vp, vp]
@@ -302,9 +317,12 @@ class Engine:
             raise EngineError("%s failed (%d): %s" % (what, rc, self.lib.mcq_last_error().decode()))
 
     # ------------------------------------------------------------------------------------------------------------------
-    def solve_batch(self, problems, **opt_kw):
+    def solve_batch(self, problems, ends=None, **opt_kw):
         """problems: list of dicts {reftrack [n,4], normvec [n,2], scaling [n] or None, kappa_bound, w_veh}.
 
+        ends: None (every problem a ring: mcq_solve_batch), or one entry per problem -- None (a ring) or a dict {closed (default False),
+        psi_s, psi_e, fix_s, fix_e} -- through mcq_solve_batch_ends.  A chain's scaling holds its n - 2 inner joints' s_i in entries
+        0..n-3 (the rest is not read; les_scalings(A, closed=False) gives the [n] vector).
         Returns (alphas: list of [n] arrays, curv_err [B], status [B] int32, info: list of dicts).
         """
         bsz = len(problems)
@@ -330,9 +348,26 @@ class Engine:
         status = np.zeros(bsz, dtype=np.int32)
         info = (McqInfo * bsz)()
         opts = self._opts(**opt_kw)
-        rc = self.lib.mcq_solve_batch(self.h, arr, bsz, ctypes.byref(opts), _as_dp(alpha), _as_dp(curv),
-                                      status.ctypes.data_as(_ip), info)
-        self._check(rc, "mcq_solve_batch")
+        if ends is None:
+            rc = self.lib.mcq_solve_batch(self.h, arr, bsz, ctypes.byref(opts), _as_dp(alpha), _as_dp(curv),
+                                          status.ctypes.data_as(_ip), info)
+            self._check(rc, "mcq_solve_batch")
+        else:
+            if len(ends) != bsz:
+                raise ValueError("ends must have one entry per problem")
+            er = (McqEnds * bsz)()
+            for k, e in enumerate(ends):
+                if e is None or e.get("closed", False):
+                    er[k].closed = 1
+                    continue
+                er[k].closed = 0
+                er[k].fix_s = 1 if e.get("fix_s", False) else 0
+                er[k].fix_e = 1 if e.get("fix_e", False) else 0
+                er[k].psi_s = float(e["psi_s"])
+                er[k].psi_e = float(e["psi_e"])
+            rc = self.lib.mcq_solve_batch_ends(self.h, arr, er, bsz, ctypes.byref(opts), _as_dp(alpha), _as_dp(curv),
+                                               status.ctypes.data_as(_ip), info)
+            self._check(rc, "mcq_solve_batch_ends")
         out, off = [], 0
         for ref, _, _ in keep:
             out.append(alpha[off:off + ref.shape[0]].copy())
@@ -894,12 +929,28 @@ class Engine:
 _LIB_FOR_HOST_HELPERS = None
 
 
-def les_scalings(A, check=True):
+def les_scalings(A, check=True, closed=True):
     """The N spline scalings out of the dense [4N, 4N] matrix the reference passes as `A` (mcq_les_scalings: one threaded pass over the matrix in
     C, no GPU, no handle) -- the structural check of trajectory_planning_helpers.calc_splines.scalings_from_les_matrix, which stays as its
     numpy statement (and takes any array this entry cannot: other dtypes, non-contiguous views).  Raises RuntimeError with upstream-style
-    wording when `A` is not calc_splines' closed-spline system."""
+    wording when `A` is not calc_splines' closed-spline system.
+
+    closed=False: `A` is the [4(N-1), 4(N-1)] matrix of calc_splines' OPEN system through N waypoints (mcq_les_scalings_open); returns [N]
+    scalings, the inner joints' in entries 0..N-3 and ones in the last two (what solve_batch reads for a chain)."""
     global _LIB_FOR_HOST_HELPERS
+    if not closed:
+        if not (isinstance(A, np.ndarray) and A.dtype == np.float64 and A.ndim == 2 and A.shape[0] == A.shape[1] and A.shape[0] % 4 == 0
+                and A.shape[0] >= 8 and A.flags["C_CONTIGUOUS"]):
+            from .trajectory_planning_helpers import calc_splines as _cs
+            return _cs.scalings_from_open_les_matrix(A, check=check)
+        if _LIB_FOR_HOST_HELPERS is None:
+            _LIB_FOR_HOST_HELPERS = _DEFAULT_ENGINE.lib if _DEFAULT_ENGINE is not None else load_library()
+        n = A.shape[0] // 4 + 1
+        s = np.empty(n)
+        if _LIB_FOR_HOST_HELPERS.mcq_les_scalings_open(A.ctypes.data, n, s.ctypes.data, 1 if check else 0) != 0:
+            raise RuntimeError("Spline equation system matrix A does not have the structure of calc_splines' open-spline system (the MI355X "
+                               "engine derives everything from the spline scalings it encodes): " + _LIB_FOR_HOST_HELPERS.mcq_last_error().decode())
+        return s
     if not (isinstance(A, np.ndarray) and A.dtype == np.float64 and A.ndim == 2 and A.shape[0] == A.shape[1] and A.shape[0] % 4 == 0
             and A.shape[0] >= 12 and A.flags["C_CONTIGUOUS"]):
         from .trajectory_planning_helpers import calc_splines as _cs

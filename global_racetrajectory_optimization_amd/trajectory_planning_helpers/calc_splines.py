@@ -1,6 +1,7 @@
 """
 Host-side shim of tph.calc_splines.calc_splines -- boundary [REF helper_funcs_glob/src/prep_track.py:48-51],
-[REF main_globaltraj.py:568-569].  Closed tracks only (the only case the reference's mincurv flow exercises).
+[REF main_globaltraj.py:568-569].  Closed tracks (the reference's mincurv flow) and open paths with given end headings
+(psi_s, psi_e: DESIGN.md "Open chains").
 
 Instead of the dense 4N x 4N solve of the upstream formulation, the closed cubic-spline conditions are reduced to the
 cyclic tridiagonal system in the quadratic coefficients c_i (derivation in DESIGN.md section 3):
@@ -126,14 +127,110 @@ def scalings_from_les_matrix(A, check=True):
     return s
 
 
+# ----------------------------------------------------------------------------------------------------------------------
+# open paths: N points, N - 1 splines, headings psi_s / psi_e at the ends (tph convention: rad, 0 = north)
+# ----------------------------------------------------------------------------------------------------------------------
+# tph.calc_splines multiplies its heading rows by el_lengths[0] / el_lengths[-1] (1.0 when el_lengths is None), while tph.opt_min_curv's own
+# heading rows use the unit vectors (include/mcq.h MCQ_HEADING_SCALE).  Reproduced, not fixed: the two disagree upstream too.
+
+def open_spline_coeffs(points, scaling, h_s, h_e):
+    """points [N, k], scaling [N - 2] (inner joints), h_s / h_e [k] heading vectors as the heading rows carry them -> a, b, c, d [N - 1, k].
+
+    Unknowns c_0 .. c_(N-1) (x'' = 2 c; c_(N-1) is half the second derivative at t = 1 of the last spline), s_(N-2) := 1:
+        2 c_0 + s_0^2 c_1 = 3 (D_0 - h_s)
+        c_(m-1) + (2 s_(m-1)^2 + 2 s_(m-1)) c_m + s_(m-1) s_m^2 c_(m+1) = 3 (s_(m-1) D_m - D_(m-1))     1 <= m <= N-2
+        c_(N-2) + 2 c_(N-1) = 3 (h_e - D_(N-2))
+    """
+    n = points.shape[0]
+    s = np.append(np.asarray(scaling, dtype=np.float64), 1.0)          # s_0 .. s_(N-2)
+    delta = np.diff(points, axis=0)                                    # D_0 .. D_(N-2)
+    diag = np.empty(n)
+    sup = np.zeros(n)
+    sub = np.ones(n)
+    diag[0], diag[-1] = 2.0, 2.0
+    diag[1:-1] = 2.0 * s[:-1] ** 2 + 2.0 * s[:-1]
+    sup[0] = s[0] ** 2
+    sup[1:-1] = s[:-1] * s[1:] ** 2
+    rhs = np.empty((n, points.shape[1]))
+    rhs[0] = 3.0 * (delta[0] - h_s)
+    rhs[1:-1] = 3.0 * (s[:-1, None] * delta[1:] - delta[:-1])
+    rhs[-1] = 3.0 * (h_e - delta[-1])
+    ab = np.zeros((3, n))
+    ab[0, 1:] = sup[:-1]
+    ab[1, :] = diag
+    ab[2, :-1] = sub[1:]
+    c = solve_banded((1, 1), ab, rhs)
+    cn = c[1:]
+    cc = c[:-1]
+    d = (s[:, None] ** 2 * cn - cc) / 3.0
+    b = delta - (2.0 * cc + s[:, None] ** 2 * cn) / 3.0
+    return points[:-1].copy(), b, cc, d
+
+
+def build_open_les_matrix(n, scaling):
+    """The dense [4(N-1), 4(N-1)] matrix of tph's open system through N points (12 N - 15 non-zeros)."""
+    ns = n - 1
+    M = np.zeros((4 * ns, 4 * ns))
+    i = np.arange(ns)
+    j = 4 * i
+    M[j, j] = 1.0
+    for k in range(4):
+        M[j + 1, j + k] = 1.0
+    ji = 4 * i[:-1]
+    M[ji + 2, ji + 1], M[ji + 2, ji + 2], M[ji + 2, ji + 3] = 1.0, 2.0, 3.0
+    M[ji + 2, ji + 5] = -np.asarray(scaling)
+    M[ji + 3, ji + 2], M[ji + 3, ji + 3] = 2.0, 6.0
+    M[ji + 3, ji + 6] = -2.0 * np.asarray(scaling) ** 2
+    M[-2, 1] = 1.0
+    M[-1, -4:] = (0.0, 1.0, 2.0, 3.0)
+    return M
+
+
+def scalings_from_open_les_matrix(A, check=True):
+    """[N] scalings out of the open matrix (N - 2 inner joints, then two ones), with the structural check of mcq_les_scalings_open."""
+    A = np.asarray(A)
+    ns = A.shape[0] // 4
+    n = ns + 1
+    i = np.arange(ns - 1)
+    s = np.ones(n)
+    s[:-2] = -A[4 * i + 2, 4 * i + 5]
+    if check:
+        ok = A.ndim == 2 and A.shape[0] == A.shape[1] == 4 * ns and ns >= 2
+        ok = ok and bool(np.all(np.isfinite(s)) and np.all(s > 0.0))
+        if ok:
+            ok = bool(np.array_equal(A, build_open_les_matrix(n, s[:-2])) or
+                      (np.count_nonzero(A) == 12 * n - 15 and np.allclose(A, build_open_les_matrix(n, s[:-2]), rtol=1e-12, atol=0.0)))
+        if not ok:
+            raise RuntimeError("Spline equation system matrix A does not have the structure of calc_splines' open-spline system (the "
+                               "MI355X engine derives everything from the spline scalings it encodes and cannot use an arbitrary matrix)")
+    return s
+
+
 def calc_splines(path: np.ndarray, el_lengths: np.ndarray = None, psi_s: float = None, psi_e: float = None,
                  use_dist_scaling: bool = True) -> tuple:
     path = np.asarray(path, dtype=np.float64)
     closed = bool(np.all(np.isclose(path[0], path[-1]))) and psi_s is None
-    if not closed:
-        raise NotImplementedError("calc_splines shim: only closed paths (first point repeated at the end) are supported")
+    if not closed and (psi_s is None or psi_e is None):
+        raise RuntimeError("Headings must be provided for unclosed spline calculation!")
     if el_lengths is not None and path.shape[0] != el_lengths.size + 1:
         raise RuntimeError("el_lengths input must be one element smaller than path input!")
+    if not closed:
+        n = path.shape[0]
+        if use_dist_scaling:
+            el = np.sqrt(np.sum(np.diff(path, axis=0) ** 2, axis=1)) if el_lengths is None else np.array(el_lengths, dtype=np.float64)
+            scaling = el[:-1] / el[1:]
+        else:
+            scaling = np.ones(n - 2)
+        l_s = 1.0 if el_lengths is None else float(el_lengths[0])
+        l_e = 1.0 if el_lengths is None else float(el_lengths[-1])
+        h_s = np.array((np.cos(psi_s + np.pi / 2), np.sin(psi_s + np.pi / 2))) * l_s
+        h_e = np.array((np.cos(psi_e + np.pi / 2), np.sin(psi_e + np.pi / 2))) * l_e
+        a, b, c, d = open_spline_coeffs(path, scaling, h_s, h_e)
+        coeffs_x = np.column_stack((a[:, 0], b[:, 0], c[:, 0], d[:, 0]))
+        coeffs_y = np.column_stack((a[:, 1], b[:, 1], c[:, 1], d[:, 1]))
+        normvec = np.stack((coeffs_y[:, 1], -coeffs_x[:, 1]), axis=1)
+        normvec_normalized = normvec / np.sqrt(np.sum(normvec ** 2, axis=1))[:, None]
+        return coeffs_x, coeffs_y, build_open_les_matrix(n, scaling), normvec_normalized
     n = path.shape[0] - 1
     scaling = spline_scalings(path, el_lengths, use_dist_scaling)
     a, b, c, d = closed_spline_coeffs(path[:-1], scaling)

@@ -8,7 +8,7 @@
  * which end in quadprog.solve_qp (C).  The entry points below are what a ctypes binding inside those two Python
  * functions binds instead (INTEGRATION.md shows the stub).  Plain pointers and sizes only; no torch / numpy types.
  *
- * One "problem" = one closed reference track:
+ * One "problem" = one closed reference track (or an open chain with end headings: mcq_solve_batch_ends below):
  *     reftrack  [n][4] row-major double  = [x_m, y_m, w_tr_right_m, w_tr_left_m]   (producer [REF prep_track.py:39-45,104])
  *     normvec   [n][2] row-major double  = unit normals pointing right             (producer [REF prep_track.py:50-51])
  *     scaling   [n]    double            = s_i = l_i / l_{i+1}, the only information opt_min_curv needs from the
@@ -148,6 +148,30 @@ void mcq_default_opts(mcq_opts* o);
  * vectors (sum of n over the batch); curv_err_out/status_out/info_out have `batch` entries (info_out may be NULL). */
 int mcq_solve_batch(mcq_handle* h, const mcq_problem* probs, int batch, const mcq_opts* opts, double* alpha_out,
                     double* curv_err_out, int* status_out, mcq_info* info_out);
+
+/* ---- open chains (tph.opt_min_curv(..., closed=False, psi_s, psi_e, fix_s, fix_e)) ----------------------------------------------------------
+ * One record per problem of the batch.  closed != 0: the problem is a ring, solved exactly as by mcq_solve_batch (bitwise; the other fields
+ * are ignored).  closed == 0: the n waypoints are an OPEN chain of n - 1 splines whose end headings are psi_s / psi_e (rad, tph convention: 0
+ * points north, the heading vector is (cos(psi + pi/2), sin(psi + pi/2))).  The spline system loses the couplings between waypoint n - 1 and
+ * waypoint 0 and gains the heading rows (DESIGN.md "Open chains"); E, f, the curvature rows and the curvature-error post-check follow.
+ *   - scaling[n]: entries 0..n-3 are the inner joints' s_i = l_i / l_(i+1) (s_i = -A[4i+2][4i+5] of the open calc_splines matrix,
+ *     mcq_les_scalings_open); entries n-2, n-1 are not read; NULL => all ones.
+ *   - fix_s / fix_e pin the first / last waypoint to |alpha| <= MCQ_FIX_HALF_WIDTH (applied before the infeasibility check, like tph).
+ *   - The heading rows use the UNIT heading vectors, unscaled (tph.opt_min_curv's q_x / q_y); tph.calc_splines scales its own heading rows by
+ *     the first / last element length -- a quirk reproduced, not fixed (MCQ_HEADING_SCALE).
+ *   - A chain needs normvec (no derived normals) and the minimum-curvature objective: MCQ_E_ARG otherwise.  A chain of more than
+ *     MCQ_CHAIN_MAXN waypoints, or a non-finite psi_s / psi_e, is MCQ_BAD_INPUT for that problem.
+ * Mixed batches of rings and chains are allowed; ends == NULL is exactly mcq_solve_batch. */
+#define MCQ_FIX_HALF_WIDTH 0.05
+#define MCQ_HEADING_SCALE 1.0   /* opt_min_curv's heading rows: unit vectors (calc_splines scales its own by el_lengths[0] / [-1]) */
+#define MCQ_CHAIN_MAXN 2048
+typedef struct {
+    int closed;         /* != 0: ring (the other fields are ignored) */
+    int fix_s, fix_e;   /* pin the first / last waypoint (chains only) */
+    double psi_s, psi_e;  /* end headings (chains only) */
+} mcq_ends;
+int mcq_solve_batch_ends(mcq_handle* h, const mcq_problem* probs, const mcq_ends* ends, int batch, const mcq_opts* opts, double* alpha_out,
+                         double* curv_err_out, int* status_out, mcq_info* info_out);
 
 /* Device-resident entry points (uniform n, inputs already in HBM; used by bench.py, the IQP driver and the multi-GPU
  * shard path).  All pointers are DEVICE pointers on the handle's device; layouts as above with a leading batch axis:
@@ -388,6 +412,10 @@ int mcq_iqp_set_round_callback(mcq_handle* h, mcq_iqp_round_cb cb, void* user);
  * a call whose kernel takes 3; round 6).  No GPU involved, no handle.  Returns 0, or MCQ_E_ARG when A does not have the structure (the message
  * names the first offending entry). */
 int mcq_les_scalings(const double* A, int n, double* s_out, int check);
+/* The same for the [4(n-1)][4(n-1)] matrix of tph.calc_splines' OPEN system through n waypoints: s_out[i] = -A[4i+2][4i+5] for i <= n-3,
+ * s_out[n-2] = s_out[n-1] = 1.  check != 0 verifies the 12 n - 15 structural entries: the closed template for splines 0..n-3, the last spline's
+ * rows [1 0 0 0] and [1 1 1 1], the heading rows A[-2][1] = 1 and A[-1][-4:] = [0 1 2 3], and nothing else. */
+int mcq_les_scalings_open(const double* A, int n, double* s_out, int check);
 
 /* Pinned (page-locked) host memory for callers that want their buffers copied at PCIe speed (mcq_solve_host, mcq_solve_batch,
  * mcq_copy_*). */

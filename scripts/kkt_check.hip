@@ -1,7 +1,7 @@
 // kkt_check.hip -- DIAGNOSTIC (not part of the library): the saddle-point elimination of mcq_kkt.inc in isolation.  One workgroup per problem
 // copy, `reps` factorisations + solves of the same system; every solution is compared with the first one (determinism: races show up as
 // differences between repetitions) and with a dense LU of the same saddle-point system on the host (correctness).
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -mllvm -enable-ipra=0 --gpu-max-threads-per-block=512 [-DKKT_TIMERS=1] [-DKC_F32=1] -o kc scripts/kkt_check.hip ;  ./kc [n 333] [reps 50] [batch 4] [sigma exponent range 12] [host reference 1] [fused 0] [pinned fraction 0]
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -mllvm -enable-ipra=0 --gpu-max-threads-per-block=512 [-DKKT_TIMERS=1] [-DKC_F32=1] -o kc scripts/kkt_check.hip ;  ./kc [n 333] [reps 50] [batch 4] [sigma exponent range 12] [host reference 1] [fused 0] [pinned fraction 0] [open chain 0]
 // (also builds against tests/emu: g++ -O2 -std=c++17 -x c++ -I tests/emu/include scripts/kkt_check.hip)
 #include "../global_racetrajectory_optimization_amd/csrc/mcq_kernels.hip"
 #ifndef KC_F32
@@ -64,6 +64,7 @@ int main(int argc, char** argv)
     const int with_ref = argc > 5 ? atoi(argv[5]) : 1;
     const int fused = argc > 6 ? atoi(argv[6]) : 0;
     const double pin_frac = argc > 7 ? atof(argv[7]) : 0.0;        // fraction of pinned waypoints (rows / columns of the reduced system replaced by identity)
+    const int chain = argc > 8 ? atoi(argv[8]) : 0;                // 1: every problem an OPEN chain (mcq_ends.closed = 0: no coupling between n - 1 and 0)
     const size_t elems = (size_t)batch * n;
     unsigned long long seed = 12345;
     // geometry of an oval: reference derivatives and unit normals; spline scalings near one
@@ -81,6 +82,7 @@ int main(int argc, char** argv)
         vec[(size_t)V_SIG * n + i] = srange < -90.0 ? 0.0 : pow(10.0, -6.0 + (srange + 6.0) * urand(seed));      // sigma range < -90: no diagonal at all (the active-set phase's systems)
         rhs[i] = 2.0 * urand(seed) - 1.0;
     }
+    if (chain) vec[(size_t)V_SC * n + n - 2] = vec[(size_t)V_SC * n + n - 1] = 1.0;     // (what the assembly stores for a chain)
     double *L, *vecd, *rhsd, *outd;
     signed char* state;
     int *status, *fsd;
@@ -107,6 +109,14 @@ int main(int argc, char** argv)
     B.L = L; B.vec = vecd; B.state = state; B.status = status;
     B.Z = L;      // unused by the saddle-point path
     B.ref = L; B.kappa_bound = 1.0; B.w_veh = 0.0;
+    mcq_ends* ends = nullptr;
+    if (chain) {
+        std::vector<mcq_ends> he(batch);
+        for (auto& e : he) { e.closed = 0; e.fix_s = e.fix_e = 0; e.psi_s = e.psi_e = 0.0; }
+        CK(hipMalloc((void**)&ends, batch * sizeof(mcq_ends)));
+        CK(hipMemcpy(ends, he.data(), batch * sizeof(mcq_ends), hipMemcpyHostToDevice));
+        B.ends = ends;
+    }
     hipLaunchKernelGGL(kc_kernel, dim3(batch), dim3(MCQ_NT), 0, 0, B, reps, rhsd, outd, fsd, fused, pin_frac > 0.0 ? 1 : 0, srange < -90.0 ? 1 : 0);
     CK(hipGetLastError());
     CK(hipDeviceSynchronize());
@@ -133,6 +143,16 @@ int main(int argc, char** argv)
         for (int m = 0; m < n; ++m) {
             const int m1 = (m + n - 1) % n, p1 = (m + 1) % n;
             const double s1 = SC[m1], s0 = SC[m];
+            if (chain && m == 0) {              // open chain: heading rows, no coupling between n - 1 and 0 (DESIGN.md "Open chains")
+                T[0] = 2.0; T[1] = s0 * s0;
+                R[0] = -3.0; R[1] = 3.0;
+                continue;
+            }
+            if (chain && m == n - 1) {
+                T[(size_t)m * n + m1] = 1.0; T[(size_t)m * n + m] = 2.0;
+                R[(size_t)m * n + m1] = 3.0; R[(size_t)m * n + m] = -3.0;
+                continue;
+            }
             T[(size_t)m * n + m1] += 1.0; T[(size_t)m * n + m] += 2.0 * s1 * s1 + 2.0 * s1; T[(size_t)m * n + p1] += s1 * s0 * s0;
             R[(size_t)m * n + m1] += 3.0; R[(size_t)m * n + m] += -3.0 * (s1 + 1.0); R[(size_t)m * n + p1] += 3.0 * s1;
         }

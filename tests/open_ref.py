@@ -1,0 +1,160 @@
+"""
+TEST ORACLE for open chains (closed=False) -- test infrastructure only, like oracle/tph_ref.py (whose header applies).
+
+A literal DENSE restatement of tph 0.76's open calc_splines and opt_min_curv (not importable here; restated from the published
+algorithm, DESIGN.md "Open chains"): the [4(N-1), 4(N-1)] spline system inverted densely, the extraction matrices, q with the heading
+rows, H / f / E_kappa / k_ref by dense products, the fix clamps before the "too small" check, and the QP handed with all 4N rows to the
+dense Goldfarb-Idnani solver (oracle.qp_ref.solve_qp_gi, the qpgen2 restatement).  No structure is exploited.
+
+scaled_headings=True is the variant whose q heading rows are scaled by the first / last element length like calc_splines' own rows --
+what opt_min_curv upstream does NOT do; the heading-quirk test checks that the engine does not match it.
+"""
+import math
+
+import numpy as np
+
+from oracle import qp_ref
+
+F_SCALE = 2.0
+FIX_HALF_WIDTH = 0.05
+
+
+def calc_splines_open(path, el_lengths=None, psi_s=None, psi_e=None, use_dist_scaling=True):
+    """(coeffs_x [N-1,4], coeffs_y [N-1,4], A [4(N-1),4(N-1)], normvec_normalized [N-1,2]) by the dense solve."""
+    path = np.asarray(path, dtype=np.float64)
+    if psi_s is None or psi_e is None:
+        raise RuntimeError("Headings must be provided for unclosed spline calculation!")
+    ns = path.shape[0] - 1
+    if use_dist_scaling:
+        el = np.sqrt(np.sum(np.diff(path, axis=0) ** 2, axis=1)) if el_lengths is None else np.array(el_lengths, dtype=np.float64)
+        scaling = el[:-1] / el[1:]
+    else:
+        scaling = np.ones(ns - 1)
+    M = np.zeros((4 * ns, 4 * ns))
+    bx = np.zeros(4 * ns)
+    by = np.zeros(4 * ns)
+    for i in range(ns):
+        j = 4 * i
+        M[j, j] = 1.0
+        M[j + 1, j:j + 4] = 1.0
+        bx[j], bx[j + 1] = path[i, 0], path[i + 1, 0]
+        by[j], by[j + 1] = path[i, 1], path[i + 1, 1]
+        if i < ns - 1:
+            M[j + 2, j + 1:j + 4] = (1.0, 2.0, 3.0)
+            M[j + 2, j + 5] = -scaling[i]
+            M[j + 3, j + 2:j + 4] = (2.0, 6.0)
+            M[j + 3, j + 6] = -2.0 * scaling[i] ** 2
+    M[-2, 1] = 1.0
+    M[-1, -4:] = (0.0, 1.0, 2.0, 3.0)
+    l_s = 1.0 if el_lengths is None else el_lengths[0]
+    l_e = 1.0 if el_lengths is None else el_lengths[-1]
+    bx[-2], by[-2] = math.cos(psi_s + math.pi / 2) * l_s, math.sin(psi_s + math.pi / 2) * l_s
+    bx[-1], by[-1] = math.cos(psi_e + math.pi / 2) * l_e, math.sin(psi_e + math.pi / 2) * l_e
+    cx = np.linalg.solve(M, bx).reshape(ns, 4)
+    cy = np.linalg.solve(M, by).reshape(ns, 4)
+    nv = np.stack((cy[:, 1], -cx[:, 1]), axis=1)
+    nv /= np.sqrt(np.sum(nv ** 2, axis=1))[:, None]
+    return cx, cy, M, nv
+
+
+def assemble_open(reftrack, normvectors, A, psi_s, psi_e, scaled_headings=False, el_lengths=None):
+    reftrack = np.asarray(reftrack, dtype=np.float64)
+    normvectors = np.asarray(normvectors, dtype=np.float64)
+    n = reftrack.shape[0]
+    ns = n - 1
+    if A.shape != (4 * ns, 4 * ns):
+        raise RuntimeError("Spline equation system matrix A has wrong dimensions!")
+    A_ex_b = np.zeros((n, 4 * ns))
+    A_ex_c = np.zeros((n, 4 * ns))
+    for i in range(ns):
+        A_ex_b[i, 4 * i + 1] = 1.0
+        A_ex_c[i, 4 * i + 2] = 2.0
+    A_ex_b[-1, -4:] = (0.0, 1.0, 2.0, 3.0)
+    A_ex_c[-1, -4:] = (0.0, 0.0, 2.0, 6.0)
+    A_inv = np.linalg.inv(A)
+    T_c = A_ex_c @ A_inv
+    T_b = A_ex_b @ A_inv
+    M_x = np.zeros((4 * ns, n))
+    M_y = np.zeros((4 * ns, n))
+    q_x = np.zeros(4 * ns)
+    q_y = np.zeros(4 * ns)
+    for i in range(ns):
+        M_x[4 * i, i], M_x[4 * i + 1, i + 1] = normvectors[i, 0], normvectors[i + 1, 0]
+        M_y[4 * i, i], M_y[4 * i + 1, i + 1] = normvectors[i, 1], normvectors[i + 1, 1]
+        q_x[4 * i], q_x[4 * i + 1] = reftrack[i, 0], reftrack[i + 1, 0]
+        q_y[4 * i], q_y[4 * i + 1] = reftrack[i, 1], reftrack[i + 1, 1]
+    l_s = l_e = 1.0
+    if scaled_headings:
+        el = np.sqrt(np.sum(np.diff(reftrack[:, :2], axis=0) ** 2, axis=1)) if el_lengths is None else el_lengths
+        l_s, l_e = el[0], el[-1]
+    q_x[-2], q_y[-2] = math.cos(psi_s + math.pi / 2) * l_s, math.sin(psi_s + math.pi / 2) * l_s
+    q_x[-1], q_y[-1] = math.cos(psi_e + math.pi / 2) * l_e, math.sin(psi_e + math.pi / 2) * l_e
+    x_p = T_b @ q_x
+    y_p = T_b @ q_y
+    den = (x_p ** 2 + y_p ** 2) ** 1.5
+    c = 1.0 / den
+    P_xx = np.diag(c ** 2 * y_p ** 2)
+    P_yy = np.diag(c ** 2 * x_p ** 2)
+    P_xy = np.diag(-2.0 * c ** 2 * x_p * y_p)
+    T_nx = T_c @ M_x
+    T_ny = T_c @ M_y
+    H = T_nx.T @ P_xx @ T_nx + T_ny.T @ P_xy @ T_nx + T_ny.T @ P_yy @ T_ny
+    H = 0.5 * (H + H.T)
+    tcqx = T_c @ q_x
+    tcqy = T_c @ q_y
+    f = F_SCALE * tcqx @ P_xx @ T_nx + tcqx @ P_xy @ T_ny + tcqy @ P_xy @ T_nx + F_SCALE * tcqy @ P_yy @ T_ny
+    Q_x = np.diag(c * y_p)
+    Q_y = np.diag(c * x_p)
+    E_kappa = Q_y @ T_ny - Q_x @ T_nx
+    k_ref = Q_y @ tcqy - Q_x @ tcqx
+    aux = dict(T_b=T_b, T_c=T_c, M_x=M_x, M_y=M_y, q_x=q_x, q_y=q_y, x_p=x_p, y_p=y_p, T_nx=T_nx, T_ny=T_ny)
+    return H, f, E_kappa, k_ref, aux
+
+
+def bounds_open(reftrack, w_veh, fix_s=False, fix_e=False):
+    """dev_max_right, dev_max_left with the fix clamps applied BEFORE the "too small" check (as upstream)."""
+    dev_max_right = reftrack[:, 2] - w_veh / 2
+    dev_max_left = reftrack[:, 3] - w_veh / 2
+    if fix_s:
+        dev_max_left[0] = dev_max_right[0] = FIX_HALF_WIDTH
+    if fix_e:
+        dev_max_left[-1] = dev_max_right[-1] = FIX_HALF_WIDTH
+    if np.any(-dev_max_right > dev_max_left) or np.any(-dev_max_left > dev_max_right):
+        raise RuntimeError("Problem not solvable, track might be too small to run with current safety distance!")
+    return dev_max_right, dev_max_left
+
+
+def curv_error(alpha, aux):
+    q_x_t = aux["q_x"] + aux["M_x"] @ alpha
+    q_y_t = aux["q_y"] + aux["M_y"] @ alpha
+    x_p_t = aux["T_b"] @ q_x_t
+    y_p_t = aux["T_b"] @ q_y_t
+    x_pp = aux["T_c"] @ aux["q_x"] + aux["T_nx"] @ alpha
+    y_pp = aux["T_c"] @ aux["q_y"] + aux["T_ny"] @ alpha
+    x_p, y_p = aux["x_p"], aux["y_p"]
+    k_orig = (x_p * y_pp - y_p * x_pp) / (x_p ** 2 + y_p ** 2) ** 1.5
+    k_sol = (x_p_t * y_pp - y_p_t * x_pp) / (x_p_t ** 2 + y_p_t ** 2) ** 1.5
+    return float(np.max(np.abs(k_sol - k_orig)))
+
+
+def opt_min_curv_open(reftrack, normvectors, A, kappa_bound, w_veh, psi_s, psi_e, fix_s=False, fix_e=False, solver=None,
+                      scaled_headings=False, return_internals=False):
+    """(alpha [N], curv_error_max) of tph.opt_min_curv(..., closed=False, psi_s, psi_e, fix_s, fix_e), densely."""
+    reftrack = np.asarray(reftrack, dtype=np.float64)
+    H, f, E, k_ref, aux = assemble_open(reftrack, normvectors, A, psi_s, psi_e, scaled_headings=scaled_headings)
+    dev_max_right, dev_max_left = bounds_open(reftrack, w_veh, fix_s, fix_e)
+    n = reftrack.shape[0]
+    G = np.vstack((np.eye(n), -np.eye(n), E, -E))
+    h = np.concatenate((dev_max_right, dev_max_left, kappa_bound - k_ref, kappa_bound + k_ref))
+    alpha = (solver or qp_ref.solve_qp_gi)(H, f, G, h)
+    err = curv_error(alpha, aux)
+    if return_internals:
+        return alpha, err, dict(H=H, f=f, E=E, k_ref=k_ref, G=G, h=h, lo=-dev_max_left, hi=dev_max_right)
+    return alpha, err
+
+
+def scalings_of(A):
+    """[N] scalings the engine takes for a chain: -A[4i+2, 4i+5] for the N - 2 inner joints, then two ones."""
+    ns = A.shape[0] // 4
+    i = np.arange(ns - 1)
+    return np.concatenate((-A[4 * i + 2, 4 * i + 5], [1.0, 1.0]))
