@@ -153,8 +153,149 @@ def opt_min_curv_open(reftrack, normvectors, A, kappa_bound, w_veh, psi_s, psi_e
     return alpha, err
 
 
+def seeded_path(n, seed, step=1.5, ragged=False):
+    """A wavy open reference line of n waypoints, about `step` apart; ragged=True: element lengths alternating 1 : 3 (same mean step)."""
+    rng = np.random.default_rng(seed)
+    t = np.linspace(0.0, 1.0, n)
+    if ragged:
+        t = np.concatenate(([0.0], np.cumsum(np.where(np.arange(n - 1) % 2 == 0, 1.0, 3.0))))
+        t /= t[-1]
+    L = step * (n - 1)
+    x = L * t + rng.uniform(-0.1, 0.1, n) * step * (0.25 if ragged else 1.0)
+    y = 0.08 * L * np.sin(3 * np.pi * t * rng.uniform(0.5, 1.5)) + 0.02 * L * np.cos(7 * t)
+    return np.column_stack((x, y))
+
+
+def own_headings(xy):
+    """(psi_s, psi_e) of the line's own first and last element (tph convention: atan2(dy, dx) - pi / 2)."""
+    return (float(np.arctan2(xy[1, 1] - xy[0, 1], xy[1, 0] - xy[0, 0]) - np.pi / 2),
+            float(np.arctan2(xy[-1, 1] - xy[-2, 1], xy[-1, 0] - xy[-2, 0]) - np.pi / 2))
+
+
+def chain_from_line(xy, psi_s, psi_e, widths):
+    """(reftrack, normvec, A): the open spline's normals (the last one repeated) and its dense system matrix."""
+    _, _, A, nv = calc_splines_open(xy, psi_s=psi_s, psi_e=psi_e)
+    return np.column_stack((xy, widths)), np.vstack((nv, nv[-1])), A
+
+
+def seeded_chain(n, seed, w=(2.5, 4.0), ragged=False, w_step=None):
+    """Reference line, normals (the open spline's, last one repeated), dense A, end headings near the line's own.
+    w_step: widths rounded to multiples of it (fixtures: a few distinct values compress)."""
+    rng = np.random.default_rng(seed + 1000)
+    xy = seeded_path(n, seed, ragged=ragged)
+    ps, pe = own_headings(xy)
+    psi_s, psi_e = ps + 0.05, pe - 0.03
+    widths = rng.uniform(w[0], w[1], size=(n, 2))
+    if w_step is not None:
+        widths = np.round(widths / w_step) * w_step
+    ref, nv, A = chain_from_line(xy, psi_s, psi_e, widths)
+    return ref, nv, A, psi_s, psi_e
+
+
+def open_scalings(reftrack):
+    """The [N] chain scalings of calc_splines_open's distance scaling, from the waypoints alone (bitwise scalings_of(A) of that A)."""
+    el = np.sqrt(np.sum(np.diff(np.asarray(reftrack)[:, :2], axis=0) ** 2, axis=1))
+    return np.concatenate((el[:-1] / el[1:], [1.0, 1.0]))
+
+
+def mirror(reftrack, normvec, psi_s, psi_e, fix_s=False, fix_e=False):
+    """The same chain driven the other way: waypoints reversed, w_r / w_l swapped, normals -nv[::-1], headings turned by pi and
+    swapped, fix flags swapped.  Its optimum is -alpha[::-1] of the original's (the open spline and the QP are reversal-symmetric)."""
+    ref = np.ascontiguousarray(np.asarray(reftrack)[::-1][:, [0, 1, 3, 2]])
+    return ref, np.ascontiguousarray(-np.asarray(normvec)[::-1]), psi_e + math.pi, psi_s + math.pi, fix_e, fix_s
+
+
 def scalings_of(A):
     """[N] scalings the engine takes for a chain: -A[4i+2, 4i+5] for the N - 2 inner joints, then two ones."""
     ns = A.shape[0] // 4
     i = np.arange(ns - 1)
     return np.concatenate((-A[4 * i + 2, 4 * i + 5], [1.0, 1.0]))
+
+
+class OpenFixture:
+    """A ragged open-chain fixture of scripts/make_golden_open_edges.py (tests/golden/open_edges.npz, open_kappa_fuzz.npz): problem k is
+    chain chain[k] (waypoint rows [chain_offsets[c], chain_offsets[c + 1])) with its own bound, fix flags and oracle outputs."""
+
+    def __init__(self, path):
+        z = np.load(path)
+        self.z = {k: z[k] for k in z.files}
+        self.count = len(self.z["chain"])
+        self.families = [str(s) for s in self.z["family_names"]]
+
+    def __len__(self):
+        return self.count
+
+    def family(self, k):
+        return self.families[int(self.z["chain_family"][self.z["chain"][k]])]
+
+    def case(self, k):
+        return str(self.z["case"][k])
+
+    def rows(self, k):
+        c = int(self.z["chain"][k])
+        return slice(int(self.z["chain_offsets"][c]), int(self.z["chain_offsets"][c + 1]))
+
+    def n(self, k):
+        r = self.rows(k)
+        return r.stop - r.start
+
+    def problem(self, k):
+        r = self.rows(k)
+        return dict(reftrack=self.z["reftrack"][r], normvec=self.z["normvec"][r], scaling=self.z["scaling"][r],
+                    kappa_bound=float(self.z["kappa_bound"][k]), w_veh=float(self.z["w_veh"][k]))
+
+    def ends(self, k):
+        c = int(self.z["chain"][k])
+        return dict(psi_s=float(self.z["psi_s"][c]), psi_e=float(self.z["psi_e"][c]), fix_s=bool(self.z["fix_s"][k]),
+                    fix_e=bool(self.z["fix_e"][k]))
+
+    def mirrored(self, k):
+        """(problem, ends) of the chain driven the other way (mirror); its optimum is -alpha[::-1]."""
+        p, e = self.problem(k), self.ends(k)
+        ref, nv, ps, pe, fs, fe = mirror(p["reftrack"], p["normvec"], e["psi_s"], e["psi_e"], e["fix_s"], e["fix_e"])
+        return (dict(p, reftrack=ref, normvec=nv, scaling=open_scalings(ref)), dict(psi_s=ps, psi_e=pe, fix_s=fs, fix_e=fe))
+
+    def alpha(self, k):
+        return self.z["alpha"][int(self.z["offsets"][k]):int(self.z["offsets"][k + 1])]
+
+    def __getitem__(self, key):
+        return self.z[key]
+
+    def guard(self, k):
+        """max(1e-8, 4 x alpha_spread): the tight check on top of the contract, from the fixture's own determinacy."""
+        return max(1e-8, 4.0 * float(self.z["alpha_spread"][k]))
+
+    def select(self, pred):
+        return [k for k in range(self.count) if pred(k)]
+
+
+def check_fixture_results(fx, ks, al, curv, st, info, contract, curv_tol, worst, n_active=False, tag=""):
+    """Engine results for fixture problems ks: statuses as stored; for status 0 the CONTRACT and the GUARD (fx.guard) on alpha, the
+    curvature error, the fix clamps and (n_active=True) the number of active curvature rows.  worst[family] = [|d alpha|, guard, spread]."""
+    from global_racetrajectory_optimization_amd import engine
+    for j, k in enumerate(ks):
+        what = (tag, fx.family(k), fx.n(k), fx.case(k))
+        assert st[j] == fx["status_ref"][k], (what, st[j], fx["status_ref"][k])
+        if st[j] != 0:
+            continue
+        d = float(np.max(np.abs(al[j] - fx.alpha(k))))
+        g = fx.guard(k)
+        assert d < contract, (what, d)                                       # contract
+        assert d < g, (what, d, g)                                           # guard
+        assert abs(curv[j] - fx["curv_error_max"][k]) < curv_tol, (what, curv[j], fx["curv_error_max"][k])
+        e = fx.ends(k)
+        if e["fix_s"]:
+            assert abs(al[j][0]) <= engine.FIX_HALF_WIDTH + 1e-12, what
+        if e["fix_e"]:
+            assert abs(al[j][-1]) <= engine.FIX_HALF_WIDTH + 1e-12, what
+        if n_active:
+            assert info[j]["n_active_kappa"] == fx["n_active_kappa"][k], (what, info[j]["n_active_kappa"], fx["n_active_kappa"][k])
+        w = worst.setdefault(fx.family(k), [0.0, 0.0, 0.0])
+        if d > w[0]:
+            worst[fx.family(k)] = [d, g, float(fx["alpha_spread"][k])]
+    return worst
+
+
+def worst_report(title, worst):
+    return "%s: worst |alpha - oracle| per family (guard, spread): %s" % (title, ", ".join(
+        "%s %.1e (%.1e, %.1e)" % (f, *w) for f, w in sorted(worst.items())))

@@ -1,10 +1,13 @@
 """Open chains (opt_min_curv(..., closed=False, psi_s, psi_e, fix_s, fix_e), calc_splines(path, psi_s=, psi_e=)) without a GPU: the host
 spline path against the dense open solve of tests/open_ref.py, the open-matrix scalings, and the UNCHANGED kernel sources on the SIMT
 interpreter (tests/emu) against the dense oracle."""
+import os
+
 import numpy as np
 import pytest
 
 import open_ref
+from conftest import GOLDEN_DIR
 from global_racetrajectory_optimization_amd import engine
 from global_racetrajectory_optimization_amd.trajectory_planning_helpers import calc_splines as cs
 
@@ -16,25 +19,8 @@ def emu(emu_lib):
     eng.close()
 
 
-def _path(n, seed, step=1.5):
-    rng = np.random.default_rng(seed)
-    t = np.linspace(0.0, 1.0, n)
-    L = step * (n - 1)
-    x = L * t + rng.uniform(-0.1, 0.1, n) * step
-    y = 0.08 * L * np.sin(3 * np.pi * t * rng.uniform(0.5, 1.5)) + 0.02 * L * np.cos(7 * t)
-    return np.column_stack((x, y))
-
-
-def _chain(n, seed, w=(2.5, 4.0)):
-    """Reference line, normals (the open spline's, last one repeated), dense A, end headings near the line's own."""
-    rng = np.random.default_rng(seed + 1000)
-    xy = _path(n, seed)
-    psi_s = float(np.arctan2(xy[1, 1] - xy[0, 1], xy[1, 0] - xy[0, 0]) - np.pi / 2 + 0.05)
-    psi_e = float(np.arctan2(xy[-1, 1] - xy[-2, 1], xy[-1, 0] - xy[-2, 0]) - np.pi / 2 - 0.03)
-    _, _, A, nv = open_ref.calc_splines_open(xy, psi_s=psi_s, psi_e=psi_e)
-    nv = np.vstack((nv, nv[-1]))
-    ref = np.column_stack((xy, rng.uniform(w[0], w[1], size=(n, 2))))
-    return ref, nv, A, psi_s, psi_e
+_path = open_ref.seeded_path
+_chain = open_ref.seeded_chain
 
 
 def _solve(eng, ref, nv, A, kb, wv, ps, pe, fs=False, fe=False, **kw):
@@ -209,3 +195,60 @@ def test_chain_elimination_in_isolation(kc_emu, n, fused, pinned):
     assert m and m.group(1) == "0" and m.group(2) == "0" and m.group(3) == "0", out
     berr = float(re.search(r"backward error .*: ([0-9.e+-]+)", out).group(1))
     assert berr <= 1e-13, out
+
+
+# ---- the edge fixtures (tests/golden/open_edges.npz, open_kappa_fuzz.npz) on the interpreter: their small members ----------------------
+CONTRACT = 1e-6      # the project's parity contract against the oracle (metres); the guard is the fixture's own (OpenFixture.guard)
+
+
+@pytest.fixture(scope="module")
+def edge_fx():
+    return open_ref.OpenFixture(os.path.join(GOLDEN_DIR, "open_edges.npz"))
+
+
+def _fx_solve(eng, fx, ks, **kw):
+    return eng.solve_batch([fx.problem(k) for k in ks], ends=[fx.ends(k) for k in ks], **kw)
+
+
+def test_edge_ladder_against_fixture(emu, edge_fx):
+    """The ladder's n = 3 .. 73 (box only, both ends pinned, curvature rows active), the ragged chain n = 49 and the narrow end in one
+    ragged launch: statuses as stored, contract + guard (max(1e-8, 4 x the fixture's alpha spread))."""
+    ks = edge_fx.select(lambda k: edge_fx.family(k) != "stadium" and edge_fx.n(k) <= 129)
+    assert {edge_fx.n(k) for k in ks} >= {3, 4, 5, 16, 47, 48, 49, 63, 64, 65, 71, 72, 73}
+    al, curv, st, info = _fx_solve(emu, edge_fx, ks)
+    print(open_ref.worst_report("interpreter ladder", open_ref.check_fixture_results(edge_fx, ks, al, curv, st, info, CONTRACT, 1e-9, {})))
+
+
+def test_edge_reversal_symmetry(emu, edge_fx):
+    """Each ladder length n = 4 .. 73 and its mirror in one launch, one case per length in turn (box only, both ends pinned, curvature rows:
+    the interpreter runs a solve in about a second): -alpha'[::-1] is alpha within max(guard, 10 x the oracle's own reversal gap); the
+    curvature errors agree within 1e-9."""
+    ns = sorted({edge_fx.n(k) for k in range(len(edge_fx)) if edge_fx.family(k) == "ladder" and 4 <= edge_fx.n(k) <= 73})
+    ks = edge_fx.select(lambda k: edge_fx.family(k) == "ladder" and edge_fx.n(k) in ns and edge_fx["status_ref"][k] == 0
+                        and edge_fx.case(k) == "abc"[ns.index(edge_fx.n(k)) % 3])
+    assert len(ks) == len(ns)
+    probs, ends = [], []
+    for k in ks:
+        mp, me = edge_fx.mirrored(k)
+        probs += [edge_fx.problem(k), mp]
+        ends += [edge_fx.ends(k), me]
+    al, curv, st, _ = emu.solve_batch(probs, ends=ends)
+    assert np.all(st == 0), list(st)
+    for j, k in enumerate(ks):
+        d = float(np.max(np.abs(-al[2 * j + 1][::-1] - al[2 * j])))
+        tol = max(edge_fx.guard(k), 10.0 * float(edge_fx["rev_gap"][k]))
+        assert d < tol, (edge_fx.n(k), edge_fx.case(k), d, tol)
+        assert abs(curv[2 * j + 1] - curv[2 * j]) < 1e-9, (edge_fx.n(k), edge_fx.case(k))
+
+
+def test_kappa_fuzz_sample_against_fixture(emu):
+    """Ten of the curvature-tight chain fuzz problems (the smallest; three of them the dense GI's "inconsistent"): status 0 /
+    MCQ_KAPPA_INFEASIBLE as stored, contract + guard, the active curvature rows.  (The GPU suite runs all 120.)"""
+    fx = open_ref.OpenFixture(os.path.join(GOLDEN_DIR, "open_kappa_fuzz.npz"))
+    by_n = sorted(range(len(fx)), key=lambda k: (fx.n(k), k))
+    bad = [k for k in by_n if fx["status_ref"][k] == 5][:3]
+    ks = sorted(bad + [k for k in by_n if fx["status_ref"][k] == 0][:10 - len(bad)])
+    assert len(bad) == 3 and len(ks) == 10
+    al, curv, st, info = _fx_solve(emu, fx, ks)
+    print(open_ref.worst_report("interpreter fuzz", open_ref.check_fixture_results(fx, ks, al, curv, st, info, CONTRACT, 1e-9, {},
+                                                                                   n_active=True)))
