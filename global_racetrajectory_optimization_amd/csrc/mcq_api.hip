@@ -1163,7 +1163,8 @@ static int host_slices(int batch, const mcq_opts& o)
     // problem of slice k on its stream: 600 curvature-tight long rings then take 76 s instead of 45 (docs/NOTEBOOK.md R6.5).  $MCQ_HOST_SLICES: 2 .. 8
     int nsl = 2;
     if (const char* e = getenv("MCQ_HOST_SLICES")) nsl = std::min(std::max(atoi(e), 2), 8);
-    return (batch >= slice_min && o.objective == MCQ_OBJ_MIN_CURV && o.algorithm != MCQ_ALG_GI && !getenv("MCQ_HOST_ONE_LAUNCH")) ? nsl : 1;
+    nsl = std::min(nsl, batch);        // (a slice per problem at most: eight slices of a batch of four to seven had empty ones)
+    return (nsl > 1 && batch >= slice_min && o.objective == MCQ_OBJ_MIN_CURV && o.algorithm != MCQ_ALG_GI && !getenv("MCQ_HOST_ONE_LAUNCH")) ? nsl : 1;
 }
 // the compute stream of slice k: the handle's two, in turn.  (Tried, round 6: a stream per slice -- 14.0 ms where two streams give 11.5 for four
 // slices of 256 problems, and the 600 curvature-tight long rings 105 s where the one launch takes 45: more than two queues of large workgroups
@@ -1239,6 +1240,7 @@ extern "C" int mcq_solve_host(mcq_handle* h, int batch, int n, const double* ref
         h->timing_valid = false;
         for (int k = 0; k < nsl; ++k) {
             const int b0 = (int)((long long)batch * k / nsl), b1 = (int)((long long)batch * (k + 1) / nsl);
+            if (b1 == b0) continue;            // (none with nsl <= batch; a grid of 0 workgroups is a launch error)
             const size_t off = (size_t)b0 * n, cnt = (size_t)(b1 - b0) * n;
             HIP_TRY_SLICE(hipMemcpyAsync(h->d_ref + off * 4, reftrack + off * 4, cnt * 4 * sizeof(double), hipMemcpyHostToDevice, h->cs_in));
             if (normvec) HIP_TRY_SLICE(hipMemcpyAsync(h->d_nv + off * 2, normvec + off * 2, cnt * 2 * sizeof(double), hipMemcpyHostToDevice, h->cs_in));
@@ -1869,6 +1871,7 @@ static int solve_batch_impl(mcq_handle* h, const mcq_problem* probs, const mcq_e
         PinLayout* Pp = &P;
         rc = pack_and_upload(h, probs, batch, nmax, any_sc, probs[0].normvec != nullptr, 0, P, "mcq_solve_batch", nsl,
                              [&](int k, int b0, int b1) -> int {
+                                 if (b1 == b0) return 0;        // (as in mcq_solve_host)
                                  HIP_TRY_SLICE(hipEventRecord(h->ev_slice[k], h->cs_in));
                                  hipStream_t st = slice_stream(h, k);
                                  HIP_TRY_SLICE(hipStreamWaitEvent(st, h->ev_slice[k], 0));

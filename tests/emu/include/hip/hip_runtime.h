@@ -379,7 +379,7 @@ inline void __threadfence() {}
 
 // ---- host runtime subset -------------------------------------------------------------------------------------------
 typedef int hipError_t;
-enum { hipSuccess = 0, hipErrorInvalidValue = 1 };
+enum { hipSuccess = 0, hipErrorInvalidValue = 1, hipErrorInvalidConfiguration = 9 };
 typedef void* hipStream_t;
 struct hipemu_event { double t; };
 typedef hipemu_event* hipEvent_t;
@@ -387,7 +387,9 @@ enum hipMemcpyKind { hipMemcpyHostToDevice, hipMemcpyDeviceToHost, hipMemcpyDevi
 enum hipFuncAttribute { hipFuncAttributeMaxDynamicSharedMemorySize };
 
 inline const char* hipGetErrorString(hipError_t) { return "hipemu error"; }
-inline hipError_t hipGetLastError() { return hipSuccess; }
+/* the launch error the runtime keeps until hipGetLastError reads it: a grid with no workgroups is refused, as the HIP runtime refuses it */
+inline hipError_t& hipemu_last_error_() { static hipError_t e = hipSuccess; return e; }
+inline hipError_t hipGetLastError() { const hipError_t e = hipemu_last_error_(); hipemu_last_error_() = hipSuccess; return e; }
 inline hipError_t hipGetDeviceCount(int* n) { *n = 1; return hipSuccess; }
 inline hipError_t hipSetDevice(int) { return hipSuccess; }
 inline hipError_t hipStreamCreate(hipStream_t* s) { *s = (void*)1; return hipSuccess; }
@@ -449,6 +451,7 @@ inline hipError_t hipEventElapsedTime(float* ms, hipEvent_t a, hipEvent_t b) { *
 template <typename K, typename... Args>
 inline void hipLaunchKernelGGL(K kernel, dim3 grid, dim3 block, size_t smem, hipStream_t, Args... args)
 {
+    if (grid.x == 0 || grid.y == 0 || grid.z == 0) { hipemu_last_error_() = hipErrorInvalidConfiguration; return; }
     hipemu::bdim() = {block.x, block.y, block.z};
     hipemu::gdim() = {grid.x, grid.y, grid.z};
     for (unsigned by = 0; by < grid.y; ++by)

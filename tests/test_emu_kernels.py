@@ -764,6 +764,44 @@ def test_solve_host_in_slices_is_bitwise_the_one_launch(emu, monkeypatch):
     assert [i["ipm_iters"] for i in i_sl] == [i["ipm_iters"] for i in i_one]
 
 
+def _slice_clamp_batches():
+    """Batches of 4, 5 and 7 small rings (distinct widths): fewer problems than the eight slices $MCQ_HOST_SLICES allows."""
+    n = 22
+    base = [_small_track(n, seed=500 + k) for k in range(3)]
+    rng = np.random.default_rng(13)
+    out = []
+    for bsz in (4, 5, 7):
+        refs = np.stack([base[k % 3][0] for k in range(bsz)])
+        refs[:, :, 2:] += rng.uniform(0.0, 0.8, size=(bsz, n, 2))
+        out.append((refs, np.stack([base[k % 3][1] for k in range(bsz)]), np.stack([base[k % 3][3] for k in range(bsz)])))
+    return out
+
+
+def check_slice_count_clamped_to_the_batch(eng, monkeypatch):
+    """$MCQ_HOST_SLICES = 8 with $MCQ_HOST_SLICE_MIN = 4: batches of 4, 5 and 7 problems through mcq_solve_host and mcq_solve_batch take at
+    most one slice per problem (an empty slice was a launch of 0 workgroups: MCQ_E_DEVICE) and return the one launch's answer bit for bit."""
+    monkeypatch.setenv("MCQ_HOST_SLICE_MIN", "4")
+    monkeypatch.setenv("MCQ_HOST_SLICES", "8")
+    for refs, nvs, scs in _slice_clamp_batches():
+        monkeypatch.delenv("MCQ_HOST_ONE_LAUNCH", raising=False)
+        al, cu, st, info = eng.solve_host(refs, nvs, scs, 0.5, 2.0)
+        probs = [dict(reftrack=refs[k], normvec=nvs[k], scaling=scs[k], kappa_bound=0.5, w_veh=2.0) for k in range(len(refs))]
+        a_b, c_b, s_b, _ = eng.solve_batch(probs)
+        monkeypatch.setenv("MCQ_HOST_ONE_LAUNCH", "1")
+        al1, cu1, st1, info1 = eng.solve_host(refs, nvs, scs, 0.5, 2.0)
+        a_b1, c_b1, s_b1, _ = eng.solve_batch(probs)
+        assert np.all(st == 0) and np.array_equal(st, st1) and list(s_b) == list(s_b1) == list(st1), len(refs)
+        assert np.array_equal(al, al1) and np.array_equal(cu, cu1), len(refs)
+        assert [i.ipm_iters for i in info] == [i.ipm_iters for i in info1]
+        assert all(np.array_equal(x, y) for x, y in zip(a_b, a_b1)) and np.array_equal(c_b, c_b1), len(refs)
+        assert all(np.array_equal(x, y) for x, y in zip(a_b1, al1))
+    monkeypatch.delenv("MCQ_HOST_ONE_LAUNCH", raising=False)
+
+
+def test_solve_host_slice_count_is_clamped_to_the_batch(emu, monkeypatch):
+    check_slice_count_clamped_to_the_batch(emu, monkeypatch)
+
+
 def test_uniform_pinned_batches_skip_the_packing_pass(emu, golden, monkeypatch):
     """Round 6: a uniform batch whose arrays lie in page-locked memory as one contiguous block each (rows of engine.host_array blocks; what a batch
     service keeps between calls) is uploaded straight from there -- one strided copy per array, rows of n waypoints into rows of nmax -- instead

@@ -8,11 +8,21 @@ import os
 import numpy as np
 import pytest
 
+import ring_guard
 from global_racetrajectory_optimization_amd import engine, synthetic
+from ring_guard import dmax, guard
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ALPHA_TOL = 1e-6        # north_star's fp64 tolerance against quadprog
+ALPHA_TOL = 1e-6        # north_star's fp64 tolerance against quadprog (the contract)
+GUARD = ring_guard.FIXED    # the guard against the live dense oracle (the stadiums) and between two GPU paths
+WORST = ring_guard.Worst()
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _worst_report(request):
+    yield
+    ring_guard.print_uncaptured(request.config, WORST.report("test_gpu_gi"))
 
 
 def _stadium_cases():
@@ -46,12 +56,14 @@ def test_gi_mode_reference_tracks_and_stadiums(gpu_engine, golden, stadiums):
     assert np.all(st == 0), st
     for k, t in enumerate(names):
         assert np.max(np.abs(al[k] - golden[t]["alpha"])) < 2e-8, (t, float(np.max(np.abs(al[k] - golden[t]["alpha"]))))
+        assert WORST.add("GI mode", dmax(al[k], golden[t]["alpha"]), guard(t)) < guard(t), t                   # guard
         assert abs(curv[k] - float(golden[t]["curv_error_max"])) < 1e-9
         assert info[k]["second_attempt"] & 4 and info[k]["gi_iters"] > 0 and info[k]["ipm_iters"] == 0
     for k, (a_ref, err_ref, nk) in enumerate(want):
         i = info[len(names) + k]
         assert i["n_active_kappa"] == nk, (i["n_active_kappa"], nk)
-        assert np.max(np.abs(al[len(names) + k] - a_ref)) < ALPHA_TOL and abs(curv[len(names) + k] - err_ref) < 1e-9
+        assert np.max(np.abs(al[len(names) + k] - a_ref)) < ALPHA_TOL and abs(curv[len(names) + k] - err_ref) < 1e-9   # contract
+        assert WORST.add("stadiums", dmax(al[len(names) + k], a_ref), GUARD) < GUARD, (k, dmax(al[len(names) + k], a_ref))   # guard
     print("GI mode: steps %s, ms per problem %s, polish rejected %s, max |alpha - oracle| %s" % (
         [i["gi_iters"] for i in info], ["%.1f" % (i["ticks"][3] / 1e5) for i in info], [bool(i["second_attempt"] & 8) for i in info],
         ["%.1e" % float(np.max(np.abs(al[k] - (golden[names[k]]["alpha"] if k < 4 else want[k - 4][0])))) for k in range(len(al))]))
@@ -80,7 +92,8 @@ def test_arithmetic_variants_on_the_stadium(stadiums):
         assert np.all(st == 0), (name, st)
         for k, (a_ref, err_ref, nk) in enumerate(want):
             d = float(np.max(np.abs(al[k] - a_ref)))
-            assert d < ALPHA_TOL, (name, k, d)
+            assert d < ALPHA_TOL, (name, k, d)                                                         # contract
+            assert WORST.add("variant builds", d, GUARD) < GUARD, (name, k, d)                        # guard
             assert abs(curv[k] - err_ref) < 1e-9 and info[k]["n_active_kappa"] == nk, (name, k)
         report[name] = [(i["as_iters"], i["gi_iters"]) for i in info]
     print("stadium 360 / 720, (block-pivoting rounds, Goldfarb-Idnani steps) per build:", report)
@@ -107,7 +120,8 @@ def test_curvature_tight_fuzz_against_dense_gi(gpu_engine):
             continue
         d = float(np.max(np.abs(al[k] - z["alpha"][off[k]:off[k + 1]])))
         worst = max(worst, d)
-        assert d < ALPHA_TOL, (k, d)
+        assert d < ALPHA_TOL, (k, d)                                                                   # contract
+        assert WORST.add("kappa fuzz", d, guard("kappa_tight_fuzz", k)) < guard("kappa_tight_fuzz", k), (k, d, guard("kappa_tight_fuzz", k))   # guard
         assert abs(curv[k] - float(z["curv_error_max"][k])) < 1e-8, k
         assert info[k]["n_active_kappa"] == int(z["n_active_kappa"][k]), (k, info[k]["n_active_kappa"], int(z["n_active_kappa"][k]))
     ran = [k for k in range(nprob) if info[k]["second_attempt"] & 4]
@@ -123,7 +137,11 @@ def test_curvature_tight_fuzz_against_dense_gi(gpu_engine):
     al2, curv2, st2, info2 = gpu_engine.solve_batch(probs, algorithm=engine.ALG_GI)
     assert np.array_equal(np.asarray(st2), np.where(st_ref == 0, 0, engine.STATUS_KAPPA_INFEASIBLE))
     w2 = max(float(np.max(np.abs(al2[k] - z["alpha"][off[k]:off[k + 1]]))) for k in range(nprob) if st_ref[k] == 0)
-    assert w2 < ALPHA_TOL, w2
+    assert w2 < ALPHA_TOL, w2                                                                          # contract
+    for k in range(nprob):
+        if st_ref[k] == 0:
+            d = WORST.add("kappa fuzz, GI mode", dmax(al2[k], z["alpha"][off[k]:off[k + 1]]), guard("kappa_tight_fuzz", k))
+            assert d < guard("kappa_tight_fuzz", k), (k, d, guard("kappa_tight_fuzz", k))                # guard
     print("the same through the Goldfarb-Idnani path alone: max |alpha - dense GI| %.2e m, steps mean %.0f max %d" % (
         w2, float(np.mean([i["gi_iters"] for i in info2])), max(i["gi_iters"] for i in info2)))
 
@@ -142,19 +160,24 @@ def test_long_rings_against_dense_goldens(gpu_engine):
     al, curv, st, info = gpu_engine.solve_batch(probs)
     assert np.all(st == 0), st
     d = [float(np.max(np.abs(al[k] - gs[k]["alpha"]))) for k in range(3)]
-    assert max(d) < ALPHA_TOL, d
+    assert max(d) < ALPHA_TOL, d                                                                       # contract
+    for k, t in enumerate(names):
+        assert WORST.add("long rings", d[k], guard(t)) < guard(t), (t, d[k], guard(t))                 # guard
     assert max(abs(curv[k] - float(gs[k]["curv_error_max"])) for k in range(3)) < 1e-9
     assert info[2]["n_active_kappa"] >= 3 and abs(info[2]["kappa_max"] - float(gs[2]["kappa_bound"])) < 1e-10
     # the same three through the Goldfarb-Idnani path alone (its solves and E / E' on the long-ring route)
     al2, curv2, st2, info2 = gpu_engine.solve_batch(probs, algorithm=engine.ALG_GI)
     assert np.all(st2 == 0), st2
     d2 = [float(np.max(np.abs(al2[k] - gs[k]["alpha"]))) for k in range(3)]
-    assert max(d2) < ALPHA_TOL, d2
+    assert max(d2) < ALPHA_TOL, d2                                                                     # contract
+    for k, t in enumerate(names):
+        assert WORST.add("long rings, GI mode", d2[k], guard(t)) < guard(t), (t, d2[k], guard(t))      # guard
     g = load_golden("shortest_path_n2100")
     al3, _, st3, _ = gpu_engine.solve_batch([dict(reftrack=g["reftrack"], normvec=g["normvec"], scaling=None, kappa_bound=1.0, w_veh=float(g["w_veh"]))],
                                             objective=engine.OBJ_SHORTEST_PATH)
     d3 = float(np.max(np.abs(al3[0] - g["alpha"])))
-    assert st3[0] == 0 and d3 < ALPHA_TOL, (st3[0], d3)
+    assert st3[0] == 0 and d3 < ALPHA_TOL, (st3[0], d3)                                                # contract
+    assert WORST.add("shortest path", d3, guard("shortest_path_n2100")) < guard("shortest_path_n2100"), d3   # guard
     print("rings above 2048 waypoints, max |alpha - dense oracle|: default path %s, Goldfarb-Idnani path %s (steps %s), shortest path %.1e" % (
         ["%.1e" % v for v in d], ["%.1e" % v for v in d2], [i["gi_iters"] for i in info2], d3))
 
@@ -177,7 +200,10 @@ def test_gi_mode_on_every_full_size_golden(gpu_engine):
     assert np.all(st0 == 0)
     d = [float(np.max(np.abs(al[k] - gs[k]["alpha"]))) for k in range(len(names))]
     d0 = [float(np.max(np.abs(al[k] - al0[k]))) for k in range(len(names))]
-    assert max(d) < ALPHA_TOL and max(d0) < ALPHA_TOL, (dict(zip(names, d)), dict(zip(names, d0)))
+    assert max(d) < ALPHA_TOL and max(d0) < ALPHA_TOL, (dict(zip(names, d)), dict(zip(names, d0)))    # contract
+    for k, t in enumerate(names):
+        assert WORST.add("GI mode", d[k], guard(t)) < guard(t), (t, d[k], guard(t))                    # guard
+        assert WORST.add("GI mode vs default path", d0[k], GUARD) < GUARD, (t, d0[k])                  # guard
     for k, g in enumerate(gs):
         assert abs(curv[k] - float(g["curv_error_max"])) < 1e-8, names[k]
         assert info[k]["n_active_box"] == info0[k]["n_active_box"] and info[k]["n_active_kappa"] == info0[k]["n_active_kappa"], names[k]

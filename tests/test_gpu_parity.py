@@ -3,13 +3,23 @@ vectors and the CPU oracle.  Tolerance (north_star): |alpha_gpu - alpha_oracle| 
 import numpy as np
 import pytest
 
+import ring_guard
 from global_racetrajectory_optimization_amd import engine, synthetic
 from global_racetrajectory_optimization_amd import trajectory_planning_helpers as tph
+from ring_guard import dmax, guard
 
 pytestmark = pytest.mark.gpu
 
-ALPHA_TOL = 1e-6        # metres, stated fp64 tolerance of BASELINE.json's north_star
+ALPHA_TOL = 1e-6        # metres, stated fp64 tolerance of BASELINE.json's north_star (the contract)
 CURV_TOL = 1e-9
+GUARD = ring_guard.FIXED    # the guard where no stored fixture exists: the live dense oracle, CPU-B, two GPU paths at the same vertex
+WORST = ring_guard.Worst()
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _worst_report(request):
+    yield
+    ring_guard.print_uncaptured(request.config, WORST.report("test_gpu_parity"))
 
 
 def _problem(g):
@@ -23,7 +33,8 @@ def test_reference_tracks_match_golden(gpu_engine, golden):
     for k, name in enumerate(names):
         g = golden[name]
         assert st[k] == 0, (name, st[k])
-        assert np.max(np.abs(al[k] - g["alpha"])) < ALPHA_TOL, name
+        assert np.max(np.abs(al[k] - g["alpha"])) < ALPHA_TOL, name                                    # contract
+        assert WORST.add("reference tracks", dmax(al[k], g["alpha"]), guard(name)) < guard(name), name    # guard
         assert abs(curv[k] - float(g["curv_error_max"])) < CURV_TOL, name
         assert info[k]["kkt_res"] < 1e-9
         lo, hi = -(g["reftrack"][:, 3] - 1.7), g["reftrack"][:, 2] - 1.7
@@ -42,14 +53,16 @@ def test_berlin_n333(gpu_engine):
     assert ref.shape == (333, 4)
     al, curv, st, info = gpu_engine.solve_batch([dict(reftrack=ref, normvec=g["normvec"], scaling=g["scaling"], kappa_bound=0.12, w_veh=3.4)])
     assert st[0] == 0 and info[0]["kkt_res"] < 1e-9
-    assert np.max(np.abs(al[0] - g["alpha"])) < ALPHA_TOL
+    assert np.max(np.abs(al[0] - g["alpha"])) < ALPHA_TOL                                                        # contract
+    assert WORST.add("berlin n333", dmax(al[0], g["alpha"]), guard("berlin_2018_n333")) < guard("berlin_2018_n333")   # guard
     assert abs(curv[0] - float(g["curv_error_max"])) < CURV_TOL
     path_cl = np.vstack((ref[:, :2], ref[0, :2]))
     _, _, A, nv = tph_ref.calc_splines(path_cl)
     assert np.max(np.abs(nv - g["normvec"])) < 1e-12
     a_ref, err_ref = tph_ref.opt_min_curv(ref, nv, A, 0.12, 3.4)
     a, err = tph.opt_min_curv.opt_min_curv(ref, nv, A, 0.12, 3.4)
-    assert np.max(np.abs(a - a_ref)) < ALPHA_TOL and np.max(np.abs(a_ref - g["alpha"])) < 1e-9
+    assert np.max(np.abs(a - a_ref)) < ALPHA_TOL and np.max(np.abs(a_ref - g["alpha"])) < 1e-9             # contract
+    assert WORST.add("live oracle", dmax(a, a_ref), GUARD) < GUARD                                              # guard
     assert abs(err - err_ref) < CURV_TOL
 
 
@@ -75,8 +88,11 @@ def test_iqp_handler_reference_default_flow_berlin_modena(gpu_engine, golden):
             assert stt["rounds"] == len(q["iqp_n"])
         for a, ref_out, nv_out in outs:
             assert a.shape == q["iqp_alpha"].shape == (int(q["iqp_n"][-1]),), name
-            assert np.max(np.abs(a - q["iqp_alpha"])) < ALPHA_TOL, (name, float(np.max(np.abs(a - q["iqp_alpha"]))))
+            assert np.max(np.abs(a - q["iqp_alpha"])) < ALPHA_TOL, (name, float(np.max(np.abs(a - q["iqp_alpha"]))))    # contract
             assert np.max(np.abs(ref_out - q["iqp_reftrack"])) < 1e-6, name
+            g_a, g_r = guard(name + "_iqp", what="iqp_alpha"), guard(name + "_iqp", what="iqp_reftrack")
+            assert WORST.add("iqp end states", dmax(a, q["iqp_alpha"]), g_a) < g_a, (name, dmax(a, q["iqp_alpha"]), g_a)   # guard
+            assert dmax(ref_out, q["iqp_reftrack"]) < g_r, (name, dmax(ref_out, q["iqp_reftrack"]), g_r)                # guard
             assert np.max(np.abs(nv_out - q["iqp_normvec"])) < 1e-8, name
         # the trace the engine keeps per round (what print_debug prints) against the oracle's
         res = gpu_engine.iqp_batch(trk, 0.12, 3.4, 3.0, iters_min=3, curv_error_allowed=0.01)
@@ -92,7 +108,8 @@ def test_drop_in_opt_min_curv_signature(golden):
     _, _, A, nv = tph.calc_splines.calc_splines(path=path_cl)
     out = tph.opt_min_curv.opt_min_curv(reftrack=ref, normvectors=nv, A=A, kappa_bound=0.12, w_veh=3.4,
                                         print_debug=False, plot_debug=False)
-    assert np.max(np.abs(out[0] - g["alpha"])) < ALPHA_TOL
+    assert np.max(np.abs(out[0] - g["alpha"])) < ALPHA_TOL                                                         # contract
+    assert WORST.add("reference tracks", dmax(out[0], g["alpha"]), guard("handling_track")) < guard("handling_track")   # guard
     assert abs(out[1] - float(g["curv_error_max"])) < CURV_TOL
 
 
@@ -106,9 +123,12 @@ def test_iqp_handler_matches_golden(golden):
                                                          print_debug=False, plot_debug=False, stepsize_interp=3.0,
                                                          iters_min=3, curv_error_allowed=0.01)
         assert a.shape == g["iqp_alpha"].shape
-        assert np.max(np.abs(a - g["iqp_alpha"])) < ALPHA_TOL
+        assert np.max(np.abs(a - g["iqp_alpha"])) < ALPHA_TOL                                                       # contract
         assert np.max(np.abs(ref_out - g["iqp_reftrack"])) < 1e-6
         assert np.max(np.abs(nv_out - g["iqp_normvec"])) < 1e-8
+        g_a, g_r = guard(name, what="iqp_alpha"), guard(name, what="iqp_reftrack")
+        assert WORST.add("iqp end states", dmax(a, g["iqp_alpha"]), g_a) < g_a, name                                # guard
+        assert dmax(ref_out, g["iqp_reftrack"]) < g_r, name                                                         # guard
 
 
 def test_errors_match_reference_exceptions(golden):
@@ -154,8 +174,10 @@ def test_full_size_oval_properties(gpu_engine):
     pm = dict(reftrack=refm, normvec=nvm, scaling=sc[0], kappa_bound=0.12, w_veh=3.4)
     al3, _, st3, _ = gpu_engine.solve_batch([pr, pm])
     assert np.all(st3 == 0)
-    assert np.max(np.abs(np.roll(al3[0], -r) - al[0])) < ALPHA_TOL
-    assert np.max(np.abs(al3[1] + al[0])) < ALPHA_TOL
+    assert np.max(np.abs(np.roll(al3[0], -r) - al[0])) < ALPHA_TOL                                   # contract
+    assert np.max(np.abs(al3[1] + al[0])) < ALPHA_TOL                                                # contract
+    assert WORST.add("two GPU paths", dmax(np.roll(al3[0], -r), al[0]), GUARD) < GUARD               # guard: rotation by whole waypoints
+    # (the mirror negates the normals' x and the track's y: transformed input bits, like the similarity invariances below -- contract only)
 
 
 def test_full_size_similarity_invariances(gpu_engine):
@@ -208,12 +230,14 @@ def test_long_ring_general_path_properties(gpu_engine):
         lo, hi = -(ref[b, :, 3] - 1.7), ref[b, :, 2] - 1.7
         assert np.all(al[b] >= lo - 1e-12) and np.all(al[b] <= hi + 1e-12)
         assert np.max(np.abs(al[b] - a_cpu[b])) < 1e-7 and abs(curv[b] - c_cpu[b]) < 1e-8
+        assert WORST.add("CPU-B", dmax(al[b], a_cpu[b]), GUARD) < GUARD, (b, dmax(al[b], a_cpu[b]))        # guard
         assert info[b]["kkt_res"] < 5e-9 and 0 < info[b]["n_active_box"] < 3000
     r = 777
     pr = dict(reftrack=np.roll(ref[0], r, axis=0), normvec=np.roll(nv[0], r, axis=0), scaling=np.roll(sc[0], r),
               kappa_bound=0.12, w_veh=3.4)
     al2, _, st2, _ = gpu_engine.solve_batch([pr])
-    assert st2[0] == 0 and np.max(np.abs(np.roll(al2[0], -r) - al[0])) < ALPHA_TOL
+    assert st2[0] == 0 and np.max(np.abs(np.roll(al2[0], -r) - al[0])) < ALPHA_TOL                  # contract
+    assert WORST.add("two GPU paths", dmax(np.roll(al2[0], -r), al[0]), GUARD) < GUARD               # guard: rotation by whole waypoints
 
 
 def test_very_long_rings_run_with_few_or_no_goldfarb_idnani_slots(monkeypatch):
@@ -237,6 +261,7 @@ def test_very_long_rings_run_with_few_or_no_goldfarb_idnani_slots(monkeypatch):
             assert st[0] == 0, (n, st[0], info[0])
             a_cpu, c_cpu, st_cpu, _, _ = banded_ref.solve_batch(ref[None], nv[None], sc[None], 0.12, 3.4)
             assert st_cpu[0] == 0 and np.max(np.abs(al[0] - a_cpu[0])) < 1e-7 and abs(curv[0] - c_cpu[0]) < 1e-8, (n, float(np.max(np.abs(al[0] - a_cpu[0]))))
+            assert WORST.add("CPU-B", dmax(al[0], a_cpu[0]), GUARD) < GUARD, (n, dmax(al[0], a_cpu[0]))              # guard
             assert 0 < info[0]["n_active_box"] < n and info[0]["gi_iters"] == 0
             print("ring of %d waypoints: max |alpha - CPU-B| %.1e m, %d active rows, workspace %.2f GB" % (
                 n, float(np.max(np.abs(al[0] - a_cpu[0]))), info[0]["n_active_box"], eng.workspace_bytes() / 1e9))
@@ -255,7 +280,8 @@ def test_oval_n1000_against_dense_gi_oracle(gpu_engine):
     al, curv, st, _ = gpu_engine.solve_batch([dict(reftrack=ref[0], normvec=nv_d, scaling=sc[0], kappa_bound=0.12,
                                                    w_veh=3.4)])
     assert st[0] == 0
-    assert np.max(np.abs(al[0] - a_ref)) < ALPHA_TOL
+    assert np.max(np.abs(al[0] - a_ref)) < ALPHA_TOL                                                 # contract
+    assert WORST.add("live oracle", dmax(al[0], a_ref), GUARD) < GUARD                               # guard
     assert abs(curv[0] - err_ref) < CURV_TOL
     assert qp_ref is not None
 
@@ -353,7 +379,8 @@ def test_random_rings_against_dense_oracle(gpu_engine):
     for k, (a_ref, err_ref) in enumerate(refs):
         assert st[k] == 0, (k, st[k])
         worst = max(worst, float(np.max(np.abs(al[k] - a_ref))))
-        assert np.max(np.abs(al[k] - a_ref)) < ALPHA_TOL, (k, info[k])
+        assert np.max(np.abs(al[k] - a_ref)) < ALPHA_TOL, (k, info[k])                               # contract
+        assert WORST.add("live oracle", dmax(al[k], a_ref), GUARD) < GUARD, (k, dmax(al[k], a_ref))  # guard
         assert abs(curv[k] - err_ref) < CURV_TOL, k
     print("random rings: max |alpha - oracle| = %.2e m, active rows %d ... %d, pivoting rounds <= %d"
           % (worst, min(i["n_active_box"] for i in info), max(i["n_active_box"] for i in info), max(i["as_iters"] for i in info)))
@@ -377,9 +404,11 @@ def test_ragged_batch_and_small_rings(gpu_engine, golden):
     al, curv, st, _ = gpu_engine.solve_batch(probs)
     assert np.all(st == 0)
     for k, (a_ref, err_ref) in enumerate(refs):
-        assert np.max(np.abs(al[k] - a_ref)) < ALPHA_TOL
+        assert np.max(np.abs(al[k] - a_ref)) < ALPHA_TOL                                             # contract
+        assert WORST.add("live oracle", dmax(al[k], a_ref), GUARD) < GUARD, k                        # guard
         assert abs(curv[k] - err_ref) < CURV_TOL
-    assert np.max(np.abs(al[-1] - golden["handling_track"]["alpha"])) < ALPHA_TOL
+    assert np.max(np.abs(al[-1] - golden["handling_track"]["alpha"])) < ALPHA_TOL                    # contract
+    assert dmax(al[-1], golden["handling_track"]["alpha"]) < guard("handling_track")                 # guard
 
 
 def test_curvature_rows_active_and_infeasible_gpu(gpu_engine):
@@ -404,7 +433,8 @@ def test_curvature_rows_active_and_infeasible_gpu(gpu_engine):
                                                 dict(reftrack=ref, normvec=nv, scaling=sc, kappa_bound=1e-4, w_veh=2.0)])
     assert st[0] == 0 and st[1] == engine.STATUS_KAPPA_INFEASIBLE
     assert inf[0]["n_active_kappa"] == n_act
-    assert np.max(np.abs(al[0] - a_ref)) < ALPHA_TOL
+    assert np.max(np.abs(al[0] - a_ref)) < ALPHA_TOL                                                 # contract
+    assert WORST.add("live oracle", dmax(al[0], a_ref), GUARD) < GUARD                               # guard
     assert abs(curv[0] - err_ref) < CURV_TOL
     with pytest.raises(ValueError, match="inconsistent"):
         tph.opt_min_curv.opt_min_curv(ref, nv, A, 1e-4, 2.0)
@@ -432,7 +462,8 @@ def test_vehicle_width_sweep_mixed_tracks(gpu_engine, golden):
     al, curv, st, info = gpu_engine.solve_batch(probs)
     for k, (a_ref, err_ref) in enumerate(refs):
         assert st[k] == 0, (k, st[k])
-        assert np.max(np.abs(al[k] - a_ref)) < ALPHA_TOL, k
+        assert np.max(np.abs(al[k] - a_ref)) < ALPHA_TOL, k                                          # contract
+        assert WORST.add("live oracle", dmax(al[k], a_ref), GUARD) < GUARD, (k, dmax(al[k], a_ref))  # guard
         assert abs(curv[k] - err_ref) < CURV_TOL, k
 
 
@@ -494,9 +525,12 @@ def test_iqp_device_resident_matches_golden(gpu_engine, golden):
     for name, (a, ref_out, nv_out) in zip(names, out):
         g = golden[name]
         assert a.shape == g["iqp_alpha"].shape
-        assert np.max(np.abs(a - g["iqp_alpha"])) < ALPHA_TOL
+        assert np.max(np.abs(a - g["iqp_alpha"])) < ALPHA_TOL                                                       # contract
         assert np.max(np.abs(ref_out - g["iqp_reftrack"])) < 1e-6
         assert np.max(np.abs(nv_out - g["iqp_normvec"])) < 1e-8
+        g_a, g_r = guard(name, what="iqp_alpha"), guard(name, what="iqp_reftrack")
+        assert WORST.add("iqp end states", dmax(a, g["iqp_alpha"]), g_a) < g_a, name                                # guard
+        assert dmax(ref_out, g["iqp_reftrack"]) < g_r, name                                                         # guard
 
 
 def test_iqp_device_resident_driver_bulk_round(gpu_engine):
@@ -538,7 +572,8 @@ def test_iqp_warm_start_equals_cold_start_full_size(gpu_engine):
     for (a_w, r_w, n_w), (a_c, r_c, n_c) in zip(*outs):
         assert a_w.shape == a_c.shape
         worst = max(worst, float(np.max(np.abs(a_w - a_c))))
-        assert np.max(np.abs(a_w - a_c)) < ALPHA_TOL and np.max(np.abs(r_w - r_c)) < ALPHA_TOL
+        assert np.max(np.abs(a_w - a_c)) < ALPHA_TOL and np.max(np.abs(r_w - r_c)) < ALPHA_TOL          # contract
+        assert WORST.add("two GPU paths", dmax(a_w, a_c), GUARD) < GUARD and dmax(r_w, r_c) < GUARD      # guard
     print("IQP warm vs cold start, 32 x N=2000: max |alpha| difference %.2e m" % worst)
 
 
@@ -552,7 +587,8 @@ def test_degenerate_iqp_pass_two_attempt_driver(gpu_engine):
     al, curv, st, info = gpu_engine.solve_batch([dict(reftrack=g["reftrack"], normvec=g["normvec"], scaling=None,
                                                       kappa_bound=float(g["kappa_bound"]), w_veh=float(g["w_veh"]))])
     assert st[0] == 0
-    assert np.max(np.abs(al[0] - g["alpha"])) < ALPHA_TOL
+    assert np.max(np.abs(al[0] - g["alpha"])) < ALPHA_TOL                                             # contract
+    assert WORST.add("dense N=2000 goldens", dmax(al[0], g["alpha"]), guard("iqp_pass3_oval3")) < guard("iqp_pass3_oval3")   # guard
     assert abs(curv[0] - float(g["curv_error_max"])) < CURV_TOL
     assert info[0]["kkt_res"] < 1e-9
     assert info[0]["as_iters"] <= 12
@@ -569,7 +605,8 @@ def test_block_pivoting_pins_one_row_per_neighbourhood(gpu_engine):
         al, curv, st, info = gpu_engine.solve_batch([dict(reftrack=g["reftrack"], normvec=g["normvec"], scaling=None,
                                                           kappa_bound=float(g["kappa_bound"]), w_veh=float(g["w_veh"]))])
         assert st[0] == 0
-        assert np.max(np.abs(al[0] - g["alpha"])) < ALPHA_TOL
+        assert np.max(np.abs(al[0] - g["alpha"])) < ALPHA_TOL                                         # contract
+        assert WORST.add("dense N=2000 goldens", dmax(al[0], g["alpha"]), guard(name)) < guard(name), name   # guard
         assert abs(curv[0] - float(g["curv_error_max"])) < CURV_TOL
         assert info[0]["as_iters"] <= 8, (name, info[0]["as_iters"])
 
@@ -588,7 +625,8 @@ def test_prep_on_device_and_solve_without_normals(gpu_engine, golden):
                                               for k in names])
     for k, name in enumerate(names):
         assert st[k] == 0
-        assert np.max(np.abs(al[k] - golden[name]["alpha"])) < ALPHA_TOL, name
+        assert np.max(np.abs(al[k] - golden[name]["alpha"])) < ALPHA_TOL, name                        # contract
+        assert WORST.add("reference tracks", dmax(al[k], golden[name]["alpha"]), guard(name)) < guard(name), name   # guard
         assert abs(curv[k] - float(golden[name]["curv_error_max"])) < CURV_TOL, name
 
 
@@ -743,10 +781,12 @@ def test_pinned_variables_and_bad_input(gpu_engine, golden):
                                               dict(reftrack=bad, normvec=g["normvec"], scaling=g["scaling"], kappa_bound=0.12, w_veh=3.4),
                                               dict(reftrack=g["reftrack"], normvec=g["normvec"], scaling=g["scaling"], kappa_bound=0.12, w_veh=3.4)])
     assert list(st) == [0, engine.STATUS_BAD_INPUT, 0]
-    assert np.max(np.abs(al[0] - a_ref)) < ALPHA_TOL
+    assert np.max(np.abs(al[0] - a_ref)) < ALPHA_TOL                                                 # contract
+    assert WORST.add("live oracle", dmax(al[0], a_ref), GUARD) < GUARD                               # guard
     assert abs(al[0][5] - 0.2) < 1e-12 and abs(al[0][40] + 0.35) < 1e-12
     assert abs(curv[0] - err_ref) < CURV_TOL
-    assert np.max(np.abs(al[2] - g["alpha"])) < ALPHA_TOL
+    assert np.max(np.abs(al[2] - g["alpha"])) < ALPHA_TOL                                            # contract
+    assert dmax(al[2], g["alpha"]) < guard("rounded_rectangle")                                      # guard
 
 
 def _sp_kkt(ref, nv, w_veh, alpha):
@@ -774,7 +814,9 @@ def test_shortest_path_drop_in_matches_golden(golden):
         a = tph.opt_shortest_path.opt_shortest_path(reftrack=g["reftrack"], normvectors=g["normvec"],
                                                     w_veh=float(z["w_veh"]), print_debug=False)
         assert a.shape == (g["reftrack"].shape[0],)
-        assert np.max(np.abs(a - z[name + "_alpha"])) < ALPHA_TOL
+        assert np.max(np.abs(a - z[name + "_alpha"])) < ALPHA_TOL                                     # contract
+        g_sp = guard("shortest_path", what=name + "_alpha")
+        assert WORST.add("shortest path", dmax(a, z[name + "_alpha"]), g_sp) < g_sp, name             # guard
     with pytest.raises(RuntimeError, match="same as normvectors"):
         tph.opt_shortest_path.opt_shortest_path(g["reftrack"], g["normvec"][:-1], 3.4)
 
@@ -800,7 +842,8 @@ def test_shortest_path_full_size_properties_and_oracle(gpu_engine):
     a, _, st1, _ = gpu_engine.solve_batch([dict(reftrack=ref1[0], normvec=nv1[0], scaling=None, kappa_bound=1.0,
                                                 w_veh=3.4)], objective=engine.OBJ_SHORTEST_PATH)
     assert st1[0] == 0
-    assert np.max(np.abs(a[0] - a_ref)) < ALPHA_TOL
+    assert np.max(np.abs(a[0] - a_ref)) < ALPHA_TOL                                                  # contract
+    assert WORST.add("shortest path", dmax(a[0], a_ref), GUARD) < GUARD                              # guard (the live oracle)
     # ragged batch around the switches of the scalar tridiagonal route: one row per thread (n <= 256), partial last blocks, the
     # workspace-vector route (n > 2048)
     sizes = [100, 256, 257, 777, 2048, 2049, 2600, 4100]
@@ -833,7 +876,8 @@ def test_mintime_reopt_corridor_config(gpu_engine, golden):
     n_kappa = 0
     for k, (name, ref, (a_ref, err_ref)) in enumerate(refs):
         assert st[k] == 0, (name, st[k])
-        assert np.max(np.abs(al[k] - a_ref)) < ALPHA_TOL, (name, float(np.max(np.abs(al[k] - a_ref))))
+        assert np.max(np.abs(al[k] - a_ref)) < ALPHA_TOL, (name, float(np.max(np.abs(al[k] - a_ref))))   # contract
+        assert WORST.add("live oracle", dmax(al[k], a_ref), GUARD) < GUARD, (name, dmax(al[k], a_ref))      # guard
         assert abs(curv[k] - err_ref) < CURV_TOL, name
         assert np.all(np.abs(al[k]) <= 0.2 + 1e-12)
         assert info[k]["n_active_box"] == int(np.sum(np.abs(np.abs(a_ref) - 0.2) < 1e-9)), name
@@ -845,7 +889,8 @@ def test_mintime_reopt_corridor_config(gpu_engine, golden):
     A = tph.calc_splines.build_les_matrix(ref.shape[0], g["scaling"])
     a = tph.opt_min_curv.opt_min_curv(reftrack=ref, normvectors=g["normvec"], A=A, kappa_bound=0.12, w_veh=1.6,
                                       print_debug=False, plot_debug=False)[0]
-    assert np.max(np.abs(a - a_ref)) < ALPHA_TOL
+    assert np.max(np.abs(a - a_ref)) < ALPHA_TOL                                                     # contract
+    assert dmax(a, a_ref) < GUARD                                                                    # guard
 
 
 def _golden_n2000():
@@ -868,12 +913,14 @@ def test_oval_n2000_first_pass_against_golden(gpu_engine):
     for prob in (p, dict(p, normvec=None, scaling=None)):
         al, curv, st, info = gpu_engine.solve_batch([prob])
         assert st[0] == 0
-        assert np.max(np.abs(al[0] - g["alpha"])) < ALPHA_TOL, float(np.max(np.abs(al[0] - g["alpha"])))
+        assert np.max(np.abs(al[0] - g["alpha"])) < ALPHA_TOL, float(np.max(np.abs(al[0] - g["alpha"])))       # contract
+        assert WORST.add("dense N=2000 goldens", dmax(al[0], g["alpha"]), guard("oval_n2000")) < guard("oval_n2000"), dmax(al[0], g["alpha"])   # guard
         assert abs(curv[0] - float(g["curv_error_max"])) < CURV_TOL
         assert abs(info[0]["kappa_max"] - float(g["kappa_max"])) < 1e-9
     A = tph.calc_splines.build_les_matrix(2000, g["scaling"])
     a, err = tph.opt_min_curv.opt_min_curv(g["reftrack"], g["normvec"], A, 0.12, 3.4)
-    assert np.max(np.abs(a - g["alpha"])) < ALPHA_TOL and abs(err - float(g["curv_error_max"])) < CURV_TOL
+    assert np.max(np.abs(a - g["alpha"])) < ALPHA_TOL and abs(err - float(g["curv_error_max"])) < CURV_TOL     # contract
+    assert dmax(a, g["alpha"]) < guard("oval_n2000")                                                              # guard
 
 
 def test_oval_n2000_more_width_seeds_and_config5_tracks_against_golden(gpu_engine):
@@ -897,7 +944,8 @@ def test_oval_n2000_more_width_seeds_and_config5_tracks_against_golden(gpu_engin
         for a, c, s in ((al[k], curv[k], st[k]), (al2[k], curv2[k], st2[k])):
             assert s == 0, name
             worst = max(worst, float(np.max(np.abs(a - g["alpha"]))))
-            assert np.max(np.abs(a - g["alpha"])) < ALPHA_TOL, (name, float(np.max(np.abs(a - g["alpha"]))))
+            assert np.max(np.abs(a - g["alpha"])) < ALPHA_TOL, (name, float(np.max(np.abs(a - g["alpha"]))))   # contract
+            assert WORST.add("dense N=2000 goldens", dmax(a, g["alpha"]), guard(name)) < guard(name), (name, dmax(a, g["alpha"]))   # guard
             assert abs(c - float(g["curv_error_max"])) < CURV_TOL, name
     print("N=2000 goldens (2 width seeds, 2 config-5 tracks): max |alpha - dense oracle| = %.2e m" % worst)
 
@@ -920,7 +968,8 @@ def test_round4_dense_goldens_at_bench_size(gpu_engine):
         al, curv, st, info = gpu_engine.solve_batch([dict(reftrack=g["reftrack"], normvec=g["normvec"], scaling=sc, kappa_bound=kb, w_veh=3.4)])
         assert st[0] == 0, (name, st[0])
         worst[name] = float(np.max(np.abs(al[0] - g["alpha"])))
-        assert worst[name] < ALPHA_TOL, (name, worst[name])
+        assert worst[name] < ALPHA_TOL, (name, worst[name])                                           # contract
+        assert WORST.add("dense N=2000 goldens", worst[name], guard(name)) < guard(name), (name, worst[name], guard(name))   # guard
         assert abs(curv[0] - float(g["curv_error_max"])) < CURV_TOL, name
         if name == "oval_n2000_kappa":
             assert info[0]["n_active_kappa"] > 0 and abs(info[0]["kappa_max"] - kb) < 1e-9
@@ -946,9 +995,12 @@ def test_oval_n2000_iqp_end_state_against_golden(gpu_engine):
         assert stt["rounds"] == len(g["iqp_n"]) == 3
     for a, ref_out, nv_out in outs:
         assert a.shape == g["iqp_alpha"].shape == (int(g["iqp_n"][-1]),)
-        assert np.max(np.abs(a - g["iqp_alpha"])) < ALPHA_TOL, float(np.max(np.abs(a - g["iqp_alpha"])))
+        assert np.max(np.abs(a - g["iqp_alpha"])) < ALPHA_TOL, float(np.max(np.abs(a - g["iqp_alpha"])))   # contract
         assert np.max(np.abs(ref_out - g["iqp_reftrack"])) < 1e-6
         assert np.max(np.abs(nv_out - g["iqp_normvec"])) < 1e-8
+        g_a, g_r = guard("oval_n2000", what="iqp_alpha"), guard("oval_n2000", what="iqp_reftrack")
+        assert WORST.add("iqp end states", dmax(a, g["iqp_alpha"]), g_a) < g_a, (dmax(a, g["iqp_alpha"]), g_a)      # guard
+        assert dmax(ref_out, g["iqp_reftrack"]) < g_r, (dmax(ref_out, g["iqp_reftrack"]), g_r)                     # guard
 
 
 def test_many_active_curvature_rows_against_dense_gi(gpu_engine, golden):
@@ -973,7 +1025,8 @@ def test_many_active_curvature_rows_against_dense_gi(gpu_engine, golden):
     al, curv, st, info = gpu_engine.solve_batch(probs)
     for k, (a_ref, err_ref, nk) in enumerate(want):
         assert st[k] == 0, (cases[k], st[k])
-        assert np.max(np.abs(al[k] - a_ref)) < ALPHA_TOL, (cases[k], float(np.max(np.abs(al[k] - a_ref))))
+        assert np.max(np.abs(al[k] - a_ref)) < ALPHA_TOL, (cases[k], float(np.max(np.abs(al[k] - a_ref))))   # contract
+        assert WORST.add("live oracle", dmax(al[k], a_ref), GUARD) < GUARD, (cases[k], dmax(al[k], a_ref))     # guard
         assert abs(curv[k] - err_ref) < CURV_TOL
         assert info[k]["n_active_kappa"] == nk, (cases[k], info[k]["n_active_kappa"], nk)
         assert abs(info[k]["kappa_max"] - cases[k][1]) < 1e-9 and info[k]["refine_rounds"] >= 1
@@ -1000,7 +1053,8 @@ def test_poisoned_workspaces_and_lds_bitwise(gpu_engine, golden, monkeypatch):
         assert list(s1) == list(s0) and np.array_equal(c1, c0)
         assert all(np.array_equal(x, y) for x, y in zip(a1, a0))
         for k, name in enumerate(golden):
-            assert s1[k] == 0 and np.max(np.abs(a1[k] - golden[name]["alpha"])) < ALPHA_TOL
+            assert s1[k] == 0 and np.max(np.abs(a1[k] - golden[name]["alpha"])) < ALPHA_TOL           # contract
+            assert dmax(a1[k], golden[name]["alpha"]) < guard(name), name                             # guard
         tracks = [dict(reftrack=ref[k].copy(), normvectors=nv[k], scaling=sc[k]) for k in range(8)]
         o1 = tph.iqp_handler.iqp_handler_batch(tracks, 0.12, 2.0, 3.0, 4, 0.01, engine=eng, device_resident=True, warm_start=True)
         o0 = tph.iqp_handler.iqp_handler_batch(tracks, 0.12, 2.0, 3.0, 4, 0.01, engine=gpu_engine, device_resident=True, warm_start=True)
@@ -1035,7 +1089,8 @@ def test_config4_full_size_lap_time_matrix(gpu_engine, golden):
         A = tph.calc_splines.build_les_matrix(p["reftrack"].shape[0], p["scaling"])
         a_ref, err_ref = tph_ref.opt_min_curv(p["reftrack"], p["normvec"], A, p["kappa_bound"], p["w_veh"])
         worst = max(worst, float(np.max(np.abs(al[q] - a_ref))))
-        assert np.max(np.abs(al[q] - a_ref)) < ALPHA_TOL, q
+        assert np.max(np.abs(al[q] - a_ref)) < ALPHA_TOL, q                                          # contract
+        assert WORST.add("live oracle", dmax(al[q], a_ref), GUARD) < GUARD, (q, dmax(al[q], a_ref))  # guard
         assert abs(curv[q] - err_ref) < CURV_TOL, q
     # ---- lap times / profiles against the oracle's velocity profile on the host chain's raceline
     rng = np.random.default_rng(5)
@@ -1159,7 +1214,8 @@ def test_curvature_row_overflow_slots_against_dense_gi(gpu_engine):
     for k, (a_ref, err_ref, nk) in enumerate(want):
         assert st[k] == 0, (k, st[k])
         assert info[k]["n_active_kappa"] == nk, (k, info[k]["n_active_kappa"], nk)
-        assert np.max(np.abs(al[k] - a_ref)) < ALPHA_TOL, (k, float(np.max(np.abs(al[k] - a_ref))))
+        assert np.max(np.abs(al[k] - a_ref)) < ALPHA_TOL, (k, float(np.max(np.abs(al[k] - a_ref))))   # contract
+        assert WORST.add("live oracle", dmax(al[k], a_ref), GUARD) < GUARD, (k, dmax(al[k], a_ref))   # guard: the stadiums
         assert abs(curv[k] - err_ref) < CURV_TOL
     print("curvature-row overflow: %s active rows, max |alpha - dense GI| = %.2e m"
           % ([w[2] for w in want], max(float(np.max(np.abs(al[k] - w[0]))) for k, w in enumerate(want))))

@@ -168,13 +168,22 @@ def _replay_recorded_calls(capsys, on_build_box, with_kappa_error=True):
             assert hashlib.sha256(np.ascontiguousarray(A).tobytes()).hexdigest() == str(z[key + "_A_sha256"])
         return A
 
+    def guarded(d, what):
+        """On the GPU (not on the interpreter, which keeps its own bounds): the tight guard of tests/ring_guard.py on top of the contract."""
+        if not on_build_box:
+            import ring_guard
+            g = ring_guard.guard("harness_calls_berlin", what=what)
+            assert d < g, (what, d, g)                                                                  # guard
+        return d
+
     capsys.readouterr()
     # ---- opt_type = 'mincurv' [REF main_globaltraj.py:264-271] ----
     kw = json.loads(str(z["mincurv_kwargs"]))
     assert str(z["mincurv_entry"]) == "opt_min_curv.opt_min_curv" and kw["print_debug"] is True
     alpha = tph.opt_min_curv.opt_min_curv(reftrack=z["mincurv_reftrack"].copy(), normvectors=z["mincurv_normvectors"].copy(), A=matrix("mincurv"), **kw)[0]
     d_mc = float(np.max(np.abs(alpha - z["mincurv_oracle_alpha"])))
-    assert alpha.shape == (776,) and d_mc <= 1e-6
+    assert alpha.shape == (776,) and d_mc <= 1e-6                                                       # contract
+    guarded(d_mc, "mincurv_oracle_alpha")
     out = capsys.readouterr().out
     assert re.search(r"^Solver runtime opt_min_curv: \d+\.\d{3}s$", out, re.M), out
     # the second element of the tuple the script drops with [0]
@@ -187,7 +196,9 @@ def _replay_recorded_calls(capsys, on_build_box, with_kappa_error=True):
     a_iqp, rt, nv = tph.iqp_handler.iqp_handler(reftrack=z["iqp_reftrack"].copy(), normvectors=z["iqp_normvectors"].copy(), A=matrix("iqp"), **kw)
     assert a_iqp.shape == z["iqp_oracle_alpha"].shape and rt.shape == z["iqp_oracle_reftrack"].shape and nv.shape == z["iqp_oracle_normvectors"].shape
     d_iqp = float(np.max(np.abs(a_iqp - z["iqp_oracle_alpha"])))
-    assert d_iqp <= 1e-6 and np.max(np.abs(rt - z["iqp_oracle_reftrack"])) <= 1e-6 and np.max(np.abs(nv - z["iqp_oracle_normvectors"])) <= 1e-6
+    assert d_iqp <= 1e-6 and np.max(np.abs(rt - z["iqp_oracle_reftrack"])) <= 1e-6 and np.max(np.abs(nv - z["iqp_oracle_normvectors"])) <= 1e-6   # contract
+    guarded(d_iqp, "iqp_oracle_alpha")
+    guarded(float(np.max(np.abs(rt - z["iqp_oracle_reftrack"]))), "iqp_oracle_reftrack")
     lines = [l for l in capsys.readouterr().out.splitlines() if l.startswith(("Minimum curvature IQP", "Finished IQP"))]
     assert lines == json.loads(str(z["iqp_stdout"])) and len(lines) == 4              # the three iterations' lines and the closing one, digit for digit
     assert lines[:3] == ["Minimum curvature IQP: iteration %i, curv_error_max: %.4frad/m" % (k + 1, c) for k, c in enumerate(z["iqp_oracle_curv_error_trace"])]
@@ -195,13 +206,15 @@ def _replay_recorded_calls(capsys, on_build_box, with_kappa_error=True):
     kw = json.loads(str(z["shortest_kwargs"]))
     a_sp = tph.opt_shortest_path.opt_shortest_path(reftrack=z["shortest_reftrack"].copy(), normvectors=z["shortest_normvectors"].copy(), **kw)
     d_sp = float(np.max(np.abs(a_sp - z["shortest_oracle_alpha"])))
-    assert d_sp <= 1e-6
+    assert d_sp <= 1e-6                                                                                 # contract
+    guarded(d_sp, "shortest_oracle_alpha")
     assert re.search(r"^Solver runtime opt_shortest_path: \d+\.\d{3}s$", capsys.readouterr().out, re.M)
     # ---- the re-optimisation call of the mintime branch [REF main_globaltraj.py:337-350] ----
     kw = json.loads(str(z["reopt_kwargs"]))
     a_ro = tph.opt_min_curv.opt_min_curv(reftrack=z["reopt_reftrack"].copy(), normvectors=z["reopt_normvectors"].copy(), A=matrix("reopt"), **kw)[0]
     d_ro = float(np.max(np.abs(a_ro - z["reopt_oracle_alpha"])))
-    assert d_ro <= 1e-6 and np.max(np.abs(a_ro)) <= 0.2 + 1e-9                      # corridor 1.0 either side, vehicle 1.6
+    assert d_ro <= 1e-6 and np.max(np.abs(a_ro)) <= 0.2 + 1e-9                      # contract; corridor 1.0 either side, vehicle 1.6
+    guarded(d_ro, "reopt_oracle_alpha")
     # ---- what upstream's callers would see when the QP has no solution ----
     kw = json.loads(str(z["mincurv_kwargs"]))
     narrow = z["mincurv_reftrack"].copy()
@@ -241,7 +254,10 @@ def test_replay_of_the_recorded_calls_on_the_gpu(monkeypatch, capsys):
     d = _replay_recorded_calls(capsys, on_build_box=False)
     monkeypatch.setattr(engine, "_DEFAULT_ENGINE", None)
     with capsys.disabled():
-        print("replay of main_globaltraj.py's recorded calls on libmcq.so: max |alpha - oracle| [m] = %s" % {k: "%.1e" % v for k, v in d.items()})
+        import ring_guard
+        guards = {k: ring_guard.guard("harness_calls_berlin", what=("shortest" if k == "shortest_path" else k) + "_oracle_alpha") for k in d}
+        print("replay of main_globaltraj.py's recorded calls on libmcq.so: max |alpha - oracle| [m] (guard) = %s" % {
+            k: "%.1e (%.1e)" % (v, guards[k]) for k, v in d.items()})
 
 
 @pytest.mark.gpu
