@@ -96,8 +96,8 @@ class Worst:
             self.w[family] = [float(d), float(g)]
         return d
 
-    def report(self, title):
-        return "%s: worst |d alpha| per family (guard): %s" % (title, ", ".join(
+    def report(self, title, what="|d alpha|"):
+        return "%s: worst %s per family (guard): %s" % (title, what, ", ".join(
             "%s %.1e (%.1e)" % (f, *w) for f, w in sorted(self.w.items())))
 
 
