@@ -864,10 +864,41 @@ __device__ __noinline__ int ipm(const LCtx& c, bool with_kappa)
 #define IPB_H 4     /* entries a pass keeps in registers at a time: two halves per pass (round 3: at 256 VGPRs -- two workgroups per CU -- eight entries of a pass's arrays spilled) */
 // `resume`: continue from the pairs (X, ZL, ZU) already in memory to the tighter tolerance `tol` -- the second attempt on
 // degenerate / very ill-conditioned instances (see the driver in mcq_solve_kernel).
+//
+// What may be live across the (non-inlined) factorisation / solve / gradient calls, from the ISA (hipcc 7.2, build.sh's flags):
+//   * this function needs 256 VGPRs and so saves ALL 112 callee-saved VGPRs once in its prologue (per problem, not per iteration);
+//     what it keeps alive across a call is put into those registers;
+//   * solve_kkt<> and the solve wrapper touch no callee-saved VGPR: values there survive both solves of an iteration at no cost;
+//   * factor_kkt<> saves and restores the 80 callee-saved VGPRs it uses on every call whether the caller has anything in them or not.
+// So 64 - 80 VGPRs of per-thread state ride through an iteration without one scratch instruction more: the thread's eight entries of
+// X, ZL, ZU and G (MCQ_IPB_RESIDENT, 64 VGPRs) are loaded once and stay in registers until the return; the three passes read them there
+// and pass 3 updates them.  That is the budget, not a licence: a caller that keeps more than the callee-saved set alive spills.  Pointers
+// and index sets are still re-derived at the top of every pass, and a fifth array does not fit: with LO resident as well the allocator
+// spills inside the loop (54 scratch stores + 198 loads outside prologue / epilogue against the earlier form's 14 + 20, frame 1232 B per
+// lane against 1024), with LO and HI 90 + 287 (1456 B).  As it stands: 11 + 15, 960 B (docs/NOTEBOOK.md "Resident iterate").
+// -DMCQ_IPB_RESIDENT=0 is the earlier form (every pass loads what it needs and stores what it changed): same results bit for bit,
+// tests/test_emu_ipb_resident.py compares the two.  The steps, each with a switch of its own for A/B builds:
+//   MCQ_IPB_RESIDENT: the resident reads above; G is loaded again after a gradient() call.
+//   MCQ_IPB_DEFER (needs MCQ_IPB_RESIDENT): X, ZL, ZU, G and the Tapia indicators are stored at the returns only (X also before a
+//     gradient() call, which reads it); the indicators of the last step ride in one register, two bits per entry.
+//   MCQ_IPB_NOCOPY: the corrector's right-hand side is written to V_DXA and solved there, the predictor's solution stays in V_RHS --
+//     pass 2's copy of it goes (nothing after this function reads either vector before writing it; the zero the copy wrote for the
+//     pinned entries was read by pass 3 only, which skips them).  Nothing on the clock by itself, but pass 2 then needs fewer
+//     registers: MCQ_IPB_RESIDENT and MCQ_IPB_DEFER without it have 12 + 23 scratch instructions.
+#ifndef MCQ_IPB_RESIDENT
+#define MCQ_IPB_RESIDENT 1
+#endif
+#ifndef MCQ_IPB_DEFER
+#define MCQ_IPB_DEFER MCQ_IPB_RESIDENT
+#endif
+#ifndef MCQ_IPB_NOCOPY
+#define MCQ_IPB_NOCOPY MCQ_IPB_RESIDENT
+#endif
+#if MCQ_IPB_DEFER && !MCQ_IPB_RESIDENT
+#error "MCQ_IPB_DEFER needs MCQ_IPB_RESIDENT"
+#endif
 __device__ __noinline__ int ipm_box(const LCtx& c, double tol, bool resume)
 {
-    // Pointers and the per-thread index set are re-derived at the top of every pass: nothing but a few scalars is live
-    // across the (non-inlined) factorisation / solve calls, so nothing is spilled to scratch and reloaded around them.
 #define IPB_SETUP                                                                                                      \
     const int tid = threadIdx.x, n = c.d.n, nm = c.nm;                                                                 \
     double* red = g_sm + SM_RED;                                                                                       \
@@ -912,6 +943,14 @@ __device__ __noinline__ int ipm_box(const LCtx& c, double tol, bool resume)
     gschar* ST = c.w.state;                                                                                            \
     gdouble* IND = VEC(c.w, nm, V_T3);                                                                                 \
     (void)IND; (void)red; (void)LO; (void)HI; (void)X; (void)G; (void)ZL; (void)ZU; (void)SIG; (void)RHS; (void)DXA; (void)ST;
+    // where the corrector's right-hand side / the combined direction and the predictor's solution live
+#if MCQ_IPB_NOCOPY
+#define IPB_CORR DXA
+#define IPB_PRED RHS
+#else
+#define IPB_CORR RHS
+#define IPB_PRED DXA
+#endif
     const double zscale = c.zscale;
     const double IPM_TOL = tol;
     c.out_iters = 0;
@@ -935,6 +974,30 @@ __device__ __noinline__ int ipm_box(const LCtx& c, double tol, bool resume)
     const double npairs = 2.0 * c.nfree;
     const bool any_fixed = c.nfree < (double)c.d.n;
     if (!(npairs > 0.0)) return MCQ_OK;
+#if MCQ_IPB_RESIDENT
+    // the thread's entries of the iterate, resident from here to the return (the barrier above, or the one that ends gradient(), orders these
+    // loads behind the stores of the other threads: entry 0 stands in for the absent ones)
+    double rx[IPB_E], rl[IPB_E], ru[IPB_E], rg[IPB_E];
+    {
+        IPB_SETUP
+#pragma unroll
+        for (int u = 0; u < IPB_E; ++u) { const int i = idx[u]; rx[u] = X[i]; rl[u] = ZL[i]; ru[u] = ZU[i]; rg[u] = G[i]; }
+    }
+    // G after a gradient() call (its last barrier comes after its last store)
+#define IPB_RELOAD_G { _Pragma("unroll") for (int u = 0; u < IPB_E; ++u) rg[u] = G[tid + u * MCQ_NT < n ? tid + u * MCQ_NT : 0]; }
+#else
+#define IPB_RELOAD_G
+#endif
+#if MCQ_IPB_DEFER
+    // X to memory before a gradient() call (which starts with a barrier)
+#define IPB_STORE_X { _Pragma("unroll") for (int u = 0; u < IPB_E; ++u) if (tid + u * MCQ_NT < n) X[tid + u * MCQ_NT] = rx[u]; }
+#define IPB_RETURN(v) { rc = (v); goto ipb_flush; }
+    unsigned tapia = 0;         // two bits per entry: 0 no step taken, else 2 + the indicator of the last step
+    int rc;
+#else
+#define IPB_STORE_X
+#define IPB_RETURN(v) return (v);
+#endif
 
     // g = H x + f is carried along (see ipm()): exact on entry, exact again before convergence is declared
     bool g_exact = true;
@@ -977,7 +1040,12 @@ __device__ __noinline__ int ipm_box(const LCtx& c, double tol, bool resume)
 #pragma unroll
                 for (int u = 0; u < IPB_H; ++u) {
                     const int i = idx[u];
+#if MCQ_IPB_RESIDENT
+                    st[u] = ST[i]; lo[u] = LO[i]; hi[u] = HI[i];
+                    x[u] = rx[h * IPB_H + u]; zl[u] = rl[h * IPB_H + u]; zu[u] = ru[h * IPB_H + u]; g[u] = rg[h * IPB_H + u];
+#else
                     st[u] = ST[i]; x[u] = X[i]; lo[u] = LO[i]; hi[u] = HI[i]; zl[u] = ZL[i]; zu[u] = ZU[i]; g[u] = G[i];
+#endif
                 }
 #pragma unroll
                 for (int u = 0; u < IPB_H; ++u) {
@@ -996,20 +1064,25 @@ __device__ __noinline__ int ipm_box(const LCtx& c, double tol, bool resume)
             }
             const bool conv = mu < IPM_TOL * zscale * c.wmean && rdm < IPM_TOL * zscale;
 #ifdef IPM_TRACE
-            if (threadIdx.x == 0) printf("ipmb it %d mu %.3e rdm %.3e exact %d resume %d\n", it, mu / (zscale * c.wmean), rdm / zscale, (int)g_exact, (int)resume);
+            // (the bits of mu and rdm as well: between them they are a checksum of X, ZL, ZU and G -- tests/test_emu_ipb_resident.py compares them)
+            if (threadIdx.x == 0) printf("ipmb it %d mu %.3e rdm %.3e exact %d resume %d [%a %a]\n", it, mu / (zscale * c.wmean), rdm / zscale, (int)g_exact, (int)resume, mu, rdm);
 #endif
             if (f32 && it > 1 && rdm < MCQ_IPM_F32_RD * zscale) {      // float records have done their part
                 f32 = false;
                 if (!g_exact) {
+                    IPB_STORE_X
                     gradient(c, X, nullptr, VEC(c.w, nm, V_T0), G);
+                    IPB_RELOAD_G
                     g_exact = true;
                     g_f32 = false;
                     continue;
                 }
             }
-            if (conv && (g_exact || (MCQ_IPM_TRUST_FP64_CARRY && !resume && !g_f32))) return MCQ_OK;
+            if (conv && (g_exact || (MCQ_IPM_TRUST_FP64_CARRY && !resume && !g_f32))) IPB_RETURN(MCQ_OK)
             if (!conv) break;
+            IPB_STORE_X
             gradient(c, X, nullptr, VEC(c.w, nm, V_T0), G);     // looks converged on the carried gradient: confirm on the exact one
+            IPB_RELOAD_G
             g_exact = true;
             g_f32 = false;
         }
@@ -1019,7 +1092,7 @@ __device__ __noinline__ int ipm_box(const LCtx& c, double tol, bool resume)
             // reduction end the attempt (the active-set phase then decides)
             stalled = mu > 0.9 * mu_prev ? stalled + 1 : 0;
             mu_prev = mu;
-            if (stalled >= 3) return MCQ_OK;
+            if (stalled >= 3) IPB_RETURN(MCQ_OK)
         }
 
         // ---- factorisation, predictor solve -----------------------------------------------------------------------------
@@ -1029,7 +1102,7 @@ __device__ __noinline__ int ipm_box(const LCtx& c, double tol, bool resume)
                                     VEC(c.w, c.nm, V_RHS), f32);
         // resumed attempt (complementarity already below 1e-10): an iterate that sits ON a bound in floating point (slack 0, sig = inf) ends
         // the attempt like a stalled complementarity does -- the pairs of the last completed iteration go to the active-set phase
-        if (fs != 0) return (resume && fs == MCQ_NOT_PD) ? MCQ_OK : fs;
+        if (fs != 0) IPB_RETURN((resume && fs == MCQ_NOT_PD) ? MCQ_OK : fs)
         timed_solve(c, VEC(c.w, c.nm, V_RHS), true);
 
         // ---- pass 2: affine step lengths, centring parameter, corrector right-hand side: ONE load phase (six arrays of eight entries stay in
@@ -1042,17 +1115,27 @@ __device__ __noinline__ int ipm_box(const LCtx& c, double tol, bool resume)
 #pragma unroll
             for (int u = 0; u < IPB_E; ++u) {
                 const int i = idx[u];
-                const double x = X[i];
                 act[u] = ok[u] && ST[i] == 0;
+#if MCQ_IPB_RESIDENT
+                const double x = rx[u];
+                dxa[u] = RHS[i]; sl[u] = x - LO[i]; su[u] = HI[i] - x; zl[u] = rl[u]; zu[u] = ru[u]; g[u] = rg[u];
+#else
+                const double x = X[i];
                 dxa[u] = RHS[i]; sl[u] = x - LO[i]; su[u] = HI[i] - x; zl[u] = ZL[i]; zu[u] = ZU[i]; g[u] = G[i];
+#endif
             }
             double ap = 1.0, ad = 1.0;
 #pragma unroll
             for (int u = 0; u < IPB_E; ++u) {
                 if (!ok[u]) continue;
+#if MCQ_IPB_NOCOPY
+                if (!act[u]) continue;
+                const double dx = dxa[u];
+#else
                 if (!act[u]) { DXA[idx[u]] = 0.0; continue; }
                 const double dx = dxa[u];
                 DXA[idx[u]] = dx;
+#endif
                 const double dzla = -zl[u] - zl[u] * dx / sl[u];
                 const double dzua = -zu[u] + zu[u] * dx / su[u];
                 if (dx < 0.0) ap = fmin(ap, -sl[u] / dx);
@@ -1077,10 +1160,10 @@ __device__ __noinline__ int ipm_box(const LCtx& c, double tol, bool resume)
                 if (!ok[u]) continue;
                 const double dzla = -zl[u] - zl[u] * dxa[u] / sl[u];
                 const double dzua = -zu[u] + zu[u] * dxa[u] / su[u];
-                RHS[idx[u]] = act[u] ? -g[u] + (smu - dxa[u] * dzla) / sl[u] - (smu + dxa[u] * dzua) / su[u] : 0.0;
+                IPB_CORR[idx[u]] = act[u] ? -g[u] + (smu - dxa[u] * dzla) / sl[u] - (smu + dxa[u] * dzua) / su[u] : 0.0;
             }
         }
-        timed_solve(c, VEC(c.w, c.nm, V_RHS));
+        timed_solve(c, VEC(c.w, c.nm, MCQ_IPB_NOCOPY ? V_DXA : V_RHS));
 
         // ---- pass 3: step length of the combined direction, update: ONE load phase -- nine arrays of eight entries stay in registers
         //      across the block reduction; the multiplier steps and H dx are recomputed after it instead of being kept (at 256 VGPRs --
@@ -1102,8 +1185,12 @@ __device__ __noinline__ int ipm_box(const LCtx& c, double tol, bool resume)
             for (int u = 0; u < IPB_E; ++u) {
                 const int i = idx[u];
                 act[u] = ok[u] && ST[i] == 0;
-                dx[u] = RHS[i]; da[u] = DXA[i]; x[u] = X[i]; lo[u] = LO[i]; hi[u] = HI[i]; zl[u] = ZL[i]; zu[u] = ZU[i];
-                g[u] = G[i]; sg[u] = SIG[i];
+                dx[u] = IPB_CORR[i]; da[u] = IPB_PRED[i]; lo[u] = LO[i]; hi[u] = HI[i]; sg[u] = SIG[i];
+#if MCQ_IPB_RESIDENT
+                x[u] = rx[u]; zl[u] = rl[u]; zu[u] = ru[u]; g[u] = rg[u];
+#else
+                x[u] = X[i]; zl[u] = ZL[i]; zu[u] = ZU[i]; g[u] = G[i];
+#endif
             }
 #define IPB_STEP3(u)                                                                                                          \
                 const double sl = x[u] - lo[u], su = hi[u] - x[u];                                                              \
@@ -1122,6 +1209,13 @@ __device__ __noinline__ int ipm_box(const LCtx& c, double tol, bool resume)
             amax = block_reduce_(amax, 1, red);
             const double a = fmin(1.0, gm * amax);
             c.last_step = a;
+#if MCQ_IPB_DEFER
+            // (one value per entry, packed after the loop: each takes the place of an operand that died with its entry, where a packed word live
+            //  through the whole loop is spilled and reloaded per entry.  The active entries take a step in every iteration, the others in none.)
+            unsigned t3[IPB_E];
+#pragma unroll
+            for (int u = 0; u < IPB_E; ++u) t3[u] = 0;
+#endif
 #pragma unroll
             for (int u = 0; u < IPB_E; ++u) {
                 if (!act[u]) continue;
@@ -1131,24 +1225,64 @@ __device__ __noinline__ int ipm_box(const LCtx& c, double tol, bool resume)
                 const double rc = -g[u] + (smu - da[u] * dzla) / sl - (smu + da[u] * dzua) / su;
                 const double hdx = rc - sg[u] * dx[u];
                 const double gn = g[u] + a * hdx, xn = x[u] + a * dx[u], zln = zl[u] + a * dzl, zun = zu[u] + a * dzu;
+#if MCQ_IPB_RESIDENT
+                rg[u] = gn; rx[u] = xn; rl[u] = zln; ru[u] = zun;
+#endif
+#if !MCQ_IPB_DEFER
                 G[i] = gn;
                 X[i] = xn;
                 ZL[i] = zln;
                 ZU[i] = zun;
+#endif
                 // Tapia indicators of this step for the active-set identification (the last step's survive)
                 const double rsl = (sl + a * dx[u]) * zl[u], rzl = (zl[u] + a * dzl) * sl;     // s+/s < z+/z  <=>  s+ z < z+ s
                 const double rsu = (su - a * dx[u]) * zu[u], rzu = (zu[u] + a * dzu) * su;
                 const bool al = rsl < MCQ_TAPIA_RATIO * rzl && sl + a * dx[u] < MCQ_TAPIA_SHRINK * sl, au = rsu < MCQ_TAPIA_RATIO * rzu && su - a * dx[u] < MCQ_TAPIA_SHRINK * su;
+#if MCQ_IPB_DEFER
+                t3[u] = al ? 1u : (au ? 3u : 2u);
+                (void)i;
+#else
                 IND[i] = al ? -1.0 : (au ? 1.0 : 0.0);
+#endif
             }
+#if MCQ_IPB_DEFER
+            tapia = 0;
+#pragma unroll
+            for (int u = 0; u < IPB_E; ++u) tapia |= t3[u] << (2 * u);
+#endif
 #undef IPB_STEP3
         }
         g_exact = false;
         g_f32 |= f32;
         __syncthreads();
     }
+#if MCQ_IPB_DEFER
+    rc = MCQ_ITER_CAP;
+ipb_flush:
+    // the state of the last completed iteration, as the per-iteration stores left it (an entry on which no step was taken keeps the
+    // indicator it had)
+    {
+        IPB_SETUP
+#pragma unroll
+        for (int u = 0; u < IPB_E; ++u) {
+            if (!ok[u]) continue;
+            const int i = idx[u];
+            X[i] = rx[u]; ZL[i] = rl[u]; ZU[i] = ru[u]; G[i] = rg[u];
+            const unsigned t = (tapia >> (2 * u)) & 3u;
+            if (t != 0) IND[i] = (double)((int)t - 2);
+        }
+    }
+    __syncthreads();
+    return rc;
+#else
     return MCQ_ITER_CAP;
+#endif
 #undef IPB_SETUP
+#undef IPB_RELOAD_G
+#undef IPB_STORE_X
+#undef IPB_RETURN
+#undef IPB_CORR
+#undef IPB_PRED
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
