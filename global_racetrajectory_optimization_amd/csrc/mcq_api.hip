@@ -70,7 +70,7 @@ struct mcq_handle {
                             // on the rare one whose recycled memory happens to hold garbage
     long long ws_bytes = 0;
     bool smem_attr_set = false;
-    double* vel_scratch = nullptr;      // lap-doubled profiles of mcq_vel_profile_device, [2 nmax][batch]
+    double* vel_scratch = nullptr;      // profiles of mcq_vel_profile_device*, [2 nmax][batch] (the lap doubled) or [nmax][batch] (unclosed rows)
     mcq_iqp_round_cb iqp_cb = nullptr;  // mcq_iqp_set_round_callback
     void* iqp_cb_user = nullptr;
     void* comm = nullptr;               // ncclComm_t of mcq_comm_init (RCCL, loaded with dlopen)
@@ -794,20 +794,25 @@ extern "C" int mcq_relinearise_device(mcq_handle* h, int batch, int nmax, const 
     return 0;
 }
 
+// every velocity-profile entry ends here.  The three older entries launch the closed / ggv form (closed = 1, no loc_gg);
+// mcq_vel_profile_device_forms picks one of the four kernels: a launch has one form for all its variants.
 static int vel_profile_launch(mcq_handle* h, int batch, int n, int nmax, const int* n_of_track, const int* track_of,
                               const double* kappa, const double* el_lengths, const double* ggv, int n_ggv,
                               const double* ax_max_machines, int n_machines, const double* drag_coeff, const double* m_veh,
                               const double* v_max, double dyn_model_exp, double* vx_out, double* lap_time_out,
-                              const double* mu = nullptr, int filt_window = 0)
+                              const double* mu = nullptr, int filt_window = 0, int closed = 1, const double* loc_gg = nullptr,
+                              const double* v_start = nullptr, const double* v_end = nullptr)
 {
-    if (!h || batch <= 0 || (!n_of_track && n < 2) || nmax < n || nmax < 2 || !kappa || !el_lengths || !ggv || n_ggv < 1 ||
+    // upstream's "either ggv and optionally mu OR loc_gg"
+    const bool tables_ok = loc_gg ? (!ggv && n_ggv == 0 && !mu) : (ggv && n_ggv >= 1);
+    if (!h || batch <= 0 || (!n_of_track && n < 2) || nmax < n || nmax < 2 || !kappa || !el_lengths || !tables_ok ||
         !ax_max_machines || n_machines < 1 || !drag_coeff || !m_veh || !v_max || !vx_out || !lap_time_out ||
-        !(dyn_model_exp > 0.0)) {
+        !(dyn_model_exp > 0.0) || (!closed && !v_start)) {
         g_err = "mcq_vel_profile_device: bad argument";
         return MCQ_E_ARG;
     }
     HIP_TRY(hipSetDevice(h->device));
-    const size_t need = (size_t)2 * nmax * batch * sizeof(double);
+    const size_t need = (size_t)(closed ? 2 : 1) * nmax * batch * sizeof(double);      // the lap doubled, or the row once
     if (need > h->vel_scratch_bytes) {
         HIP_TRY(hipStreamSynchronize(h->stream));
         (void)hipFree(h->vel_scratch);
@@ -816,8 +821,9 @@ static int vel_profile_launch(mcq_handle* h, int batch, int n, int nmax, const i
         HIP_TRY(hipMalloc((void**)&h->vel_scratch, need));
         h->vel_scratch_bytes = need;
     }
-    McqVel V;
-    memset(&V, 0, sizeof(V));
+    McqVelForms F;
+    memset(&F, 0, sizeof(F));
+    McqVel& V = F.V;
     V.batch = batch; V.n = n; V.nmax = nmax;
     V.n_of_track = n_of_track;
     V.track_of = track_of; V.kappa = kappa; V.el = el_lengths;
@@ -825,7 +831,12 @@ static int vel_profile_launch(mcq_handle* h, int batch, int n, int nmax, const i
     V.drag = drag_coeff; V.mass = m_veh; V.vmax = v_max; V.dyn_exp = dyn_model_exp;
     V.mu = mu; V.filt_window = filt_window;
     V.scratch = h->vel_scratch; V.vx_out = vx_out; V.lap_time = lap_time_out;
-    hipLaunchKernelGGL(mcq_vel_profile_kernel, dim3((batch + 63) / 64), dim3(64), 0, h->stream, V);
+    F.loc_gg = loc_gg; F.v_start = v_start; F.v_end = v_end;
+    const dim3 grid((batch + 63) / 64), block(64);
+    if (closed && !loc_gg) hipLaunchKernelGGL(mcq_vel_profile_kernel, grid, block, 0, h->stream, V);
+    else if (closed) hipLaunchKernelGGL(mcq_vel_profile_locgg_kernel, grid, block, 0, h->stream, F);
+    else if (!loc_gg) hipLaunchKernelGGL(mcq_vel_profile_open_kernel, grid, block, 0, h->stream, F);
+    else hipLaunchKernelGGL(mcq_vel_profile_open_locgg_kernel, grid, block, 0, h->stream, F);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -861,6 +872,25 @@ extern "C" int mcq_vel_profile_device_opts(mcq_handle* h, int batch, int n, int 
     return vel_profile_launch(h, batch, n_of_track ? 0 : n, nmax, n_of_track, track_of, kappa, el_lengths, ggv, n_ggv, ax_max_machines,
                               n_machines, drag_coeff, m_veh, v_max, opts->dyn_model_exp, vx_out, lap_time_out, opts->mu,
                               opts->filt_window);
+}
+
+extern "C" int mcq_vel_profile_device_forms(mcq_handle* h, int batch, int n, int nmax, const int* n_of_track, const int* track_of,
+                                            const double* kappa, const double* el_lengths, const double* ggv, int n_ggv,
+                                            const double* ax_max_machines, int n_machines, const double* drag_coeff,
+                                            const double* m_veh, const double* v_max, const mcq_vel_forms* forms, double* vx_out,
+                                            double* lap_time_out)
+{
+    if (!forms) { g_err = "mcq_vel_profile_device_forms: forms is NULL"; return MCQ_E_ARG; }
+    if (forms->filt_window < 0) { g_err = "mcq_vel_profile_device_forms: negative filt_window"; return MCQ_E_ARG; }
+    if (forms->loc_gg && (ggv || n_ggv != 0 || forms->mu)) {
+        g_err = "mcq_vel_profile_device_forms: either ggv and optionally mu OR loc_gg, not both";
+        return MCQ_E_ARG;
+    }
+    if (!forms->loc_gg && !ggv) { g_err = "mcq_vel_profile_device_forms: either ggv or loc_gg must be supplied"; return MCQ_E_ARG; }
+    if (!forms->closed && !forms->v_start) { g_err = "mcq_vel_profile_device_forms: v_start is required when closed == 0"; return MCQ_E_ARG; }
+    return vel_profile_launch(h, batch, n_of_track ? 0 : n, nmax, n_of_track, track_of, kappa, el_lengths, ggv, n_ggv, ax_max_machines,
+                              n_machines, drag_coeff, m_veh, v_max, forms->dyn_model_exp, vx_out, lap_time_out, forms->mu,
+                              forms->filt_window, forms->closed != 0, forms->loc_gg, forms->v_start, forms->v_end);
 }
 
 extern "C" int mcq_raceline_device(mcq_handle* h, int batch, int nmax, const int* n_in, const double* reftrack,

@@ -242,3 +242,17 @@ struct McqVel {
     double* lap_time;        // [batch]
 };
 __global__ void mcq_vel_profile_kernel(McqVel V);
+
+/* ---- the other forms of tph.calc_vel_profile's signature (mcq_vel_profile_device_forms): unclosed rows (n curvatures, n - 1 element
+ *      lengths, a start speed and optionally an end speed; V.scratch then holds [nmax][batch]) and / or local tyre limits per waypoint
+ *      in place of the ggv diagram (V.ggv / V.mu nullptr, V.ng 0).  One kernel per form: the same body as mcq_vel_profile_kernel with the
+ *      form as a compile-time parameter. ---- */
+struct McqVelForms {
+    McqVel V;
+    const double* loc_gg;    // [tracks][nmax][2] (ax_max, ay_max) per waypoint (the _locgg kernels), else unused
+    const double* v_start;   // [batch] (the _open kernels), else unused
+    const double* v_end;     // [batch], NaN: none for that variant, or nullptr: none at all (the _open kernels)
+};
+__global__ void mcq_vel_profile_open_kernel(McqVelForms F);
+__global__ void mcq_vel_profile_locgg_kernel(McqVelForms F);
+__global__ void mcq_vel_profile_open_locgg_kernel(McqVelForms F);

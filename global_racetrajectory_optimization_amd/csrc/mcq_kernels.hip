@@ -2366,13 +2366,12 @@ __device__ __forceinline__ double vp_interp(double x, const gdouble* tab, int cn
     return y0 + (y1 - y0) * (x - x0) / (x1 - x0);
 }
 
-// longitudinal acceleration still available at speed v on radius `rad` with friction coefficient mu (tph.calc_vel_profile.calc_ax_poss:
+// longitudinal acceleration still available at speed v on radius `rad`, the tyre limits (ax_t >= 0, ay_t) given (tph.calc_vel_profile.calc_ax_poss:
 // tyre potential shared with the lateral acceleration through the friction ellipse of exponent e, machine limit when accelerating,
 // drag -- which helps when the deceleration is integrated backwards)
-__device__ __forceinline__ double vp_ax_possible(double v, double rad, double mu, const gdouble* ggv, int ng, const gdouble* axm, int nam,
-                                                 bool accel, double e, double drag_over_m)
+__device__ __forceinline__ double vp_ax_from_limits(double ax_t, double ay_t, double v, double rad, const gdouble* axm, int nam, bool accel,
+                                                    double e, double drag_over_m)
 {
-    const double ax_t = fabs(mu * vp_interp(v, ggv, ng, 3, 1)), ay_t = mu * vp_interp(v, ggv, ng, 3, 2);
     const double ay_used = v * v / rad;
     const double radicand = 1.0 - pow(ay_used / ay_t, e);
     const double ax_tires = radicand > 0.0 ? ax_t * pow(radicand, 1.0 / e) : 0.0;
@@ -2381,22 +2380,50 @@ __device__ __forceinline__ double vp_ax_possible(double v, double rad, double mu
     return ax_tires - ax_drag;
 }
 
-// One thread per (track, vehicle) variant; the lap-doubled profile lives in a variant-minor scratch (S[j * batch]: coalesced
-// across the threads of a wave).  Follows tph.calc_vel_profile step by step (restated in oracle/vel_ref.py, the checker):
-//   lateral limit: fixed point of v = sqrt(ay_max(v) R) over ALL ggv rows, at most 100 rounds, stopped when the largest relative
-//     change is below 0.5 % (a NaN in that maximum -- kappa == 0 gives inf / inf -- never passes, as numpy.max behaves);
-//   forward sweep over two laps, backward sweep over the doubled SECOND lap of the forward result, second lap of that out;
+// the same with the tyre limits of the speed-dependent ggv diagram, scaled by the friction coefficient mu of the point
+__device__ __forceinline__ double vp_ax_possible(double v, double rad, double mu, const gdouble* ggv, int ng, const gdouble* axm, int nam,
+                                                 bool accel, double e, double drag_over_m)
+{
+    const double ax_t = fabs(mu * vp_interp(v, ggv, ng, 3, 1)), ay_t = mu * vp_interp(v, ggv, ng, 3, 2);
+    return vp_ax_from_limits(ax_t, ay_t, v, rad, axm, nam, accel, e, drag_over_m);
+}
+
+#define VP_RAD(i_) ((kap[(i_)] != 0.0) ? fabs(1.0 / kap[(i_)]) : (double)INFINITY)
+#define VP_MU(i_) (muv ? muv[(i_)] : 1.0)
+// ... at point i of a row: from the diagram and mu, or (LOCGG, a compile-time constant: the other arm is not compiled) from the local pair
+// lg[i] = (ax_max, ay_max) of the point -- no mu, no interpolation
+#define VP_AX(v_, i_, accel_)                                                                                                       \
+    (LOCGG ? vp_ax_from_limits(fabs(lg[2 * (size_t)(i_)]), lg[2 * (size_t)(i_) + 1], (v_), VP_RAD(i_), axm, nam, (accel_), e, dom)  \
+           : vp_ax_possible((v_), VP_RAD(i_), VP_MU(i_), ggv, ng, axm, nam, (accel_), e, dom))
+
+// One thread per (track, vehicle) variant; the profile lives in a variant-minor scratch (S[j * batch]: coalesced across the threads of a
+// wave).  Follows tph.calc_vel_profile step by step (restated in oracle/vel_ref.py, the checker).  The forms of upstream's signature are
+// compile-time parameters of this one body -- a launch has ONE form for all its variants, no step branches on a run-time flag:
+//   CLOSED (a lap) or not (a section with a start speed and optionally an end speed), LOCGG (local tyre limits per waypoint) or not (a global,
+//   speed-dependent ggv diagram, optionally scaled by a friction coefficient per waypoint).
+//   lateral limit, ggv: fixed point of v = sqrt(ay_max(v) R) over ALL ggv rows, at most 100 rounds, stopped when the largest relative
+//     change is below 0.5 % (a NaN in that maximum -- kappa == 0 gives inf / inf -- never passes, as numpy.max behaves); closed and unclosed
+//     rows alike (oracle/vel_ref.py runs the same iteration for both: THE place to change should upstream's unclosed form turn out to
+//     refine only once, include/mcq.h);  LOCGG: sqrt(ay_max_i R_i), which does not depend on the speed -- no iteration;
+//   CLOSED: forward sweep over two laps, backward sweep over the doubled SECOND lap of the forward result, second lap of that out;
+//   unclosed: cut at v_max, v[0] = min(v[0], v_start), ONE forward sweep over the n points, v[n-1] = min(v[n-1], v_end) where an end speed
+//     is given (v_end non-null and the entry not NaN), ONE backward sweep; negative v_start / v_end count as 0; the scratch holds n entries;
 //   a sweep is switched on at the first point of every acceleration phase of the profile it starts from (v[i+1] > v[i] and not
 //     v[i] > v[i-1], both on the values before the sweep touched them) and switched off where the attainable speed exceeds v_max;
 //   the backward sweep re-evaluates the deceleration one point ahead at the attainable speed and keeps the smaller speed;
-//   backward, step p -> p-1 uses el[p] (upstream flips its arrays as a whole);
+//   backward, step p -> p-1 uses el[p] on a lap (upstream flips its doubled arrays as a whole) and el[p-1], the element between the two
+//     points, on an unclosed row (its n - 1 lengths flipped as a whole);
 //   optional: a friction coefficient per waypoint (V.mu: scales both tyre limits; the first estimate of the lateral limit uses its MEAN, as
-//     upstream -- the fixed point stops on a 0.5 % change, so the start matters at that level) and tph.conv_filt's closed moving average
+//     upstream -- the fixed point stops on a 0.5 % change, so the start matters at that level) and tph.conv_filt's moving average
 //     of odd width V.filt_window over the finished profile [REF main_globaltraj.py:407, params/racecar.ini:54-57], lap time from the
-//     filtered profile.
-// A ggv / machine table that ends below v_max (upstream raises RuntimeError) gives lap_time = NaN; so does a filter window that is even
-// or wider than the ring.
-__global__ void __launch_bounds__(64) mcq_vel_profile_kernel(McqVel V)
+//     filtered profile; unclosed (tph.conv_filt(closed=False)): only entries w .. n-1-w, w = (fw - 1) / 2, are averaged, both ends keep
+//     their values bit for bit;
+//   time: sum of 2 l / (v_a + v_b) over the n elements of a lap / the n - 1 elements of an unclosed row (+inf where v_a + v_b == 0: two
+//     points from a standing start to a standstill -- the formula's own value, not an error).
+// A ggv / machine table that ends below v_max (upstream raises RuntimeError; LOCGG: the machine table alone) gives lap_time = NaN; so does a
+// filter window that is even or wider than the row, and a non-finite v_start.
+template <bool CLOSED, bool LOCGG>
+__device__ __forceinline__ void vel_profile_body(const McqVel V, const double* loc_gg, const double* v_start, const double* v_end)
 {
     const int v = blockIdx.x * 64 + threadIdx.x;
     if (v >= V.batch) return;
@@ -2413,51 +2440,62 @@ __global__ void __launch_bounds__(64) mcq_vel_profile_kernel(McqVel V)
     const size_t row = (size_t)trk * V.nmax;
     const gdouble* kap = (const gdouble*)(V.kappa + row);
     const gdouble* el = (const gdouble*)(V.el + row);
-    const gdouble* ggv = (const gdouble*)(V.ggv + (size_t)v * V.ng * 3);
+    const gdouble* ggv = LOCGG ? nullptr : (const gdouble*)(V.ggv + (size_t)v * V.ng * 3);
     const gdouble* axm = (const gdouble*)(V.axm + (size_t)v * V.nam * 2);
-    const gdouble* muv = V.mu ? (const gdouble*)(V.mu + row) : nullptr;
+    const gdouble* muv = !LOCGG && V.mu ? (const gdouble*)(V.mu + row) : nullptr;
+    const gdouble* lg = LOCGG ? (const gdouble*)(loc_gg + row * 2) : nullptr;
     const int fw = V.filt_window > 1 ? V.filt_window : 0;
     gdouble* S = (gdouble*)V.scratch + v;       // S[j * bt]
     const double vmax = V.vmax[v], e = V.dyn_exp, dom = V.drag[v] / V.mass[v];
     const int ng = V.ng, nam = V.nam;
-    if (ggv[(size_t)(ng - 1) * 3] < vmax || axm[(size_t)(nam - 1) * 2] < vmax || (fw && (fw % 2 == 0 || fw > n))) {
+    double vs = 0.0;
+    if constexpr (!CLOSED) vs = v_start[v];
+    // (LOCGG: only the machine table is range-checked; unclosed: a start speed that is not finite is flagged too)
+    if ((LOCGG ? false : ggv[(size_t)(ng - 1) * 3] < vmax) || axm[(size_t)(nam - 1) * 2] < vmax || (fw && (fw % 2 == 0 || fw > n)) ||
+        (CLOSED ? false : (vs != vs || fabs(vs) == (double)INFINITY))) {
         V.lap_time[v] = NAN;
         for (int i = 0; i < n; ++i) V.vx_out[(size_t)v * V.nmax + i] = NAN;
         return;
     }
-    double aymin = ggv[2];
-    for (int k = 1; k < ng; ++k) aymin = fmin(aymin, ggv[(size_t)k * 3 + 2]);
-#define VP_RAD(i_) ((kap[(i_)] != 0.0) ? fabs(1.0 / kap[(i_)]) : (double)INFINITY)
-#define VP_MU(i_) (muv ? muv[(i_)] : 1.0)
+    vs = vs < 0.0 ? 0.0 : vs;
 
     // ---- lateral limit ------------------------------------------------------------------------------------------------------------
-    double mu_mean = 1.0;
-    if (muv) {
-        mu_mean = 0.0;
-        for (int i = 0; i < n; ++i) mu_mean += muv[i];
-        mu_mean /= (double)n;
-    }
-    for (int i = 0; i < n; ++i) S[(size_t)i * bt] = sqrt(mu_mean * aymin * VP_RAD(i));
-    for (int it = 0; it < 100; ++it) {
-        double worst = 0.0;
-        bool any_nan = false;
-        for (int i = 0; i < n; ++i) {
-            const double vx = S[(size_t)i * bt];
-            const double vn = sqrt(VP_MU(i) * vp_interp(vx, ggv, ng, 3, 2) * VP_RAD(i));
-            const double ch = fabs(vn / vx - 1.0);
-            if (ch != ch) any_nan = true;
-            worst = fmax(worst, ch);
-            S[(size_t)i * bt] = vn;
+    if constexpr (LOCGG) {
+        for (int i = 0; i < n; ++i) S[(size_t)i * bt] = sqrt(lg[2 * (size_t)i + 1] * VP_RAD(i));
+    } else {
+        double aymin = ggv[2];
+        for (int k = 1; k < ng; ++k) aymin = fmin(aymin, ggv[(size_t)k * 3 + 2]);
+        double mu_mean = 1.0;
+        if (muv) {
+            mu_mean = 0.0;
+            for (int i = 0; i < n; ++i) mu_mean += muv[i];
+            mu_mean /= (double)n;
         }
-        if (!any_nan && worst < 0.005) break;
+        for (int i = 0; i < n; ++i) S[(size_t)i * bt] = sqrt(mu_mean * aymin * VP_RAD(i));
+        for (int it = 0; it < 100; ++it) {
+            double worst = 0.0;
+            bool any_nan = false;
+            for (int i = 0; i < n; ++i) {
+                const double vx = S[(size_t)i * bt];
+                const double vn = sqrt(VP_MU(i) * vp_interp(vx, ggv, ng, 3, 2) * VP_RAD(i));
+                const double ch = fabs(vn / vx - 1.0);
+                if (ch != ch) any_nan = true;
+                worst = fmax(worst, ch);
+                S[(size_t)i * bt] = vn;
+            }
+            if (!any_nan && worst < 0.005) break;
+        }
     }
-    // ---- lap doubled, cut at the top speed ------------------------------------------------------------------------------------------
+    // ---- cut at the top speed; the lap doubled, or the start speed on the first point of an unclosed row ---------------------------------
     for (int i = 0; i < n; ++i) {
         const double vx = fmin(S[(size_t)i * bt], vmax);
         S[(size_t)i * bt] = vx;
-        S[(size_t)(n + i) * bt] = vx;
+        if constexpr (CLOSED) S[(size_t)(n + i) * bt] = vx;
     }
-    const int m2 = 2 * n;
+    if constexpr (!CLOSED) {
+        if (S[0] > vs) S[0] = vs;
+    }
+    const int m2 = CLOSED ? 2 * n : n;
     // ---- forward: acceleration-limited --------------------------------------------------------------------------------------------
     {
         bool active = false, prev_rising = false;
@@ -2471,7 +2509,7 @@ __global__ void __launch_bounds__(64) mcq_vel_profile_kernel(McqVel V)
             prev_rising = rising;
             o_cur = nxt;
             if (active) {
-                const double ax = vp_ax_possible(cur, VP_RAD(i), VP_MU(i), ggv, ng, axm, nam, true, e, dom);
+                const double ax = VP_AX(cur, i, true);
                 const double vnext = sqrt(cur * cur + 2.0 * ax * el[i]);
                 if (vnext < nxt) { nxt = vnext; S[(size_t)(j + 1) * bt] = nxt; }
                 if (vnext > vmax) active = false;
@@ -2479,8 +2517,15 @@ __global__ void __launch_bounds__(64) mcq_vel_profile_kernel(McqVel V)
             cur = nxt;
         }
     }
-    // second lap of the forward result, doubled
-    for (int i = 0; i < n; ++i) S[(size_t)i * bt] = S[(size_t)(n + i) * bt];
+    if constexpr (CLOSED) {
+        // second lap of the forward result, doubled
+        for (int i = 0; i < n; ++i) S[(size_t)i * bt] = S[(size_t)(n + i) * bt];
+    } else if (v_end) {
+        // the end speed, where one is given, caps the last point
+        double ve = v_end[v];
+        ve = ve < 0.0 ? 0.0 : ve;
+        if (S[(size_t)(n - 1) * bt] > ve) S[(size_t)(n - 1) * bt] = ve;     // (a NaN entry -- none for this variant -- compares false)
+    }
     // ---- backward: deceleration-limited, in flipped order  q = m2 - 1 - j ------------------------------------------------------------
     {
         bool active = false, prev_rising = false;
@@ -2495,10 +2540,10 @@ __global__ void __launch_bounds__(64) mcq_vel_profile_kernel(McqVel V)
             prev_rising = rising;
             o_cur = prv;
             if (active) {
-                const double c2 = cur * cur, l2 = 2.0 * el[i];
-                const double ax = vp_ax_possible(cur, VP_RAD(i), VP_MU(i), ggv, ng, axm, nam, false, e, dom);
+                const double c2 = cur * cur, l2 = 2.0 * el[CLOSED ? i : j - 1];
+                const double ax = VP_AX(cur, i, false);
                 double vprev = sqrt(c2 + ax * l2);
-                const double ax2 = vp_ax_possible(vprev, VP_RAD(im), VP_MU(im), ggv, ng, axm, nam, false, e, dom);
+                const double ax2 = VP_AX(vprev, im, false);
                 const double vtmp = sqrt(c2 + ax2 * l2);
                 if (vtmp < vprev) vprev = vtmp;
                 if (vprev < prv) { prv = vprev; S[(size_t)(j - 1) * bt] = prv; }
@@ -2507,40 +2552,84 @@ __global__ void __launch_bounds__(64) mcq_vel_profile_kernel(McqVel V)
             cur = prv;
         }
     }
+    if constexpr (CLOSED) {
+        // ---- tph.conv_filt, closed: the mean over fw consecutive points of the ring, products summed in numpy.convolve's order; from the
+        //      second lap into the first (done with), which then is the profile --------------------------------------------------------
+        size_t lap = (size_t)n;
+        if (fw) {
+            const int hw = (fw - 1) / 2;
+            const double ker = 1.0 / (double)fw;
+            for (int i = 0; i < n; ++i) {
+                double acc = 0.0;
+                for (int d = hw; d >= -hw; --d) {
+                    int j = i + d;
+                    j = j < 0 ? j + n : j >= n ? j - n : j;
+                    acc += S[(size_t)(n + j) * bt] * ker;
+                }
+                S[(size_t)i * bt] = acc;
+            }
+            lap = 0;
+        }
+        // ---- the profile out; lap time from the piecewise-constant accelerations (tph.calc_ax_profile / calc_t_profile) -----------
+        gdouble* out = (gdouble*)(V.vx_out + (size_t)v * V.nmax);
+        double t = 0.0;
+        const double v0 = S[lap * bt];
+        double va = v0;
+        for (int i = 0; i < n; ++i) {
+            const double vb = i + 1 < n ? S[(lap + i + 1) * bt] : v0;
+            out[i] = va;
+            // constant acceleration over the element: t = 2 l / (v_a + v_b).  Algebraically tph.calc_t_profile's
+            // (-v_a + sqrt(v_a^2 + 2 a l)) / a with a = (v_b^2 - v_a^2) / (2 l), which cancels catastrophically as a -> 0 (a 1e-15
+            // ripple on a speed-limited stretch moves that expression by 0.1 s per element); this form has no such case.
+            t += 2.0 * el[i] / (va + vb);
+            va = vb;
+        }
+        V.lap_time[v] = t;
+    } else {
+        // ---- tph.conv_filt, unclosed: entries hw .. n-1-hw are the mean over the fw points around them (the same order of summation), the
+        //      ends keep their values; straight from the scratch (n entries: no room for a second copy) into the output row, the time of
+        //      the n - 1 elements along the way -------------------------------------------------------------------------------------
+        gdouble* out = (gdouble*)(V.vx_out + (size_t)v * V.nmax);
+        const int hw = fw ? (fw - 1) / 2 : n;
+        const double ker = fw ? 1.0 / (double)fw : 0.0;
+        double t = 0.0, va = 0.0;
+        for (int i = 0; i < n; ++i) {
+            double vb = S[(size_t)i * bt];
+            if (i >= hw && i <= n - 1 - hw) {
+                vb = 0.0;
+                for (int d = hw; d >= -hw; --d) vb += S[(size_t)(i + d) * bt] * ker;
+            }
+            out[i] = vb;
+            if (i) t += 2.0 * el[i - 1] / (va + vb);
+            va = vb;
+        }
+        V.lap_time[v] = t;
+    }
+}
 #undef VP_RAD
 #undef VP_MU
-    // ---- tph.conv_filt, closed: the mean over fw consecutive points of the ring, products summed in numpy.convolve's order; from the
-    //      second lap into the first (done with), which then is the profile ------------------------------------------------------------
-    size_t lap = (size_t)n;
-    if (fw) {
-        const int hw = (fw - 1) / 2;
-        const double ker = 1.0 / (double)fw;
-        for (int i = 0; i < n; ++i) {
-            double acc = 0.0;
-            for (int d = hw; d >= -hw; --d) {
-                int j = i + d;
-                j = j < 0 ? j + n : j >= n ? j - n : j;
-                acc += S[(size_t)(n + j) * bt] * ker;
-            }
-            S[(size_t)i * bt] = acc;
-        }
-        lap = 0;
-    }
-    // ---- the profile out; lap time from the piecewise-constant accelerations (tph.calc_ax_profile / calc_t_profile) -----------
-    gdouble* out = (gdouble*)(V.vx_out + (size_t)v * V.nmax);
-    double t = 0.0;
-    const double v0 = S[lap * bt];
-    double va = v0;
-    for (int i = 0; i < n; ++i) {
-        const double vb = i + 1 < n ? S[(lap + i + 1) * bt] : v0;
-        out[i] = va;
-        // constant acceleration over the element: t = 2 l / (v_a + v_b).  Algebraically tph.calc_t_profile's
-        // (-v_a + sqrt(v_a^2 + 2 a l)) / a with a = (v_b^2 - v_a^2) / (2 l), which cancels catastrophically as a -> 0 (a 1e-15
-        // ripple on a speed-limited stretch moves that expression by 0.1 s per element); this form has no such case.
-        t += 2.0 * el[i] / (va + vb);
-        va = vb;
-    }
-    V.lap_time[v] = t;
+#undef VP_AX
+
+// the form every call site of the reference uses: a lap, a global ggv diagram (mcq_vel_profile_device / _ragged / _opts)
+__global__ void __launch_bounds__(64) mcq_vel_profile_kernel(McqVel V)
+{
+    vel_profile_body<true, false>(V, nullptr, nullptr, nullptr);
+}
+
+// the other forms of tph.calc_vel_profile's signature (mcq_vel_profile_device_forms)
+__global__ void __launch_bounds__(64) mcq_vel_profile_open_kernel(McqVelForms F)
+{
+    vel_profile_body<false, false>(F.V, nullptr, F.v_start, F.v_end);
+}
+
+__global__ void __launch_bounds__(64) mcq_vel_profile_locgg_kernel(McqVelForms F)
+{
+    vel_profile_body<true, true>(F.V, F.loc_gg, nullptr, nullptr);
+}
+
+__global__ void __launch_bounds__(64) mcq_vel_profile_open_locgg_kernel(McqVelForms F)
+{
+    vel_profile_body<false, true>(F.V, F.loc_gg, F.v_start, F.v_end);
 }
 
 // ---- what main_globaltraj.py does with alpha before the velocity profile [REF main_globaltraj.py:371-387]: tph.create_raceline

@@ -89,6 +89,11 @@ class McqVelOpts(ctypes.Structure):
     _fields_ = [("dyn_model_exp", ctypes.c_double), ("filt_window", ctypes.c_int), ("reserved_", ctypes.c_int), ("mu", ctypes.c_void_p)]
 
 
+class McqVelForms(ctypes.Structure):
+    _fields_ = [("dyn_model_exp", ctypes.c_double), ("filt_window", ctypes.c_int), ("closed", ctypes.c_int), ("mu", ctypes.c_void_p),
+                ("loc_gg", ctypes.c_void_p), ("v_start", ctypes.c_void_p), ("v_end", ctypes.c_void_p)]
+
+
 class McqInfo(ctypes.Structure):
     _fields_ = [("ipm_iters", ctypes.c_int), ("as_iters", ctypes.c_int), ("n_active_box", ctypes.c_int),
                 ("n_active_kappa", ctypes.c_int), ("kappa_max", ctypes.c_double), ("kkt_res", ctypes.c_double),
@@ -107,7 +112,7 @@ EXPORTED_SYMBOLS = ("mcq_create", "mcq_destroy", "mcq_last_error", "mcq_default_
                     "mcq_iqp_device", "mcq_iqp_batch", "mcq_iqp_set_round_callback", "mcq_host_alloc", "mcq_host_free",
                     "mcq_solve_device", "mcq_solve_device_f32", "mcq_solve_device_f32_rows", "mcq_solve_batch_f32",
                     "mcq_solve_host_pipelined", "mcq_solve_device_stream", "mcq_solve_device_ragged", "mcq_solve_device_ragged_params", "mcq_prep_device", "mcq_relinearise_device",
-                    "mcq_vel_profile_device", "mcq_vel_profile_device_ragged", "mcq_vel_profile_device_opts", "mcq_raceline_device", "mcq_normals_crossing_device",
+                    "mcq_vel_profile_device", "mcq_vel_profile_device_ragged", "mcq_vel_profile_device_opts", "mcq_vel_profile_device_forms", "mcq_raceline_device", "mcq_normals_crossing_device",
                     "mcq_device_alloc",
                     "mcq_device_free", "mcq_copy_to_device", "mcq_copy_to_host", "mcq_sync", "mcq_stream",
                     "mcq_last_timing", "mcq_timing_begin", "mcq_timing_end", "mcq_workspace_bytes",
@@ -201,6 +206,9 @@ def load_library(path=None):
     lib.mcq_vel_profile_device_opts.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, ctypes.c_int, vp,
                                                 ctypes.c_int, vp, vp, vp, ctypes.POINTER(McqVelOpts), vp, vp]
     lib.mcq_vel_profile_device_opts.restype = ctypes.c_int
+    lib.mcq_vel_profile_device_forms.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, ctypes.c_int, vp,
+                                                 ctypes.c_int, vp, vp, vp, ctypes.POINTER(McqVelForms), vp, vp]
+    lib.mcq_vel_profile_device_forms.restype = ctypes.c_int
     lib.mcq_raceline_device.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, ctypes.c_double, ctypes.c_int, vp, vp,
                                         vp, vp, vp, vp]
     lib.mcq_raceline_device.restype = ctypes.c_int
@@ -690,23 +698,44 @@ class Engine:
         return [nv[k, :ns[k]].copy() for k in range(bsz)], [sc[k, :ns[k]].copy() for k in range(bsz)]
 
     def vel_profile_batch(self, kappa, el_lengths, ggv, ax_max_machines, drag_coeff, m_veh, v_max, dyn_model_exp=1.0,
-                          track_of=None, n_of_track=None, mu=None, filt_window=None):
-        """ggv velocity profiles and lap times of a batch of variants on the device (mcq_vel_profile_device; with mu -- friction
-        coefficient per waypoint, [tracks, n] -- or filt_window -- tph.conv_filt's odd moving-average width over the finished profile --
-        mcq_vel_profile_device_opts).
+                          track_of=None, n_of_track=None, mu=None, filt_window=None, closed=True, loc_gg=None, v_start=None, v_end=None,
+                          timed=False):
+        """Velocity profiles and lap times of a batch of variants on the device: tph.calc_vel_profile in all the forms of its signature
+        (mcq_vel_profile_device; with mu -- friction coefficient per waypoint, [tracks, n] -- or filt_window -- tph.conv_filt's odd
+        moving-average width over the finished profile -- mcq_vel_profile_device_opts; unclosed rows or local limits:
+        mcq_vel_profile_device_forms).
 
         kappa, el_lengths: [tracks, n]; ggv: [batch, g, 3]; ax_max_machines: [batch, m, 2]; drag_coeff, m_veh, v_max: [batch];
         track_of: [batch] ints (row of kappa / el per variant) or None when tracks == batch; n_of_track: [tracks] valid entries
-        per row (ragged tracks, mcq_vel_profile_device_ragged) or None (all rows full).  Returns (vx [batch, n], lap_time
-        [batch])."""
+        per row (ragged tracks, mcq_vel_profile_device_ragged) or None (all rows full).
+        closed=False: unclosed rows -- a row of n curvatures has n - 1 element lengths (el_lengths keeps the shape of kappa, entry n - 1 of a
+        row is not read); v_start (scalar or [batch]) is required, v_end (scalar or [batch], NaN entries: none for that variant) optional;
+        the returned time is that of the n - 1 elements (+inf for a profile that stands at both ends of an element).
+        loc_gg: [tracks, n, 2] = (ax_max, ay_max) per waypoint in place of the diagram: ggv=None, no mu.
+        Returns (vx [batch, n], lap_time [batch]); timed=True: a third entry, the milliseconds the launch took on the device (a span of
+        mcq_timing_begin / mcq_timing_end around the entry alone: no copies; after a call of the same size, no allocation either)."""
         kappa = np.ascontiguousarray(kappa, dtype=np.float64)
         el = np.ascontiguousarray(el_lengths, dtype=np.float64)
-        ggv = np.ascontiguousarray(ggv, dtype=np.float64)
         axm = np.ascontiguousarray(ax_max_machines, dtype=np.float64)
-        bsz, n = ggv.shape[0], kappa.shape[1]
+        # the argument errors of tph.calc_vel_profile, in its words
+        if (ggv is not None or mu is not None) and loc_gg is not None:
+            raise RuntimeError("Either ggv and optionally mu OR loc_gg must be supplied, not both (or all) of them!")
+        if ggv is None and loc_gg is None:
+            raise RuntimeError("Either ggv or loc_gg must be supplied!")
+        if loc_gg is not None:
+            if v_max is None:
+                raise RuntimeError("v_max must be supplied if loc_gg is used!")
+            loc_gg = np.ascontiguousarray(loc_gg, dtype=np.float64)
+            if loc_gg.shape != kappa.shape + (2,):
+                raise RuntimeError("loc_gg must have the shape [no_points, 2]!")
+        if not closed and v_start is None:
+            raise RuntimeError("v_start must be provided for the unclosed case!")
+        if ggv is not None:
+            ggv = np.ascontiguousarray(ggv, dtype=np.float64)
+        bsz, n = (ggv if ggv is not None else axm).shape[0], kappa.shape[1]
         scal = [np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float64), (bsz,))) for a in (drag_coeff, m_veh, v_max)]
         # what tph.calc_vel_profile raises on (the kernel itself flags such a variant with lap_time = NaN)
-        if np.any(ggv[:, -1, 0] < scal[2]):
+        if ggv is not None and np.any(ggv[:, -1, 0] < scal[2]):
             raise RuntimeError("ggv has to cover the entire velocity range of the car (i.e. >= v_max)!")
         if np.any(axm[:, -1, 0] < scal[2]):
             raise RuntimeError("ax_max_machines has to cover the entire velocity range of the car (i.e. >= v_max)!")
@@ -732,25 +761,42 @@ class Engine:
             self.upload(p, a)
             return p
         try:
-            d_k, d_e, d_g, d_a = up(kappa), up(el), up(ggv), up(axm)
+            d_k, d_e, d_a = up(kappa), up(el), up(axm)
+            d_g, n_g = (up(ggv), ggv.shape[1]) if ggv is not None else (None, 0)
             d_s = [up(a) for a in scal]
             d_t = up(tr) if tr is not None else None
             d_vx = self.alloc(bsz * n * 8); ptrs.append(d_vx)
             d_lt = self.alloc(bsz * 8); ptrs.append(d_lt)
-            if mu is not None or filt_window is not None:
-                vo = McqVelOpts(float(dyn_model_exp), int(filt_window or 0), 0, up(mu) if mu is not None else None)
-                rc = self.lib.mcq_vel_profile_device_opts(self.h, bsz, n, n, up(nt) if nt is not None else None, d_t, d_k, d_e, d_g,
+            d_n = up(nt) if nt is not None else None
+            d_mu = up(mu) if mu is not None else None
+            d_lg = up(loc_gg) if loc_gg is not None else None
+            d_vs = d_ve = None
+            if not closed:
+                d_vs = up(np.ascontiguousarray(np.broadcast_to(np.asarray(v_start, dtype=np.float64), (bsz,))))
+                if v_end is not None:
+                    d_ve = up(np.ascontiguousarray(np.broadcast_to(np.asarray(v_end, dtype=np.float64), (bsz,))))
+            if timed:
+                self.timing_begin()
+            if not closed or loc_gg is not None:
+                vf = McqVelForms(float(dyn_model_exp), int(filt_window or 0), 1 if closed else 0, d_mu, d_lg, d_vs, d_ve)
+                rc = self.lib.mcq_vel_profile_device_forms(self.h, bsz, n, n, d_n, d_t, d_k, d_e, d_g, n_g,
+                                                           d_a, axm.shape[1], d_s[0], d_s[1], d_s[2], ctypes.byref(vf), d_vx, d_lt)
+            elif mu is not None or filt_window is not None:
+                vo = McqVelOpts(float(dyn_model_exp), int(filt_window or 0), 0, d_mu)
+                rc = self.lib.mcq_vel_profile_device_opts(self.h, bsz, n, n, d_n, d_t, d_k, d_e, d_g,
                                                           ggv.shape[1], d_a, axm.shape[1], d_s[0], d_s[1], d_s[2], ctypes.byref(vo),
                                                           d_vx, d_lt)
             elif nt is not None:
-                rc = self.lib.mcq_vel_profile_device_ragged(self.h, bsz, n, up(nt), d_t, d_k, d_e, d_g, ggv.shape[1], d_a,
+                rc = self.lib.mcq_vel_profile_device_ragged(self.h, bsz, n, d_n, d_t, d_k, d_e, d_g, ggv.shape[1], d_a,
                                                             axm.shape[1], d_s[0], d_s[1], d_s[2], float(dyn_model_exp),
                                                             d_vx, d_lt)
             else:
                 rc = self.lib.mcq_vel_profile_device(self.h, bsz, n, n, d_t, d_k, d_e, d_g, ggv.shape[1], d_a, axm.shape[1],
                                                      d_s[0], d_s[1], d_s[2], float(dyn_model_exp), d_vx, d_lt)
             self._check(rc, "mcq_vel_profile_device")
-            return self.download(d_vx, (bsz, n), np.float64), self.download(d_lt, (bsz,), np.float64)
+            ms = self.timing_end()[0] if timed else None
+            res = (self.download(d_vx, (bsz, n), np.float64), self.download(d_lt, (bsz,), np.float64))
+            return res + (ms,) if timed else res
         finally:
             for p in ptrs:
                 self.free(p)

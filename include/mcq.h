@@ -299,6 +299,42 @@ int mcq_vel_profile_device_opts(mcq_handle* h, int batch, int n, int nmax, const
                                 const double* ax_max_machines, int n_machines, const double* drag_coeff, const double* m_veh,
                                 const double* v_max, const mcq_vel_opts* opts, double* vx_out, double* lap_time_out);
 
+/* The whole signature of tph.calc_vel_profile on the device: the entry above plus its two other forms.
+ *   closed == 0 -- UNCLOSED rows: a row of n curvatures has n - 1 element lengths (el_lengths keeps the layout [tracks][nmax]; entry n - 1
+ *     of a row is not read).  After the lateral limit and the cut at v_max, v[0] = min(v[0], v_start); one forward sweep over the n points (the
+ *     lap is not doubled); v[n-1] = min(v[n-1], v_end) where an end speed is given; one backward sweep.  v_start: DEVICE [batch], required.
+ *     v_end: DEVICE [batch], or NULL (no variant has one); a NaN entry means none for that variant.  Negative v_start / v_end count as 0, as
+ *     upstream.  filt_window is tph.conv_filt(closed=False): only entries w .. n-1-w, w = (filt_window - 1) / 2, are averaged, both ends
+ *     keep their unfiltered values bit for bit.  lap_time_out is the time over the n - 1 elements, sum of 2 l / (v_a + v_b): +inf where
+ *     v_a + v_b == 0 (two points, v_start = v_end = 0) -- the formula's own value, not an error and not a NaN.
+ *     With closed != 0, v_start and v_end are not read.
+ *   loc_gg -- LOCAL LIMITS: DEVICE [tracks][nmax][2] = (ax_max, ay_max) per waypoint, indexed like kappa / mu, in place of the diagram, for
+ *     closed and unclosed rows.  Then ggv must be NULL, n_ggv 0 and mu NULL (upstream's "either ggv and optionally mu OR loc_gg"); anything
+ *     else, and neither ggv nor loc_gg, is MCQ_E_ARG.  The lateral limit is sqrt(ay_max_i R_i) without iteration; a step takes |ax_max| and
+ *     ay_max of the point it leaves, the look-ahead of the backward sweep those of the point it reaches; machine table and drag as before.
+ *     Only the machine table is range-checked against v_max.
+ *   dyn_model_exp, filt_window, mu: as in mcq_vel_opts.  The other arguments: as in mcq_vel_profile_device_opts.  The caller owns every
+ *     buffer; the handle owns the scratch ([2 nmax][batch] doubles for closed rows, [nmax][batch] for unclosed ones, grown on demand).
+ * NaN rules: lap_time NaN and a vx_out row of NaNs for a bad row length (n < 2, n > nmax), a ggv / machine table that ends below v_max, an
+ *   even filter window or one wider than the row, and a non-finite v_start.
+ * CAVEAT (open question): the lateral limit of the unclosed + ggv form is iterated exactly as for closed rows (first estimate from the mean
+ *   mu, at most 100 rounds, 0.5 %), because the project's specification oracle/vel_ref.py does so.  Whether upstream iterates there or refines
+ *   once could not be checked against the package itself; the kernel keeps that step in one place.
+ * Asynchronous on the handle's stream. */
+typedef struct mcq_vel_forms {
+    double dyn_model_exp;
+    int filt_window;
+    int closed;
+    const double* mu;
+    const double* loc_gg;
+    const double* v_start;
+    const double* v_end;
+} mcq_vel_forms;
+int mcq_vel_profile_device_forms(mcq_handle* h, int batch, int n, int nmax, const int* n_of_track, const int* track_of,
+                                 const double* kappa, const double* el_lengths, const double* ggv, int n_ggv,
+                                 const double* ax_max_machines, int n_machines, const double* drag_coeff, const double* m_veh,
+                                 const double* v_max, const mcq_vel_forms* forms, double* vx_out, double* lap_time_out);
+
 /* What main_globaltraj.py runs between the QP and the velocity profile [REF main_globaltraj.py:371-387], batched on the device:
  * tph.create_raceline (raceline = refline + alpha * normal, closed cubic spline through it with unit scalings, re-sampled at
  * ~stepsize = stepsize_interp_after_opt) and tph.calc_head_curv_an (heading and curvature from the spline's derivatives).

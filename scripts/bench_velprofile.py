@@ -2,7 +2,11 @@
 """Measurement for row f-3: ggv velocity profile + lap time of 16384 (track, vehicle) variants -- BASELINE config 4's sweep
 size -- on the racelines of the committed reference tracks; the host chain timed on a sample beside it.  One JSON line.
 
-  python scripts/bench_velprofile.py [--variants 16384] [--cpu-sample 16]
+  python scripts/bench_velprofile.py [--variants 16384] [--cpu-sample 16] [--form closed|open|locgg|open_locgg] [--kernel-runs 3]
+
+--form: the same variants on the other forms of tph.calc_vel_profile (mcq_vel_profile_device_forms) -- open: the raceline cut open (its closing
+element dropped), v_start = 0, no v_end; locgg: a synthetic per-waypoint loc_gg (12 m/s^2 +- 10 % along the lap, scaled per variant as the
+diagram is) in place of the diagram.  kernel_ms: the launch alone, timed on the device (no copies, no allocation), one entry per run.
 """
 import argparse
 import json
@@ -24,7 +28,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--variants", type=int, default=16384)
     ap.add_argument("--cpu-sample", type=int, default=16)
+    ap.add_argument("--form", choices=("closed", "open", "locgg", "open_locgg"), default="closed")
+    ap.add_argument("--kernel-runs", type=int, default=3)
     args = ap.parse_args()
+    closed, local = args.form in ("closed", "locgg"), "locgg" in args.form
     eng = engine.Engine(0)
     g = np.load(os.path.join(ROOT, "tests", "golden", "berlin_2018.npz"))
     out = cr.create_raceline(refline=g["reftrack"][:, :2], normvectors=g["normvec"], alpha=g["alpha"], stepsize_interp=3.0)
@@ -41,24 +48,41 @@ def main():
     ggv[:, :, 1:] *= scales[:, None, None]
     axms = np.repeat(axm[None], bsz, axis=0)
     tr = np.zeros(bsz, dtype=np.int32)
-    eng.vel_profile_batch(kappa[None], el[None], ggv[:64], axms[:64], 0.75, 1200.0, tops[:64], 1.0, tr[:64])     # warm-up
+    kap_rows, el_rows, kw = kappa[None], el[None], {}
+    if not closed:
+        kw.update(closed=False, v_start=0.0)            # (el keeps its shape: entry n - 1, the closing element, is not read)
+    if local:
+        # one row of local limits per scale (128 of them), the raceline repeated under each: the variants of the diagram's sweep
+        lg_row = 12.0 * (1.0 + 0.1 * np.column_stack((np.sin(0.05 * np.arange(n)), np.cos(0.03 * np.arange(n)))))
+        loc_gg = lg_row[None] * (0.3 + 0.7 * np.arange(128) / 127.0)[:, None, None]
+        kap_rows, el_rows, tr = np.repeat(kappa[None], 128, axis=0), np.repeat(el[None], 128, axis=0), (np.arange(bsz) % 128).astype(np.int32)
+        ggv = None
+        kw.update(loc_gg=loc_gg)
+
+    def launch(sl=slice(None), **more):
+        return eng.vel_profile_batch(kap_rows, el_rows, None if local else ggv[sl], axms[sl], 0.75, 1200.0, tops[sl], 1.0, tr[sl], **kw, **more)
+    launch(slice(0, 64))                                # warm-up
     t0 = time.perf_counter()
-    vx, lt = eng.vel_profile_batch(kappa[None], el[None], ggv, axms, 0.75, 1200.0, tops, 1.0, tr)
+    vx, lt = launch()
     t_gpu = time.perf_counter() - t0                    # includes the PCIe copies of the tables and of the profiles
+    kernel_ms = [launch(timed=True)[2] for _ in range(args.kernel_runs)]
     ks = np.linspace(0, bsz - 1, args.cpu_sample).astype(int)
     t0 = time.perf_counter()
     worst, worst_t_host = 0.0, 0.0
+    el_h = el if closed else el[:-1]
     for k in ks:
-        vx_h = cv.calc_vel_profile(ggv=ggv[k], ax_max_machines=axm, v_max=tops[k], kappa=kappa, el_lengths=el, closed=True,
-                                   filt_window=None, dyn_model_exp=1.0, drag_coeff=0.75, m_veh=1200.0)
-        ax_h = ca.calc_ax_profile(vx_profile=np.append(vx_h, vx_h[0]), el_lengths=el, eq_length_output=False)
-        t_h = ct.calc_t_profile(vx_profile=vx_h, ax_profile=ax_h, el_lengths=el)
-        vx_cl = np.append(vx_h, vx_h[0])
-        worst = max(worst, float(np.max(np.abs(vx[k] - vx_h))), abs(float(lt[k] - np.sum(2.0 * el / (vx_cl[:-1] + vx_cl[1:])))))
+        vx_h = cv.calc_vel_profile(ggv=None if local else ggv[k], loc_gg=loc_gg[tr[k]] if local else None, ax_max_machines=axm, v_max=tops[k],
+                                   kappa=kappa, el_lengths=el_h, closed=closed, filt_window=None, dyn_model_exp=1.0, drag_coeff=0.75,
+                                   m_veh=1200.0, v_start=None if closed else 0.0)
+        vx_cl = np.append(vx_h, vx_h[0]) if closed else vx_h
+        ax_h = ca.calc_ax_profile(vx_profile=vx_cl, el_lengths=el_h, eq_length_output=False)
+        t_h = ct.calc_t_profile(vx_profile=vx_h, ax_profile=ax_h, el_lengths=el_h)
+        worst = max(worst, float(np.max(np.abs(vx[k] - vx_h))), abs(float(lt[k] - np.sum(2.0 * el_h / (vx_cl[:-1] + vx_cl[1:])))))
         worst_t_host = max(worst_t_host, abs(float(lt[k] - t_h[-1])))
     t_cpu = (time.perf_counter() - t0) / len(ks)
-    print(json.dumps({"variants": bsz, "n": int(n), "track": "berlin_2018 raceline", "gpu_seconds_incl_pcie": t_gpu,
-                      "variants_per_s_gpu": bsz / t_gpu, "cpu_seconds_per_variant": t_cpu, "variants_per_s_cpu_1core": 1.0 / t_cpu,
+    print(json.dumps({"variants": bsz, "n": int(n), "track": "berlin_2018 raceline", "form": args.form, "gpu_seconds_incl_pcie": t_gpu,
+                      "variants_per_s_gpu": bsz / t_gpu, "kernel_ms": kernel_ms,
+                      "variants_per_s_kernel": (bsz / (1e-3 * min(kernel_ms))) if kernel_ms else None, "cpu_seconds_per_variant": t_cpu, "variants_per_s_cpu_1core": 1.0 / t_cpu,
                       "cpu_sample": len(ks), "max_abs_diff_vs_host": worst, "max_lap_time_diff_vs_host_unstable_formula_s": worst_t_host,
                       "lap_time_range_s": [float(lt.min()), float(lt.max())]}))
 
