@@ -23,41 +23,47 @@
 
 static thread_local std::string g_err;
 
-#define HIP_TRY(expr)                                                                                     \
-    do {                                                                                                  \
-        hipError_t e_ = (expr);                                                                           \
-        if (e_ != hipSuccess) {                                                                           \
-            char buf_[512];                                                                               \
-            snprintf(buf_, sizeof(buf_), "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, \
-                     __LINE__);                                                                           \
-            g_err = buf_;                                                                                 \
-            return MCQ_E_DEVICE;                                                                          \
-        }                                                                                                 \
-    } while (0)
+// A compute stream and the device workspace ("slabs") of the solver launches on it.  The handle has two: [0] serves every entry; [1] is
+// mcq_solve_host_pipelined's and mcq_solve_device_stream's SECOND compute stream with a workspace of its own -- the kernels of consecutive
+// steps run on alternating streams, so the tail of one launch (its slowest problems, on CUs the others have left) overlaps the start of the
+// next (round 5).  What only [0] has stays in the handle: state2 and the warm start, the small Goldfarb-Idnani pool, the event timing.
+struct Workspace {
+    hipStream_t stream = nullptr;       // [0]: created with the handle; [1]: on first use (ensure_workspace, ensure_slice_streams)
+    double *L = nullptr, *vec = nullptr, *Z = nullptr;
+    signed char* state = nullptr;
+    double* kbig = nullptr;             // overflow slots of the curvature-row working set (MCQ_KBIG_SLOTS x MCQ_KBIG_SLOT doubles)
+    int* slot_flags = nullptr;          // [MCQ_SLOT_FLAGS] = overflow slots | full Goldfarb-Idnani slots | small ones: 0 free / 1 taken, claimed and released by the workgroups (never reset by the host)
+    double* gi = nullptr;               // FULL slots of the Goldfarb-Idnani path (mcq_gi.inc): gi_slots x MCQ_GI_SLOT_DOUBLES(gi_nmax, gi_nmax)
+    int gi_slots = 0, gi_nmax = 0;      // ([1]: gi_nmax is the ring size the workspace was sized for, with or without slots)
+    size_t elems = 0, batch = 0;        // batch * nmax, and the batch, the slabs are sized for
+    long long bytes = 0;                // of mcq_workspace_bytes.  [0]: the slabs (its pools are counted in gi_bytes / gis_bytes); [1]: slabs and slots
+};
+
+// One set of device buffers a uniform or padded batch is staged in.  The handle has two: [0] serves every host-buffer entry, [1] is the second
+// slot of mcq_solve_host_pipelined.
+struct Staging {
+    double *ref = nullptr, *nv = nullptr, *sc = nullptr, *alpha = nullptr, *curv = nullptr;
+    int* status = nullptr;
+    size_t elems = 0, batch = 0;
+};
 
 struct mcq_handle {
     int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    Workspace ws[2];
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};      // launches on ws[0] only, like timing_valid and span_launches
     bool timing_valid = false;
     hipEvent_t ev_st[2] = {nullptr, nullptr};       // mcq_solve_device_stream: joins the second compute stream to the first and back
     hipEvent_t ev_span[2] = {nullptr, nullptr};     // mcq_timing_begin / mcq_timing_end: a span of launches on the compute stream
     int span_launches = 0;
     bool span_open = false;
-    // workspace slabs
-    size_t cap_elems = 0;   // batch * nmax the slabs are sized for
-    size_t cap_batch = 0;
-    double *L = nullptr, *vec = nullptr, *Z = nullptr;
-    signed char* state = nullptr;
     signed char* state2 = nullptr;     // working sets carried through the IQP glue (warm start of the next pass)
     bool state2_valid = false;
     int state2_batch = 0, state2_nmax = 0;   // the layout mcq_relinearise_device wrote state2 with: a warm start is honoured only for it
-    // staging for the host-buffer entry point
-    double *d_ref = nullptr, *d_nv = nullptr, *d_sc = nullptr, *d_alpha = nullptr, *d_curv = nullptr, *d_kb = nullptr,
-           *d_wv = nullptr;
-    int *d_n = nullptr, *d_status = nullptr;
+    Staging stage[2];
+    // what exists once, allocated and freed with stage[0]
+    double *d_kb = nullptr, *d_wv = nullptr;
+    int* d_n = nullptr;
     mcq_info* d_info = nullptr;
-    size_t stage_elems = 0, stage_batch = 0;
     double *d_ref2 = nullptr, *d_nv2 = nullptr;      // second set of the IQP double buffer (mcq_iqp_batch)
     size_t stage2_elems = 0;
     int* d_iqp = nullptr;                             // bookkeeping arrays of mcq_iqp_device, 8 ints per track + 1
@@ -68,7 +74,6 @@ struct mcq_handle {
     bool poison = false;    // MCQ_POISON=1 (debugging aid): every workspace / staging allocation is filled with 0xFF bytes (NaN as a
                             // double), so that a read of memory nothing has written shows up as a wrong result on every box instead of
                             // on the rare one whose recycled memory happens to hold garbage
-    long long ws_bytes = 0;
     bool smem_attr_set = false;
     double* vel_scratch = nullptr;      // profiles of mcq_vel_profile_device*, [2 nmax][batch] (the lap doubled) or [nmax][batch] (unclosed rows)
     mcq_iqp_round_cb iqp_cb = nullptr;  // mcq_iqp_set_round_callback
@@ -79,37 +84,51 @@ struct mcq_handle {
     hipEvent_t comm_ready = nullptr, comm_t0[4] = {nullptr, nullptr, nullptr, nullptr}, comm_done[4] = {nullptr, nullptr, nullptr, nullptr};
     unsigned comm_seq = 0;              // gathers enqueued so far (event ring index)
     size_t vel_scratch_bytes = 0;
-    double* kbig = nullptr;             // overflow slots of the curvature-row working set (MCQ_KBIG_SLOTS x MCQ_KBIG_SLOT doubles)
-    int* slot_flags = nullptr;          // [MCQ_SLOT_FLAGS] = overflow slots | full Goldfarb-Idnani slots | small ones: 0 free / 1 taken, claimed and released by the workgroups (never reset by the host)
-    double* gi = nullptr;               // FULL slots of the Goldfarb-Idnani path (mcq_gi.inc): gi_slots x MCQ_GI_SLOT_DOUBLES(gi_nmax, gi_nmax)
-    int gi_slots = 0, gi_nmax = 0;
-    long long gi_bytes = 0;
-    size_t gi_none_nmax = 0;            // > 0: no full slot could be had for rings of this many waypoints (beyond the byte cap, or hipMalloc said no) -- not tried again
+    long long gi_bytes = 0;             // ws[0]'s full slots
+    size_t gi_none_nmax = 0;           // > 0: no full slot could be had for rings of this many waypoints (beyond the byte cap, or hipMalloc said no) -- not tried again
     double* gis = nullptr;              // SMALL slots (MCQ_ALG_GI: one per resident workgroup): gis_slots x MCQ_GI_SLOT_DOUBLES(gis_nmax, gi_small_qcap(gis_nmax))
     int gis_slots = 0, gis_nmax = 0;
     long long gis_bytes = 0;
-    // mcq_solve_host_pipelined: a SECOND compute stream with a workspace of its own -- the kernels of consecutive steps run on alternating
-    // streams, so the tail of one launch (its slowest problems, on CUs the others have left) overlaps the start of the next (round 5)
-    hipStream_t stream2 = nullptr;
-    double *L2 = nullptr, *vec2 = nullptr, *Z2 = nullptr, *kbig2 = nullptr, *gi2 = nullptr;
-    signed char* state_alt = nullptr;
-    int* slot_flags2 = nullptr;
-    size_t alt_elems = 0, alt_batch = 0;
-    int gi2_slots = 0, gi2_nmax = 0;
-    long long alt_bytes = 0;
     double* d_org = nullptr;            // per-track origins of the fp32 row entries, [batch][2]
     double* d_trace = nullptr;          // curvature-error trace of mcq_iqp_batch, [batch][MCQ_IQP_TRACE] (grown with d_iqp)
-    // mcq_solve_host_pipelined: two copy streams, the second set of staging buffers, one event triple per slot
+    // mcq_solve_host_pipelined: two copy streams, one event triple per staging slot
     hipStream_t cs_in = nullptr, cs_out = nullptr;
     hipEvent_t ev_up[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr}, ev_down[2] = {nullptr, nullptr};
     hipEvent_t ev_slice[16] = {};      // mcq_solve_host / mcq_solve_batch in slices: upload / kernel done, per slice
     int last_upload_direct = 0;         // the last host-buffer batch went up without the packing pass (mcq_last_upload_was_direct)
-    double *p_ref = nullptr, *p_nv = nullptr, *p_sc = nullptr, *p_alpha = nullptr, *p_curv = nullptr;
-    int* p_status = nullptr;
-    size_t pipe_elems = 0, pipe_batch = 0;
     mcq_ends* d_ends = nullptr;         // per-problem ring / open-chain records of mcq_solve_batch_ends (device), ends_cap of them
     size_t ends_cap = 0;
 };
+
+// ---- the one error path of the HIP calls ----------------------------------------------------------------------------------------
+// the message callers and tests match on: "<expr> failed: <hip error> (<file>:<line>)"
+static int hip_failed(const char* expr, hipError_t e, const char* file, int line)
+{
+    char buf[512];
+    snprintf(buf, sizeof(buf), "%s failed: %s (%s:%d)", expr, hipGetErrorString(e), file, line);
+    g_err = buf;
+    return MCQ_E_DEVICE;
+}
+
+// every stream the handle has created is drained: copies from / into the caller's buffers (or the pinned staging) may still be queued on any of them
+static void drain(mcq_handle* h)
+{
+    for (hipStream_t st : {h->cs_in, h->ws[0].stream, h->ws[1].stream, h->cs_out, h->comm_stream})
+        if (st) (void)hipStreamSynchronize(st);
+}
+
+// HIP_TRY returns only: the device-resident, asynchronous entries and the allocations, which leave nothing queued on the caller's host memory.
+// HIP_TRY_DRAIN(expr), in a function with the handle `h`: the host-buffer entries, whose caller may free or reuse its buffers on return.
+#define HIP_TRY(expr)                                                                             \
+    do {                                                                                          \
+        hipError_t e_ = (expr);                                                                   \
+        if (e_ != hipSuccess) return hip_failed(#expr, e_, __FILE__, __LINE__);                   \
+    } while (0)
+#define HIP_TRY_DRAIN(expr)                                                                       \
+    do {                                                                                          \
+        hipError_t e_ = (expr);                                                                   \
+        if (e_ != hipSuccess) { drain(h); return hip_failed(#expr, e_, __FILE__, __LINE__); }     \
+    } while (0)
 
 extern "C" const char* mcq_last_error(void) { return g_err.c_str(); }
 
@@ -158,7 +177,7 @@ extern "C" int mcq_create(int device_id, mcq_handle** out)
         const char* e = getenv("MCQ_POISON");
         h->poison = e && e[0] == '1';
     }
-    hipError_t e = hipStreamCreate(&h->stream);
+    hipError_t e = hipStreamCreate(&h->ws[0].stream);
     for (int k = 0; k < 5 && e == hipSuccess; ++k) e = hipEventCreate(&h->ev[k]);
     if (e != hipSuccess) {
         g_err = std::string("mcq_create: ") + hipGetErrorString(e);
@@ -169,73 +188,58 @@ extern "C" int mcq_create(int device_id, mcq_handle** out)
     return 0;
 }
 
-static void free_ws(mcq_handle* h)
+static void free_workspace(mcq_handle* h, int which)
 {
-    (void)hipFree(h->L); (void)hipFree(h->vec); (void)hipFree(h->Z); (void)hipFree(h->state);
-    (void)hipFree(h->state2);
-    (void)hipFree(h->kbig); (void)hipFree(h->slot_flags); (void)hipFree(h->gi); (void)hipFree(h->gis);
-    h->kbig = nullptr; h->slot_flags = nullptr; h->gi = nullptr; h->gis = nullptr;
-    h->gi_slots = h->gi_nmax = 0;
-    h->gis_slots = h->gis_nmax = 0;
-    h->gi_bytes = h->gis_bytes = 0;
-    h->L = h->vec = h->Z = nullptr;
-    h->state = h->state2 = nullptr;
-    h->state2_valid = false;
-    h->cap_elems = h->cap_batch = 0;
+    Workspace& w = h->ws[which];
+    (void)hipFree(w.L); (void)hipFree(w.vec); (void)hipFree(w.Z); (void)hipFree(w.state); (void)hipFree(w.kbig);
+    (void)hipFree(w.slot_flags); (void)hipFree(w.gi);
+    const Workspace old = w;
+    w = Workspace();
+    w.stream = old.stream;
+    if (which == 0) {
+        w.bytes = old.bytes;            // (kept until the next successful growth, as ever: docs/NOTEBOOK.md, "Host API")
+        (void)hipFree(h->state2); (void)hipFree(h->gis);
+        h->state2 = nullptr;
+        h->gis = nullptr;
+        h->gis_slots = h->gis_nmax = 0;
+        h->gi_bytes = h->gis_bytes = 0;
+        h->state2_valid = false;
+    }
 }
 
-static void free_alt(mcq_handle* h)
+// stage[0] takes what exists once with it: the per-problem scalars and records, the IQP double buffer and bookkeeping
+static void free_staging(mcq_handle* h, int which)
 {
-    (void)hipFree(h->L2); (void)hipFree(h->vec2); (void)hipFree(h->Z2); (void)hipFree(h->state_alt); (void)hipFree(h->kbig2);
-    (void)hipFree(h->slot_flags2); (void)hipFree(h->gi2);
-    h->L2 = h->vec2 = h->Z2 = h->kbig2 = h->gi2 = nullptr;
-    h->state_alt = nullptr;
-    h->slot_flags2 = nullptr;
-    h->alt_elems = h->alt_batch = 0;
-    h->gi2_slots = h->gi2_nmax = 0;
-    h->alt_bytes = 0;
-}
-
-static void free_stage(mcq_handle* h)
-{
-    (void)hipFree(h->d_ref); (void)hipFree(h->d_nv); (void)hipFree(h->d_sc); (void)hipFree(h->d_alpha); (void)hipFree(h->d_curv); (void)hipFree(h->d_kb);
-    (void)hipFree(h->d_wv); (void)hipFree(h->d_n); (void)hipFree(h->d_status); (void)hipFree(h->d_info);
-    h->d_ref = h->d_nv = h->d_sc = h->d_alpha = h->d_curv = h->d_kb = h->d_wv = nullptr;
-    h->d_n = h->d_status = nullptr;
-    h->d_info = nullptr;
-    h->stage_elems = h->stage_batch = 0;
-    (void)hipFree(h->d_ref2); (void)hipFree(h->d_nv2); (void)hipFree(h->d_iqp); (void)hipFree(h->d_iqp_curv);
-    h->d_ref2 = h->d_nv2 = h->d_iqp_curv = nullptr;
-    h->d_iqp = nullptr;
-    h->stage2_elems = h->iqp_batch = 0;
-    (void)hipFree(h->d_org); (void)hipFree(h->d_trace);
-    h->d_org = h->d_trace = nullptr;
-}
-
-static void free_pipe(mcq_handle* h)
-{
-    (void)hipFree(h->p_ref); (void)hipFree(h->p_nv); (void)hipFree(h->p_sc); (void)hipFree(h->p_alpha); (void)hipFree(h->p_curv); (void)hipFree(h->p_status);
-    h->p_ref = h->p_nv = h->p_sc = h->p_alpha = h->p_curv = nullptr;
-    h->p_status = nullptr;
-    h->pipe_elems = h->pipe_batch = 0;
+    Staging& s = h->stage[which];
+    (void)hipFree(s.ref); (void)hipFree(s.nv); (void)hipFree(s.sc); (void)hipFree(s.alpha); (void)hipFree(s.curv); (void)hipFree(s.status);
+    s = Staging();
+    if (which == 0) {
+        (void)hipFree(h->d_kb); (void)hipFree(h->d_wv); (void)hipFree(h->d_n); (void)hipFree(h->d_info);
+        h->d_kb = h->d_wv = nullptr;
+        h->d_n = nullptr;
+        h->d_info = nullptr;
+        (void)hipFree(h->d_ref2); (void)hipFree(h->d_nv2); (void)hipFree(h->d_iqp); (void)hipFree(h->d_iqp_curv);
+        h->d_ref2 = h->d_nv2 = h->d_iqp_curv = nullptr;
+        h->d_iqp = nullptr;
+        h->stage2_elems = h->iqp_batch = 0;
+        (void)hipFree(h->d_org); (void)hipFree(h->d_trace);
+        h->d_org = h->d_trace = nullptr;
+    }
 }
 
 extern "C" void mcq_destroy(mcq_handle* h)
 {
     if (!h) return;
     (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    if (h->ws[0].stream) (void)hipStreamSynchronize(h->ws[0].stream);
     if (h->cs_in) (void)hipStreamSynchronize(h->cs_in);
     if (h->cs_out) (void)hipStreamSynchronize(h->cs_out);
     (void)mcq_comm_destroy(h);
-    if (h->stream2) (void)hipStreamSynchronize(h->stream2);
-    free_ws(h);
-    free_alt(h);
-    free_stage(h);
-    free_pipe(h);
+    if (h->ws[1].stream) (void)hipStreamSynchronize(h->ws[1].stream);
+    for (int k = 0; k < 2; ++k) { free_workspace(h, k); free_staging(h, k); }
     (void)hipFree(h->d_ends);
     h->d_ends = nullptr;
-    if (h->stream2) (void)hipStreamDestroy(h->stream2);
+    if (h->ws[1].stream) (void)hipStreamDestroy(h->ws[1].stream);
     for (int k = 0; k < 2; ++k) {
         if (h->ev_up[k]) (void)hipEventDestroy(h->ev_up[k]);
         if (h->ev_done[k]) (void)hipEventDestroy(h->ev_done[k]);
@@ -249,7 +253,7 @@ extern "C" void mcq_destroy(mcq_handle* h)
     for (int k = 0; k < 5; ++k) if (h->ev[k]) (void)hipEventDestroy(h->ev[k]);
     for (int k = 0; k < 2; ++k) if (h->ev_span[k]) (void)hipEventDestroy(h->ev_span[k]);
     for (int k = 0; k < 2; ++k) if (h->ev_st[k]) (void)hipEventDestroy(h->ev_st[k]);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
+    if (h->ws[0].stream) (void)hipStreamDestroy(h->ws[0].stream);
     delete h;
 }
 
@@ -289,8 +293,10 @@ static int alloc_slots(double** out, int slots, size_t per)
     return 0;
 }
 
+// the full pool of workspace 0, regrown on its own
 static void ensure_gi(mcq_handle* h, size_t batch, size_t nmax)
 {
+    Workspace& w = h->ws[0];
     if (h->gi_none_nmax && nmax >= h->gi_none_nmax) return;
     const size_t cap_bytes = gi_byte_cap();
     int want = MCQ_GI_FULL_MAX;
@@ -298,21 +304,21 @@ static void ensure_gi(mcq_handle* h, size_t batch, size_t nmax)
     const size_t per = MCQ_GI_SLOT_DOUBLES(nmax, nmax) * sizeof(double);
     int slots = (int)std::min<size_t>((size_t)want, cap_bytes / per);
     slots = (int)std::min<size_t>((size_t)slots, std::max<size_t>(batch, 1));
-    if (h->gi && (size_t)h->gi_nmax >= nmax && h->gi_slots >= slots) return;
-    nmax = std::max(nmax, (size_t)h->gi_nmax);
+    if (w.gi && (size_t)w.gi_nmax >= nmax && w.gi_slots >= slots) return;
+    nmax = std::max(nmax, (size_t)w.gi_nmax);
     const size_t per2 = MCQ_GI_SLOT_DOUBLES(nmax, nmax) * sizeof(double);
-    slots = std::max(slots, h->gi_slots);
+    slots = std::max(slots, w.gi_slots);
     slots = (int)std::min<size_t>((size_t)slots, cap_bytes / per2);
-    (void)hipStreamSynchronize(h->stream);
-    (void)hipFree(h->gi);
-    h->gi = nullptr;
-    h->gi_slots = h->gi_nmax = 0;
+    (void)hipStreamSynchronize(w.stream);
+    (void)hipFree(w.gi);
+    w.gi = nullptr;
+    w.gi_slots = w.gi_nmax = 0;
     h->gi_bytes = 0;
-    slots = alloc_slots(&h->gi, slots, per2);
+    slots = alloc_slots(&w.gi, slots, per2);
     if (slots < 1) { h->gi_none_nmax = nmax; return; }
-    if (h->poison) (void)hipMemsetAsync(h->gi, 0xff, (size_t)slots * per2, h->stream);
-    h->gi_slots = slots;
-    h->gi_nmax = (int)nmax;
+    if (h->poison) (void)hipMemsetAsync(w.gi, 0xff, (size_t)slots * per2, w.stream);
+    w.gi_slots = slots;
+    w.gi_nmax = (int)nmax;
     h->gi_bytes = (long long)((size_t)slots * per2);
 }
 
@@ -326,137 +332,155 @@ static int ensure_gi_small(mcq_handle* h, size_t batch, size_t nmax)
         const size_t per = MCQ_GI_SLOT_DOUBLES(nmax, gi_small_qcap(nmax)) * sizeof(double);
         const size_t cap_bytes = std::max(gi_byte_cap(), (size_t)8 << 30);
         slots = (int)std::min<size_t>((size_t)slots, cap_bytes / per);
-        (void)hipStreamSynchronize(h->stream);
+        (void)hipStreamSynchronize(h->ws[0].stream);
         (void)hipFree(h->gis);
         h->gis = nullptr;
         h->gis_slots = h->gis_nmax = 0;
         h->gis_bytes = 0;
         slots = alloc_slots(&h->gis, slots, per);
         if (slots >= 1) {
-            if (h->poison) (void)hipMemsetAsync(h->gis, 0xff, (size_t)slots * per, h->stream);
+            if (h->poison) (void)hipMemsetAsync(h->gis, 0xff, (size_t)slots * per, h->ws[0].stream);
             h->gis_slots = slots;
             h->gis_nmax = (int)nmax;
             h->gis_bytes = (long long)((size_t)slots * per);
         }
     }
-    if (!h->gis && !h->gi) { g_err = "MCQ_ALG_GI: no device memory for a Goldfarb-Idnani slot at this ring size"; return MCQ_E_DEVICE; }
+    if (!h->gis && !h->ws[0].gi) { g_err = "MCQ_ALG_GI: no device memory for a Goldfarb-Idnani slot at this ring size"; return MCQ_E_DEVICE; }
     return 0;
 }
 
-static int ensure_ws(mcq_handle* h, size_t batch, size_t nmax)
+// Workspace `which`, grown to batch x nmax.  The two differ in what the handle keeps once: workspace 0 carries state2 (two state bytes per
+// element in its byte count against one) and regrows its full Goldfarb-Idnani pool on its own, counted apart (ensure_gi); workspace 1 -- the
+// second compute stream, created here -- takes half of workspace 0's full slots when it is sized, counted with its slabs, and is sized anew
+// for longer rings than those slots hold.
+static int ensure_workspace(mcq_handle* h, int which, size_t batch, size_t nmax)
 {
+    Workspace& w = h->ws[which];
+    if (!w.stream) HIP_TRY(hipStreamCreate(&w.stream));
     const size_t elems = batch * nmax;
-    if (elems <= h->cap_elems && batch <= h->cap_batch) { ensure_gi(h, batch, nmax); return 0; }
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    free_ws(h);
-    HIP_TRY(hipMalloc((void**)&h->L, elems * MCQ_LLD * sizeof(double)));
-    HIP_TRY(hipMalloc((void**)&h->vec, elems * MCQ_NVEC * sizeof(double)));
-    HIP_TRY(hipMalloc((void**)&h->Z, (elems + batch * (size_t)MCQ_KMAX * MCQ_KMAX) * sizeof(double)));
-    HIP_TRY(hipMalloc((void**)&h->state, elems));
-    HIP_TRY(hipMalloc((void**)&h->state2, elems));
-    HIP_TRY(hipMalloc((void**)&h->kbig, (size_t)MCQ_KBIG_SLOTS * MCQ_KBIG_SLOT * sizeof(double)));
-    HIP_TRY(hipMalloc((void**)&h->slot_flags, MCQ_SLOT_FLAGS * sizeof(int)));
-    HIP_TRY(hipMemsetAsync(h->slot_flags, 0, MCQ_SLOT_FLAGS * sizeof(int), h->stream));
-    ensure_gi(h, batch, nmax);
-    if (h->poison) HIP_TRY(hipMemsetAsync(h->kbig, 0xff, (size_t)MCQ_KBIG_SLOTS * MCQ_KBIG_SLOT * sizeof(double), h->stream));
-    HIP_TRY(hipMemsetAsync(h->state, 0, elems, h->stream));
-    HIP_TRY(hipMemsetAsync(h->state2, 0, elems, h->stream));
-    if (h->poison) {
-        HIP_TRY(hipMemsetAsync(h->L, 0xff, elems * MCQ_LLD * sizeof(double), h->stream));
-        HIP_TRY(hipMemsetAsync(h->vec, 0xff, elems * MCQ_NVEC * sizeof(double), h->stream));
-        HIP_TRY(hipMemsetAsync(h->Z, 0xff, (elems + batch * (size_t)MCQ_KMAX * MCQ_KMAX) * sizeof(double), h->stream));
+    if (elems <= w.elems && batch <= w.batch && (which == 0 || (size_t)w.gi_nmax >= nmax)) {
+        if (which == 0) ensure_gi(h, batch, nmax);
+        return 0;
     }
-    h->cap_elems = elems;
-    h->cap_batch = batch;
-    h->ws_bytes = (long long)(elems * ((MCQ_LLD + MCQ_NVEC + 1) * sizeof(double) + 2) +
-                              batch * (size_t)MCQ_KMAX * MCQ_KMAX * sizeof(double) +
-                              (size_t)MCQ_KBIG_SLOTS * MCQ_KBIG_SLOT * sizeof(double));
+    HIP_TRY(hipStreamSynchronize(w.stream));
+    free_workspace(h, which);
+    const size_t l_bytes = elems * MCQ_LLD * sizeof(double), vec_bytes = elems * MCQ_NVEC * sizeof(double),
+                 z_bytes = (elems + batch * (size_t)MCQ_KMAX * MCQ_KMAX) * sizeof(double),
+                 kbig_bytes = (size_t)MCQ_KBIG_SLOTS * MCQ_KBIG_SLOT * sizeof(double);
+    HIP_TRY(hipMalloc((void**)&w.L, l_bytes));
+    HIP_TRY(hipMalloc((void**)&w.vec, vec_bytes));
+    HIP_TRY(hipMalloc((void**)&w.Z, z_bytes));
+    HIP_TRY(hipMalloc((void**)&w.state, elems));
+    if (which == 0) HIP_TRY(hipMalloc((void**)&h->state2, elems));
+    HIP_TRY(hipMalloc((void**)&w.kbig, kbig_bytes));
+    HIP_TRY(hipMalloc((void**)&w.slot_flags, MCQ_SLOT_FLAGS * sizeof(int)));
+    HIP_TRY(hipMemsetAsync(w.slot_flags, 0, MCQ_SLOT_FLAGS * sizeof(int), w.stream));
+    size_t slot_bytes = 0;
+    if (which == 0) ensure_gi(h, batch, nmax);
+    else {
+        // half the first workspace's full slots (none where it has none: the kernel then returns what its own phases left)
+        const Workspace& w0 = h->ws[0];
+        const size_t per = MCQ_GI_SLOT_DOUBLES(nmax, nmax) * sizeof(double);
+        const int slots = w0.gi && (size_t)w0.gi_nmax >= nmax ? alloc_slots(&w.gi, std::max(1, w0.gi_slots / 2), per) : 0;
+        slot_bytes = (size_t)slots * per;
+        if (h->poison && w.gi) HIP_TRY(hipMemsetAsync(w.gi, 0xff, slot_bytes, w.stream));
+        w.gi_slots = slots;
+        w.gi_nmax = (int)nmax;
+    }
+    HIP_TRY(hipMemsetAsync(w.state, 0, elems, w.stream));
+    if (which == 0) HIP_TRY(hipMemsetAsync(h->state2, 0, elems, w.stream));
+    if (h->poison) {
+        HIP_TRY(hipMemsetAsync(w.L, 0xff, l_bytes, w.stream));
+        HIP_TRY(hipMemsetAsync(w.vec, 0xff, vec_bytes, w.stream));
+        HIP_TRY(hipMemsetAsync(w.Z, 0xff, z_bytes, w.stream));
+        HIP_TRY(hipMemsetAsync(w.kbig, 0xff, kbig_bytes, w.stream));
+    }
+    w.elems = elems;
+    w.batch = batch;
+    w.bytes = (long long)(elems * ((MCQ_LLD + MCQ_NVEC + 1) * sizeof(double) + (which == 0 ? 2 : 1)) +
+                          batch * (size_t)MCQ_KMAX * MCQ_KMAX * sizeof(double) + kbig_bytes + slot_bytes);
     return 0;
 }
 
-// the second workspace of the pipelined host entry (same slabs as ensure_ws, half the Goldfarb-Idnani slots)
-static int ensure_alt(mcq_handle* h, size_t batch, size_t nmax)
+// Staging set `which`, grown to batch x nmax.  What exists once -- the per-problem scalars, records and origins -- comes and goes with set 0,
+// which is also the only one MCQ_POISON fills.
+static int ensure_staging(mcq_handle* h, int which, size_t batch, size_t nmax)
 {
-    if (!h->stream2) HIP_TRY(hipStreamCreate(&h->stream2));
+    Staging& s = h->stage[which];
     const size_t elems = batch * nmax;
-    if (elems <= h->alt_elems && batch <= h->alt_batch && (size_t)h->gi2_nmax >= nmax) return 0;
-    HIP_TRY(hipStreamSynchronize(h->stream2));
-    free_alt(h);
-    HIP_TRY(hipMalloc((void**)&h->L2, elems * MCQ_LLD * sizeof(double)));
-    HIP_TRY(hipMalloc((void**)&h->vec2, elems * MCQ_NVEC * sizeof(double)));
-    HIP_TRY(hipMalloc((void**)&h->Z2, (elems + batch * (size_t)MCQ_KMAX * MCQ_KMAX) * sizeof(double)));
-    HIP_TRY(hipMalloc((void**)&h->state_alt, elems));
-    HIP_TRY(hipMalloc((void**)&h->kbig2, (size_t)MCQ_KBIG_SLOTS * MCQ_KBIG_SLOT * sizeof(double)));
-    HIP_TRY(hipMalloc((void**)&h->slot_flags2, MCQ_SLOT_FLAGS * sizeof(int)));
-    HIP_TRY(hipMemsetAsync(h->slot_flags2, 0, MCQ_SLOT_FLAGS * sizeof(int), h->stream2));
-    const size_t per = MCQ_GI_SLOT_DOUBLES(nmax, nmax) * sizeof(double);
-    // half the first workspace's full slots (none where it has none: the kernel then returns what its own phases left)
-    int slots = h->gi && (size_t)h->gi_nmax >= nmax ? alloc_slots(&h->gi2, std::max(1, h->gi_slots / 2), per) : 0;
-    HIP_TRY(hipMemsetAsync(h->state_alt, 0, elems, h->stream2));
-    if (h->poison) {
-        HIP_TRY(hipMemsetAsync(h->L2, 0xff, elems * MCQ_LLD * sizeof(double), h->stream2));
-        HIP_TRY(hipMemsetAsync(h->vec2, 0xff, elems * MCQ_NVEC * sizeof(double), h->stream2));
-        HIP_TRY(hipMemsetAsync(h->Z2, 0xff, (elems + batch * (size_t)MCQ_KMAX * MCQ_KMAX) * sizeof(double), h->stream2));
-        HIP_TRY(hipMemsetAsync(h->kbig2, 0xff, (size_t)MCQ_KBIG_SLOTS * MCQ_KBIG_SLOT * sizeof(double), h->stream2));
-        if (h->gi2) HIP_TRY(hipMemsetAsync(h->gi2, 0xff, (size_t)slots * per, h->stream2));
+    if (elems <= s.elems && batch <= s.batch) return 0;
+    HIP_TRY(hipStreamSynchronize(h->ws[0].stream));
+    if (which == 1) {       // (the pipeline's copy streams: ensure_pipe has created them)
+        HIP_TRY(hipStreamSynchronize(h->cs_in));
+        HIP_TRY(hipStreamSynchronize(h->cs_out));
     }
-    h->alt_elems = elems;
-    h->alt_batch = batch;
-    h->gi2_slots = slots;
-    h->gi2_nmax = (int)nmax;      // (the ring size this workspace was sized for, with or without slots)
-    h->alt_bytes = (long long)(elems * ((MCQ_LLD + MCQ_NVEC + 1) * sizeof(double) + 1) + batch * (size_t)MCQ_KMAX * MCQ_KMAX * sizeof(double) +
-                               (size_t)MCQ_KBIG_SLOTS * MCQ_KBIG_SLOT * sizeof(double) + (size_t)slots * per);
+    free_staging(h, which);
+    HIP_TRY(hipMalloc((void**)&s.ref, elems * 4 * sizeof(double)));
+    HIP_TRY(hipMalloc((void**)&s.nv, elems * 2 * sizeof(double)));
+    HIP_TRY(hipMalloc((void**)&s.sc, elems * sizeof(double)));
+    HIP_TRY(hipMalloc((void**)&s.alpha, elems * sizeof(double)));
+    HIP_TRY(hipMalloc((void**)&s.curv, batch * sizeof(double)));
+    HIP_TRY(hipMalloc((void**)&s.status, batch * sizeof(int)));
+    if (which == 0) {
+        HIP_TRY(hipMalloc((void**)&h->d_kb, batch * sizeof(double)));
+        HIP_TRY(hipMalloc((void**)&h->d_wv, batch * sizeof(double)));
+        HIP_TRY(hipMalloc((void**)&h->d_n, batch * sizeof(int)));
+        HIP_TRY(hipMalloc((void**)&h->d_info, batch * sizeof(mcq_info)));
+        HIP_TRY(hipMalloc((void**)&h->d_org, batch * 2 * sizeof(double)));
+        if (h->poison) {
+            HIP_TRY(hipMemsetAsync(s.ref, 0xff, elems * 4 * sizeof(double), h->ws[0].stream));
+            HIP_TRY(hipMemsetAsync(s.nv, 0xff, elems * 2 * sizeof(double), h->ws[0].stream));
+            HIP_TRY(hipMemsetAsync(s.sc, 0xff, elems * sizeof(double), h->ws[0].stream));
+            HIP_TRY(hipMemsetAsync(s.alpha, 0xff, elems * sizeof(double), h->ws[0].stream));
+        }
+    }
+    s.elems = elems;
+    s.batch = batch;
     return 0;
 }
 
-static int ensure_stage(mcq_handle* h, size_t batch, size_t nmax)
+// a uniform (n_list == nullptr) or ragged batch over these rows and result arrays; everything else of McqBatch is zero: an entry sets what is
+// special to it, fill_batch the workspace, options and slots
+static McqBatch make_batch(int batch, int nmax, const int* n_list, const double* ref, const double* nv, const double* sc, double* alpha,
+                           double* curv_err, int* status, mcq_info* info, double kappa_bound, double w_veh)
 {
-    const size_t elems = batch * nmax;
-    if (elems <= h->stage_elems && batch <= h->stage_batch) return 0;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    free_stage(h);
-    HIP_TRY(hipMalloc((void**)&h->d_ref, elems * 4 * sizeof(double)));
-    HIP_TRY(hipMalloc((void**)&h->d_nv, elems * 2 * sizeof(double)));
-    HIP_TRY(hipMalloc((void**)&h->d_sc, elems * sizeof(double)));
-    HIP_TRY(hipMalloc((void**)&h->d_alpha, elems * sizeof(double)));
-    HIP_TRY(hipMalloc((void**)&h->d_curv, batch * sizeof(double)));
-    HIP_TRY(hipMalloc((void**)&h->d_kb, batch * sizeof(double)));
-    HIP_TRY(hipMalloc((void**)&h->d_wv, batch * sizeof(double)));
-    HIP_TRY(hipMalloc((void**)&h->d_n, batch * sizeof(int)));
-    HIP_TRY(hipMalloc((void**)&h->d_status, batch * sizeof(int)));
-    HIP_TRY(hipMalloc((void**)&h->d_info, batch * sizeof(mcq_info)));
-    HIP_TRY(hipMalloc((void**)&h->d_org, batch * 2 * sizeof(double)));
-    if (h->poison) {
-        HIP_TRY(hipMemsetAsync(h->d_ref, 0xff, elems * 4 * sizeof(double), h->stream));
-        HIP_TRY(hipMemsetAsync(h->d_nv, 0xff, elems * 2 * sizeof(double), h->stream));
-        HIP_TRY(hipMemsetAsync(h->d_sc, 0xff, elems * sizeof(double), h->stream));
-        HIP_TRY(hipMemsetAsync(h->d_alpha, 0xff, elems * sizeof(double), h->stream));
-    }
-    h->stage_elems = elems;
-    h->stage_batch = batch;
-    return 0;
+    McqBatch B;
+    memset(&B, 0, sizeof(B));
+    B.batch = batch;
+    B.n = nmax;
+    B.nmax = nmax;
+    B.n_list = n_list;
+    B.ref = ref;
+    B.nv = nv;
+    B.sc = sc;
+    B.alpha = alpha;
+    B.curv_err = curv_err;
+    B.status = status;
+    B.info = info;
+    B.kappa_bound = kappa_bound;
+    B.w_veh = w_veh;
+    return B;
 }
 
-// alt: on the handle's second compute stream and workspace (ensure_alt; mcq_solve_host_pipelined's odd steps) -- no event timing there
 // workspace, options and slots of a solver launch (everything of McqBatch the caller does not set)
-static int fill_batch(mcq_handle* h, McqBatch& B, const mcq_opts& o, bool alt)
+static int fill_batch(mcq_handle* h, McqBatch& B, const mcq_opts& o, Workspace& w)
 {
-    B.L = alt ? h->L2 : h->L; B.vec = alt ? h->vec2 : h->vec; B.Z = alt ? h->Z2 : h->Z; B.state = alt ? h->state_alt : h->state;
+    B.L = w.L; B.vec = w.vec; B.Z = w.Z; B.state = w.state;
     B.max_ipm_iter = o.max_ipm_iter;
     B.max_as_iter = o.max_as_iter;
     B.refine_steps = o.refine_steps;
     B.check_kappa = o.check_kappa;
     B.objective = o.objective;
     B.poison_lds = h->poison ? 1 : 0;
-    B.kbig = alt ? h->kbig2 : h->kbig;
-    B.slot_flags = alt ? h->slot_flags2 : h->slot_flags;      // (zero between launches: the workgroups release what they claim)
+    B.kbig = w.kbig;
+    B.slot_flags = w.slot_flags;      // (zero between launches: the workgroups release what they claim)
     B.kbig_slots = MCQ_KBIG_SLOTS;
     B.algorithm = o.algorithm;
     // the Goldfarb-Idnani slots hold working sets of up to gi_nmax constraints on rings of up to gi_nmax waypoints (slot stride: B.nmax)
     const bool gi_path = o.objective == MCQ_OBJ_MIN_CURV && !B.prep_only;
     B.gis = nullptr;
     B.gis_slots = B.gis_qcap = 0;
-    if (!alt && o.algorithm == MCQ_ALG_GI && gi_path) {
+    if (&w == &h->ws[0] && o.algorithm == MCQ_ALG_GI && gi_path) {
         // every problem takes the Goldfarb-Idnani path: a (small) slot per resident workgroup, so that they run side by side
         if (int rc = ensure_gi_small(h, (size_t)B.batch, (size_t)B.nmax)) return rc;
         if (h->gis && B.nmax <= h->gis_nmax) {
@@ -465,10 +489,9 @@ static int fill_batch(mcq_handle* h, McqBatch& B, const mcq_opts& o, bool alt)
             B.gis_qcap = (int)gi_small_qcap((size_t)B.nmax);
         }
     }
-    double* gi_mem = alt ? h->gi2 : h->gi;
-    const bool gi_on = gi_mem && (alt ? h->gi2_slots : h->gi_slots) > 0 && B.nmax <= (alt ? h->gi2_nmax : h->gi_nmax) && gi_path;
-    B.gi = gi_on ? gi_mem : nullptr;
-    B.gi_slots = gi_on ? (alt ? h->gi2_slots : h->gi_slots) : 0;
+    const bool gi_on = w.gi && w.gi_slots > 0 && B.nmax <= w.gi_nmax && gi_path;
+    B.gi = gi_on ? w.gi : nullptr;
+    B.gi_slots = gi_on ? w.gi_slots : 0;
     B.gi_qcap = B.nmax;
     // The overflow slots of the curvature-row working set (rounds 3-4) serve only where no Goldfarb-Idnani slot exists: which of more than eight
     // such problems of a launch got one depended on the order the GPU scheduled workgroups in, and so did the last bits of their results
@@ -478,46 +501,42 @@ static int fill_batch(mcq_handle* h, McqBatch& B, const mcq_opts& o, bool alt)
     return 0;
 }
 
-static int launch(mcq_handle* h, McqBatch& B, const mcq_opts& o, bool alt = false)
+// One solver launch on workspace w and its stream.  The warm start, the event timing and the launch count of a span are workspace 0's: a launch
+// on workspace 1 (mcq_solve_host_pipelined's and mcq_solve_device_stream's odd steps) neither reads nor touches them.
+static int launch(mcq_handle* h, McqBatch& B, const mcq_opts& o, Workspace& w)
 {
-    hipStream_t st = alt ? h->stream2 : h->stream;
-    if (int rc = fill_batch(h, B, o, alt)) return rc;
+    const bool first = &w == &h->ws[0];
+    hipStream_t st = w.stream;
+    if (int rc = fill_batch(h, B, o, w)) return rc;
     // warm start: only the working sets mcq_relinearise_device carried over for exactly this batch layout
-    B.warm = (!alt && o.warm_start > 0 && h->state2_valid && !B.prep_only && h->state2_batch == B.batch && h->state2_nmax == B.nmax)
+    B.warm = (first && o.warm_start > 0 && h->state2_valid && !B.prep_only && h->state2_batch == B.batch && h->state2_nmax == B.nmax)
                  ? h->state2 : nullptr;
-    if (!B.prep_only && !alt) h->state2_valid = false;
-    if (B.objective == MCQ_OBJ_SHORTEST_PATH && !B.prep_only) {
-        if (!B.nv) { g_err = "shortest-path objective: normvec is required"; return MCQ_E_ARG; }
-        B.check_kappa = 0;
-        if (!alt) HIP_TRY(hipEventRecord(h->ev[0], st));
-        hipLaunchKernelGGL(mcq_assemble_sp_kernel, dim3(B.batch), dim3(256), 0, st, B);
-        HIP_TRY(hipGetLastError());
-        if (!alt) HIP_TRY(hipEventRecord(h->ev[1], st));
-        if (!alt) HIP_TRY(hipEventRecord(h->ev[2], st));
-        hipLaunchKernelGGL(mcq_solve_kernel, dim3(B.batch), dim3(256), 0, st, B);
-        HIP_TRY(hipGetLastError());
-        if (!alt) HIP_TRY(hipEventRecord(h->ev[3], st));
-        if (!alt) HIP_TRY(hipEventRecord(h->ev[4], st));
-        if (!alt) h->timing_valid = true;
-        return 0;
-    }
-    if (!alt) HIP_TRY(hipEventRecord(h->ev[0], st));
+    if (!B.prep_only && first) h->state2_valid = false;
+    const bool sp = B.objective == MCQ_OBJ_SHORTEST_PATH && !B.prep_only;
+    if (sp && !B.nv) { g_err = "shortest-path objective: normvec is required"; return MCQ_E_ARG; }
+    if (sp) B.check_kappa = 0;
+    if (first) HIP_TRY(hipEventRecord(h->ev[0], st));
     if (B.prep_only) {
         hipLaunchKernelGGL(mcq_assemble_kernel, dim3(B.batch), dim3(256), 0, st, B);
         HIP_TRY(hipGetLastError());
         return 0;
     }
-    // (no assembly launch: the solver kernel assembles its problem itself -- assemble_problem() -- since round 4)
-    if (!alt) HIP_TRY(hipEventRecord(h->ev[1], st));
-    if (!alt) HIP_TRY(hipEventRecord(h->ev[2], st));
+    // (minimum curvature has no assembly launch: the solver kernel assembles its problem itself -- assemble_problem() -- since round 4)
+    if (sp) {
+        hipLaunchKernelGGL(mcq_assemble_sp_kernel, dim3(B.batch), dim3(256), 0, st, B);
+        HIP_TRY(hipGetLastError());
+    }
+    if (first) HIP_TRY(hipEventRecord(h->ev[1], st));
+    if (first) HIP_TRY(hipEventRecord(h->ev[2], st));
     hipLaunchKernelGGL(mcq_solve_kernel, dim3(B.batch), dim3(256), 0, st, B);
     HIP_TRY(hipGetLastError());
-    if (!alt) HIP_TRY(hipEventRecord(h->ev[3], st));
-    if (!alt) HIP_TRY(hipEventRecord(h->ev[4], st));
-    if (!alt) h->timing_valid = true;
-    if (!alt && h->span_open) ++h->span_launches;
+    if (first) HIP_TRY(hipEventRecord(h->ev[3], st));
+    if (first) HIP_TRY(hipEventRecord(h->ev[4], st));
+    if (first) h->timing_valid = true;
+    if (first && h->span_open && !sp) ++h->span_launches;       // (a shortest-path launch has never been counted: docs/NOTEBOOK.md, "Host API")
     return 0;
 }
+static int launch(mcq_handle* h, McqBatch& B, const mcq_opts& o) { return launch(h, B, o, h->ws[0]); }
 
 extern "C" int mcq_solve_device(mcq_handle* h, int batch, int n, const double* reftrack, const double* normvec,
                                 const double* scaling, double kappa_bound, double w_veh, const mcq_opts* opts,
@@ -529,30 +548,29 @@ extern "C" int mcq_solve_device(mcq_handle* h, int batch, int n, const double* r
     }
     HIP_TRY(hipSetDevice(h->device));
     const mcq_opts o = resolve_opts(opts);
-    int rc = ensure_ws(h, (size_t)batch, (size_t)n);
+    int rc = ensure_workspace(h, 0, (size_t)batch, (size_t)n);
     if (rc) return rc;
-    McqBatch B;
-    memset(&B, 0, sizeof(B));
-    B.batch = batch;
-    B.n = n;
-    B.nmax = n;
-    B.n_list = nullptr;
-    B.ref = reftrack;
-    B.nv = normvec;
-    B.sc = scaling;
-    B.alpha = alpha_out;
-    B.curv_err = curv_err_out;
-    B.status = status_out;
-    B.info = info_out;
-    B.kappa_bound = kappa_bound;
-    B.w_veh = w_veh;
+    McqBatch B = make_batch(batch, n, nullptr, reftrack, normvec, scaling, alpha_out, curv_err_out, status_out, info_out, kappa_bound, w_veh);
     return launch(h, B, o);
 }
 
-static int convert_launch(mcq_handle* h, const float* src, double* dst, size_t count)
+// grid of the streaming conversions: four values per work-item, 4096 workgroups at most
+static dim3 convert_grid(size_t count)
 {
-    const unsigned blocks = (unsigned)((count / 4 + 255) / 256 < 4096 ? (count / 4 + 255) / 256 + 1 : 4096);
-    hipLaunchKernelGGL(mcq_widen_kernel, dim3(blocks), dim3(256), 0, h->stream, src, dst, count);
+    const size_t blocks = (count / 4 + 255) / 256;
+    return dim3((unsigned)(blocks < 4096 ? blocks + 1 : 4096));
+}
+
+static int widen_launch(mcq_handle* h, const float* src, double* dst, size_t count)
+{
+    hipLaunchKernelGGL(mcq_widen_kernel, convert_grid(count), dim3(256), 0, h->ws[0].stream, src, dst, count);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+static int narrow_launch(mcq_handle* h, const double* src, float* dst, size_t count)
+{
+    hipLaunchKernelGGL(mcq_narrow_kernel, convert_grid(count), dim3(256), 0, h->ws[0].stream, src, dst, count);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -570,35 +588,21 @@ extern "C" int mcq_solve_device_f32(mcq_handle* h, int batch, int n, const float
     }
     HIP_TRY(hipSetDevice(h->device));
     const mcq_opts o = resolve_opts(opts);
-    int rc = ensure_ws(h, (size_t)batch, (size_t)n);
+    int rc = ensure_workspace(h, 0, (size_t)batch, (size_t)n);
     if (rc) return rc;
-    rc = ensure_stage(h, (size_t)batch, (size_t)n);
+    rc = ensure_staging(h, 0, (size_t)batch, (size_t)n);
     if (rc) return rc;
     const size_t elems = (size_t)batch * n;
-    rc = convert_launch(h, reftrack, h->d_ref, elems * 4);
+    const Staging& s = h->stage[0];
+    rc = widen_launch(h, reftrack, s.ref, elems * 4);
     if (rc) return rc;
-    if (normvec) { rc = convert_launch(h, normvec, h->d_nv, elems * 2); if (rc) return rc; }
-    if (scaling) { rc = convert_launch(h, scaling, h->d_sc, elems); if (rc) return rc; }
-    McqBatch B;
-    memset(&B, 0, sizeof(B));
-    B.batch = batch;
-    B.n = n;
-    B.nmax = n;
-    B.ref = h->d_ref;
-    B.nv = normvec ? h->d_nv : nullptr;
-    B.sc = scaling ? h->d_sc : nullptr;
-    B.alpha = h->d_alpha;
-    B.curv_err = curv_err_out;
-    B.status = status_out;
-    B.info = info_out;
-    B.kappa_bound = kappa_bound;
-    B.w_veh = w_veh;
+    if (normvec) { rc = widen_launch(h, normvec, s.nv, elems * 2); if (rc) return rc; }
+    if (scaling) { rc = widen_launch(h, scaling, s.sc, elems); if (rc) return rc; }
+    McqBatch B = make_batch(batch, n, nullptr, s.ref, normvec ? s.nv : nullptr, scaling ? s.sc : nullptr, s.alpha, curv_err_out, status_out, info_out,
+                            kappa_bound, w_veh);
     rc = launch(h, B, o);
     if (rc) return rc;
-    const unsigned blocks = (unsigned)((elems / 4 + 255) / 256 < 4096 ? (elems / 4 + 255) / 256 + 1 : 4096);
-    hipLaunchKernelGGL(mcq_narrow_kernel, dim3(blocks), dim3(256), 0, h->stream, (const double*)h->d_alpha, alpha_out, elems);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return narrow_launch(h, s.alpha, alpha_out, elems);
 }
 
 // fp32 rows in either layout (include/mcq.h: MCQ_F32_ABSOLUTE / MCQ_F32_INCREMENTS), device-resident: the rows are rebuilt as fp64
@@ -608,26 +612,12 @@ static int solve_f32_rows(mcq_handle* h, int batch, int n, int layout, const flo
                           double w_veh, const mcq_opts& o, float* d_alpha_out, double* curv_err_out, int* status_out, mcq_info* info_out)
 {
     const size_t elems = (size_t)batch * n;
-    hipLaunchKernelGGL(mcq_widen_rows_kernel, dim3((unsigned)batch), dim3(64), 0, h->stream, d_rows, d_origin, h->d_ref, n, layout);
+    hipLaunchKernelGGL(mcq_widen_rows_kernel, dim3((unsigned)batch), dim3(64), 0, h->ws[0].stream, d_rows, d_origin, h->stage[0].ref, n, layout);
     HIP_TRY(hipGetLastError());
-    McqBatch B;
-    memset(&B, 0, sizeof(B));
-    B.batch = batch;
-    B.n = n;
-    B.nmax = n;
-    B.ref = h->d_ref;
-    B.alpha = h->d_alpha;
-    B.curv_err = curv_err_out;
-    B.status = status_out;
-    B.info = info_out;
-    B.kappa_bound = kappa_bound;
-    B.w_veh = w_veh;
+    McqBatch B = make_batch(batch, n, nullptr, h->stage[0].ref, nullptr, nullptr, h->stage[0].alpha, curv_err_out, status_out, info_out, kappa_bound, w_veh);
     int rc = launch(h, B, o);
     if (rc) return rc;
-    const unsigned blocks = (unsigned)((elems / 4 + 255) / 256 < 4096 ? (elems / 4 + 255) / 256 + 1 : 4096);
-    hipLaunchKernelGGL(mcq_narrow_kernel, dim3(blocks), dim3(256), 0, h->stream, (const double*)h->d_alpha, d_alpha_out, elems);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return narrow_launch(h, h->stage[0].alpha, d_alpha_out, elems);
 }
 
 extern "C" int mcq_solve_device_f32_rows(mcq_handle* h, int batch, int n, int layout, const float* reftrack, const double* origin,
@@ -641,9 +631,9 @@ extern "C" int mcq_solve_device_f32_rows(mcq_handle* h, int batch, int n, int la
     }
     HIP_TRY(hipSetDevice(h->device));
     const mcq_opts o = resolve_opts(opts);
-    int rc = ensure_ws(h, (size_t)batch, (size_t)n);
+    int rc = ensure_workspace(h, 0, (size_t)batch, (size_t)n);
     if (rc) return rc;
-    rc = ensure_stage(h, (size_t)batch, (size_t)n);
+    rc = ensure_staging(h, 0, (size_t)batch, (size_t)n);
     if (rc) return rc;
     return solve_f32_rows(h, batch, n, layout, reftrack, origin, kappa_bound, w_veh, o, alpha_out, curv_err_out, status_out, info_out);
 }
@@ -659,23 +649,9 @@ extern "C" int mcq_solve_device_ragged(mcq_handle* h, int batch, int nmax, const
     }
     HIP_TRY(hipSetDevice(h->device));
     const mcq_opts o = resolve_opts(opts);
-    int rc = ensure_ws(h, (size_t)batch, (size_t)nmax);
+    int rc = ensure_workspace(h, 0, (size_t)batch, (size_t)nmax);
     if (rc) return rc;
-    McqBatch B;
-    memset(&B, 0, sizeof(B));
-    B.batch = batch;
-    B.n = nmax;
-    B.nmax = nmax;
-    B.n_list = n_list;
-    B.ref = reftrack;
-    B.nv = normvec;
-    B.sc = scaling;
-    B.alpha = alpha_out;
-    B.curv_err = curv_err_out;
-    B.status = status_out;
-    B.info = info_out;
-    B.kappa_bound = kappa_bound;
-    B.w_veh = w_veh;
+    McqBatch B = make_batch(batch, nmax, n_list, reftrack, normvec, scaling, alpha_out, curv_err_out, status_out, info_out, kappa_bound, w_veh);
     return launch(h, B, o);
 }
 
@@ -692,23 +668,9 @@ extern "C" int mcq_solve_device_ragged_params(mcq_handle* h, int batch, int nmax
     }
     HIP_TRY(hipSetDevice(h->device));
     const mcq_opts o = resolve_opts(opts);
-    int rc = ensure_ws(h, (size_t)batch, (size_t)nmax);
+    int rc = ensure_workspace(h, 0, (size_t)batch, (size_t)nmax);
     if (rc) return rc;
-    McqBatch B;
-    memset(&B, 0, sizeof(B));
-    B.batch = batch;
-    B.n = nmax;
-    B.nmax = nmax;
-    B.n_list = n_list;
-    B.ref = reftrack;
-    B.nv = normvec;
-    B.sc = scaling;
-    B.alpha = alpha_out;
-    B.curv_err = curv_err_out;
-    B.status = status_out;
-    B.info = info_out;
-    B.kappa_bound = kappa_bound;
-    B.w_veh = w_veh;
+    McqBatch B = make_batch(batch, nmax, n_list, reftrack, normvec, scaling, alpha_out, curv_err_out, status_out, info_out, kappa_bound, w_veh);
     B.kappa_bound_list = kappa_bound_list;
     B.w_veh_list = w_veh_list;
     return launch(h, B, o);
@@ -723,21 +685,13 @@ extern "C" int mcq_prep_device(mcq_handle* h, int batch, int nmax, const int* n_
     }
     HIP_TRY(hipSetDevice(h->device));
     const mcq_opts o = resolve_opts(nullptr);
-    int rc = ensure_ws(h, (size_t)batch, (size_t)nmax);
+    int rc = ensure_workspace(h, 0, (size_t)batch, (size_t)nmax);
     if (rc) return rc;
-    McqBatch B;
-    memset(&B, 0, sizeof(B));
-    B.batch = batch;
-    B.n = nmax;
-    B.nmax = nmax;
-    B.n_list = n_list;
-    B.ref = reftrack;
-    B.status = status_out;
+    // (kappa_bound 1, w_veh 0: the bounds computed along the way are not used -- any widths are "feasible")
+    McqBatch B = make_batch(batch, nmax, n_list, reftrack, nullptr, nullptr, nullptr, nullptr, status_out, nullptr, 1.0, 0.0);
     B.nv_out = normvec_out;
     B.sc_out = scaling_out;
     B.prep_only = 1;
-    B.w_veh = 0.0;              // the bounds computed along the way are not used: any widths are "feasible"
-    B.kappa_bound = 1.0;
     return launch(h, B, o);
 }
 
@@ -749,7 +703,7 @@ extern "C" int mcq_normals_crossing_device(mcq_handle* h, int batch, int nmax, c
         return MCQ_E_ARG;
     }
     HIP_TRY(hipSetDevice(h->device));
-    hipLaunchKernelGGL(mcq_normals_crossing_kernel, dim3(batch), dim3(256), 0, h->stream, nmax, n_list, reftrack, normvec,
+    hipLaunchKernelGGL(mcq_normals_crossing_kernel, dim3(batch), dim3(256), 0, h->ws[0].stream, nmax, n_list, reftrack, normvec,
                        horizon, crossing_out);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -766,7 +720,7 @@ extern "C" int mcq_relinearise_device(mcq_handle* h, int batch, int nmax, const 
         return MCQ_E_ARG;
     }
     HIP_TRY(hipSetDevice(h->device));
-    int rc = ensure_ws(h, (size_t)batch, (size_t)nmax);
+    int rc = ensure_workspace(h, 0, (size_t)batch, (size_t)nmax);
     if (rc) return rc;
     McqRelin R;
     memset(&R, 0, sizeof(R));
@@ -783,13 +737,13 @@ extern "C" int mcq_relinearise_device(mcq_handle* h, int batch, int nmax, const 
     R.nv_out = normvec_out;
     R.n_out = n_out;
     R.status = status_out;
-    R.vec = h->vec;
-    R.state_in = h->state;          // what the last solve on this handle left (the caller solves, then re-linearises, the same batch)
+    R.vec = h->ws[0].vec;
+    R.state_in = h->ws[0].state;          // what the last solve on this handle left (the caller solves, then re-linearises, the same batch)
     R.state_out = h->state2;
     h->state2_valid = true;
     h->state2_batch = batch;
     h->state2_nmax = nmax;
-    hipLaunchKernelGGL(mcq_relinearise_kernel, dim3(batch), dim3(256), 0, h->stream, R);
+    hipLaunchKernelGGL(mcq_relinearise_kernel, dim3(batch), dim3(256), 0, h->ws[0].stream, R);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -814,7 +768,7 @@ static int vel_profile_launch(mcq_handle* h, int batch, int n, int nmax, const i
     HIP_TRY(hipSetDevice(h->device));
     const size_t need = (size_t)(closed ? 2 : 1) * nmax * batch * sizeof(double);      // the lap doubled, or the row once
     if (need > h->vel_scratch_bytes) {
-        HIP_TRY(hipStreamSynchronize(h->stream));
+        HIP_TRY(hipStreamSynchronize(h->ws[0].stream));
         (void)hipFree(h->vel_scratch);
         h->vel_scratch = nullptr;
         h->vel_scratch_bytes = 0;
@@ -833,10 +787,10 @@ static int vel_profile_launch(mcq_handle* h, int batch, int n, int nmax, const i
     V.scratch = h->vel_scratch; V.vx_out = vx_out; V.lap_time = lap_time_out;
     F.loc_gg = loc_gg; F.v_start = v_start; F.v_end = v_end;
     const dim3 grid((batch + 63) / 64), block(64);
-    if (closed && !loc_gg) hipLaunchKernelGGL(mcq_vel_profile_kernel, grid, block, 0, h->stream, V);
-    else if (closed) hipLaunchKernelGGL(mcq_vel_profile_locgg_kernel, grid, block, 0, h->stream, F);
-    else if (!loc_gg) hipLaunchKernelGGL(mcq_vel_profile_open_kernel, grid, block, 0, h->stream, F);
-    else hipLaunchKernelGGL(mcq_vel_profile_open_locgg_kernel, grid, block, 0, h->stream, F);
+    if (closed && !loc_gg) hipLaunchKernelGGL(mcq_vel_profile_kernel, grid, block, 0, h->ws[0].stream, V);
+    else if (closed) hipLaunchKernelGGL(mcq_vel_profile_locgg_kernel, grid, block, 0, h->ws[0].stream, F);
+    else if (!loc_gg) hipLaunchKernelGGL(mcq_vel_profile_open_kernel, grid, block, 0, h->ws[0].stream, F);
+    else hipLaunchKernelGGL(mcq_vel_profile_open_locgg_kernel, grid, block, 0, h->ws[0].stream, F);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -904,7 +858,7 @@ extern "C" int mcq_raceline_device(mcq_handle* h, int batch, int nmax, const int
         return MCQ_E_ARG;
     }
     HIP_TRY(hipSetDevice(h->device));
-    int rc = ensure_ws(h, (size_t)batch, (size_t)nmax);
+    int rc = ensure_workspace(h, 0, (size_t)batch, (size_t)nmax);
     if (rc) return rc;
     McqRace Q;
     memset(&Q, 0, sizeof(Q));
@@ -912,8 +866,8 @@ extern "C" int mcq_raceline_device(mcq_handle* h, int batch, int nmax, const int
     Q.n_in = n_in; Q.ref = reftrack; Q.nv = normvec; Q.alpha = alpha; Q.stepsize = stepsize;
     Q.xy_out = raceline_out; Q.psi_out = psi_out; Q.kappa_out = kappa_out; Q.el_out = el_lengths_out;
     Q.m_out = m_out; Q.status = status_out;
-    Q.vec = h->vec;
-    hipLaunchKernelGGL(mcq_raceline_kernel, dim3(batch), dim3(256), 0, h->stream, Q);
+    Q.vec = h->ws[0].vec;
+    hipLaunchKernelGGL(mcq_raceline_kernel, dim3(batch), dim3(256), 0, h->ws[0].stream, Q);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -925,7 +879,7 @@ extern "C" int mcq_device_alloc(mcq_handle* h, size_t bytes, void** out)
     if (!h || !out || bytes == 0) { g_err = "mcq_device_alloc: bad argument"; return MCQ_E_ARG; }
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipMalloc(out, bytes));
-    HIP_TRY(hipMemsetAsync(*out, 0, bytes, h->stream));
+    HIP_TRY(hipMemsetAsync(*out, 0, bytes, h->ws[0].stream));
     return 0;
 }
 
@@ -934,7 +888,7 @@ extern "C" int mcq_device_free(mcq_handle* h, void* ptr)
     if (!h) { g_err = "mcq_device_free: NULL handle"; return MCQ_E_ARG; }
     if (!ptr) return 0;
     HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipStreamSynchronize(h->ws[0].stream));
     if (h->comm_stream) HIP_TRY(hipStreamSynchronize(h->comm_stream));      // (a gather in flight may read or write the buffer)
     HIP_TRY(hipFree(ptr));
     return 0;
@@ -944,8 +898,8 @@ extern "C" int mcq_copy_to_device(mcq_handle* h, void* dst, const void* src, siz
 {
     if (!h || !dst || !src) { g_err = "mcq_copy_to_device: bad argument"; return MCQ_E_ARG; }
     HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));          // the host buffer may be reused on return
+    HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->ws[0].stream));
+    HIP_TRY(hipStreamSynchronize(h->ws[0].stream));          // the host buffer may be reused on return
     return 0;
 }
 
@@ -955,9 +909,9 @@ extern "C" int mcq_copy_to_host(mcq_handle* h, void* dst, const void* src, size_
     HIP_TRY(hipSetDevice(h->device));
     // a gather enqueued before this copy may be writing `src` on the comm stream: the copy is ordered behind the latest one (ADVICE r4:
     // parallel.solve_sharded read its receive buffer before the gather had finished)
-    if (h->comm_stream && h->comm_seq > 0) HIP_TRY(hipStreamWaitEvent(h->stream, h->comm_done[(h->comm_seq - 1) & 3u], 0));
-    HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (h->comm_stream && h->comm_seq > 0) HIP_TRY(hipStreamWaitEvent(h->ws[0].stream, h->comm_done[(h->comm_seq - 1) & 3u], 0));
+    HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->ws[0].stream));
+    HIP_TRY(hipStreamSynchronize(h->ws[0].stream));
     return 0;
 }
 
@@ -965,13 +919,13 @@ extern "C" int mcq_sync(mcq_handle* h)
 {
     if (!h) { g_err = "mcq_sync: NULL handle"; return MCQ_E_ARG; }
     HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipStreamSynchronize(h->ws[0].stream));
     if (h->comm_stream) HIP_TRY(hipStreamSynchronize(h->comm_stream));      // gathers in flight (mcq_comm_allgather) are work of the handle too
-    if (h->stream2) HIP_TRY(hipStreamSynchronize(h->stream2));
+    if (h->ws[1].stream) HIP_TRY(hipStreamSynchronize(h->ws[1].stream));
     return 0;
 }
 
-extern "C" void* mcq_stream(mcq_handle* h) { return h ? (void*)h->stream : nullptr; }
+extern "C" void* mcq_stream(mcq_handle* h) { return h ? (void*)h->ws[0].stream : nullptr; }
 
 extern "C" int mcq_last_timing(mcq_handle* h, float ms[5])
 {
@@ -992,7 +946,7 @@ extern "C" int mcq_timing_begin(mcq_handle* h)
     if (!h) { g_err = "mcq_timing_begin: NULL handle"; return MCQ_E_ARG; }
     HIP_TRY(hipSetDevice(h->device));
     for (int k = 0; k < 2; ++k) if (!h->ev_span[k]) HIP_TRY(hipEventCreate(&h->ev_span[k]));
-    HIP_TRY(hipEventRecord(h->ev_span[0], h->stream));
+    HIP_TRY(hipEventRecord(h->ev_span[0], h->ws[0].stream));
     h->span_launches = 0;
     h->span_open = true;
     return 0;
@@ -1003,7 +957,7 @@ extern "C" int mcq_timing_end(mcq_handle* h, float* ms_out, int* launches_out)
     if (!h || !ms_out || !launches_out) { g_err = "mcq_timing_end: bad argument"; return MCQ_E_ARG; }
     if (!h->span_open) { g_err = "mcq_timing_end: no span open (mcq_timing_begin)"; return MCQ_E_ARG; }
     HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipEventRecord(h->ev_span[1], h->stream));
+    HIP_TRY(hipEventRecord(h->ev_span[1], h->ws[0].stream));
     HIP_TRY(hipEventSynchronize(h->ev_span[1]));
     HIP_TRY(hipEventElapsedTime(ms_out, h->ev_span[0], h->ev_span[1]));
     *launches_out = h->span_launches;
@@ -1013,12 +967,12 @@ extern "C" int mcq_timing_end(mcq_handle* h, float* ms_out, int* launches_out)
 
 extern "C" int mcq_last_upload_was_direct(mcq_handle* h) { return h ? h->last_upload_direct : 0; }
 
-extern "C" long long mcq_workspace_bytes(mcq_handle* h) { return h ? h->ws_bytes + h->gi_bytes + h->gis_bytes + h->alt_bytes : 0; }
+extern "C" long long mcq_workspace_bytes(mcq_handle* h) { return h ? h->ws[0].bytes + h->gi_bytes + h->gis_bytes + h->ws[1].bytes : 0; }
 
 static int ensure_pin(mcq_handle* h, size_t bytes)
 {
     if (bytes <= h->pin_bytes) return 0;
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipStreamSynchronize(h->ws[0].stream));
     if (h->pin) (void)hipHostFree(h->pin);
     h->pin = nullptr;
     h->pin_bytes = 0;
@@ -1027,20 +981,6 @@ static int ensure_pin(mcq_handle* h, size_t bytes)
     h->pin_bytes = bytes;
     return 0;
 }
-
-// error paths of the host-buffer entries: copies from / to the pinned staging may still be queued
-#define HIP_TRY_SYNC(expr)                                                                                \
-    do {                                                                                                  \
-        hipError_t e_ = (expr);                                                                           \
-        if (e_ != hipSuccess) {                                                                           \
-            char buf_[512];                                                                               \
-            snprintf(buf_, sizeof(buf_), "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, \
-                     __LINE__);                                                                           \
-            g_err = buf_;                                                                                 \
-            (void)hipStreamSynchronize(h->stream);                                                        \
-            return MCQ_E_DEVICE;                                                                          \
-        }                                                                                                 \
-    } while (0)
 
 // ---- the n spline scalings out of the dense matrix the reference passes (include/mcq.h); host code, no GPU ----------------------------------
 extern "C" int mcq_les_scalings(const double* A, int n, double* s_out, int check)
@@ -1177,7 +1117,7 @@ extern "C" int mcq_host_free(mcq_handle* h, void* ptr)
     if (!h) { g_err = "mcq_host_free: NULL handle"; return MCQ_E_ARG; }
     if (!ptr) return 0;
     HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipStreamSynchronize(h->ws[0].stream));
     HIP_TRY(hipHostFree(ptr));
     return 0;
 }
@@ -1199,33 +1139,58 @@ static int host_slices(int batch, const mcq_opts& o)
 // the compute stream of slice k: the handle's two, in turn.  (Tried, round 6: a stream per slice -- 14.0 ms where two streams give 11.5 for four
 // slices of 256 problems, and the 600 curvature-tight long rings 105 s where the one launch takes 45: more than two queues of large workgroups
 // cost more in the hardware scheduler than they overlap.)
-static hipStream_t slice_stream(mcq_handle* h, int k) { return (k & 1) ? h->stream2 : h->stream; }
+static hipStream_t slice_stream(mcq_handle* h, int k) { return h->ws[k & 1].stream; }
 static int ensure_slice_streams(mcq_handle* h)
 {
     if (!h->cs_in) { HIP_TRY(hipStreamCreate(&h->cs_in)); HIP_TRY(hipStreamCreate(&h->cs_out)); }
-    if (!h->stream2) HIP_TRY(hipStreamCreate(&h->stream2));
+    if (!h->ws[1].stream) HIP_TRY(hipStreamCreate(&h->ws[1].stream));
     for (int k = 0; k < 16; ++k) if (!h->ev_slice[k]) HIP_TRY(hipEventCreate(&h->ev_slice[k]));
-    HIP_TRY(hipStreamSynchronize(h->stream));          // whatever ran before on the handle is done with the staging buffers and the workspace
-    HIP_TRY(hipStreamSynchronize(h->stream2));
+    HIP_TRY(hipStreamSynchronize(h->ws[0].stream));          // whatever ran before on the handle is done with the staging buffers and the workspace
+    HIP_TRY(hipStreamSynchronize(h->ws[1].stream));
     return 0;
 }
 
-// (the slices of mcq_solve_host: every stream that may hold copies from / into the caller's buffers is drained before an error is reported)
-#define HIP_TRY_SLICE(expr)                                                                               \
-    do {                                                                                                  \
-        hipError_t e_ = (expr);                                                                           \
-        if (e_ != hipSuccess) {                                                                           \
-            char buf_[512];                                                                               \
-            snprintf(buf_, sizeof(buf_), "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, \
-                     __LINE__);                                                                           \
-            g_err = buf_;                                                                                 \
-            (void)hipStreamSynchronize(h->cs_in);                                                         \
-            (void)hipStreamSynchronize(h->stream);                                                        \
-            (void)hipStreamSynchronize(h->stream2);                                                       \
-            (void)hipStreamSynchronize(h->cs_out);                                                        \
-            return MCQ_E_DEVICE;                                                                          \
-        }                                                                                                 \
-    } while (0)
+// what a sliced entry does where the others call launch(): the streams; workspace 0, options and slots of the batch; no warm start, no event timing
+static int begin_slices(mcq_handle* h, McqBatch& B, const mcq_opts& o)
+{
+    if (int rc = ensure_slice_streams(h)) return rc;
+    if (int rc = fill_batch(h, B, o, h->ws[0])) return rc;
+    B.warm = nullptr;
+    h->state2_valid = false;
+    h->timing_valid = false;
+    return 0;
+}
+
+// Slice k = problems b0 .. b1 - 1 of B, whose uploads have just been queued on h->cs_in: its kernel behind them on the slice's compute stream,
+// its rows of alpha (B.nmax each) behind the kernel on h->cs_out into alpha_host ([batch][nmax], the caller's array or the pinned staging).
+static int launch_slice(mcq_handle* h, const McqBatch& B, int k, int b0, int b1, double* alpha_host)
+{
+    if (b1 == b0) return 0;            // (none with nsl <= batch; a grid of 0 workgroups is a launch error)
+    HIP_TRY_DRAIN(hipEventRecord(h->ev_slice[k], h->cs_in));
+    hipStream_t st = slice_stream(h, k);
+    HIP_TRY_DRAIN(hipStreamWaitEvent(st, h->ev_slice[k], 0));
+    McqBatch S = B;
+    S.pb0 = b0;
+    hipLaunchKernelGGL(mcq_solve_kernel, dim3(b1 - b0), dim3(256), 0, st, S);
+    HIP_TRY_DRAIN(hipGetLastError());
+    HIP_TRY_DRAIN(hipEventRecord(h->ev_slice[8 + k], st));
+    HIP_TRY_DRAIN(hipStreamWaitEvent(h->cs_out, h->ev_slice[8 + k], 0));
+    const size_t off = (size_t)b0 * B.nmax, cnt = (size_t)(b1 - b0) * B.nmax;
+    HIP_TRY_DRAIN(hipMemcpyAsync(alpha_host + off, B.alpha + off, cnt * sizeof(double), hipMemcpyDeviceToHost, h->cs_out));
+    return 0;
+}
+
+// The results of a host-buffer batch, from staging set 0 to the host on `st`: alpha_bytes of alpha (alpha_dst == nullptr: it went down slice by
+// slice), curv_error, status, and the info records where the caller wants them.
+static int download_results(mcq_handle* h, hipStream_t st, int batch, void* alpha_dst, const void* alpha_src, size_t alpha_bytes,
+                            double* curv_err_dst, int* status_dst, mcq_info* info_dst)
+{
+    if (alpha_dst) HIP_TRY_DRAIN(hipMemcpyAsync(alpha_dst, alpha_src, alpha_bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY_DRAIN(hipMemcpyAsync(curv_err_dst, h->stage[0].curv, batch * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY_DRAIN(hipMemcpyAsync(status_dst, h->stage[0].status, batch * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (info_dst) HIP_TRY_DRAIN(hipMemcpyAsync(info_dst, h->d_info, batch * sizeof(mcq_info), hipMemcpyDeviceToHost, st));
+    return 0;
+}
 
 extern "C" int mcq_solve_host(mcq_handle* h, int batch, int n, const double* reftrack, const double* normvec,
                               const double* scaling, double kappa_bound, double w_veh, const mcq_opts* opts, double* alpha_out,
@@ -1237,25 +1202,14 @@ extern "C" int mcq_solve_host(mcq_handle* h, int batch, int n, const double* ref
     }
     HIP_TRY(hipSetDevice(h->device));
     const mcq_opts o = resolve_opts(opts);
-    int rc = ensure_ws(h, (size_t)batch, (size_t)n);
+    int rc = ensure_workspace(h, 0, (size_t)batch, (size_t)n);
     if (rc) return rc;
-    rc = ensure_stage(h, (size_t)batch, (size_t)n);
+    rc = ensure_staging(h, 0, (size_t)batch, (size_t)n);
     if (rc) return rc;
     const size_t elems = (size_t)batch * n;
-    McqBatch B;
-    memset(&B, 0, sizeof(B));
-    B.batch = batch;
-    B.n = n;
-    B.nmax = n;
-    B.ref = h->d_ref;
-    B.nv = normvec ? h->d_nv : nullptr;
-    B.sc = scaling ? h->d_sc : nullptr;
-    B.alpha = h->d_alpha;
-    B.curv_err = h->d_curv;
-    B.status = h->d_status;
-    B.info = info_out ? h->d_info : nullptr;
-    B.kappa_bound = kappa_bound;
-    B.w_veh = w_veh;
+    const Staging& s = h->stage[0];
+    McqBatch B = make_batch(batch, n, nullptr, s.ref, normvec ? s.nv : nullptr, scaling ? s.sc : nullptr, s.alpha, s.curv, s.status,
+                            info_out ? h->d_info : nullptr, kappa_bound, w_veh);
     // A large batch in (two) SLICES (round 6): the upload of slice k + 1 and the download of slice k - 1 run while slice k's kernel does -- on a
     // copy stream each way --, and the kernels of consecutive slices go to the handle's two compute streams; all of them work on disjoint rows of
     // the ONE workspace (McqBatch.pb0).  The blocking single-batch entry had paid its 115 MB of H2D and 16 MB of D2H in full next to the kernel: 13.3 ms
@@ -1263,48 +1217,34 @@ extern "C" int mcq_solve_host(mcq_handle* h, int batch, int n, const double* ref
     // the one launch (A/B knob).
     const int nsl = host_slices(batch, o);
     if (nsl > 1) {
-        if (int src = ensure_slice_streams(h)) return src;
-        if (int frc = fill_batch(h, B, o, false)) return frc;
-        B.warm = nullptr;
-        h->state2_valid = false;
-        h->timing_valid = false;
+        rc = begin_slices(h, B, o);
+        if (rc) return rc;
         for (int k = 0; k < nsl; ++k) {
             const int b0 = (int)((long long)batch * k / nsl), b1 = (int)((long long)batch * (k + 1) / nsl);
-            if (b1 == b0) continue;            // (none with nsl <= batch; a grid of 0 workgroups is a launch error)
             const size_t off = (size_t)b0 * n, cnt = (size_t)(b1 - b0) * n;
-            HIP_TRY_SLICE(hipMemcpyAsync(h->d_ref + off * 4, reftrack + off * 4, cnt * 4 * sizeof(double), hipMemcpyHostToDevice, h->cs_in));
-            if (normvec) HIP_TRY_SLICE(hipMemcpyAsync(h->d_nv + off * 2, normvec + off * 2, cnt * 2 * sizeof(double), hipMemcpyHostToDevice, h->cs_in));
-            if (scaling) HIP_TRY_SLICE(hipMemcpyAsync(h->d_sc + off, scaling + off, cnt * sizeof(double), hipMemcpyHostToDevice, h->cs_in));
-            HIP_TRY_SLICE(hipEventRecord(h->ev_slice[k], h->cs_in));
-            hipStream_t st = slice_stream(h, k);
-            HIP_TRY_SLICE(hipStreamWaitEvent(st, h->ev_slice[k], 0));
-            McqBatch S = B;
-            S.pb0 = b0;
-            hipLaunchKernelGGL(mcq_solve_kernel, dim3(b1 - b0), dim3(256), 0, st, S);
-            HIP_TRY_SLICE(hipGetLastError());
-            HIP_TRY_SLICE(hipEventRecord(h->ev_slice[8 + k], st));
-            HIP_TRY_SLICE(hipStreamWaitEvent(h->cs_out, h->ev_slice[8 + k], 0));
-            HIP_TRY_SLICE(hipMemcpyAsync(alpha_out + off, h->d_alpha + off, cnt * sizeof(double), hipMemcpyDeviceToHost, h->cs_out));
+            HIP_TRY_DRAIN(hipMemcpyAsync(s.ref + off * 4, reftrack + off * 4, cnt * 4 * sizeof(double), hipMemcpyHostToDevice, h->cs_in));
+            if (normvec) HIP_TRY_DRAIN(hipMemcpyAsync(s.nv + off * 2, normvec + off * 2, cnt * 2 * sizeof(double), hipMemcpyHostToDevice, h->cs_in));
+            if (scaling) HIP_TRY_DRAIN(hipMemcpyAsync(s.sc + off, scaling + off, cnt * sizeof(double), hipMemcpyHostToDevice, h->cs_in));
+            rc = launch_slice(h, B, k, b0, b1, alpha_out);
+            if (rc) return rc;
         }
         // (cs_out is behind every slice's kernel now: the small arrays follow the last slice's alpha)
-        HIP_TRY_SLICE(hipMemcpyAsync(curv_err_out, h->d_curv, batch * sizeof(double), hipMemcpyDeviceToHost, h->cs_out));
-        HIP_TRY_SLICE(hipMemcpyAsync(status_out, h->d_status, batch * sizeof(int), hipMemcpyDeviceToHost, h->cs_out));
-        if (info_out) HIP_TRY_SLICE(hipMemcpyAsync(info_out, h->d_info, batch * sizeof(mcq_info), hipMemcpyDeviceToHost, h->cs_out));
+        rc = download_results(h, h->cs_out, batch, nullptr, nullptr, 0, curv_err_out, status_out, info_out);
+        if (rc) return rc;
         HIP_TRY(hipStreamSynchronize(h->cs_out));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream2));
+        HIP_TRY(hipStreamSynchronize(h->ws[0].stream));
+        HIP_TRY(hipStreamSynchronize(h->ws[1].stream));
         return 0;
     }
-    HIP_TRY_SYNC(hipMemcpyAsync(h->d_ref, reftrack, elems * 4 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    if (normvec) HIP_TRY_SYNC(hipMemcpyAsync(h->d_nv, normvec, elems * 2 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    if (scaling) HIP_TRY_SYNC(hipMemcpyAsync(h->d_sc, scaling, elems * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    hipStream_t st = h->ws[0].stream;
+    HIP_TRY_DRAIN(hipMemcpyAsync(s.ref, reftrack, elems * 4 * sizeof(double), hipMemcpyHostToDevice, st));
+    if (normvec) HIP_TRY_DRAIN(hipMemcpyAsync(s.nv, normvec, elems * 2 * sizeof(double), hipMemcpyHostToDevice, st));
+    if (scaling) HIP_TRY_DRAIN(hipMemcpyAsync(s.sc, scaling, elems * sizeof(double), hipMemcpyHostToDevice, st));
     rc = launch(h, B, o);
-    if (rc) { (void)hipStreamSynchronize(h->stream); return rc; }
-    HIP_TRY_SYNC(hipMemcpyAsync(alpha_out, h->d_alpha, elems * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY_SYNC(hipMemcpyAsync(curv_err_out, h->d_curv, batch * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY_SYNC(hipMemcpyAsync(status_out, h->d_status, batch * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    if (info_out) HIP_TRY_SYNC(hipMemcpyAsync(info_out, h->d_info, batch * sizeof(mcq_info), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (rc) { drain(h); return rc; }
+    rc = download_results(h, st, batch, alpha_out, s.alpha, elems * sizeof(double), curv_err_out, status_out, info_out);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(st));
     // (MCQ_KAPPA_NO_SLOT never arrives here since round 5: the Goldfarb-Idnani path inside the solver kernel takes such problems)
     return 0;
 }
@@ -1323,27 +1263,27 @@ extern "C" int mcq_solve_batch_f32(mcq_handle* h, int batch, int n, int layout, 
     }
     HIP_TRY(hipSetDevice(h->device));
     const mcq_opts o = resolve_opts(opts);
-    int rc = ensure_ws(h, (size_t)batch, (size_t)n);
+    int rc = ensure_workspace(h, 0, (size_t)batch, (size_t)n);
     if (rc) return rc;
-    rc = ensure_stage(h, (size_t)batch, (size_t)n);
+    rc = ensure_staging(h, 0, (size_t)batch, (size_t)n);
     if (rc) return rc;
     const size_t elems = (size_t)batch * n;
-    float* d_rows = (float*)h->d_nv;
-    float* d_al32 = (float*)h->d_sc;
-    HIP_TRY_SYNC(hipMemcpyAsync(d_rows, reftrack, elems * 4 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    if (origin) HIP_TRY_SYNC(hipMemcpyAsync(h->d_org, origin, (size_t)batch * 2 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    rc = solve_f32_rows(h, batch, n, layout, d_rows, origin ? h->d_org : nullptr, kappa_bound, w_veh, o, d_al32, h->d_curv, h->d_status,
+    hipStream_t st = h->ws[0].stream;
+    float* d_rows = (float*)h->stage[0].nv;
+    float* d_al32 = (float*)h->stage[0].sc;
+    HIP_TRY_DRAIN(hipMemcpyAsync(d_rows, reftrack, elems * 4 * sizeof(float), hipMemcpyHostToDevice, st));
+    if (origin) HIP_TRY_DRAIN(hipMemcpyAsync(h->d_org, origin, (size_t)batch * 2 * sizeof(double), hipMemcpyHostToDevice, st));
+    rc = solve_f32_rows(h, batch, n, layout, d_rows, origin ? h->d_org : nullptr, kappa_bound, w_veh, o, d_al32, h->stage[0].curv, h->stage[0].status,
                         info_out ? h->d_info : nullptr);
-    if (rc) { (void)hipStreamSynchronize(h->stream); return rc; }
-    HIP_TRY_SYNC(hipMemcpyAsync(alpha_out, d_al32, elems * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY_SYNC(hipMemcpyAsync(curv_err_out, h->d_curv, batch * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY_SYNC(hipMemcpyAsync(status_out, h->d_status, batch * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    if (info_out) HIP_TRY_SYNC(hipMemcpyAsync(info_out, h->d_info, batch * sizeof(mcq_info), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (rc) { drain(h); return rc; }
+    rc = download_results(h, st, batch, alpha_out, d_al32, elems * sizeof(float), curv_err_out, status_out, info_out);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(st));
     return 0;
 }
 
 // ---- a stream of uniform host batches with the PCIe behind the kernels (include/mcq.h) ------------------------------------------
+// two copy streams, one event triple per staging slot, the second slot
 static int ensure_pipe(mcq_handle* h, size_t batch, size_t nmax)
 {
     if (!h->cs_in) {                    // (mcq_solve_host's slices may have created the two copy streams already)
@@ -1357,39 +1297,8 @@ static int ensure_pipe(mcq_handle* h, size_t batch, size_t nmax)
             HIP_TRY(hipEventCreate(&h->ev_down[k]));
         }
     }
-    const size_t elems = batch * nmax;
-    if (elems <= h->pipe_elems && batch <= h->pipe_batch) return 0;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(hipStreamSynchronize(h->cs_in));
-    HIP_TRY(hipStreamSynchronize(h->cs_out));
-    free_pipe(h);
-    HIP_TRY(hipMalloc((void**)&h->p_ref, elems * 4 * sizeof(double)));
-    HIP_TRY(hipMalloc((void**)&h->p_nv, elems * 2 * sizeof(double)));
-    HIP_TRY(hipMalloc((void**)&h->p_sc, elems * sizeof(double)));
-    HIP_TRY(hipMalloc((void**)&h->p_alpha, elems * sizeof(double)));
-    HIP_TRY(hipMalloc((void**)&h->p_curv, batch * sizeof(double)));
-    HIP_TRY(hipMalloc((void**)&h->p_status, batch * sizeof(int)));
-    h->pipe_elems = elems;
-    h->pipe_batch = batch;
-    return 0;
+    return ensure_staging(h, 1, batch, nmax);
 }
-
-// every stream of the pipeline is drained before an error is reported: copies from / into the caller's buffers may be queued
-#define HIP_TRY_PIPE(expr)                                                                                \
-    do {                                                                                                  \
-        hipError_t e_ = (expr);                                                                           \
-        if (e_ != hipSuccess) {                                                                           \
-            char buf_[512];                                                                               \
-            snprintf(buf_, sizeof(buf_), "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, \
-                     __LINE__);                                                                           \
-            g_err = buf_;                                                                                 \
-            (void)hipStreamSynchronize(h->cs_in);                                                         \
-            (void)hipStreamSynchronize(h->stream);                                                        \
-            if (h->stream2) (void)hipStreamSynchronize(h->stream2);                                       \
-            (void)hipStreamSynchronize(h->cs_out);                                                        \
-            return MCQ_E_DEVICE;                                                                          \
-        }                                                                                                 \
-    } while (0)
 
 extern "C" int mcq_solve_host_pipelined(mcq_handle* h, int steps, int batch, int n, const double* const* reftrack,
                                         const double* const* normvec, const double* const* scaling, double kappa_bound, double w_veh,
@@ -1405,9 +1314,9 @@ extern "C" int mcq_solve_host_pipelined(mcq_handle* h, int steps, int batch, int
     }
     HIP_TRY(hipSetDevice(h->device));
     const mcq_opts o = resolve_opts(opts);
-    int rc = ensure_ws(h, (size_t)batch, (size_t)n);
+    int rc = ensure_workspace(h, 0, (size_t)batch, (size_t)n);
     if (rc) return rc;
-    rc = ensure_stage(h, (size_t)batch, (size_t)n);
+    rc = ensure_staging(h, 0, (size_t)batch, (size_t)n);
     if (rc) return rc;
     rc = ensure_pipe(h, (size_t)batch, (size_t)n);
     if (rc) return rc;
@@ -1421,29 +1330,24 @@ extern "C" int mcq_solve_host_pipelined(mcq_handle* h, int steps, int batch, int
     // kernels of odd steps on the second compute stream / workspace (the variable: A/B knob); MCQ_ALG_GI stays on one stream: its slots
     // (one per resident workgroup) belong to the first workspace (the second one's few slots made odd steps run ~32 problems at a time)
     const bool two = steps > 1 && !getenv("MCQ_PIPE_ONE_STREAM") && o.algorithm != MCQ_ALG_GI;
-    if (two) { rc = ensure_alt(h, (size_t)batch, (size_t)n); if (rc) return rc; }
-    HIP_TRY(hipStreamSynchronize(h->stream));          // whatever ran before on the handle's stream is done with the staging buffers
+    if (two) { rc = ensure_workspace(h, 1, (size_t)batch, (size_t)n); if (rc) return rc; }
+    HIP_TRY(hipStreamSynchronize(h->ws[0].stream));          // whatever ran before on the handle's stream is done with the staging buffers
     const size_t elems = (size_t)batch * n;
-    double* s_ref[2] = {h->d_ref, h->p_ref};
-    double* s_nv[2] = {h->d_nv, h->p_nv};
-    double* s_sc[2] = {h->d_sc, h->p_sc};
-    double* s_al[2] = {h->d_alpha, h->p_alpha};
-    double* s_cu[2] = {h->d_curv, h->p_curv};
-    int* s_st[2] = {h->d_status, h->p_status};
     // Order of the host's enqueues: upload(0); then per step  kernels(k), upload(k + 1), download(k).  The copies of both directions
     // drain through one in-order copy queue of the runtime (rocprofv3 --memory-copy-trace, round 3: with download(k) enqueued ahead
     // of upload(k + 1) the upload sat behind it, i.e. behind the kernels of step k, and nothing overlapped): the upload of the NEXT
     // step therefore goes in first -- it only depends on kernels two steps back -- and runs while step k computes.
     auto upload = [&](int k) -> int {
         const int s = k & 1;
+        const Staging& S = h->stage[s];
         const double* nv_k = normvec ? normvec[k] : nullptr;
         const double* sc_k = scaling ? scaling[k] : nullptr;
         // the kernels of step k - 2 were the last readers of this slot's rows
-        if (k >= 2) HIP_TRY_PIPE(hipStreamWaitEvent(h->cs_in, h->ev_done[s], 0));
-        HIP_TRY_PIPE(hipMemcpyAsync(s_ref[s], reftrack[k], elems * 4 * sizeof(double), hipMemcpyHostToDevice, h->cs_in));
-        if (nv_k) HIP_TRY_PIPE(hipMemcpyAsync(s_nv[s], nv_k, elems * 2 * sizeof(double), hipMemcpyHostToDevice, h->cs_in));
-        if (sc_k) HIP_TRY_PIPE(hipMemcpyAsync(s_sc[s], sc_k, elems * sizeof(double), hipMemcpyHostToDevice, h->cs_in));
-        HIP_TRY_PIPE(hipEventRecord(h->ev_up[s], h->cs_in));
+        if (k >= 2) HIP_TRY_DRAIN(hipStreamWaitEvent(h->cs_in, h->ev_done[s], 0));
+        HIP_TRY_DRAIN(hipMemcpyAsync(S.ref, reftrack[k], elems * 4 * sizeof(double), hipMemcpyHostToDevice, h->cs_in));
+        if (nv_k) HIP_TRY_DRAIN(hipMemcpyAsync(S.nv, nv_k, elems * 2 * sizeof(double), hipMemcpyHostToDevice, h->cs_in));
+        if (sc_k) HIP_TRY_DRAIN(hipMemcpyAsync(S.sc, sc_k, elems * sizeof(double), hipMemcpyHostToDevice, h->cs_in));
+        HIP_TRY_DRAIN(hipEventRecord(h->ev_up[s], h->cs_in));
         return 0;
     };
     rc = upload(0);
@@ -1453,42 +1357,32 @@ extern "C" int mcq_solve_host_pipelined(mcq_handle* h, int steps, int batch, int
     clock_gettime(CLOCK_MONOTONIC, &ts0);
     for (int k = 0; k < steps; ++k) {
         const int s = k & 1;
+        const Staging& S = h->stage[s];
         if (trace) { struct timespec t1; clock_gettime(CLOCK_MONOTONIC, &t1); fprintf(stderr, "pipe: step %d enqueued from %.3f ms\n", k, (t1.tv_sec - ts0.tv_sec) * 1e3 + (t1.tv_nsec - ts0.tv_nsec) * 1e-6); }
         const double* nv_k = normvec ? normvec[k] : nullptr;
         const double* sc_k = scaling ? scaling[k] : nullptr;
         // kernels of step k: after its upload, and after the download of step k - 2 has left the slot's result buffers
         // (slot s's kernels always run on compute stream s: step k - 2, the last user of this slot's workspace and buffers, precedes in stream order)
-        hipStream_t cst = (two && s) ? h->stream2 : h->stream;
-        HIP_TRY_PIPE(hipStreamWaitEvent(cst, h->ev_up[s], 0));
-        if (k >= 2) HIP_TRY_PIPE(hipStreamWaitEvent(cst, h->ev_down[s], 0));
-        McqBatch B;
-        memset(&B, 0, sizeof(B));
-        B.batch = batch;
-        B.n = n;
-        B.nmax = n;
-        B.ref = s_ref[s];
-        B.nv = nv_k ? s_nv[s] : nullptr;
-        B.sc = sc_k ? s_sc[s] : nullptr;
-        B.alpha = s_al[s];
-        B.curv_err = s_cu[s];
-        B.status = s_st[s];
-        B.kappa_bound = kappa_bound;
-        B.w_veh = w_veh;
-        rc = launch(h, B, o, two && s);
-        if (rc) { (void)hipStreamSynchronize(h->cs_in); (void)hipStreamSynchronize(h->stream); if (h->stream2) (void)hipStreamSynchronize(h->stream2); (void)hipStreamSynchronize(h->cs_out); return rc; }
-        HIP_TRY_PIPE(hipEventRecord(h->ev_done[s], cst));
+        Workspace& w = h->ws[two ? s : 0];
+        HIP_TRY_DRAIN(hipStreamWaitEvent(w.stream, h->ev_up[s], 0));
+        if (k >= 2) HIP_TRY_DRAIN(hipStreamWaitEvent(w.stream, h->ev_down[s], 0));
+        McqBatch B = make_batch(batch, n, nullptr, S.ref, nv_k ? S.nv : nullptr, sc_k ? S.sc : nullptr, S.alpha, S.curv, S.status, nullptr,
+                                kappa_bound, w_veh);
+        rc = launch(h, B, o, w);
+        if (rc) { drain(h); return rc; }
+        HIP_TRY_DRAIN(hipEventRecord(h->ev_done[s], w.stream));
         if (k + 1 < steps) { rc = upload(k + 1); if (rc) return rc; }
         // download of step k
-        HIP_TRY_PIPE(hipStreamWaitEvent(h->cs_out, h->ev_done[s], 0));
-        HIP_TRY_PIPE(hipMemcpyAsync(alpha_out[k], s_al[s], elems * sizeof(double), hipMemcpyDeviceToHost, h->cs_out));
-        HIP_TRY_PIPE(hipMemcpyAsync(pin_cu + (size_t)k * batch, s_cu[s], batch * sizeof(double), hipMemcpyDeviceToHost, h->cs_out));
-        HIP_TRY_PIPE(hipMemcpyAsync(pin_st + (size_t)k * batch, s_st[s], batch * sizeof(int), hipMemcpyDeviceToHost, h->cs_out));
-        HIP_TRY_PIPE(hipEventRecord(h->ev_down[s], h->cs_out));
+        HIP_TRY_DRAIN(hipStreamWaitEvent(h->cs_out, h->ev_done[s], 0));
+        HIP_TRY_DRAIN(hipMemcpyAsync(alpha_out[k], S.alpha, elems * sizeof(double), hipMemcpyDeviceToHost, h->cs_out));
+        HIP_TRY_DRAIN(hipMemcpyAsync(pin_cu + (size_t)k * batch, S.curv, batch * sizeof(double), hipMemcpyDeviceToHost, h->cs_out));
+        HIP_TRY_DRAIN(hipMemcpyAsync(pin_st + (size_t)k * batch, S.status, batch * sizeof(int), hipMemcpyDeviceToHost, h->cs_out));
+        HIP_TRY_DRAIN(hipEventRecord(h->ev_down[s], h->cs_out));
     }
-    HIP_TRY_PIPE(hipStreamSynchronize(h->cs_in));
-    HIP_TRY_PIPE(hipStreamSynchronize(h->stream));
-    if (two) HIP_TRY_PIPE(hipStreamSynchronize(h->stream2));
-    HIP_TRY_PIPE(hipStreamSynchronize(h->cs_out));
+    HIP_TRY_DRAIN(hipStreamSynchronize(h->cs_in));
+    HIP_TRY_DRAIN(hipStreamSynchronize(h->ws[0].stream));
+    if (two) HIP_TRY_DRAIN(hipStreamSynchronize(h->ws[1].stream));
+    HIP_TRY_DRAIN(hipStreamSynchronize(h->cs_out));
     for (int k = 0; k < steps; ++k) {
         memcpy(curv_err_out[k], pin_cu + (size_t)k * batch, batch * sizeof(double));
         memcpy(status_out[k], pin_st + (size_t)k * batch, batch * sizeof(int));
@@ -1500,7 +1394,7 @@ extern "C" int mcq_solve_host_pipelined(mcq_handle* h, int steps, int batch, int
 static int ensure_iqp(mcq_handle* h, size_t batch)
 {
     if (batch <= h->iqp_batch) return 0;
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipStreamSynchronize(h->ws[0].stream));
     (void)hipFree(h->d_iqp); (void)hipFree(h->d_iqp_curv); (void)hipFree(h->d_trace);
     h->d_iqp = nullptr; h->d_iqp_curv = nullptr; h->d_trace = nullptr; h->iqp_batch = 0;
     HIP_TRY(hipMalloc((void**)&h->d_iqp, (batch * 8 + 16) * sizeof(int)));
@@ -1525,12 +1419,12 @@ extern "C" int mcq_iqp_device(mcq_handle* h, int batch, int nmax, int* n_io, dou
     HIP_TRY(hipSetDevice(h->device));
     mcq_opts o = resolve_opts(opts);
     const bool warm = !(opts && opts->warm_start < 0);        // passes 2+ start from the carried working sets unless switched off
-    int rc = ensure_ws(h, (size_t)batch, (size_t)nmax);
+    int rc = ensure_workspace(h, 0, (size_t)batch, (size_t)nmax);
     if (rc) return rc;
     rc = ensure_iqp(h, (size_t)batch);
     if (rc) return rc;
     const bool timed = stats && stats->timed;
-    if (timed) { rc = ensure_stage(h, (size_t)batch, (size_t)nmax); if (rc) return rc; }
+    if (timed) { rc = ensure_staging(h, 0, (size_t)batch, (size_t)nmax); if (rc) return rc; }
     // bookkeeping arrays: live | n of the other set | glue status | pass status | final_n (= n_io on return) ... live count
     int* live = h->d_iqp;
     int* n_b = live + batch;
@@ -1545,10 +1439,10 @@ extern "C" int mcq_iqp_device(mcq_handle* h, int batch, int nmax, int* n_io, dou
     // every track starts live (a track with n == 0 ends in its first, empty pass: status MCQ_BAD_INPUT, rounds_out 1)
     {
         std::vector<int> ones((size_t)batch, 1);
-        HIP_TRY(hipMemcpyAsync(live, ones.data(), batch * sizeof(int), hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipMemsetAsync(rounds_out, 0, batch * sizeof(int), h->stream));
-        HIP_TRY(hipMemsetAsync(buf_out, 0, batch * sizeof(int), h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));      // `ones` goes out of scope
+        HIP_TRY(hipMemcpyAsync(live, ones.data(), batch * sizeof(int), hipMemcpyHostToDevice, h->ws[0].stream));
+        HIP_TRY(hipMemsetAsync(rounds_out, 0, batch * sizeof(int), h->ws[0].stream));
+        HIP_TRY(hipMemsetAsync(buf_out, 0, batch * sizeof(int), h->ws[0].stream));
+        HIP_TRY(hipStreamSynchronize(h->ws[0].stream));      // `ones` goes out of scope
     }
     McqIqpStep S;
     memset(&S, 0, sizeof(S));
@@ -1565,13 +1459,13 @@ extern "C" int mcq_iqp_device(mcq_handle* h, int batch, int nmax, int* n_io, dou
     S.final_rounds = rounds_out;
     S.live_count = live_count;
     S.curv_trace = curv_trace_out;
-    if (curv_trace_out) HIP_TRY(hipMemsetAsync(curv_trace_out, 0, (size_t)batch * MCQ_IQP_TRACE * sizeof(double), h->stream));
+    if (curv_trace_out) HIP_TRY(hipMemsetAsync(curv_trace_out, 0, (size_t)batch * MCQ_IQP_TRACE * sizeof(double), h->ws[0].stream));
     const dim3 sgrid((unsigned)((batch + 255) / 256)), sblock(256);
     int cur = 0, rounds = 0, n_live = batch;
     long long solves = 0;
     if (stats) { stats->rounds = 0; stats->qp_solves = 0; for (int k = 0; k < 16; ++k) { stats->solver_ms[k] = 0.f; stats->fallbacks[k] = 0; } }
     // the final ring sizes are collected in a scratch array and moved to n_io at the end (n_io doubles as set 0's sizes)
-    HIP_TRY(hipMemsetAsync(d_final_n, 0, batch * sizeof(int), h->stream));
+    HIP_TRY(hipMemsetAsync(d_final_n, 0, batch * sizeof(int), h->ws[0].stream));
     S.final_n = d_final_n;
     int err = 0;
     int it0 = 1;
@@ -1590,23 +1484,16 @@ extern "C" int mcq_iqp_device(mcq_handle* h, int batch, int nmax, int* n_io, dou
         const int ra = iters_min < max_rounds ? iters_min : max_rounds;
         McqIqpRounds F;
         memset(&F, 0, sizeof(F));
-        F.B.batch = batch;
-        F.B.n = nmax;
-        F.B.nmax = nmax;
-        F.B.alpha = alpha_out;
-        F.B.curv_err = pass_curv;
-        F.B.status = pass_status;
-        F.B.kappa_bound = kappa_bound;
-        F.B.w_veh = w_veh;
-        if ((err = fill_batch(h, F.B, o, false)) != 0) return err;
+        F.B = make_batch(batch, nmax, nullptr, nullptr, nullptr, nullptr, alpha_out, pass_curv, pass_status, nullptr, kappa_bound, w_veh);
+        if ((err = fill_batch(h, F.B, o, h->ws[0])) != 0) return err;
         F.R.batch = batch;
         F.R.nmax = nmax;
         F.R.alpha = alpha_out;
         F.R.live = live;
         F.R.stepsize = stepsize_interp;
         F.R.status = rst;
-        F.R.vec = h->vec;
-        F.R.state_in = h->state;
+        F.R.vec = h->ws[0].vec;
+        F.R.state_in = h->ws[0].state;
         F.R.state_out = h->state2;
         F.S = S;
         F.S.live_count = live_count;
@@ -1614,38 +1501,26 @@ extern "C" int mcq_iqp_device(mcq_handle* h, int batch, int nmax, int* n_io, dou
         F.sc = scaling;
         F.warm = warm ? h->state2 : nullptr;
         F.rounds = ra;
-        if (hipMemsetAsync(live_count, 0, sizeof(int), h->stream) != hipSuccess) err = MCQ_E_DEVICE;
+        if (hipMemsetAsync(live_count, 0, sizeof(int), h->ws[0].stream) != hipSuccess) err = MCQ_E_DEVICE;
         if (!err) {
-            hipLaunchKernelGGL(mcq_iqp_rounds_kernel, dim3((unsigned)batch), dim3(256), 0, h->stream, F);
+            hipLaunchKernelGGL(mcq_iqp_rounds_kernel, dim3((unsigned)batch), dim3(256), 0, h->ws[0].stream, F);
             if (hipGetLastError() != hipSuccess) err = MCQ_E_DEVICE;
         }
         // (the loop below may go on from the working sets the last round's glue carried over)
         h->state2_valid = true;
         h->state2_batch = batch;
         h->state2_nmax = nmax;
-        if (!err && (hipMemcpyAsync(&n_live, live_count, sizeof(int), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-                     hipStreamSynchronize(h->stream) != hipSuccess)) err = MCQ_E_DEVICE;
+        if (!err && (hipMemcpyAsync(&n_live, live_count, sizeof(int), hipMemcpyDeviceToHost, h->ws[0].stream) != hipSuccess ||
+                     hipStreamSynchronize(h->ws[0].stream) != hipSuccess)) err = MCQ_E_DEVICE;
         cur = ra & 1;
         rounds = ra;
         it0 = ra + 1;
     }
     for (int it = it0; it <= max_rounds && n_live > 0 && !err; ++it) {
         rounds = it;
-        McqBatch B;
-        memset(&B, 0, sizeof(B));
-        B.batch = batch;
-        B.n = nmax;
-        B.nmax = nmax;
-        B.n_list = n_set[cur];
-        B.ref = ref_set[cur];
-        B.nv = nv_set[cur];
-        B.sc = it == 1 ? scaling : nullptr;                 // the re-spline of passes 2+ uses unit scalings (upstream)
-        B.alpha = alpha_out;
-        B.curv_err = pass_curv;
-        B.status = pass_status;
-        B.info = timed ? h->d_info : nullptr;
-        B.kappa_bound = kappa_bound;
-        B.w_veh = w_veh;
+        // (scalings: the re-spline of passes 2+ uses unit ones, as upstream)
+        McqBatch B = make_batch(batch, nmax, n_set[cur], ref_set[cur], nv_set[cur], it == 1 ? scaling : nullptr, alpha_out, pass_curv, pass_status,
+                                timed ? h->d_info : nullptr, kappa_bound, w_veh);
         o.warm_start = (warm && it > 1) ? 1 : 0;
         if ((err = launch(h, B, o)) != 0) break;
         if (timed && it <= 16) {
@@ -1653,9 +1528,9 @@ extern "C" int mcq_iqp_device(mcq_handle* h, int batch, int nmax, int* n_io, dou
             if (mcq_last_timing(h, ms) == 0) stats->solver_ms[it - 1] = ms[4];
             std::vector<mcq_info> info((size_t)batch);
             std::vector<int> lv((size_t)batch);
-            if (hipMemcpyAsync(info.data(), h->d_info, batch * sizeof(mcq_info), hipMemcpyDeviceToHost, h->stream) == hipSuccess &&
-                hipMemcpyAsync(lv.data(), live, batch * sizeof(int), hipMemcpyDeviceToHost, h->stream) == hipSuccess &&
-                hipStreamSynchronize(h->stream) == hipSuccess) {
+            if (hipMemcpyAsync(info.data(), h->d_info, batch * sizeof(mcq_info), hipMemcpyDeviceToHost, h->ws[0].stream) == hipSuccess &&
+                hipMemcpyAsync(lv.data(), live, batch * sizeof(int), hipMemcpyDeviceToHost, h->ws[0].stream) == hipSuccess &&
+                hipStreamSynchronize(h->ws[0].stream) == hipSuccess) {
                 int fb = 0;
                 for (int k = 0; k < batch; ++k) if (lv[k] && (info[k].second_attempt & 2)) ++fb;
                 stats->fallbacks[it - 1] = fb;
@@ -1664,33 +1539,33 @@ extern "C" int mcq_iqp_device(mcq_handle* h, int batch, int nmax, int* n_io, dou
         if (h->iqp_cb) {        // print_debug: the pass's curvature errors and who ran it, before the termination test decides
             std::vector<double> cv((size_t)batch);
             std::vector<int> lv((size_t)batch);
-            if (hipMemcpyAsync(cv.data(), pass_curv, batch * sizeof(double), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-                hipMemcpyAsync(lv.data(), live, batch * sizeof(int), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-                hipStreamSynchronize(h->stream) != hipSuccess) { err = MCQ_E_DEVICE; break; }
+            if (hipMemcpyAsync(cv.data(), pass_curv, batch * sizeof(double), hipMemcpyDeviceToHost, h->ws[0].stream) != hipSuccess ||
+                hipMemcpyAsync(lv.data(), live, batch * sizeof(int), hipMemcpyDeviceToHost, h->ws[0].stream) != hipSuccess ||
+                hipStreamSynchronize(h->ws[0].stream) != hipSuccess) { err = MCQ_E_DEVICE; break; }
             h->iqp_cb(h->iqp_cb_user, it, batch, cv.data(), lv.data());
         }
-        if (hipMemsetAsync(live_count, 0, sizeof(int), h->stream) != hipSuccess) { err = MCQ_E_DEVICE; break; }
+        if (hipMemsetAsync(live_count, 0, sizeof(int), h->ws[0].stream) != hipSuccess) { err = MCQ_E_DEVICE; break; }
         S.phase = 0;
         S.round = it;
         S.cur = cur;
         S.n_ring = n_set[cur];
         S.n_next = n_set[1 - cur];
-        hipLaunchKernelGGL(mcq_iqp_step_kernel, sgrid, sblock, 0, h->stream, S);
+        hipLaunchKernelGGL(mcq_iqp_step_kernel, sgrid, sblock, 0, h->ws[0].stream, S);
         const double scale = it < iters_min ? (double)it / (double)iters_min : 1.0;
         if ((err = mcq_relinearise_device(h, batch, nmax, n_set[cur], ref_set[cur], nv_set[cur], alpha_out, live, scale,
                                           stepsize_interp, ref_set[1 - cur], nv_set[1 - cur], n_set[1 - cur], rst)) != 0) break;
         S.phase = 1;
-        hipLaunchKernelGGL(mcq_iqp_step_kernel, sgrid, sblock, 0, h->stream, S);
+        hipLaunchKernelGGL(mcq_iqp_step_kernel, sgrid, sblock, 0, h->ws[0].stream, S);
         if (hipGetLastError() != hipSuccess) { err = MCQ_E_DEVICE; break; }
         cur = 1 - cur;
         // the first iters_min - 1 rounds cannot end a healthy track: no need to look
         if (it >= iters_min || it == max_rounds) {
-            if (hipMemcpyAsync(&n_live, live_count, sizeof(int), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-                hipStreamSynchronize(h->stream) != hipSuccess) { err = MCQ_E_DEVICE; break; }
+            if (hipMemcpyAsync(&n_live, live_count, sizeof(int), hipMemcpyDeviceToHost, h->ws[0].stream) != hipSuccess ||
+                hipStreamSynchronize(h->ws[0].stream) != hipSuccess) { err = MCQ_E_DEVICE; break; }
         }
     }
-    if (!err && hipMemcpyAsync(n_io, d_final_n, batch * sizeof(int), hipMemcpyDeviceToDevice, h->stream) != hipSuccess) err = MCQ_E_DEVICE;
-    if (hipStreamSynchronize(h->stream) != hipSuccess && !err) err = MCQ_E_DEVICE;
+    if (!err && hipMemcpyAsync(n_io, d_final_n, batch * sizeof(int), hipMemcpyDeviceToDevice, h->ws[0].stream) != hipSuccess) err = MCQ_E_DEVICE;
+    if (hipStreamSynchronize(h->ws[0].stream) != hipSuccess && !err) err = MCQ_E_DEVICE;
     h->state2_valid = false;        // the working sets belong to this run's last glue call, not to a later solve
     if (err) { if (err == MCQ_E_DEVICE && g_err.empty()) g_err = "mcq_iqp_device: HIP runtime error"; return err; }
     if (stats) {
@@ -1724,11 +1599,21 @@ struct PinLayout {
     mcq_info* info;
 };
 
+// the per-problem scalars of a ragged host batch, through the pinned block to the device on `up`
+static int upload_scalars(mcq_handle* h, const mcq_problem* probs, int batch, const PinLayout& P, hipStream_t up)
+{
+    for (int b = 0; b < batch; ++b) { P.kb[b] = probs[b].kappa_bound; P.wv[b] = probs[b].w_veh; P.n[b] = probs[b].n; }
+    HIP_TRY_DRAIN(hipMemcpyAsync(h->d_kb, P.kb, batch * sizeof(double), hipMemcpyHostToDevice, up));
+    HIP_TRY_DRAIN(hipMemcpyAsync(h->d_wv, P.wv, batch * sizeof(double), hipMemcpyHostToDevice, up));
+    HIP_TRY_DRAIN(hipMemcpyAsync(h->d_n, P.n, batch * sizeof(int), hipMemcpyHostToDevice, up));
+    return 0;
+}
+
 // after_chunk (round 6, mcq_solve_batch in slices): the uploads go to the handle's copy stream h->cs_in instead of its compute stream, in exactly
 // `force_chunks` chunks of tracks, the per-problem scalars first, and after_chunk(k, b0, b1) is called as soon as chunk k's uploads are queued
 // (it queues that slice's kernel behind them while the next chunk is packed).
 static int pack_and_upload(mcq_handle* h, const mcq_problem* probs, int batch, size_t nmax, bool any_sc, bool with_nv,
-                           size_t extra_bytes, PinLayout& P, const char* who, int force_chunks = 0,
+                           size_t extra_bytes, PinLayout& P, int force_chunks = 0,
                            const std::function<int(int, int, int)>& after_chunk = nullptr)
 {
     const size_t elems = (size_t)batch * nmax;
@@ -1744,6 +1629,8 @@ static int pack_and_upload(mcq_handle* h, const mcq_problem* probs, int batch, s
     P.wv = P.kb + batch;
     P.info = (mcq_info*)(P.wv + batch);
     P.n = (int*)(P.info + batch);
+    const Staging& s = h->stage[0];
+    hipStream_t up = force_chunks > 0 ? h->cs_in : h->ws[0].stream;
     // (the padding behind a track's n waypoints is never read by a kernel: no need to clear it)
     auto pack_range = [&](int b0, int b1) {
         for (int b = b0; b < b1; ++b) {
@@ -1754,9 +1641,6 @@ static int pack_and_upload(mcq_handle* h, const mcq_problem* probs, int batch, s
                 if (probs[b].scaling) memcpy(P.sc + (size_t)b * nmax, probs[b].scaling, n * sizeof(double));
                 else for (size_t q = 0; q < n; ++q) P.sc[(size_t)b * nmax + q] = 1.0;
             }
-            P.kb[b] = probs[b].kappa_bound;
-            P.wv[b] = probs[b].w_veh;
-            P.n[b] = probs[b].n;
         }
     };
     // ---- no packing at all (round 6): a UNIFORM batch that lies in the caller's memory as one contiguous, page-locked block per array (what
@@ -1779,19 +1663,15 @@ static int pack_and_upload(mcq_handle* h, const mcq_problem* probs, int batch, s
         direct = direct && pinned(probs[0].reftrack) && (!with_nv || pinned(probs[0].normvec)) && (!probs[0].scaling || pinned(probs[0].scaling));
         h->last_upload_direct = direct ? 1 : 0;
         if (direct) {
-            hipStream_t up = force_chunks > 0 ? h->cs_in : h->stream;
-            for (int b = 0; b < batch; ++b) { P.kb[b] = probs[b].kappa_bound; P.wv[b] = probs[b].w_veh; P.n[b] = probs[b].n; }
-            HIP_TRY_SYNC(hipMemcpyAsync(h->d_kb, P.kb, batch * sizeof(double), hipMemcpyHostToDevice, up));
-            HIP_TRY_SYNC(hipMemcpyAsync(h->d_wv, P.wv, batch * sizeof(double), hipMemcpyHostToDevice, up));
-            HIP_TRY_SYNC(hipMemcpyAsync(h->d_n, P.n, batch * sizeof(int), hipMemcpyHostToDevice, up));
+            if (int rc2 = upload_scalars(h, probs, batch, P, up)) return rc2;
             const size_t w = (size_t)n0 * sizeof(double), pitch = nmax * sizeof(double);
             const int nck = force_chunks > 0 ? std::min(force_chunks, batch) : 1;
             for (int ck = 0; ck < nck; ++ck) {
                 const int b0 = (int)((long long)batch * ck / nck), b1 = (int)((long long)batch * (ck + 1) / nck);
                 const size_t rows = (size_t)(b1 - b0);
-                HIP_TRY_SYNC(hipMemcpy2DAsync(h->d_ref + (size_t)b0 * nmax * 4, pitch * 4, probs[b0].reftrack, w * 4, w * 4, rows, hipMemcpyHostToDevice, up));
-                if (with_nv) HIP_TRY_SYNC(hipMemcpy2DAsync(h->d_nv + (size_t)b0 * nmax * 2, pitch * 2, probs[b0].normvec, w * 2, w * 2, rows, hipMemcpyHostToDevice, up));
-                if (any_sc) HIP_TRY_SYNC(hipMemcpy2DAsync(h->d_sc + (size_t)b0 * nmax, pitch, probs[b0].scaling, w, w, rows, hipMemcpyHostToDevice, up));
+                HIP_TRY_DRAIN(hipMemcpy2DAsync(s.ref + (size_t)b0 * nmax * 4, pitch * 4, probs[b0].reftrack, w * 4, w * 4, rows, hipMemcpyHostToDevice, up));
+                if (with_nv) HIP_TRY_DRAIN(hipMemcpy2DAsync(s.nv + (size_t)b0 * nmax * 2, pitch * 2, probs[b0].normvec, w * 2, w * 2, rows, hipMemcpyHostToDevice, up));
+                if (any_sc) HIP_TRY_DRAIN(hipMemcpy2DAsync(s.sc + (size_t)b0 * nmax, pitch, probs[b0].scaling, w, w, rows, hipMemcpyHostToDevice, up));
                 if (after_chunk) { if (int rc2 = after_chunk(ck, b0, b1)) return rc2; }
             }
             return 0;
@@ -1812,13 +1692,8 @@ static int pack_and_upload(mcq_handle* h, const mcq_problem* probs, int batch, s
     int nchunks = (forced && nthreads > 1) || (payload > ((size_t)32 << 20) && batch >= 16) ? 4 : 1;
     if (force_chunks > 0) nchunks = force_chunks;
     if (nchunks > batch) nchunks = batch;
-    (void)who;
-    hipStream_t up = force_chunks > 0 ? h->cs_in : h->stream;
     if (force_chunks > 0) {        // the slices' kernels read the per-problem scalars: first
-        for (int b = 0; b < batch; ++b) { P.kb[b] = probs[b].kappa_bound; P.wv[b] = probs[b].w_veh; P.n[b] = probs[b].n; }
-        HIP_TRY_SYNC(hipMemcpyAsync(h->d_kb, P.kb, batch * sizeof(double), hipMemcpyHostToDevice, up));
-        HIP_TRY_SYNC(hipMemcpyAsync(h->d_wv, P.wv, batch * sizeof(double), hipMemcpyHostToDevice, up));
-        HIP_TRY_SYNC(hipMemcpyAsync(h->d_n, P.n, batch * sizeof(int), hipMemcpyHostToDevice, up));
+        if (int rc2 = upload_scalars(h, probs, batch, P, up)) return rc2;
     }
     for (int ck = 0; ck < nchunks; ++ck) {
         const int b0 = (int)((long long)batch * ck / nchunks), b1 = (int)((long long)batch * (ck + 1) / nchunks);
@@ -1834,16 +1709,12 @@ static int pack_and_upload(mcq_handle* h, const mcq_problem* probs, int batch, s
             for (auto& t : th) t.join();
         } else pack_range(b0, b1);
         const size_t off = (size_t)b0 * nmax, cnt = (size_t)(b1 - b0) * nmax;
-        HIP_TRY_SYNC(hipMemcpyAsync(h->d_ref + off * 4, P.ref + off * 4, cnt * 4 * sizeof(double), hipMemcpyHostToDevice, up));
-        if (with_nv) HIP_TRY_SYNC(hipMemcpyAsync(h->d_nv + off * 2, P.nv + off * 2, cnt * 2 * sizeof(double), hipMemcpyHostToDevice, up));
-        if (any_sc) HIP_TRY_SYNC(hipMemcpyAsync(h->d_sc + off, P.sc + off, cnt * sizeof(double), hipMemcpyHostToDevice, up));
+        HIP_TRY_DRAIN(hipMemcpyAsync(s.ref + off * 4, P.ref + off * 4, cnt * 4 * sizeof(double), hipMemcpyHostToDevice, up));
+        if (with_nv) HIP_TRY_DRAIN(hipMemcpyAsync(s.nv + off * 2, P.nv + off * 2, cnt * 2 * sizeof(double), hipMemcpyHostToDevice, up));
+        if (any_sc) HIP_TRY_DRAIN(hipMemcpyAsync(s.sc + off, P.sc + off, cnt * sizeof(double), hipMemcpyHostToDevice, up));
         if (after_chunk) { if (int rc2 = after_chunk(ck, b0, b1)) return rc2; }
     }
-    if (force_chunks > 0) return 0;
-    HIP_TRY_SYNC(hipMemcpyAsync(h->d_kb, P.kb, batch * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY_SYNC(hipMemcpyAsync(h->d_wv, P.wv, batch * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY_SYNC(hipMemcpyAsync(h->d_n, P.n, batch * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    return 0;
+    return force_chunks > 0 ? 0 : upload_scalars(h, probs, batch, P, up);      // (one launch: the scalars follow the rows)
 }
 
 // mcq_solve_batch and mcq_solve_batch_ends: d_ends = the device copy of the per-problem mcq_ends records, or nullptr (all rings)
@@ -1866,24 +1737,15 @@ static int solve_batch_impl(mcq_handle* h, const mcq_problem* probs, const mcq_e
         if ((size_t)probs[b].n > nmax) nmax = (size_t)probs[b].n;
         if (probs[b].scaling) any_sc = true;
     }
-    int rc = ensure_ws(h, (size_t)batch, nmax);
+    int rc = ensure_workspace(h, 0, (size_t)batch, nmax);
     if (rc) return rc;
-    rc = ensure_stage(h, (size_t)batch, nmax);
+    rc = ensure_staging(h, 0, (size_t)batch, nmax);
     if (rc) return rc;
     PinLayout P;
-    McqBatch B;
-    memset(&B, 0, sizeof(B));
-    B.batch = batch;
-    B.n = (int)nmax;
-    B.nmax = (int)nmax;
-    B.n_list = h->d_n;
-    B.ref = h->d_ref;
-    B.nv = probs[0].normvec ? h->d_nv : nullptr;      // none given: derived on the device (scalings too)
-    B.sc = any_sc ? h->d_sc : nullptr;
-    B.alpha = h->d_alpha;
-    B.curv_err = h->d_curv;
-    B.status = h->d_status;
-    B.info = h->d_info;
+    const Staging& s = h->stage[0];
+    const bool with_nv = probs[0].normvec != nullptr;       // none given: normals (and scalings) are derived on the device
+    McqBatch B = make_batch(batch, (int)nmax, h->d_n, s.ref, with_nv ? s.nv : nullptr, any_sc ? s.sc : nullptr, s.alpha, s.curv, s.status, h->d_info,
+                            0.0, 0.0);
     B.kappa_bound_list = h->d_kb;
     B.w_veh_list = h->d_wv;
     B.ends = d_ends;
@@ -1891,56 +1753,26 @@ static int solve_batch_impl(mcq_handle* h, const mcq_problem* probs, const mcq_e
     if (nsl > 1) {
         // in slices, as mcq_solve_host (see there): chunk k's kernel is queued behind its uploads while chunk k + 1 is packed; the padded alpha
         // rows come back slice by slice into the pinned staging
-        rc = ensure_slice_streams(h);
+        rc = begin_slices(h, B, o);
         if (rc) return rc;
-        rc = fill_batch(h, B, o, false);
+        rc = pack_and_upload(h, probs, batch, nmax, any_sc, with_nv, 0, P, nsl,
+                             [&](int k, int b0, int b1) -> int { return launch_slice(h, B, k, b0, b1, P.alpha); });
+        if (rc) { drain(h); return rc; }
+        rc = download_results(h, h->cs_out, batch, nullptr, nullptr, 0, curv_err_out, status_out, P.info);
         if (rc) return rc;
-        B.warm = nullptr;
-        h->state2_valid = false;
-        h->timing_valid = false;
-        PinLayout* Pp = &P;
-        rc = pack_and_upload(h, probs, batch, nmax, any_sc, probs[0].normvec != nullptr, 0, P, "mcq_solve_batch", nsl,
-                             [&](int k, int b0, int b1) -> int {
-                                 if (b1 == b0) return 0;        // (as in mcq_solve_host)
-                                 HIP_TRY_SLICE(hipEventRecord(h->ev_slice[k], h->cs_in));
-                                 hipStream_t st = slice_stream(h, k);
-                                 HIP_TRY_SLICE(hipStreamWaitEvent(st, h->ev_slice[k], 0));
-                                 McqBatch S = B;
-                                 S.pb0 = b0;
-                                 hipLaunchKernelGGL(mcq_solve_kernel, dim3(b1 - b0), dim3(256), 0, st, S);
-                                 HIP_TRY_SLICE(hipGetLastError());
-                                 HIP_TRY_SLICE(hipEventRecord(h->ev_slice[8 + k], st));
-                                 HIP_TRY_SLICE(hipStreamWaitEvent(h->cs_out, h->ev_slice[8 + k], 0));
-                                 const size_t off = (size_t)b0 * nmax, cnt = (size_t)(b1 - b0) * nmax;
-                                 HIP_TRY_SLICE(hipMemcpyAsync(Pp->alpha + off, h->d_alpha + off, cnt * sizeof(double), hipMemcpyDeviceToHost, h->cs_out));
-                                 return 0;
-                             });
-        if (rc) { (void)hipStreamSynchronize(h->cs_in); (void)hipStreamSynchronize(h->stream); (void)hipStreamSynchronize(h->stream2); (void)hipStreamSynchronize(h->cs_out); return rc; }
-        HIP_TRY_SLICE(hipMemcpyAsync(curv_err_out, h->d_curv, batch * sizeof(double), hipMemcpyDeviceToHost, h->cs_out));
-        HIP_TRY_SLICE(hipMemcpyAsync(status_out, h->d_status, batch * sizeof(int), hipMemcpyDeviceToHost, h->cs_out));
-        HIP_TRY_SLICE(hipMemcpyAsync(P.info, h->d_info, batch * sizeof(mcq_info), hipMemcpyDeviceToHost, h->cs_out));
-        HIP_TRY_SLICE(hipStreamSynchronize(h->cs_out));
-        HIP_TRY_SLICE(hipStreamSynchronize(h->stream));
-        HIP_TRY_SLICE(hipStreamSynchronize(h->stream2));
-        size_t off2 = 0;
-        for (int b = 0; b < batch; ++b) {
-            const size_t nb = (size_t)probs[b].n;
-            memcpy(alpha_out + off2, P.alpha + (size_t)b * nmax, nb * sizeof(double));
-            off2 += nb;
-            if (info_out) info_out[b] = P.info[b];
-        }
-        return 0;
+        HIP_TRY_DRAIN(hipStreamSynchronize(h->cs_out));
+        HIP_TRY_DRAIN(hipStreamSynchronize(h->ws[0].stream));
+        HIP_TRY_DRAIN(hipStreamSynchronize(h->ws[1].stream));
+    } else {
+        rc = pack_and_upload(h, probs, batch, nmax, any_sc, with_nv, 0, P);
+        if (rc) return rc;
+        rc = launch(h, B, o);
+        if (rc) { drain(h); return rc; }
+        rc = download_results(h, h->ws[0].stream, batch, P.alpha, s.alpha, (size_t)batch * nmax * sizeof(double), curv_err_out, status_out, P.info);
+        if (rc) return rc;
+        HIP_TRY(hipStreamSynchronize(h->ws[0].stream));
     }
-    rc = pack_and_upload(h, probs, batch, nmax, any_sc, probs[0].normvec != nullptr, 0, P, "mcq_solve_batch");
-    if (rc) return rc;
-    rc = launch(h, B, o);
-    if (rc) { (void)hipStreamSynchronize(h->stream); return rc; }
-
-    HIP_TRY_SYNC(hipMemcpyAsync(P.alpha, h->d_alpha, (size_t)batch * nmax * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY_SYNC(hipMemcpyAsync(curv_err_out, h->d_curv, batch * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY_SYNC(hipMemcpyAsync(status_out, h->d_status, batch * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY_SYNC(hipMemcpyAsync(P.info, h->d_info, batch * sizeof(mcq_info), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    // the padded rows of the pinned staging, back to back into the caller's array
     size_t off = 0;
     for (int b = 0; b < batch; ++b) {
         const size_t n = (size_t)probs[b].n;
@@ -1974,7 +1806,7 @@ extern "C" int mcq_solve_batch_ends(mcq_handle* h, const mcq_problem* probs, con
     }
     HIP_TRY(hipSetDevice(h->device));
     if (h->ends_cap < (size_t)batch) {
-        HIP_TRY(hipStreamSynchronize(h->stream));       // (the previous records may still be read by a launch in flight)
+        HIP_TRY(hipStreamSynchronize(h->ws[0].stream));       // (the previous records may still be read by a launch in flight)
         (void)hipFree(h->d_ends);
         h->d_ends = nullptr;
         h->ends_cap = 0;
@@ -1982,8 +1814,8 @@ extern "C" int mcq_solve_batch_ends(mcq_handle* h, const mcq_problem* probs, con
         h->ends_cap = (size_t)batch;
     }
     // ordered before every launch of the solve (and the copy streams of its slices) by the synchronisation: the caller's array is pageable
-    HIP_TRY(hipMemcpyAsync(h->d_ends, ends, (size_t)batch * sizeof(mcq_ends), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpyAsync(h->d_ends, ends, (size_t)batch * sizeof(mcq_ends), hipMemcpyHostToDevice, h->ws[0].stream));
+    HIP_TRY(hipStreamSynchronize(h->ws[0].stream));
     return solve_batch_impl(h, probs, h->d_ends, batch, opts, alpha_out, curv_err_out, status_out, info_out);
 }
 
@@ -2000,37 +1832,27 @@ extern "C" int mcq_solve_device_stream(mcq_handle* h, int steps, int batch, int 
         if (!reftrack[k] || !alpha_out[k] || !curv_err_out[k] || !status_out[k]) { g_err = "mcq_solve_device_stream: NULL buffer in step list"; return MCQ_E_ARG; }
     HIP_TRY(hipSetDevice(h->device));
     const mcq_opts o = resolve_opts(opts);
-    int rc = ensure_ws(h, (size_t)batch, (size_t)n);
+    int rc = ensure_workspace(h, 0, (size_t)batch, (size_t)n);
     if (rc) return rc;
     const bool two = steps > 1 && !getenv("MCQ_PIPE_ONE_STREAM") && o.algorithm != MCQ_ALG_GI;
-    if (two) { rc = ensure_alt(h, (size_t)batch, (size_t)n); if (rc) return rc; }
+    if (two) { rc = ensure_workspace(h, 1, (size_t)batch, (size_t)n); if (rc) return rc; }
     // the second stream starts behind whatever the caller has enqueued on the first (uploads of the inputs, an earlier call)
     if (two) {
         for (int k = 0; k < 2; ++k) if (!h->ev_st[k]) HIP_TRY(hipEventCreate(&h->ev_st[k]));
-        HIP_TRY(hipEventRecord(h->ev_st[0], h->stream));
-        HIP_TRY(hipStreamWaitEvent(h->stream2, h->ev_st[0], 0));
+        HIP_TRY(hipEventRecord(h->ev_st[0], h->ws[0].stream));
+        HIP_TRY(hipStreamWaitEvent(h->ws[1].stream, h->ev_st[0], 0));
     }
     for (int k = 0; k < steps; ++k) {
-        McqBatch B;
-        memset(&B, 0, sizeof(B));
-        B.batch = batch;
-        B.n = n;
-        B.nmax = n;
-        B.ref = reftrack[k];
-        B.nv = normvec ? normvec[k] : nullptr;
-        B.sc = (scaling && B.nv) ? scaling[k] : nullptr;
-        B.alpha = alpha_out[k];
-        B.curv_err = curv_err_out[k];
-        B.status = status_out[k];
-        B.kappa_bound = kappa_bound;
-        B.w_veh = w_veh;
-        rc = launch(h, B, o, two && (k & 1));
-        if (rc) { (void)hipStreamSynchronize(h->stream); if (h->stream2) (void)hipStreamSynchronize(h->stream2); return rc; }
+        const double* nv_k = normvec ? normvec[k] : nullptr;
+        McqBatch B = make_batch(batch, n, nullptr, reftrack[k], nv_k, (scaling && nv_k) ? scaling[k] : nullptr, alpha_out[k], curv_err_out[k],
+                                status_out[k], nullptr, kappa_bound, w_veh);
+        rc = launch(h, B, o, h->ws[two ? (k & 1) : 0]);
+        if (rc) { drain(h); return rc; }
     }
     // the handle's first stream ends behind the second one: mcq_sync / a later call on the handle sees every step done
     if (two) {
-        HIP_TRY(hipEventRecord(h->ev_st[1], h->stream2));
-        HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_st[1], 0));
+        HIP_TRY(hipEventRecord(h->ev_st[1], h->ws[1].stream));
+        HIP_TRY(hipStreamWaitEvent(h->ws[0].stream, h->ev_st[1], 0));
     }
     return 0;
 }
@@ -2074,13 +1896,13 @@ extern "C" int mcq_iqp_batch(mcq_handle* h, const mcq_problem* probs, int batch,
         }
         if (probs[b].scaling) any_sc = true;
     }
-    int rc = ensure_ws(h, (size_t)batch, nmax);
+    int rc = ensure_workspace(h, 0, (size_t)batch, nmax);
     if (rc) return rc;
-    rc = ensure_stage(h, (size_t)batch, nmax);
+    rc = ensure_staging(h, 0, (size_t)batch, nmax);
     if (rc) return rc;
     const size_t elems = (size_t)batch * nmax;
     if (elems > h->stage2_elems) {
-        HIP_TRY(hipStreamSynchronize(h->stream));
+        HIP_TRY(hipStreamSynchronize(h->ws[0].stream));
         (void)hipFree(h->d_ref2); (void)hipFree(h->d_nv2);
         h->d_ref2 = h->d_nv2 = nullptr; h->stage2_elems = 0;
         HIP_TRY(hipMalloc((void**)&h->d_ref2, elems * 4 * sizeof(double)));
@@ -2090,7 +1912,7 @@ extern "C" int mcq_iqp_batch(mcq_handle* h, const mcq_problem* probs, int batch,
     PinLayout P;
     // results need room for both buffer sets' ref / nv in the worst case: one extra set
     stamp("checked, buffers ready");
-    rc = pack_and_upload(h, probs, batch, nmax, any_sc, true, elems * 6 * sizeof(double) + (size_t)batch * 3 * sizeof(int), P, "mcq_iqp_batch");
+    rc = pack_and_upload(h, probs, batch, nmax, any_sc, true, elems * 6 * sizeof(double) + (size_t)batch * 3 * sizeof(int), P);
     if (rc) return rc;
     stamp("packed, uploads queued");
     rc = ensure_iqp(h, (size_t)batch);                 // the trace staging lives in the handle (no allocation / hipFree -- an implicit
@@ -2099,9 +1921,9 @@ extern "C" int mcq_iqp_batch(mcq_handle* h, const mcq_problem* probs, int batch,
     // d_kb / d_wv staging doubles as the per-track outputs of the loop: curvature error (double), buffer index / rounds (ints)
     int* d_buf = (int*)h->d_kb;                 // batch doubles >= 2 * batch ints
     int* d_rounds = d_buf + batch;
-    rc = mcq_iqp_device(h, batch, (int)nmax, h->d_n, h->d_ref, h->d_nv, h->d_ref2, h->d_nv2, any_sc ? h->d_sc : nullptr,
+    rc = mcq_iqp_device(h, batch, (int)nmax, h->d_n, h->stage[0].ref, h->stage[0].nv, h->d_ref2, h->d_nv2, any_sc ? h->stage[0].sc : nullptr,
                         probs[0].kappa_bound, probs[0].w_veh, stepsize_interp, iters_min, curv_error_allowed, max_rounds, opts,
-                        h->d_alpha, d_buf, h->d_curv, h->d_status, d_rounds, d_trace, stats);
+                        h->stage[0].alpha, d_buf, h->stage[0].curv, h->stage[0].status, d_rounds, d_trace, stats);
     stamp("rounds done");
     if (!rc && d_trace && hipMemcpy(curv_trace_out, d_trace, (size_t)batch * MCQ_IQP_TRACE * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) {
         g_err = "mcq_iqp_batch: read-back of the curvature-error trace failed";
@@ -2109,25 +1931,24 @@ extern "C" int mcq_iqp_batch(mcq_handle* h, const mcq_problem* probs, int batch,
     }
     if (rc) return rc;
     int* buf_h = P.n;                            // the pinned int block: n | (extra) buf, rounds
-    HIP_TRY_SYNC(hipMemcpyAsync(n_out, h->d_n, batch * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY_SYNC(hipMemcpyAsync(buf_h, d_buf, batch * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY_SYNC(hipMemcpyAsync(rounds_out, d_rounds, batch * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY_SYNC(hipMemcpyAsync(curv_err_out, h->d_curv, batch * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY_SYNC(hipMemcpyAsync(status_out, h->d_status, batch * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY_DRAIN(hipMemcpyAsync(n_out, h->d_n, batch * sizeof(int), hipMemcpyDeviceToHost, h->ws[0].stream));
+    HIP_TRY_DRAIN(hipMemcpyAsync(buf_h, d_buf, batch * sizeof(int), hipMemcpyDeviceToHost, h->ws[0].stream));
+    HIP_TRY_DRAIN(hipMemcpyAsync(rounds_out, d_rounds, batch * sizeof(int), hipMemcpyDeviceToHost, h->ws[0].stream));
     // alpha straight into the caller's [batch][nmax_out] array (its padding holds whatever the device buffer held)
-    HIP_TRY_SYNC(hipMemcpyAsync(alpha_out, h->d_alpha, elems * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    rc = download_results(h, h->ws[0].stream, batch, alpha_out, h->stage[0].alpha, elems * sizeof(double), curv_err_out, status_out, nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(h->ws[0].stream));
     stamp("alpha and per-track results down");
     bool use[2] = {false, false};
     for (int b = 0; b < batch; ++b) use[buf_h[b] ? 1 : 0] = true;
-    const double* d_ref_set[2] = {h->d_ref, h->d_ref2};
-    const double* d_nv_set[2] = {h->d_nv, h->d_nv2};
+    const double* d_ref_set[2] = {h->stage[0].ref, h->d_ref2};
+    const double* d_nv_set[2] = {h->stage[0].nv, h->d_nv2};
     if (use[0] != use[1]) {
         // the usual case (one iters_min for all: every track ends in the same round): the final set goes out in two copies
         const int q = use[1] ? 1 : 0;
-        HIP_TRY_SYNC(hipMemcpyAsync(reftrack_out, d_ref_set[q], elems * 4 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY_SYNC(hipMemcpyAsync(normvec_out, d_nv_set[q], elems * 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
+        HIP_TRY_DRAIN(hipMemcpyAsync(reftrack_out, d_ref_set[q], elems * 4 * sizeof(double), hipMemcpyDeviceToHost, h->ws[0].stream));
+        HIP_TRY_DRAIN(hipMemcpyAsync(normvec_out, d_nv_set[q], elems * 2 * sizeof(double), hipMemcpyDeviceToHost, h->ws[0].stream));
+        HIP_TRY(hipStreamSynchronize(h->ws[0].stream));
         stamp("rings and normals down");
         return 0;
     }
@@ -2142,10 +1963,10 @@ extern "C" int mcq_iqp_batch(mcq_handle* h, const mcq_problem* probs, int batch,
         nv_h[1] = ref_h[1] + elems * 4;
     }
     for (int q = 0; q < 2; ++q) {
-        HIP_TRY_SYNC(hipMemcpyAsync(ref_h[q], d_ref_set[q], elems * 4 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY_SYNC(hipMemcpyAsync(nv_h[q], d_nv_set[q], elems * 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY_DRAIN(hipMemcpyAsync(ref_h[q], d_ref_set[q], elems * 4 * sizeof(double), hipMemcpyDeviceToHost, h->ws[0].stream));
+        HIP_TRY_DRAIN(hipMemcpyAsync(nv_h[q], d_nv_set[q], elems * 2 * sizeof(double), hipMemcpyDeviceToHost, h->ws[0].stream));
     }
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipStreamSynchronize(h->ws[0].stream));
     for (int b = 0; b < batch; ++b) {
         const int q = buf_h[b] ? 1 : 0;
         const size_t n = n_out[b] > 0 ? (size_t)n_out[b] : 0;
@@ -2256,7 +2077,7 @@ extern "C" int mcq_comm_allgather(mcq_handle* h, const void* send, void* recv, s
     HIP_TRY(hipSetDevice(h->device));
     // behind everything enqueued on the handle's stream so far (the solve that filled `send`), on a stream of its own: the handle's
     // stream goes on with the next solve while the gather runs
-    HIP_TRY(hipEventRecord(h->comm_ready, h->stream));
+    HIP_TRY(hipEventRecord(h->comm_ready, h->ws[0].stream));
     HIP_TRY(hipStreamWaitEvent(h->comm_stream, h->comm_ready, 0));
     const unsigned slot = h->comm_seq & 3u;
     HIP_TRY(hipEventRecord(h->comm_t0[slot], h->comm_stream));
@@ -2294,7 +2115,7 @@ extern "C" int mcq_comm_destroy(mcq_handle* h)
     int ret = 0;
     (void)hipSetDevice(h->device);
     if (h->comm) {
-        if (h->stream) (void)hipStreamSynchronize(h->stream);
+        if (h->ws[0].stream) (void)hipStreamSynchronize(h->ws[0].stream);
         if (h->comm_stream) (void)hipStreamSynchronize(h->comm_stream);
         const int r = g_rccl.CommDestroy(h->comm);
         h->comm = nullptr;

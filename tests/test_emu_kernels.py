@@ -899,6 +899,59 @@ def test_resident_stream_entry_matches_single_launches(emu, golden):
         assert list(emu.download(ptr[k][5], (2,), np.int32)) == [0, 0]
 
 
+def test_workspace_bytes_over_a_fixed_sequence_of_entries(emu_lib, monkeypatch):
+    """mcq_workspace_bytes after each call of a fixed sequence on ONE fresh handle: the first workspace and its full Goldfarb-Idnani pool (a
+    sliced mcq_solve_host of eleven rings), the second workspace with half those slots (a three-step mcq_solve_host_pipelined), the small pool
+    (mcq_solve_batch with ALG_GI), and nothing more for a smaller batch afterwards.  The handle's bookkeeping has no other observable that
+    a test holds exactly; on the interpreter hipMalloc never refuses, so the figures are the same on every machine."""
+    # literals: commit c20656c (the parent of the change that folded the handle's two workspaces into one type), interpreter build
+    want = [0, 18584400, 37102488, 37223576, 37223576]
+    monkeypatch.setenv("MCQ_HOST_SLICE_MIN", "4")
+    monkeypatch.delenv("MCQ_HOST_ONE_LAUNCH", raising=False)
+    monkeypatch.delenv("MCQ_HOST_SLICES", raising=False)
+    monkeypatch.delenv("MCQ_PIPE_ONE_STREAM", raising=False)
+    monkeypatch.delenv("MCQ_GI_BYTES", raising=False)
+    monkeypatch.delenv("MCQ_GI_SLOTS", raising=False)
+    n, bsz = 24, 11
+    base = [_small_track(n, seed=600 + k) for k in range(3)]
+    refs = np.stack([base[k % 3][0] for k in range(bsz)])
+    nvs = np.stack([base[k % 3][1] for k in range(bsz)])
+    scs = np.stack([base[k % 3][3] for k in range(bsz)])
+    eng = engine.Engine(0, lib_path=emu_lib)
+    try:
+        got = [eng.workspace_bytes()]
+        _, _, st, _ = eng.solve_host(refs, nvs, scs, 0.5, 2.0)
+        assert np.all(st == 0)
+        got.append(eng.workspace_bytes())
+        outs = [np.full((bsz, n), np.nan) for _ in range(3)]
+        _, st = eng.solve_host_pipelined([refs] * 3, [nvs] * 3, [scs] * 3, 0.5, 2.0, outs)
+        assert np.all(st == 0)
+        got.append(eng.workspace_bytes())
+        probs = [dict(reftrack=refs[k], normvec=nvs[k], scaling=scs[k], kappa_bound=0.5, w_veh=2.0) for k in range(bsz)]
+        _, _, st, _ = eng.solve_batch(probs, algorithm=engine.ALG_GI)
+        assert np.all(st == 0)
+        got.append(eng.workspace_bytes())
+        # a smaller batch of shorter rings, through the blocking, the pipelined and the Goldfarb-Idnani entries: no regrowth
+        m = 20
+        r5, v5, s5 = [], [], []
+        for k in range(5):
+            r_, v_, _, s_ = _small_track(m, seed=610 + k)
+            r5.append(r_), v5.append(v_), s5.append(s_)
+        r5, v5, s5 = np.stack(r5), np.stack(v5), np.stack(s5)
+        _, _, st, _ = eng.solve_host(r5, v5, s5, 0.5, 2.0)
+        assert np.all(st == 0)
+        _, st = eng.solve_host_pipelined([r5] * 2, [v5] * 2, [s5] * 2, 0.5, 2.0, [np.empty((5, m)) for _ in range(2)])
+        assert np.all(st == 0)
+        _, _, st, _ = eng.solve_batch([dict(reftrack=r5[k], normvec=v5[k], scaling=s5[k], kappa_bound=0.5, w_veh=2.0) for k in range(5)],
+                                      algorithm=engine.ALG_GI)
+        assert np.all(st == 0)
+        got.append(eng.workspace_bytes())
+    finally:
+        eng.close()
+    print("workspace_bytes:", got)
+    assert got == want
+
+
 def _stadium(n, ls=120.0, r=40.0):
     """Two straights and two semicircles, n points equidistant in arclength (counter-clockwise)."""
     per = 2 * ls + 2 * np.pi * r
