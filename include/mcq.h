@@ -203,7 +203,10 @@ int mcq_solve_device_ragged_params(mcq_handle* h, int batch, int nmax, const int
  * leaves no room for fp32 factors -- so the result is the exact QP solution OF THE ROUNDED INPUTS, rounded once more on
  * the way out (|alpha| < 2^3 m => 2.4e-7 m); how far the rounded inputs move the solution is a property of the QP, not of
  * the engine (measured in tests/test_gpu_parity.py).  With normvec == NULL the normals and scalings are derived in fp64 from
- * the float x, y (preferred: float normals are unit vectors only to 6e-8).  curv_err_out stays double. */
+ * the float x, y (preferred: float normals are unit vectors only to 6e-8).  curv_err_out stays double.
+ * MCQ_OBJ_SHORTEST_PATH: solved on the widened rows and normals where normvec is given (H_ii = 4 |n_i|^2 takes float normals as they
+ * are); with normvec == NULL, and through mcq_solve_device_f32_rows / mcq_solve_batch_f32 below (which always derive their normals), the
+ * objective is refused with MCQ_E_ARG, as on every entry without normals (tests/sp_checks.py: check_f32). */
 int mcq_solve_device_f32(mcq_handle* h, int batch, int n, const float* reftrack, const float* normvec,
                          const float* scaling, double kappa_bound, double w_veh, const mcq_opts* opts, float* alpha_out,
                          double* curv_err_out, int* status_out, mcq_info* info_out);
