@@ -223,6 +223,29 @@ __shared__ SolveCtx g_ctx;
 #include "mcq_kkt.inc"
 #include "mcq_tri.inc"
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Per-entry loops around the solver (MCQ_ENTRY_BATCH, default 1).  `for (i = tid; i < n; i += MCQ_NT) { load; compute; store; }` compiles
+// to one round trip to memory per trip -- the store keeps the next trip's loads behind it -- eight in a row at n = 2000.  Written as
+//     EB_FOR { EB_INDEX;  <arrays of EB_E>;  EB_EACH { const int i = idx[u]; <loads> }  EB_EACH if (ok[u]) { <compute, store> } }
+// a thread's up-to-eight entries i = tid + 256 u are all loaded before the first is used: one round trip per loop (rings beyond 2048
+// waypoints run the batch more than once).  An absent entry loads the thread's first one and stores nothing, as in ipm_box's IPB_SETUP;
+// entries are taken in ascending order, so a reduction sees its operands in the order of the plain loop.  -DMCQ_ENTRY_BATCH=0 makes the
+// batch one entry long, which is the plain loop again: same results bit for bit (tests/test_emu_entry_batch.py).  Needs tid and n in scope.
+// ---------------------------------------------------------------------------------------------------------------------
+#ifndef MCQ_ENTRY_BATCH
+#define MCQ_ENTRY_BATCH 1
+#endif
+#define EB_E (MCQ_ENTRY_BATCH ? 8 : 1)
+#define EB_FOR for (int eb0_ = tid; eb0_ < n; eb0_ += EB_E * MCQ_NT)
+#define EB_EACH _Pragma("unroll") for (int u = 0; u < EB_E; ++u)
+#define EB_INDEX                                                                                                       \
+    int idx[EB_E];                                                                                                     \
+    bool ok[EB_E];                                                                                                     \
+    EB_EACH {                                                                                                          \
+        ok[u] = eb0_ + u * MCQ_NT < n;                                                                                 \
+        idx[u] = ok[u] ? eb0_ + u * MCQ_NT : eb0_;                                                                     \
+    }
+
 // =====================================================================================================================
 // K1: assembly
 // =====================================================================================================================
@@ -258,30 +281,46 @@ __device__ __noinline__ int assemble_problem(const LCtx& c, double wveh, gdouble
     // has no joint to its right (s_(n-2) := 1 of the spline rows), and with s_(n-1) = 1 the ring formulas of the rows next to the ends
     // (waypoints 1 and n-2) are the chain's own.
     if (chain && (n > MCQ_CHAIN_MAXN || derive || !(isfinite(c.psi_s) && isfinite(c.psi_e)))) flag_bad = 1.0;
-    for (int i = tid; i < n; i += MCQ_NT) {
-        const double x = w.ref[4 * i], y = w.ref[4 * i + 1], wr = w.ref[4 * i + 2], wl = w.ref[4 * i + 3];
-        const double nx = derive ? 0.0 : w.nv[2 * i], ny = derive ? 1.0 : w.nv[2 * i + 1];
-        double s = w.sc ? w.sc[i] : 1.0;
-        if (chain && i >= n - 2) s = 1.0;
-        if (derive) {
-            // s_i = l_i / l_{i+1},  l_i = |p_{i+1} - p_i|  (tph.calc_splines, use_dist_scaling=True, closed)
-            const int i1 = i + 1 >= n ? i + 1 - n : i + 1, i2 = i1 + 1 >= n ? i1 + 1 - n : i1 + 1;
-            const double l0 = hypot(w.ref[4 * i1] - x, w.ref[4 * i1 + 1] - y);
-            const double l1 = hypot(w.ref[4 * i2] - w.ref[4 * i1], w.ref[4 * i2 + 1] - w.ref[4 * i1 + 1]);
-            s = l0 / l1;
-        } else {
-            NX[i] = nx;
-            NY[i] = ny;
+    EB_FOR {
+        EB_INDEX
+        double rx[EB_E], ry[EB_E], rwr[EB_E], rwl[EB_E], rnx[EB_E], rny[EB_E], rs[EB_E], x1[EB_E], y1[EB_E], x2[EB_E], y2[EB_E];
+        EB_EACH {
+            const int i = idx[u];
+            rx[u] = w.ref[4 * i]; ry[u] = w.ref[4 * i + 1]; rwr[u] = w.ref[4 * i + 2]; rwl[u] = w.ref[4 * i + 3];
+            rnx[u] = derive ? 0.0 : w.nv[2 * i]; rny[u] = derive ? 1.0 : w.nv[2 * i + 1];
+            rs[u] = w.sc ? w.sc[i] : 1.0;
+            x1[u] = y1[u] = x2[u] = y2[u] = 0.0;
+            if (derive) {
+                const int i1 = i + 1 >= n ? i + 1 - n : i + 1, i2 = i1 + 1 >= n ? i1 + 1 - n : i1 + 1;
+                x1[u] = w.ref[4 * i1]; y1[u] = w.ref[4 * i1 + 1]; x2[u] = w.ref[4 * i2]; y2[u] = w.ref[4 * i2 + 1];
+            }
         }
-        if (!(isfinite(x) && isfinite(y) && isfinite(wr) && isfinite(wl) && isfinite(nx) && isfinite(ny) && isfinite(s)
-              && s > 0.0))
-            flag_bad = 1.0;
-        double lo = -(wl - 0.5 * wveh), hi = wr - 0.5 * wveh;
-        if ((c.fix_s && i == 0) || (c.fix_e && i == n - 1)) { lo = -MCQ_FIX_HALF_WIDTH; hi = MCQ_FIX_HALF_WIDTH; }    // (chains only: before the check, as tph)
-        if (hi < lo) flag_inf = 1.0;
-        LO[i] = lo;
-        HI[i] = hi;
-        S[i] = s;
+        EB_EACH {
+            if (!ok[u]) continue;
+            const int i = idx[u];
+            const double x = rx[u], y = ry[u], wr = rwr[u], wl = rwl[u];
+            const double nx = rnx[u], ny = rny[u];
+            double s = rs[u];
+            if (chain && i >= n - 2) s = 1.0;
+            if (derive) {
+                // s_i = l_i / l_{i+1},  l_i = |p_{i+1} - p_i|  (tph.calc_splines, use_dist_scaling=True, closed)
+                const double l0 = hypot(x1[u] - x, y1[u] - y);
+                const double l1 = hypot(x2[u] - x1[u], y2[u] - y1[u]);
+                s = l0 / l1;
+            } else {
+                NX[i] = nx;
+                NY[i] = ny;
+            }
+            if (!(isfinite(x) && isfinite(y) && isfinite(wr) && isfinite(wl) && isfinite(nx) && isfinite(ny) && isfinite(s)
+                  && s > 0.0))
+                flag_bad = 1.0;
+            double lo = -(wl - 0.5 * wveh), hi = wr - 0.5 * wveh;
+            if ((c.fix_s && i == 0) || (c.fix_e && i == n - 1)) { lo = -MCQ_FIX_HALF_WIDTH; hi = MCQ_FIX_HALF_WIDTH; }    // (chains only: before the check, as tph)
+            if (hi < lo) flag_inf = 1.0;
+            LO[i] = lo;
+            HI[i] = hi;
+            S[i] = s;
+        }
     }
     flag_bad = block_reduce_(flag_bad, 2, red);
     flag_inf = block_reduce_(flag_inf, 2, red);
@@ -313,11 +352,18 @@ __device__ __noinline__ int assemble_problem(const LCtx& c, double wveh, gdouble
     tri_prepare(c);
     gdouble* RX = VEC(w, nm, V_SK);
     gdouble* RY = VEC(w, nm, V_EDA);
-    for (int m = tid; m < n; m += MCQ_NT) {
-        const int mp = cyc1(m + 1, n), mm = cyc1(m - 1, n);
-        const double sm1 = S[mm];
-        RX[m] = 3.0 * (sm1 * (w.ref[4 * mp] - w.ref[4 * m]) - (w.ref[4 * m] - w.ref[4 * mm]));
-        RY[m] = 3.0 * (sm1 * (w.ref[4 * mp + 1] - w.ref[4 * m + 1]) - (w.ref[4 * m + 1] - w.ref[4 * mm + 1]));
+    EB_FOR {
+        EB_INDEX
+        double sm1[EB_E], xp_[EB_E], yp_[EB_E], x0[EB_E], y0[EB_E], xm_[EB_E], ym_[EB_E];
+        EB_EACH {
+            const int m = idx[u], mp = cyc1(m + 1, n), mm = cyc1(m - 1, n);
+            sm1[u] = S[mm];
+            xp_[u] = w.ref[4 * mp]; yp_[u] = w.ref[4 * mp + 1]; x0[u] = w.ref[4 * m]; y0[u] = w.ref[4 * m + 1]; xm_[u] = w.ref[4 * mm]; ym_[u] = w.ref[4 * mm + 1];
+        }
+        EB_EACH if (ok[u]) {
+            RX[idx[u]] = 3.0 * (sm1[u] * (xp_[u] - x0[u]) - (x0[u] - xm_[u]));
+            RY[idx[u]] = 3.0 * (sm1[u] * (yp_[u] - y0[u]) - (y0[u] - ym_[u]));
+        }
     }
     // open chain: the heading rows overwrite rows 0 and n - 1 (blocks of their own here and below: the rings' arithmetic stays what it was)
     double hsx = 0.0, hsy = 0.0, hex = 0.0, hey = 0.0;
@@ -336,32 +382,48 @@ __device__ __noinline__ int assemble_problem(const LCtx& c, double wveh, gdouble
     }
     tri_solve_T(c, RX, XPP);
     tri_solve_T(c, RY, YPP);
-    for (int i = tid; i < n; i += MCQ_NT) { XPP[i] *= 2.0; YPP[i] *= 2.0; }     // x''(0), y''(0) of spline i
+    EB_FOR {                                                                    // x''(0), y''(0) of spline i
+        EB_INDEX
+        double a[EB_E], b[EB_E];
+        EB_EACH { a[u] = XPP[idx[u]]; b[u] = YPP[idx[u]]; }
+        EB_EACH if (ok[u]) { XPP[idx[u]] = a[u] * 2.0; YPP[idx[u]] = b[u] * 2.0; }
+    }
     __syncthreads();
 
     // ---- phase 3a: x', y', curvature pre-factor, reference curvature ------------------------------------------------
-    for (int i = tid; i < n; i += MCQ_NT) {
-        const int ip = cyc(i + 1, n);
-        const double s2 = S[i] * S[i];
-        const double xp = (w.ref[4 * ip] - w.ref[4 * i]) - (XPP[i] + 0.5 * s2 * XPP[ip]) / 3.0;
-        const double yp = (w.ref[4 * ip + 1] - w.ref[4 * i + 1]) - (YPP[i] + 0.5 * s2 * YPP[ip]) / 3.0;
-        const double den = pow(xp * xp + yp * yp, 1.5);
-        const double cp = den != 0.0 ? 1.0 / den : 0.0;
-        XP[i] = xp;
-        YP[i] = yp;
-        CP[i] = cp;
-        KRF[i] = cp * (xp * YPP[i] - yp * XPP[i]);
-        if (derive) {
-            // unit normal to the right of the spline's tangent (b-coefficients):  (y', -x') / |.|   (tph.calc_splines)
-            const double nrm = sqrt(xp * xp + yp * yp);
-            NX[i] = yp / nrm;
-            NY[i] = -xp / nrm;
+    EB_FOR {
+        EB_INDEX
+        double si[EB_E], xn_[EB_E], yn_[EB_E], x0[EB_E], y0[EB_E], ax[EB_E], axn[EB_E], ay[EB_E], ayn[EB_E];
+        EB_EACH {
+            const int i = idx[u], ip = cyc(i + 1, n);
+            si[u] = S[i];
+            xn_[u] = w.ref[4 * ip]; yn_[u] = w.ref[4 * ip + 1]; x0[u] = w.ref[4 * i]; y0[u] = w.ref[4 * i + 1];
+            ax[u] = XPP[i]; axn[u] = XPP[ip]; ay[u] = YPP[i]; ayn[u] = YPP[ip];
         }
-        if (nv_out) {
-            nv_out[2 * i] = NX[i];
-            nv_out[2 * i + 1] = NY[i];
+        EB_EACH {
+            if (!ok[u]) continue;
+            const int i = idx[u];
+            const double s2 = si[u] * si[u];
+            const double xp = (xn_[u] - x0[u]) - (ax[u] + 0.5 * s2 * axn[u]) / 3.0;
+            const double yp = (yn_[u] - y0[u]) - (ay[u] + 0.5 * s2 * ayn[u]) / 3.0;
+            const double den = pow(xp * xp + yp * yp, 1.5);
+            const double cp = den != 0.0 ? 1.0 / den : 0.0;
+            XP[i] = xp;
+            YP[i] = yp;
+            CP[i] = cp;
+            KRF[i] = cp * (xp * ay[u] - yp * ax[u]);
+            if (derive) {
+                // unit normal to the right of the spline's tangent (b-coefficients):  (y', -x') / |.|   (tph.calc_splines)
+                const double nrm = sqrt(xp * xp + yp * yp);
+                NX[i] = yp / nrm;
+                NY[i] = -xp / nrm;
+            }
+            if (nv_out) {
+                nv_out[2 * i] = NX[i];
+                nv_out[2 * i + 1] = NY[i];
+            }
+            if (sc_out) sc_out[i] = si[u];
         }
-        if (sc_out) sc_out[i] = S[i];
     }
     if (chain) {                    // x'(1) of the last spline is the end heading
         __syncthreads();
@@ -858,7 +920,8 @@ __device__ __noinline__ int ipm(const LCtx& c, bool with_kappa)
 // workgroup that runs one wave per SIMD: every thread owns its (up to) eight entries i = tid + 256 u, ALL loads of a pass
 // are issued before the first use (one L2 round trip per pass instead of one per entry), and what a pass loaded stays in
 // registers across the block reductions that follow it -- three load phases and six reductions per iteration where the
-// generic routine above does seven dependent passes.  Arithmetic and summation order are those of ipm().
+// generic routine above does seven dependent passes (two load phases from the second iteration on: pass 3 then does the next
+// pass 1 on what it holds, MCQ_IPB_FOLD_P1).  Arithmetic and summation order are those of ipm().
 // ---------------------------------------------------------------------------------------------------------------------
 #define IPB_E 8
 #define IPB_H 4     /* entries a pass keeps in registers at a time: two halves per pass (round 3: at 256 VGPRs -- two workgroups per CU -- eight entries of a pass's arrays spilled) */
@@ -875,7 +938,8 @@ __device__ __noinline__ int ipm(const LCtx& c, bool with_kappa)
 // and pass 3 updates them.  That is the budget, not a licence: a caller that keeps more than the callee-saved set alive spills.  Pointers
 // and index sets are still re-derived at the top of every pass, and a fifth array does not fit: with LO resident as well the allocator
 // spills inside the loop (54 scratch stores + 198 loads outside prologue / epilogue against the earlier form's 14 + 20, frame 1232 B per
-// lane against 1024), with LO and HI 90 + 287 (1456 B).  As it stands: 11 + 15, 960 B (docs/NOTEBOOK.md "Resident iterate").
+// lane against 1024), with LO and HI 90 + 287 (1456 B).  With these three steps: 11 + 15, 960 B (docs/NOTEBOOK.md "Resident iterate"); with
+// pass 1 folded into pass 3 as well (MCQ_IPB_FOLD_P1, "One round trip per vector loop"): 7 + 12, 944 B.
 // -DMCQ_IPB_RESIDENT=0 is the earlier form (every pass loads what it needs and stores what it changed): same results bit for bit,
 // tests/test_emu_ipb_resident.py compares the two.  The steps, each with a switch of its own for A/B builds:
 //   MCQ_IPB_RESIDENT: the resident reads above; G is loaded again after a gradient() call.
@@ -896,6 +960,10 @@ __device__ __noinline__ int ipm(const LCtx& c, bool with_kappa)
 #endif
 #if MCQ_IPB_DEFER && !MCQ_IPB_RESIDENT
 #error "MCQ_IPB_DEFER needs MCQ_IPB_RESIDENT"
+#endif
+//   MCQ_IPB_FOLD_P1: pass 3 ends with pass 1 of the next iteration, computed from the updated entries it holds (see pass 3).
+#ifndef MCQ_IPB_FOLD_P1
+#define MCQ_IPB_FOLD_P1 1
 #endif
 __device__ __noinline__ int ipm_box(const LCtx& c, double tol, bool resume)
 {
@@ -956,18 +1024,31 @@ __device__ __noinline__ int ipm_box(const LCtx& c, double tol, bool resume)
     c.out_iters = 0;
     {
     IPB_SETUP
+#if MCQ_ENTRY_BATCH
+    // (the bounds of all eight entries first: loaded entry by entry they alternate with stores they cannot pass)
+    double lo[IPB_E], hi[IPB_E];
+#pragma unroll
+    for (int u = 0; u < IPB_E; ++u) { lo[u] = LO[idx[u]]; hi[u] = HI[idx[u]]; }
+#define IPB_LO(u, i) lo[u]
+#define IPB_HI(u, i) hi[u]
+#else
+#define IPB_LO(u, i) LO[i]
+#define IPB_HI(u, i) HI[i]
+#endif
 #pragma unroll
     for (int u = 0; u < IPB_E; ++u) {
         if (!ok[u]) continue;
         const int i = idx[u];
-        const bool fixed = !(HI[i] - LO[i] > 1e-12);
+        const bool fixed = !(IPB_HI(u, i) - IPB_LO(u, i) > 1e-12);
         ST[i] = fixed ? 2 : 0;
         if (!resume) {
-            X[i] = 0.5 * (LO[i] + HI[i]);
+            X[i] = 0.5 * (IPB_LO(u, i) + IPB_HI(u, i));
             ZL[i] = fixed ? 0.0 : zscale;
             ZU[i] = ZL[i];
         }
     }
+#undef IPB_LO
+#undef IPB_HI
     }
     __syncthreads();
     if (resume) gradient(c, VEC(c.w, c.nm, V_X), nullptr, VEC(c.w, c.nm, V_T0), VEC(c.w, c.nm, V_G));
@@ -1024,6 +1105,10 @@ __device__ __noinline__ int ipm_box(const LCtx& c, double tol, bool resume)
 #define MCQ_IPM_TRUST_FP64_CARRY 1
 #endif
     bool g_f32 = false;
+#if MCQ_IPB_FOLD_P1
+    bool folded = false;                    // pass 3 has left the next iteration's mu, rdm, SIG and RHS
+    double mu_fold = 0.0, rdm_fold = 0.0;
+#endif
     for (int it = 1; it <= c.max_ipm_iter; ++it) {
         // ---- pass 1: complementarity, dual residual, sig, predictor right-hand side ----------------------------------------
         double mu;
@@ -1031,6 +1116,11 @@ __device__ __noinline__ int ipm_box(const LCtx& c, double tol, bool resume)
             IPB_PTRS
             double rdm = 0.0;
             mu = 0.0;
+#if MCQ_IPB_FOLD_P1
+            // pass 3 of the previous iteration has done this pass on the values it had in registers (see there)
+            if (folded) { mu = mu_fold; rdm = rdm_fold; folded = false; }
+            else
+#endif
             {
 #pragma unroll
             for (int h = 0; h < IPB_E / IPB_H; ++h) {
@@ -1167,8 +1257,10 @@ __device__ __noinline__ int ipm_box(const LCtx& c, double tol, bool resume)
 
         // ---- pass 3: step length of the combined direction, update: ONE load phase -- nine arrays of eight entries stay in registers
         //      across the block reduction; the multiplier steps and H dx are recomputed after it instead of being kept (at 256 VGPRs --
-        //      two workgroups per CU -- twelve arrays spilled).  (Folding the next iteration's residual pass into this one was tried: the
-        //      extra live values cost more than the seven vector reads it saves.) --------------------------------------------------
+        //      two workgroups per CU -- twelve arrays spilled).  The next iteration's pass 1 is folded into the update loop below
+        //      (MCQ_IPB_FOLD_P1).  That fold had lost to register pressure while the passes still loaded the iterate: it needed seven more
+        //      arrays live then; with X, ZL, ZU, G resident and LO, HI already loaded here it needs two accumulators, and the function has
+        //      7 + 12 scratch instructions outside prologue / epilogue against 11 + 15 without it (frame 944 B against 960). ----------
         {
             IPB_SETUP
             // fraction of the way to the boundary: 0.995 far from the solution, closer to 1 as the complementarity shrinks
@@ -1216,8 +1308,19 @@ __device__ __noinline__ int ipm_box(const LCtx& c, double tol, bool resume)
 #pragma unroll
             for (int u = 0; u < IPB_E; ++u) t3[u] = 0;
 #endif
+#if MCQ_IPB_FOLD_P1
+            // Pass 1 of the next iteration, here: an updated entry has xn, zln, zun, gn and its bounds in registers, which is all that pass
+            // reads -- its contributions to the complementarity and the dual residual (same expressions, entries in the same order), SIG and
+            // the predictor's right-hand side are formed now, and one block reduction ends this pass instead of opening the next one.  Saves
+            // the next pass's load phase (ST, LO, HI: 17 bytes per waypoint) and a barrier; the explicit pass stays for iteration 1 and for
+            // the re-evaluation after a gradient() call.
+            double mu_n = 0.0, rdm_n = 0.0;
+#endif
 #pragma unroll
             for (int u = 0; u < IPB_E; ++u) {
+#if MCQ_IPB_FOLD_P1
+                if (ok[u] && !act[u]) RHS[idx[u]] = 0.0;
+#endif
                 if (!act[u]) continue;
                 const int i = idx[u];
                 IPB_STEP3(u)
@@ -1244,7 +1347,22 @@ __device__ __noinline__ int ipm_box(const LCtx& c, double tol, bool resume)
 #else
                 IND[i] = al ? -1.0 : (au ? 1.0 : 0.0);
 #endif
+#if MCQ_IPB_FOLD_P1
+                {
+                    const double sl = xn - lo[u], su = hi[u] - xn;
+                    mu_n += sl * zln + su * zun;
+                    rdm_n = fmax(rdm_n, fabs(gn - zln + zun));
+                    SIG[idx[u]] = zln / sl + zun / su;
+                    RHS[idx[u]] = -gn;
+                }
+#endif
             }
+#if MCQ_IPB_FOLD_P1
+            block_reduce2_(mu_n, 0, rdm_n, 2, red);
+            mu_fold = mu_n / npairs;
+            rdm_fold = rdm_n;
+            folded = true;
+#endif
 #if MCQ_IPB_DEFER
             tapia = 0;
 #pragma unroll
@@ -1254,7 +1372,9 @@ __device__ __noinline__ int ipm_box(const LCtx& c, double tol, bool resume)
         }
         g_exact = false;
         g_f32 |= f32;
-        __syncthreads();
+#if !MCQ_IPB_FOLD_P1
+        __syncthreads();        // (folded: the reduction that ends pass 3 has its barriers behind the pass's last store)
+#endif
     }
 #if MCQ_IPB_DEFER
     rc = MCQ_ITER_CAP;
@@ -1490,36 +1610,50 @@ __device__ __noinline__ int active_set(const LCtx& c, bool with_kappa, bool tapi
 
     // ---- identification ---------------------------------------------------------------------------------------------------
     // (identify == false: the working set is given -- carried over from the previous IQP pass -- and the pairs are not read)
-    for (int i = tid; i < n; i += MCQ_NT) {
-        if (identify == 1 && ST[i] == 0) {
-            // magnitude test on the final pair: active when the scaled multiplier exceeds the scaled slack
-            const double wdt = HI[i] - LO[i];
-            const double sl = X[i] - LO[i], su = HI[i] - X[i];
-            signed char st = 0;
-            if (sl * zscale < ZL[i] * wdt) st = -1;
-            else if (su * zscale < ZU[i] * wdt) st = 1;
-            // ... plus the rows it misses at mu = 1e-10 (weakly active: slack and multiplier both ~ sqrt(mu)) when the last
-            // interior-point step gave Tapia evidence for them: slack shrinking faster than the multiplier,
-            // s+/s < MCQ_TAPIA_SHRINK and s+/s < MCQ_TAPIA_RATIO z+/z.  One-sided (it only adds rows).  The thresholds were
-            // 0.5 / 0.3 while a free row pinned by mistake could send block pivoting into dozens of rounds; with the
-            // one-row-per-neighbourhood exchange below a false positive costs one round like a miss does, and 0.7 / 0.7
-            // measured best on the 3 x 1024 problems of the IQP workload (rounds 1.60 -> 1.27 in the first passes;
-            // 1.0 / 1.0: 1.23 but a 6-round straggler).
-            if (tapia && st == 0) st = (signed char)VEC(c.w, nm, V_T3)[i];
-            ST[i] = st;
+    EB_FOR {
+        EB_INDEX
+        signed char st0[EB_E];
+        double lo[EB_E], hi[EB_E], x[EB_E], zl[EB_E], zu[EB_E], t3[EB_E];
+        if (identify == 1) {
+            EB_EACH {
+                const int i = idx[u];
+                st0[u] = ST[i]; lo[u] = LO[i]; hi[u] = HI[i]; x[u] = X[i]; zl[u] = ZL[i]; zu[u] = ZU[i];
+                t3[u] = tapia ? VEC(c.w, nm, V_T3)[i] : 0.0;
+            }
         }
-        double kf = 0.0;
-        if (with_kappa && identify == 2) kf = KF[i];
-        else if (with_kappa) {
-            const gdouble* TL = VEC(c.w, nm, V_TL);
-            const gdouble* TU = VEC(c.w, nm, V_TU);
-            const gdouble* YL = VEC(c.w, nm, V_YL);
-            const gdouble* YU = VEC(c.w, nm, V_YU);
-            const double mu0 = 0.5 * zscale * c.wmean;
-            if (TL[i] * mu0 < YL[i] * kb * kb) kf = -1.0;
-            else if (TU[i] * mu0 < YU[i] * kb * kb) kf = 1.0;
+        EB_EACH {
+            if (!ok[u]) continue;
+            const int i = idx[u];
+            if (identify == 1 && st0[u] == 0) {
+                // magnitude test on the final pair: active when the scaled multiplier exceeds the scaled slack
+                const double wdt = hi[u] - lo[u];
+                const double sl = x[u] - lo[u], su = hi[u] - x[u];
+                signed char st = 0;
+                if (sl * zscale < zl[u] * wdt) st = -1;
+                else if (su * zscale < zu[u] * wdt) st = 1;
+                // ... plus the rows it misses at mu = 1e-10 (weakly active: slack and multiplier both ~ sqrt(mu)) when the last
+                // interior-point step gave Tapia evidence for them: slack shrinking faster than the multiplier,
+                // s+/s < MCQ_TAPIA_SHRINK and s+/s < MCQ_TAPIA_RATIO z+/z.  One-sided (it only adds rows).  The thresholds were
+                // 0.5 / 0.3 while a free row pinned by mistake could send block pivoting into dozens of rounds; with the
+                // one-row-per-neighbourhood exchange below a false positive costs one round like a miss does, and 0.7 / 0.7
+                // measured best on the 3 x 1024 problems of the IQP workload (rounds 1.60 -> 1.27 in the first passes;
+                // 1.0 / 1.0: 1.23 but a 6-round straggler).
+                if (tapia && st == 0) st = (signed char)t3[u];
+                ST[i] = st;
+            }
+            double kf = 0.0;
+            if (with_kappa && identify == 2) kf = KF[i];
+            else if (with_kappa) {
+                const gdouble* TL = VEC(c.w, nm, V_TL);
+                const gdouble* TU = VEC(c.w, nm, V_TU);
+                const gdouble* YL = VEC(c.w, nm, V_YL);
+                const gdouble* YU = VEC(c.w, nm, V_YU);
+                const double mu0 = 0.5 * zscale * c.wmean;
+                if (TL[i] * mu0 < YL[i] * kb * kb) kf = -1.0;
+                else if (TU[i] * mu0 < YU[i] * kb * kb) kf = 1.0;
+            }
+            KF[i] = kf;
         }
-        KF[i] = kf;
     }
     __syncthreads();
     const double TOLX = 1e-10;
@@ -1545,12 +1679,21 @@ __device__ __noinline__ int active_set(const LCtx& c, bool with_kappa, bool tapi
                                                          // with an overflow slot)
         c.out_nk = nk;
 
-        for (int i = tid; i < n; i += MCQ_NT) {
-            const signed char st = ST[i];
-            T1[i] = st == 0 ? 0.0 : (st < 0 ? LO[i] : (st == 1 ? HI[i] : 0.5 * (LO[i] + HI[i])));
+        EB_FOR {
+            EB_INDEX
+            signed char st[EB_E];
+            double lo[EB_E], hi[EB_E];
+            EB_EACH { const int i = idx[u]; st[u] = ST[i]; lo[u] = LO[i]; hi[u] = HI[i]; }
+            EB_EACH if (ok[u]) T1[idx[u]] = st[u] == 0 ? 0.0 : (st[u] < 0 ? lo[u] : (st[u] == 1 ? hi[u] : 0.5 * (lo[u] + hi[u])));
         }
         gradient(c, T1, nullptr, T0, T2);       // T2 = H x_A + f
-        for (int i = tid; i < n; i += MCQ_NT) RHS[i] = ST[i] == 0 ? -T2[i] : T1[i];
+        EB_FOR {
+            EB_INDEX
+            signed char st[EB_E];
+            double t1[EB_E], t2[EB_E];
+            EB_EACH { const int i = idx[u]; st[u] = ST[i]; t1[u] = T1[i]; t2[u] = T2[i]; }
+            EB_EACH if (ok[u]) RHS[idx[u]] = st[u] == 0 ? -t2[u] : t1[u];
+        }
         const int fs = timed_factor(c, nullptr, ST, RHS);
         if (fs != 0) return fs;
         timed_solve(c, RHS, true);   // x0 (pinned rows carry their bounds)
@@ -1581,32 +1724,46 @@ __device__ __noinline__ int active_set(const LCtx& c, bool with_kappa, bool tapi
             for (int i = tid; i < n; i += MCQ_NT) RHS[i] -= Zs[i];
             __syncthreads();
         }
-        for (int i = tid; i < n; i += MCQ_NT) X[i] = ST[i] == 0 ? RHS[i] : T1[i];
+        EB_FOR {
+            EB_INDEX
+            signed char st[EB_E];
+            double t1[EB_E], rh[EB_E];
+            EB_EACH { const int i = idx[u]; st[u] = ST[i]; t1[u] = T1[i]; rh[u] = RHS[i]; }
+            EB_EACH if (ok[u]) X[idx[u]] = st[u] == 0 ? rh[u] : t1[u];
+        }
         gradient(c, X, nk > 0 ? Q : nullptr, T0, G);      // Lagrangian gradient  H x + f + E_K' mu
         if (with_kappa) tri_apply_E(c, X, KR, 1.0, T2);      // r = E x + k_ref
         double nv = 0.0, imax = -1.0, kk = 0.0;
-        for (int i = tid; i < n; i += MCQ_NT) {
-            const signed char st = ST[i];
-            int v = 0;
-            double pv = 0.0;
-            if (st == 0) {
-                if (X[i] < LO[i] - TOLX) { v = -1; pv = LO[i] - X[i]; }
-                else if (X[i] > HI[i] + TOLX) { v = 1; pv = X[i] - HI[i]; }
-                kk = fmax(kk, fabs(G[i]));
-            } else if (st == -1) { if (G[i] < -toly) v = 2; }
-            else if (st == 1) { if (G[i] > toly) v = 2; }
-            PV[i] = pv;
-            int vk = 0;
-            if (with_kappa) {
-                const double kf = KF[i];
-                if (kf == 0.0) {
-                    if (T2[i] > kb + tolk) vk = 1;
-                    else if (T2[i] < -kb - tolk) vk = -1;
-                } else if (kf * Q[i] < -toly) vk = 2;      // multiplier of an active row must push inward
+        EB_FOR {
+            EB_INDEX
+            signed char sta[EB_E];
+            double x[EB_E], lo[EB_E], hi[EB_E], g[EB_E];
+            EB_EACH { const int i = idx[u]; sta[u] = ST[i]; x[u] = X[i]; lo[u] = LO[i]; hi[u] = HI[i]; g[u] = G[i]; }
+            EB_EACH {
+                if (!ok[u]) continue;
+                const int i = idx[u];
+                const signed char st = sta[u];
+                int v = 0;
+                double pv = 0.0;
+                if (st == 0) {
+                    if (x[u] < lo[u] - TOLX) { v = -1; pv = lo[u] - x[u]; }
+                    else if (x[u] > hi[u] + TOLX) { v = 1; pv = x[u] - hi[u]; }
+                    kk = fmax(kk, fabs(g[u]));
+                } else if (st == -1) { if (g[u] < -toly) v = 2; }
+                else if (st == 1) { if (g[u] > toly) v = 2; }
+                PV[i] = pv;
+                int vk = 0;
+                if (with_kappa) {
+                    const double kf = KF[i];
+                    if (kf == 0.0) {
+                        if (T2[i] > kb + tolk) vk = 1;
+                        else if (T2[i] < -kb - tolk) vk = -1;
+                    } else if (kf * Q[i] < -toly) vk = 2;      // multiplier of an active row must push inward
+                }
+                T3[i] = (double)(v + 8 * vk);
+                if (v != 0) { nv += 1.0; imax = fmax(imax, (double)i); }
+                if (vk != 0) { nv += 1.0; imax = fmax(imax, (double)(n + i)); }
             }
-            T3[i] = (double)(v + 8 * vk);
-            if (v != 0) { nv += 1.0; imax = fmax(imax, (double)i); }
-            if (vk != 0) { nv += 1.0; imax = fmax(imax, (double)(n + i)); }
         }
         nv = block_reduce_(nv, 0, red);
         imax = block_reduce_(imax, 2, red);
@@ -1617,7 +1774,13 @@ __device__ __noinline__ int active_set(const LCtx& c, bool with_kappa, bool tapi
             // A round whose correction is already below 1e-8 m is the last one: the next would move alpha by (cond * eps)
             // times that, i.e. far below the 1e-9 m at which the dense oracle itself is known.
             for (int r = 0; r < c.refine_steps; ++r) {
-                for (int i = tid; i < n; i += MCQ_NT) RHS[i] = ST[i] == 0 ? -G[i] : 0.0;
+                EB_FOR {
+                    EB_INDEX
+                    signed char st[EB_E];
+                    double g[EB_E];
+                    EB_EACH { const int i = idx[u]; st[u] = ST[i]; g[u] = G[i]; }
+                    EB_EACH if (ok[u]) RHS[idx[u]] = st[u] == 0 ? -g[u] : 0.0;
+                }
                 timed_solve(c, RHS);
                 if (nk > 0) {
                     // curvature rows in the working set: one step on the KKT system [M E_K'; E_K 0] through the factored Schur
@@ -1638,7 +1801,13 @@ __device__ __noinline__ int active_set(const LCtx& c, bool with_kappa, bool tapi
                     __syncthreads();
                 }
                 double dm = 0.0;
-                for (int i = tid; i < n; i += MCQ_NT) if (ST[i] == 0) { X[i] += RHS[i]; dm = fmax(dm, fabs(RHS[i])); }
+                EB_FOR {
+                    EB_INDEX
+                    signed char st[EB_E];
+                    double x[EB_E], rh[EB_E];
+                    EB_EACH { const int i = idx[u]; st[u] = ST[i]; x[u] = X[i]; rh[u] = RHS[i]; }
+                    EB_EACH if (ok[u] && st[u] == 0) { X[idx[u]] = x[u] + rh[u]; dm = fmax(dm, fabs(rh[u])); }
+                }
                 dm = block_reduce_(dm, 2, red);
                 gradient(c, X, nk > 0 ? Q : nullptr, T0, G);
                 if (nk > 0) tri_apply_E(c, X, KR, 1.0, T2);      // r = E x + k_ref
@@ -1646,7 +1815,13 @@ __device__ __noinline__ int active_set(const LCtx& c, bool with_kappa, bool tapi
                 if (!(dm > 1e-8)) break;
             }
             double k2 = 0.0;
-            for (int i = tid; i < n; i += MCQ_NT) if (ST[i] == 0) k2 = fmax(k2, fabs(G[i]));
+            EB_FOR {
+                EB_INDEX
+                signed char st[EB_E];
+                double g[EB_E];
+                EB_EACH { const int i = idx[u]; st[u] = ST[i]; g[u] = G[i]; }
+                EB_EACH if (ok[u] && st[u] == 0) k2 = fmax(k2, fabs(g[u]));
+            }
             c.out_kkt = block_reduce_(k2, 2, red);
             return MCQ_OK;
         }
@@ -1742,19 +1917,32 @@ MCQ_FN_PROLOGUE void problem_scales(const LCtx& c)
     gdouble* G = VEC(c.w, nm, V_G);
     gschar* ST = c.w.state;
     double wsum = 0.0, nfree_d = 0.0, fmaxl = 0.0;
-    for (int i = tid; i < n; i += MCQ_NT) {
-        const double wdt = HI[i] - LO[i];
-        const bool fixed = !(wdt > 1e-12);
-        ST[i] = fixed ? 2 : 0;
-        X[i] = 0.5 * (LO[i] + HI[i]);
-        if (!fixed) { wsum += wdt; nfree_d += 1.0; }
-        fmaxl = fmax(fmaxl, fabs(F[i]));
+    EB_FOR {
+        EB_INDEX
+        double lo[EB_E], hi[EB_E], f[EB_E];
+        EB_EACH { const int i = idx[u]; lo[u] = LO[i]; hi[u] = HI[i]; f[u] = F[i]; }
+        EB_EACH {
+            if (!ok[u]) continue;
+            const int i = idx[u];
+            const double wdt = hi[u] - lo[u];
+            const bool fixed = !(wdt > 1e-12);
+            ST[i] = fixed ? 2 : 0;
+            X[i] = 0.5 * (lo[u] + hi[u]);
+            if (!fixed) { wsum += wdt; nfree_d += 1.0; }
+            fmaxl = fmax(fmaxl, fabs(f[u]));
+        }
     }
     wsum = block_reduce_(wsum, 0, red);
     const double nfree_s = block_reduce_(nfree_d, 0, red), fscale_s = block_reduce_(fmaxl, 2, red);
     gradient(c, X, nullptr, VEC(c.w, nm, V_T0), G);
     double gm = 0.0;
-    for (int i = tid; i < n; i += MCQ_NT) if (ST[i] == 0) gm = fmax(gm, fabs(G[i]));
+    EB_FOR {
+        EB_INDEX
+        signed char st[EB_E];
+        double g[EB_E];
+        EB_EACH { const int i = idx[u]; st[u] = ST[i]; g[u] = G[i]; }
+        EB_EACH if (ok[u] && st[u] == 0) gm = fmax(gm, fabs(g[u]));
+    }
     double zscale_s = block_reduce_(gm, 2, red);
     if (!(zscale_s > 0.0)) zscale_s = fscale_s > 0.0 ? fscale_s : 1.0;
     if (tid == 0) {
@@ -1786,9 +1974,16 @@ MCQ_FN_PROLOGUE void write_outputs(const LCtx& c, const McqOutcome& r)
     gdouble* Q = VEC(c.w, nm, V_Q);
     const gschar* ST = c.w.state;
     double nact = 0.0;
-    for (int i = tid; i < n; i += MCQ_NT) {
-        c.w.alpha[i] = X[i];
-        if (ST[i] == -1 || ST[i] == 1) nact += 1.0;
+    EB_FOR {
+        EB_INDEX
+        signed char st[EB_E];
+        double x[EB_E];
+        EB_EACH { const int i = idx[u]; st[u] = ST[i]; x[u] = X[i]; }
+        EB_EACH {
+            if (!ok[u]) continue;
+            c.w.alpha[idx[u]] = x[u];
+            if (st[u] == -1 || st[u] == 1) nact += 1.0;
+        }
     }
     nact = block_reduce_(nact, 0, red);
     const gdouble* XP = VEC(c.w, nm, V_XP);
@@ -1796,12 +1991,22 @@ MCQ_FN_PROLOGUE void write_outputs(const LCtx& c, const McqOutcome& r)
     const gdouble* XPP = VEC(c.w, nm, V_XPP);
     const gdouble* YPP = VEC(c.w, nm, V_YPP);
     if (!c.direct) {
-        for (int i = tid; i < n; i += MCQ_NT) { T1[i] = VEC(c.w, nm, V_NX)[i] * X[i]; T2[i] = VEC(c.w, nm, V_NY)[i] * X[i]; }
+        EB_FOR {
+            EB_INDEX
+            double nx[EB_E], ny[EB_E], x[EB_E];
+            EB_EACH { const int i = idx[u]; nx[u] = VEC(c.w, nm, V_NX)[i]; ny[u] = VEC(c.w, nm, V_NY)[i]; x[u] = X[i]; }
+            EB_EACH if (ok[u]) { T1[idx[u]] = nx[u] * x[u]; T2[idx[u]] = ny[u] * x[u]; }
+        }
         __syncthreads();
         if (r.dd_valid) {
             const gdouble* D1 = VEC(c.w, nm, V_TL);
             const gdouble* D2 = VEC(c.w, nm, V_TU);
-            for (int i = tid; i < n; i += MCQ_NT) { T0[i] = D1[i]; T3[i] = D2[i]; }
+            EB_FOR {
+                EB_INDEX
+                double d1[EB_E], d2[EB_E];
+                EB_EACH { d1[u] = D1[idx[u]]; d2[u] = D2[idx[u]]; }
+                EB_EACH if (ok[u]) { T0[idx[u]] = d1[u]; T3[idx[u]] = d2[u]; }
+            }
         } else {
             tri_apply_E(c, X, nullptr, 0.0, Q, T0, T3);      // D (n_x alpha), D (n_y alpha) are by-products of E alpha
         }
@@ -1884,7 +2089,12 @@ __device__ __forceinline__ void solve_body(const McqBatch& B, const McqSet& IN, 
     if (!c.direct) {   // f = F_SCALE E' k_ref
         gdouble* Fw = VEC(c.w, nm, V_F);
         tri_apply_Et(c, VEC(c.w, nm, V_KREF), Fw);        // (the pivots of T, V_IDL / V_TUC, are the assembly kernel's)
-        for (int i = tid; i < n; i += MCQ_NT) Fw[i] *= MCQ_F_SCALE;
+        EB_FOR {
+            EB_INDEX
+            double f[EB_E];
+            EB_EACH f[u] = Fw[idx[u]];
+            EB_EACH if (ok[u]) Fw[idx[u]] = f[u] * MCQ_F_SCALE;
+        }
         __syncthreads();
     }
     problem_scales(c);
@@ -1942,7 +2152,12 @@ __device__ __forceinline__ void solve_body(const McqBatch& B, const McqSet& IN, 
         // interior point resumes from its own pairs down to mu = 1e-13 -- where the magnitude test separates those rows --
         // and the active-set phase starts again with the full budget.
         gdouble* XS = VEC(c.w, nm, V_TL);
-        for (int i = tid; i < n; i += MCQ_NT) XS[i] = X[i];
+        EB_FOR {
+            EB_INDEX
+            double x[EB_E];
+            EB_EACH x[u] = X[idx[u]];
+            EB_EACH if (ok[u]) XS[idx[u]] = x[u];
+        }
         const int cap1 = B.max_as_iter < 6 ? B.max_as_iter : 6;
         status = active_set(c, false, ipm_iters >= 1 && c.last_step >= 0.9, cap1, 1, kappa_mem_lds(c));
         as_iters = c.out_iters;
@@ -1982,7 +2197,12 @@ __device__ __forceinline__ void solve_body(const McqBatch& B, const McqSet& IN, 
     const long long t_epi0 = TICK();
 
     // kappa(alpha) = k_ref + E alpha
-    for (int i = tid; i < n; i += MCQ_NT) X[i] = fmin(fmax(X[i], LO[i]), HI[i]);
+    EB_FOR {
+        EB_INDEX
+        double x[EB_E], lo[EB_E], hi[EB_E];
+        EB_EACH { const int i = idx[u]; x[u] = X[i]; lo[u] = LO[i]; hi[u] = HI[i]; }
+        EB_EACH if (ok[u]) X[idx[u]] = fmin(fmax(x[u], lo[u]), hi[u]);
+    }
     __syncthreads();
     double km = 0.0;
     bool dd_valid = false;
@@ -1991,7 +2211,12 @@ __device__ __forceinline__ void solve_body(const McqBatch& B, const McqSet& IN, 
         //  vectors only the curvature-row phase uses, so the post-check repeats the product only if that phase ran)
         tri_apply_E(c, X, VEC(c.w, nm, V_KREF), 1.0, T0, VEC(c.w, nm, V_TL), VEC(c.w, nm, V_TU));
         dd_valid = true;
-        for (int i = tid; i < n; i += MCQ_NT) km = fmax(km, fabs(T0[i]));
+        EB_FOR {
+            EB_INDEX
+            double t0[EB_E];
+            EB_EACH t0[u] = T0[idx[u]];
+            EB_EACH if (ok[u]) km = fmax(km, fabs(t0[u]));
+        }
         km = block_reduce_(km, 2, red);
     }
 

@@ -26,11 +26,21 @@
 // plus the full blocks at both ends of the segment); the separators' own block-cyclic system (nseg x nseg blocks) is eliminated the same
 // way by one wave with both spikes pointing at separator 0; its step records keep D_k^-1, G_k, M_k = D_k^-1 RL_k and the spike to 0.
 // A solve is: forward chain y_k = D~^-1 (r_k e_0 - Lo_k y_(k-1)), backward chain x_k = y_k - G_k x_(k+1), the separators' system,
-// alpha_m -= X^L_m xs_j + X^R_m xs_(j+1).   Chains read their blocks from LDS chunks staged by the group's own lanes one chunk ahead.
+// alpha_m -= X^L_m xs_j + X^R_m xs_(j+1).   Chains read their blocks from LDS chunks staged by the group's own lanes one chunk ahead; the
+// correction, issued after the barrier that follows the separators' system, has the loads of four (float records: eight) of a lane's
+// waypoints in flight at once -- two round trips to memory per segment of 124 waypoints (one for float records).
 // ---------------------------------------------------------------------------------------------------------------------
 #ifndef MCQ_KKT
 #define MCQ_KKT 1
 #endif
+// MCQ_KKT_CORR_BATCH (default 1): the correction at the end of solve_kkt<> loads the spike rows and the alpha of several of a lane's
+// waypoints before it uses the first (0: the earlier form, one waypoint per trip -- same results bit for bit, tests/test_emu_entry_batch.py).
+// Trips per batch: what keeps solve_kkt<> free of scratch memory (fp64 records: eight trips need 248 VGPRs and spill, four do not).
+#ifndef MCQ_KKT_CORR_BATCH
+#define MCQ_KKT_CORR_BATCH 1
+#endif
+#define KKT_CORR_TRIPS_F64 4
+#define KKT_CORR_TRIPS_F32 8
 #define KKT_FN __device__ __noinline__
 #ifndef KKT_TIMERS
 #define KKT_TIMERS 0     /* scripts/kkt_check.hip: wall-clock ticks of the phases of factor_kkt / solve_kkt summed into SolveCtx.tk[0..7] */
@@ -1068,6 +1078,39 @@ KKT_FN void solve_kkt(const LCtx& c, gdouble* vv, bool fwd_done)
                 xb[2] = fma(sr[1] / sr[2], xb[0], xb[2]);
             }
         }
+#if MCQ_KKT_CORR_BATCH
+        // A lane's waypoints k, k + 16, ... KKT_CB at a time: every load of the batch is issued before the first value is used, then the
+        // accumulations, then the stores -- one round trip to memory per batch.  (One waypoint per trip, the stores to vv keep the next trip's
+        // loads behind them: a trip per round trip, eight of them at L = 124.)  A trip past L loads the lane's first waypoint of the batch
+        // and stores nothing.
+        constexpr int KKT_CB = F32 ? KKT_CORR_TRIPS_F32 : KKT_CORR_TRIPS_F64;
+        for (int k0 = cl; k0 < L; k0 += 16 * KKT_CB) {
+            int idx[KKT_CB];
+            bool ok[KKT_CB];
+#pragma unroll
+            for (int u = 0; u < KKT_CB; ++u) {
+                ok[u] = k0 + 16 * u < L;
+                idx[u] = lo_pt + (ok[u] ? k0 + 16 * u : k0);
+            }
+            RT as[KKT_CB][KAS];
+            double acc[KKT_CB];
+#pragma unroll
+            for (int u = 0; u < KKT_CB; ++u) {
+                const RG* src = AS + (size_t)idx[u] * KAS;
+#pragma unroll
+                for (int q = 0; q < KAS; ++q) as[u][q] = src[q];
+                acc[u] = vv[idx[u]];
+            }
+#pragma unroll
+            for (int u = 0; u < KKT_CB; ++u) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) acc[u] -= (double)as[u][q] * xa[1 + q] + (double)as[u][4 + q] * xb[1 + q];
+            }
+#pragma unroll
+            for (int u = 0; u < KKT_CB; ++u)
+                if (ok[u]) vv[idx[u]] = acc[u];
+        }
+#else
         for (int k = cl; k < L; k += 16) {
             const int m = lo_pt + k;
             const RG* as = AS + (size_t)m * KAS;
@@ -1076,6 +1119,7 @@ KKT_FN void solve_kkt(const LCtx& c, gdouble* vv, bool fwd_done)
             for (int q = 0; q < 4; ++q) acc -= (double)as[q] * xa[1 + q] + (double)as[4 + q] * xb[1 + q];
             vv[m] = acc;
         }
+#endif
     }
     __syncthreads();
     KT(6);
