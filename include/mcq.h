@@ -403,8 +403,11 @@ int mcq_solve_device_stream(mcq_handle* h, int steps, int batch, int n, const do
  *
  * mcq_iqp_device: everything resident.  reftrack_a / normvec_a [batch][nmax][*] hold the tracks on entry (n_io [batch] their
  * waypoint counts), reftrack_b / normvec_b are the second set of the double buffer; scaling [batch][nmax] (first pass) or NULL.
- * On return: alpha_out [batch][nmax] = alpha of the last pass (damped if the track ended in an early round -- only with
- * iters_min > the rounds run, as upstream), n_io = waypoint counts of the last re-linearisation, buf_out [batch] = 0 / 1: which
+ * On return: alpha_out [batch][nmax] = alpha of the last pass AS THE QP RETURNED IT, never damped: the damping of the early rounds
+ * belongs to the step into the next ring, and no step follows the last pass.  So reftrack + alpha_out * normvectors of the returned
+ * state is that pass's own raceline -- also for a track that max_rounds cut off before round iters_min (status MCQ_ITER_CAP,
+ * rounds_out = max_rounds, ring, normals and undamped alpha of pass max_rounds; upstream has no round cap and cannot end there).
+ * n_io = waypoint counts of the last re-linearisation, buf_out [batch] = 0 / 1: which
  * set holds a track's final reftrack / normvectors, curv_err_out / status_out / rounds_out [batch]; curv_trace_out
  * [batch][MCQ_IQP_TRACE] (optional) = curv_error_max of every round of a track (what iqp_handler prints with print_debug;
  * rounds beyond MCQ_IQP_TRACE are not recorded: rounds_out tells when the trace is truncated).  A track with n_io == 0 on entry is
