@@ -872,6 +872,43 @@ extern "C" int mcq_raceline_device(mcq_handle* h, int batch, int nmax, const int
     return 0;
 }
 
+extern "C" int mcq_raceline_device_ends(mcq_handle* h, int batch, int nmax, const int* n_in, const double* reftrack,
+                                        const double* normvec, const double* alpha, const int* closed, const double* psi,
+                                        double stepsize, int mmax, double* raceline_out, double* psi_out, double* kappa_out,
+                                        double* el_lengths_out, int* m_out, int* status_out)
+{
+    if (!h || batch <= 0 || nmax < 2 || mmax < 2 || !reftrack || !normvec || !alpha || !(stepsize > 0.0) || !kappa_out ||
+        !el_lengths_out || !m_out || !status_out || (!closed && !psi)) {
+        g_err = "mcq_raceline_device_ends: bad argument";
+        return MCQ_E_ARG;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    int rc = ensure_workspace(h, 0, (size_t)batch, (size_t)nmax);
+    if (rc) return rc;
+    if (!psi) {     // legal for a launch of rings only: the flags are read back (the one blocking path of this entry)
+        std::vector<int> flags((size_t)batch);
+        HIP_TRY(hipStreamSynchronize(h->ws[0].stream));
+        HIP_TRY(hipMemcpy(flags.data(), closed, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost));
+        for (int k = 0; k < batch; ++k)
+            if (flags[k] == 0) {
+                g_err = "mcq_raceline_device_ends: psi is NULL and a row is a chain";
+                return MCQ_E_ARG;
+            }
+    }
+    McqRaceEnds E;
+    memset(&E, 0, sizeof(E));
+    McqRace& Q = E.Q;
+    Q.batch = batch; Q.nmax = nmax; Q.mmax = mmax;
+    Q.n_in = n_in; Q.ref = reftrack; Q.nv = normvec; Q.alpha = alpha; Q.stepsize = stepsize;
+    Q.xy_out = raceline_out; Q.psi_out = psi_out; Q.kappa_out = kappa_out; Q.el_out = el_lengths_out;
+    Q.m_out = m_out; Q.status = status_out;
+    Q.vec = h->ws[0].vec;
+    E.closed = closed; E.psi = psi;
+    hipLaunchKernelGGL(mcq_raceline_ends_kernel, dim3(batch), dim3(256), 0, h->ws[0].stream, E);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // ---- device memory plumbing for callers that keep data resident between calls without a second HIP runtime in the
 //      process (the Python IQP driver): plain allocate / free / copy on the handle's device and stream ------------------
 extern "C" int mcq_device_alloc(mcq_handle* h, size_t bytes, void** out)

@@ -218,6 +218,17 @@ struct McqRace {
 };
 __global__ void mcq_raceline_kernel(McqRace Q);
 
+/* ---- the same with OPEN chains among the rows (mcq_raceline_device_ends): a chain row is tph.calc_splines(path, psi_s, psi_e,
+ *      use_dist_scaling=False) + calc_spline_lengths + interp_splines(incl_last_point=True) + calc_head_curv_an; el_out holds its m - 1
+ *      elements and a 0.  Ring rows return the bits of mcq_raceline_kernel.  status: also MCQ_BAD_INPUT for a chain of n < 2 waypoints or a
+ *      non-finite end heading. ---- */
+struct McqRaceEnds {
+    McqRace Q;
+    const int* closed;      // [batch] != 0: a ring row; nullptr: every row is a chain
+    const double* psi;      // [batch][2] (psi_s, psi_e), read for chain rows only
+};
+__global__ void mcq_raceline_ends_kernel(McqRaceEnds E);
+
 /* ---- ggv velocity profile + lap time of many (track, vehicle) variants: the forward /
  *      backward quasi-steady-state sweeps of tph.calc_vel_profile (closed track, global ggv) followed by
  *      tph.calc_ax_profile / calc_t_profile, one thread per variant. ---- */

@@ -2925,6 +2925,271 @@ __global__ void __launch_bounds__(MCQ_NT) mcq_raceline_kernel(McqRace Q)
     if (tid == 0) { *status = MCQ_OK; *m_out = m; }
 }
 
+// ---- mcq_raceline_kernel's body once more, statement for statement, for the launch that mixes rings and chains (mcq_raceline_ends_kernel).
+//      A copy, not a function shared with the kernel above: with the body shared, hipcc placed a handful of that kernel's scalar address
+//      instructions differently, and the existing entry keeps its code object as it is.  Both suites hold the two to the same bits
+//      (tests/race_open_checks.py: mixed launches). ----
+__device__ __forceinline__ void race_ring_body(const McqRace& Q, double* relin_lds)
+{
+    const int tid = threadIdx.x, pb = blockIdx.x;
+    const size_t nm = (size_t)Q.nmax, mm = (size_t)Q.mmax;
+    const int n = Q.n_in ? Q.n_in[pb] : Q.nmax;
+    const gdouble* ref = (const gdouble*)(Q.ref + (size_t)pb * nm * 4);
+    const gdouble* nv = (const gdouble*)(Q.nv + (size_t)pb * nm * 2);
+    const gdouble* al = (const gdouble*)(Q.alpha + (size_t)pb * nm);
+    gdouble* vec = (gdouble*)(Q.vec + (size_t)pb * nm * MCQ_NVEC);
+    gdouble* PX = vec + 0 * nm;   gdouble* PY = vec + 1 * nm;
+    gdouble* CX = vec + 4 * nm;   gdouble* CY = vec + 5 * nm;
+    gdouble* LEN = vec + 6 * nm;  gdouble* CUM = vec + 7 * nm;
+    gint* m_out = (gint*)(Q.m_out + pb);
+    gint* status = (gint*)(Q.status + pb);
+    if (n < 3) {
+        if (tid == 0) { *status = MCQ_BAD_INPUT; *m_out = 0; }
+        return;
+    }
+    double total;
+    const int m = relin_front(ref, nv, al, n, 1.0, Q.stepsize, vec, nm, total, relin_lds);
+    if (m < 2 || m > Q.mmax) {
+        if (tid == 0) { *status = MCQ_BAD_INPUT; *m_out = m > 0 ? m : 0; }
+        return;
+    }
+    gdouble* xy = Q.xy_out ? (gdouble*)(Q.xy_out + (size_t)pb * mm * 2) : nullptr;
+    gdouble* psi = Q.psi_out ? (gdouble*)(Q.psi_out + (size_t)pb * mm) : nullptr;
+    gdouble* kap = (gdouble*)(Q.kappa_out + (size_t)pb * mm);
+    gdouble* el = (gdouble*)(Q.el_out + (size_t)pb * mm);
+    const double step = total / (double)m;                       // numpy.linspace(0, total, m + 1): station j = j * step
+    const double pi = 3.14159265358979323846;
+    for (int j = tid; j < m; j += MCQ_NT) {
+        const double q = (double)j * step;
+        int lo = 0, hi = n;                                      // first index with CUM[idx] > q
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (CUM[mid] > q) hi = mid; else lo = mid + 1;
+        }
+        const int s = lo < n - 1 ? lo : n - 1;
+        const int sp = s + 1 == n ? 0 : s + 1;
+        const double start = s > 0 ? CUM[s - 1] : 0.0;
+        const double t = (q - start) / LEN[s];
+        const double ax = PX[s], ay = PY[s], cx = CX[s], cy = CY[s];
+        const double bx = (PX[sp] - ax) - (2.0 * cx + CX[sp]) / 3.0, by = (PY[sp] - ay) - (2.0 * cy + CY[sp]) / 3.0;
+        const double dx = (CX[sp] - cx) / 3.0, dy = (CY[sp] - cy) / 3.0;
+        if (xy) {
+            xy[2 * j] = ax + t * (bx + t * (cx + t * dx));
+            xy[2 * j + 1] = ay + t * (by + t * (cy + t * dy));
+        }
+        const double xd = bx + 2.0 * cx * t + 3.0 * dx * t * t, yd = by + 2.0 * cy * t + 3.0 * dy * t * t;
+        const double xdd = 2.0 * cx + 6.0 * dx * t, ydd = 2.0 * cy + 6.0 * dy * t;
+        if (psi) {                                               // heading, 0 = north, wrapped to [-pi, pi) (tph.normalize_psi)
+            double a = atan2(yd, xd) - 0.5 * pi;
+            if (a >= pi) a -= 2.0 * pi;
+            else if (a < -pi) a += 2.0 * pi;
+            psi[j] = a;
+        }
+        const double v2 = xd * xd + yd * yd;
+        kap[j] = (xd * ydd - yd * xdd) / (v2 * sqrt(v2));
+        el[j] = j + 1 < m ? (double)(j + 1) * step - q : total - q;
+    }
+    if (tid == 0) { *status = MCQ_OK; *m_out = m; }
+}
+
+// ---- the same for an OPEN chain of n >= 2 waypoints (mcq_raceline_device_ends; DESIGN.md "Open chains"): n - 1 splines through
+//      P_i = p_i + alpha_i n_i with the end headings psi_s / psi_e -- tph.calc_splines(path, psi_s, psi_e, use_dist_scaling=False) with
+//      el_lengths = None.  The heading rows carry the UNIT vectors h = (cos(psi + pi/2), sin(psi + pi/2)) times MCQ_HEADING_SCALE: the very
+//      rows the chain solve linearised (assemble_problem), so this raceline is the curve whose curvature the QP minimised.
+//          2 c_0 + c_1 = 3 (D_0 - h_s),   c_(i-1) + 4 c_i + c_(i+1) = 3 (D_i - D_(i-1)),   c_(n-2) + 2 c_(n-1) = 3 (h_e - D_(n-2))
+//      Rows 0 and n - 1 doubled and the chain reflected about both ends, this is circ(1, 4, 1) on a ring of 2n - 2 points with the
+//      right-hand side (2 r_0, r_1, .., r_(n-2), 2 r_(n-1), r_(n-2), .., r_1): relin_spline_c's closed-form inverse through mirrored
+//      indices (exact periodic kernel up to 2n - 2 = 2 RL_KW, truncated above).  RX / RY hold r with entries 0 and n - 1 ALREADY doubled.
+__device__ void chain_spline_c(const gdouble* RX, const gdouble* RY, int n, gdouble* CX, gdouble* CY)
+{
+    const double lam = sqrt(3.0) - 2.0, A = 1.0 / (4.0 + 2.0 * lam);
+    const int nr = 2 * n - 2;                                            // points of the mirrored ring; position j >= n is waypoint nr - j
+    for (int i = threadIdx.x; i < n; i += MCQ_NT) {
+        double cx, cy;
+        if (nr > 2 * RL_KW) {
+            cx = A * RX[i];
+            cy = A * RY[i];
+            double g = A;
+            int ju = i, jd = i;
+            for (int k = 1; k <= RL_KW; ++k) {
+                g *= lam;
+                ju = ju + 1 == nr ? 0 : ju + 1;
+                jd = jd == 0 ? nr - 1 : jd - 1;
+                const int wu = ju < n ? ju : nr - ju, wd = jd < n ? jd : nr - jd;
+                cx += g * (RX[wu] + RX[wd]);
+                cy += g * (RY[wu] + RY[wd]);
+            }
+        } else {
+            double ln = 1.0;
+            for (int k = 0; k < nr; ++k) ln *= lam;                      // lam^nr
+            const double sc = A / (1.0 - ln), il = 1.0 / lam;
+            double pk = 1.0, qk = ln;                                    // lam^k, lam^(nr-k)
+            cx = 0.0;
+            cy = 0.0;
+            int j = i;
+            for (int k = 0; k < nr; ++k) {
+                const double g = sc * (pk + qk);
+                const int w = j < n ? j : nr - j;
+                cx += g * RX[w];
+                cy += g * RY[w];
+                pk *= lam;
+                qk *= il;
+                j = j + 1 == nr ? 0 : j + 1;
+            }
+        }
+        CX[i] = cx;
+        CY[i] = cy;
+    }
+}
+
+// One chain row: spline as above, lengths of the n - 1 segments (15 points, 14 chords) and their running sum in numpy.cumsum's order,
+// m = ceil(total / stepsize) + 1 stations ALL kept (tph.interp_splines, incl_last_point = True): stations 0 .. m-2 at j * total / (m - 1) by
+// the rings' search without the wrap, station m - 1 at t = 1 of segment n - 2.  el_lengths: the m - 1 elements, then a written 0.
+// vec slots as in relin_front (0/1 points, 2/3 rhs, 4/5 c, 6 lengths, 7 running sum); lds: RELIN_LDS doubles.
+__device__ __forceinline__ void race_chain_body(const McqRace& Q, const double* psi_ends, double* lds)
+{
+    double* sbuf = lds;
+    double& s_carry = lds[2048];
+    int& s_m = *(int*)(lds + 2049);
+    const int tid = threadIdx.x, pb = blockIdx.x;
+    const size_t nm = (size_t)Q.nmax, mm = (size_t)Q.mmax;
+    const int n = Q.n_in ? Q.n_in[pb] : Q.nmax;
+    const gdouble* ref = (const gdouble*)(Q.ref + (size_t)pb * nm * 4);
+    const gdouble* nv = (const gdouble*)(Q.nv + (size_t)pb * nm * 2);
+    const gdouble* al = (const gdouble*)(Q.alpha + (size_t)pb * nm);
+    gdouble* vec = (gdouble*)(Q.vec + (size_t)pb * nm * MCQ_NVEC);
+    gdouble* PX = vec + 0 * nm;   gdouble* PY = vec + 1 * nm;
+    gdouble* RX = vec + 2 * nm;   gdouble* RY = vec + 3 * nm;
+    gdouble* CX = vec + 4 * nm;   gdouble* CY = vec + 5 * nm;
+    gdouble* LEN = vec + 6 * nm;  gdouble* CUM = vec + 7 * nm;
+    gint* m_out = (gint*)(Q.m_out + pb);
+    gint* status = (gint*)(Q.status + pb);
+    const double psi_s = psi_ends ? psi_ends[2 * pb] : NAN, psi_e = psi_ends ? psi_ends[2 * pb + 1] : NAN;
+    if (n < 2 || n > Q.nmax || !(isfinite(psi_s) && isfinite(psi_e))) {
+        if (tid == 0) { *status = MCQ_BAD_INPUT; *m_out = 0; }
+        return;
+    }
+    const int ns = n - 1;                                        // segments
+    const double hsx = MCQ_HEADING_SCALE * cos(psi_s + 0.5 * M_PI), hsy = MCQ_HEADING_SCALE * sin(psi_s + 0.5 * M_PI);
+    const double hex = MCQ_HEADING_SCALE * cos(psi_e + 0.5 * M_PI), hey = MCQ_HEADING_SCALE * sin(psi_e + 0.5 * M_PI);
+    for (int i = tid; i < n; i += MCQ_NT) {
+        PX[i] = ref[4 * i] + al[i] * nv[2 * i];
+        PY[i] = ref[4 * i + 1] + al[i] * nv[2 * i + 1];
+    }
+    __syncthreads();
+    for (int i = tid; i < n; i += MCQ_NT) {                      // rows 0 and n - 1: the heading rows, doubled for the mirrored ring
+        if (i == 0) {
+            RX[0] = 2.0 * (3.0 * ((PX[1] - PX[0]) - hsx));
+            RY[0] = 2.0 * (3.0 * ((PY[1] - PY[0]) - hsy));
+        } else if (i == n - 1) {
+            RX[i] = 2.0 * (3.0 * (hex - (PX[i] - PX[i - 1])));
+            RY[i] = 2.0 * (3.0 * (hey - (PY[i] - PY[i - 1])));
+        } else {
+            RX[i] = 3.0 * ((PX[i + 1] - PX[i]) - (PX[i] - PX[i - 1]));
+            RY[i] = 3.0 * ((PY[i + 1] - PY[i]) - (PY[i] - PY[i - 1]));
+        }
+    }
+    __syncthreads();
+    chain_spline_c(RX, RY, n, CX, CY);
+    __syncthreads();
+    for (int i = tid; i < ns; i += MCQ_NT) {
+        const double ax = PX[i], ay = PY[i], cx = CX[i], cy = CY[i];
+        const double dlx = PX[i + 1] - ax, dly = PY[i + 1] - ay;
+        const double bx = dlx - (2.0 * cx + CX[i + 1]) / 3.0, by = dly - (2.0 * cy + CY[i + 1]) / 3.0;
+        const double dx = (CX[i + 1] - cx) / 3.0, dy = (CY[i + 1] - cy) / 3.0;
+        double len = 0.0, x0 = ax, y0 = ay;
+        for (int k = 1; k < 15; ++k) {
+            const double t = (double)k / 14.0;
+            const double x1 = ax + bx * t + cx * t * t + dx * t * t * t;
+            const double y1 = ay + by * t + cy * t * t + dy * t * t * t;
+            len += hypot(x1 - x0, y1 - y0);
+            x0 = x1;
+            y0 = y1;
+        }
+        LEN[i] = len;
+    }
+    __syncthreads();
+    if (tid == 0) s_carry = 0.0;
+    for (int c0 = 0; c0 < ns; c0 += 2048) {
+        const int cn = ns - c0 < 2048 ? ns - c0 : 2048;
+        __syncthreads();
+        for (int q = tid; q < cn; q += MCQ_NT) sbuf[q] = LEN[c0 + q];
+        __syncthreads();
+        if (tid == 0) {
+            double acc = s_carry;
+            for (int q = 0; q < cn; ++q) { acc += sbuf[q]; sbuf[q] = acc; }
+            s_carry = acc;
+        }
+        __syncthreads();
+        for (int q = tid; q < cn; q += MCQ_NT) CUM[c0 + q] = sbuf[q];
+    }
+    __syncthreads();
+    const double total = s_carry;
+    if (tid == 0) {
+        const double cnt = ceil(total / Q.stepsize) + 1.0;      // no_interp_points of tph.interp_splines, all of them kept
+        s_m = (cnt >= 2.0 && cnt <= 2.0e9) ? (int)cnt : -1;
+    }
+    __syncthreads();
+    const int m = s_m;
+    if (m < 2 || m > Q.mmax) {
+        if (tid == 0) { *status = MCQ_BAD_INPUT; *m_out = m > 0 ? m : 0; }
+        return;
+    }
+    gdouble* xy = Q.xy_out ? (gdouble*)(Q.xy_out + (size_t)pb * mm * 2) : nullptr;
+    gdouble* psi = Q.psi_out ? (gdouble*)(Q.psi_out + (size_t)pb * mm) : nullptr;
+    gdouble* kap = (gdouble*)(Q.kappa_out + (size_t)pb * mm);
+    gdouble* el = (gdouble*)(Q.el_out + (size_t)pb * mm);
+    const double step = total / (double)(m - 1);                 // numpy.linspace(0, total, m): station j = j * step
+    const double pi = 3.14159265358979323846;
+    for (int j = tid; j < m; j += MCQ_NT) {
+        int s;
+        double t, q = 0.0;
+        if (j < m - 1) {
+            q = (double)j * step;
+            int lo = 0, hi = ns;                                 // first index with CUM[idx] > q
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (CUM[mid] > q) hi = mid; else lo = mid + 1;
+            }
+            s = lo < ns - 1 ? lo : ns - 1;
+            const double start = s > 0 ? CUM[s - 1] : 0.0;
+            t = (q - start) / LEN[s];
+        } else {                                                 // the last point: the end of the last segment
+            s = ns - 1;
+            t = 1.0;
+        }
+        const double ax = PX[s], ay = PY[s], cx = CX[s], cy = CY[s];
+        const double bx = (PX[s + 1] - ax) - (2.0 * cx + CX[s + 1]) / 3.0, by = (PY[s + 1] - ay) - (2.0 * cy + CY[s + 1]) / 3.0;
+        const double dx = (CX[s + 1] - cx) / 3.0, dy = (CY[s + 1] - cy) / 3.0;
+        if (xy) {
+            xy[2 * j] = ax + t * (bx + t * (cx + t * dx));
+            xy[2 * j + 1] = ay + t * (by + t * (cy + t * dy));
+        }
+        const double xd = bx + 2.0 * cx * t + 3.0 * dx * t * t, yd = by + 2.0 * cy * t + 3.0 * dy * t * t;
+        const double xdd = 2.0 * cx + 6.0 * dx * t, ydd = 2.0 * cy + 6.0 * dy * t;
+        if (psi) {                                               // heading, 0 = north, wrapped to [-pi, pi) (tph.normalize_psi)
+            double a = atan2(yd, xd) - 0.5 * pi;
+            if (a >= pi) a -= 2.0 * pi;
+            else if (a < -pi) a += 2.0 * pi;
+            psi[j] = a;
+        }
+        const double v2 = xd * xd + yd * yd;
+        kap[j] = (xd * ydd - yd * xdd) / (v2 * sqrt(v2));
+        if (j + 2 < m) el[j] = (double)(j + 1) * step - q;
+        else if (j + 2 == m) el[j] = total - q;
+        else el[j] = 0.0;                                        // no element after the last point: written, never stale
+    }
+    if (tid == 0) { *status = MCQ_OK; *m_out = m; }
+}
+
+// Rings and chains in one launch: a workgroup takes the ring code (the bits of mcq_raceline_kernel) or the chain code by its row's flag.
+__global__ void __launch_bounds__(MCQ_NT) mcq_raceline_ends_kernel(McqRaceEnds E)
+{
+    __shared__ double relin_lds[RELIN_LDS];
+    if (E.closed && E.closed[blockIdx.x] != 0) race_ring_body(E.Q, relin_lds);
+    else race_chain_body(E.Q, E.psi, relin_lds);
+}
+
 // ---- tph.check_normals_crossing as prep_track calls it [REF helper_funcs_glob/src/prep_track.py:57-59]: do the normal segments
 //      [p - w_left n, p + w_right n] of two waypoints at most `horizon` apart intersect?  One workgroup per track, thread per
 //      waypoint, 2x2 system per pair in closed form (parallel normals: no crossing). ----

@@ -117,7 +117,8 @@ EXPORTED_SYMBOLS = ("mcq_create", "mcq_destroy", "mcq_last_error", "mcq_default_
                     "mcq_device_free", "mcq_copy_to_device", "mcq_copy_to_host", "mcq_sync", "mcq_stream",
                     "mcq_last_timing", "mcq_timing_begin", "mcq_timing_end", "mcq_workspace_bytes",
                     "mcq_comm_unique_id", "mcq_comm_init", "mcq_comm_allgather", "mcq_comm_wait", "mcq_comm_world", "mcq_comm_destroy",
-                    "mcq_les_scalings", "mcq_last_upload_was_direct", "mcq_solve_batch_ends", "mcq_les_scalings_open")
+                    "mcq_les_scalings", "mcq_last_upload_was_direct", "mcq_solve_batch_ends", "mcq_les_scalings_open",
+                    "mcq_raceline_device_ends")
 
 
 IQP_ROUND_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int))
@@ -212,6 +213,9 @@ def load_library(path=None):
     lib.mcq_raceline_device.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, ctypes.c_double, ctypes.c_int, vp, vp,
                                         vp, vp, vp, vp]
     lib.mcq_raceline_device.restype = ctypes.c_int
+    lib.mcq_raceline_device_ends.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, vp, ctypes.c_double, ctypes.c_int, vp, vp,
+                                             vp, vp, vp, vp]
+    lib.mcq_raceline_device_ends.restype = ctypes.c_int
     lib.mcq_normals_crossing_device.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, ctypes.c_int, vp]
     lib.mcq_normals_crossing_device.restype = ctypes.c_int
     lib.mcq_device_alloc.argtypes = [vp, ctypes.c_size_t, ctypes.POINTER(vp)]
@@ -825,10 +829,22 @@ class Engine:
             for p in ptrs:
                 self.free(p)
 
-    def raceline_batch(self, reftracks, normvecs, alphas, stepsize, mmax=None):
+    def raceline_device_ends(self, batch, nmax, d_n, d_ref, d_nv, d_alpha, d_closed, d_psi, stepsize, mmax, d_xy, d_psi_out, d_kappa,
+                             d_el, d_m, d_status):
+        """mcq_raceline_device_ends (include/mcq.h) on device pointers; d_closed None: every row a chain.  Asynchronous."""
+        rc = self.lib.mcq_raceline_device_ends(self.h, int(batch), int(nmax), d_n, d_ref, d_nv, d_alpha, d_closed or None, d_psi or None,
+                                               float(stepsize), int(mmax), d_xy, d_psi_out, d_kappa, d_el, d_m, d_status)
+        self._check(rc, "mcq_raceline_device_ends")
+
+    def raceline_batch(self, reftracks, normvecs, alphas, stepsize, mmax=None, ends=None):
         """tph.create_raceline + tph.calc_head_curv_an of a list of tracks on the device (mcq_raceline_device)
         [REF main_globaltraj.py:371-387].  reftracks [n_k, >=2], normvecs [n_k, 2], alphas [n_k].  Returns a dict of padded
-        arrays: xy [B, mmax, 2], psi / kappa / el_lengths [B, mmax], m [B] (valid entries per row), status [B]."""
+        arrays: xy [B, mmax, 2], psi / kappa / el_lengths [B, mmax], m [B] (valid entries per row), status [B].
+
+        ends: None (every track a ring), or what solve_batch takes -- one entry per track, None or {closed: True} for a ring, else a dict
+        with psi_s, psi_e (fix_s / fix_e are ignored): that track is an open chain (mcq_raceline_device_ends: the open unit-scaling spline
+        with the solver's heading rows, every station kept, the last one being the last raceline point); el_lengths[:m - 1] are its
+        elements and el_lengths[m - 1] is 0."""
         bsz = len(reftracks)
         ns = np.array([np.asarray(r).shape[0] for r in reftracks], dtype=np.int32)
         nmax = int(ns.max())
@@ -860,9 +876,20 @@ class Engine:
             d_ref, d_nv, d_al, d_n = up(ref), up(nv), up(al), up(ns)
             d_xy, d_psi, d_k, d_el = new(bsz * mmax * 16), new(bsz * mmax * 8), new(bsz * mmax * 8), new(bsz * mmax * 8)
             d_m, d_st = new(bsz * 4), new(bsz * 4)
-            rc = self.lib.mcq_raceline_device(self.h, bsz, nmax, d_n, d_ref, d_nv, d_al, float(stepsize), int(mmax), d_xy,
-                                              d_psi, d_k, d_el, d_m, d_st)
-            self._check(rc, "mcq_raceline_device")
+            if ends is None:
+                rc = self.lib.mcq_raceline_device(self.h, bsz, nmax, d_n, d_ref, d_nv, d_al, float(stepsize), int(mmax), d_xy,
+                                                  d_psi, d_k, d_el, d_m, d_st)
+                self._check(rc, "mcq_raceline_device")
+            else:
+                if len(ends) != bsz:
+                    raise ValueError("ends must have one entry per track")
+                closed = np.array([1 if e is None or e.get("closed", False) else 0 for e in ends], dtype=np.int32)
+                heads = np.zeros((bsz, 2))
+                for k, e in enumerate(ends):
+                    if not closed[k]:
+                        heads[k] = (float(e["psi_s"]), float(e["psi_e"]))
+                self.raceline_device_ends(bsz, nmax, d_n, d_ref, d_nv, d_al, up(closed), up(heads), stepsize, mmax, d_xy, d_psi, d_k,
+                                          d_el, d_m, d_st)
             return dict(xy=self.download(d_xy, (bsz, mmax, 2), np.float64), psi=self.download(d_psi, (bsz, mmax), np.float64),
                         kappa=self.download(d_k, (bsz, mmax), np.float64),
                         el_lengths=self.download(d_el, (bsz, mmax), np.float64),

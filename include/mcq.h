@@ -349,6 +349,28 @@ int mcq_raceline_device(mcq_handle* h, int batch, int nmax, const int* n_in, con
                         const double* alpha, double stepsize, int mmax, double* raceline_out, double* psi_out,
                         double* kappa_out, double* el_lengths_out, int* m_out, int* status_out);
 
+/* The same with OPEN chains among the rows: the step between mcq_solve_batch_ends and mcq_vel_profile_device_forms (closed = 0).
+ * closed [batch] (DEVICE): an entry != 0 is a ring row and returns the bits of mcq_raceline_device; NULL: every row is a chain.
+ * psi [batch][2] (DEVICE) = (psi_s, psi_e), read for chain rows only; it must be non-NULL if any row is a chain (with psi == NULL the
+ * flags are read back once, blocking, and a chain row is MCQ_E_ARG).  A chain row of n >= 2 waypoints:
+ *   points    P_i = p_i + alpha_i n_i, i = 0 .. n-1; n - 1 segments, D_i = P_(i+1) - P_i;
+ *   spline    tph.calc_splines(path, psi_s, psi_e, use_dist_scaling=False) with el_lengths = None: unit scalings, and the heading rows
+ *             carry the UNIT vectors h = (cos(psi + pi/2), sin(psi + pi/2)) times MCQ_HEADING_SCALE -- the rows the chain solve linearised, so
+ *             the raceline is the curve whose curvature the QP minimised:
+ *               2 c_0 + c_1 = 3 (D_0 - h_s),  c_(i-1) + 4 c_i + c_(i+1) = 3 (D_i - D_(i-1)),  c_(n-2) + 2 c_(n-1) = 3 (h_e - D_(n-2)),
+ *               b_i = D_i - (2 c_i + c_(i+1)) / 3,  d_i = (c_(i+1) - c_i) / 3  (i <= n-2);
+ *   lengths   tph.calc_spline_lengths over the n - 1 segments (15 points, 14 chords), running sum in numpy.cumsum's order: total;
+ *   stations  m = ceil(total / stepsize) + 1 points, all kept (tph.interp_splines, incl_last_point = True): station j <= m-2 at
+ *             q_j = j * total / (m - 1), station m-1 at t = 1 of segment n-2 (the last raceline point; derivatives taken there);
+ *   outputs   raceline_out / psi_out / kappa_out hold m entries; el_lengths_out [j] = q_(j+1) - q_j (j <= m-3), [m-2] = total - q_(m-2),
+ *             [m-1] = 0 (written; mcq_vel_profile_device_forms with closed = 0 reads the first m - 1); m_out = m.
+ * status_out: MCQ_BAD_INPUT for a chain of n < 2 (or more than nmax) waypoints, a non-finite psi_s / psi_e, or m > mmax (m_out then
+ * reports the m needed, as for rings); ring rows as in mcq_raceline_device.  nmax >= 2.  Asynchronous on the handle's stream. */
+int mcq_raceline_device_ends(mcq_handle* h, int batch, int nmax, const int* n_in, const double* reftrack, const double* normvec,
+                             const double* alpha, const int* closed, const double* psi, double stepsize, int mmax,
+                             double* raceline_out, double* psi_out, double* kappa_out, double* el_lengths_out, int* m_out,
+                             int* status_out);
+
 /* Host-buffer entry for a UNIFORM batch (every track n waypoints): reftrack [batch][n][4], normvec [batch][n][2] or NULL,
  * scaling [batch][n] or NULL in host memory, results to host memory.  One asynchronous copy per array straight from / to the
  * caller's buffers -- no packing pass; buffers from mcq_host_alloc (pinned) are copied at PCIe speed, pageable ones go through
