@@ -84,6 +84,8 @@ struct mcq_handle {
     hipEvent_t comm_ready = nullptr, comm_t0[4] = {nullptr, nullptr, nullptr, nullptr}, comm_done[4] = {nullptr, nullptr, nullptr, nullptr};
     unsigned comm_seq = 0;              // gathers enqueued so far (event ring index)
     size_t vel_scratch_bytes = 0;
+    double* bound_scratch = nullptr;    // mcq_bound_dists_device: samples [tracks][2][nbmax][2], raw boundaries, running sums, side statuses
+    size_t bound_scratch_bytes = 0;
     long long gi_bytes = 0;             // ws[0]'s full slots
     size_t gi_none_nmax = 0;           // > 0: no full slot could be had for rings of this many waypoints (beyond the byte cap, or hipMalloc said no) -- not tried again
     double* gis = nullptr;              // SMALL slots (MCQ_ALG_GI: one per resident workgroup): gis_slots x MCQ_GI_SLOT_DOUBLES(gis_nmax, gi_small_qcap(gis_nmax))
@@ -249,6 +251,7 @@ extern "C" void mcq_destroy(mcq_handle* h)
     if (h->cs_in) (void)hipStreamDestroy(h->cs_in);
     if (h->cs_out) (void)hipStreamDestroy(h->cs_out);
     (void)hipFree(h->vel_scratch);
+    (void)hipFree(h->bound_scratch);
     if (h->pin) (void)hipHostFree(h->pin);
     for (int k = 0; k < 5; ++k) if (h->ev[k]) (void)hipEventDestroy(h->ev[k]);
     for (int k = 0; k < 2; ++k) if (h->ev_span[k]) (void)hipEventDestroy(h->ev_span[k]);
@@ -905,6 +908,99 @@ extern "C" int mcq_raceline_device_ends(mcq_handle* h, int batch, int nmax, cons
     Q.vec = h->ws[0].vec;
     E.closed = closed; E.psi = psi;
     hipLaunchKernelGGL(mcq_raceline_ends_kernel, dim3(batch), dim3(256), 0, h->ws[0].stream, E);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---- the finished trajectory and check_traj's verdicts (include/mcq.h) ----------------------------------------------------------------
+extern "C" int mcq_trajectory_device(mcq_handle* h, int batch, int m, int mmax, const int* m_of_track, const int* track_of,
+                                     const double* raceline, const double* psi, const double* kappa, const double* el_lengths,
+                                     const double* vx, int closed, const double* drag_coeff, const double* m_veh, const double* v_max,
+                                     const double* ggv, int n_ggv, const double* ax_max_machines, int n_machines, double curvlim,
+                                     double* traj_out, double* t_out, double* length_out, double* limits_out, int* flags_out)
+{
+    if (!h || batch <= 0 || mmax < 2 || (!m_of_track && (m < 2 || m > mmax)) || !raceline || !psi || !kappa || !el_lengths || !vx ||
+        !drag_coeff || !m_veh || !v_max || (ggv && n_ggv < 1) || (ax_max_machines && n_machines < 1) || curvlim != curvlim ||
+        !length_out || !limits_out || !flags_out) {
+        g_err = "mcq_trajectory_device: bad argument";
+        return MCQ_E_ARG;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    McqTraj T;
+    memset(&T, 0, sizeof(T));
+    T.batch = batch; T.m = m_of_track ? 0 : m; T.mmax = mmax;
+    T.m_of_track = m_of_track; T.track_of = track_of;
+    T.xy = raceline; T.psi = psi; T.kappa = kappa; T.el = el_lengths; T.vx = vx;
+    T.closed = closed != 0;
+    T.drag = drag_coeff; T.mass = m_veh; T.vmax = v_max;
+    T.ggv = ggv; T.ng = ggv ? n_ggv : 0; T.axm = ax_max_machines; T.nam = ax_max_machines ? n_machines : 0;
+    T.curvlim = curvlim;
+    T.traj = traj_out; T.t_out = t_out; T.length = length_out; T.limits = limits_out; T.flags = flags_out;
+    hipLaunchKernelGGL(mcq_trajectory_kernel, dim3(batch), dim3(64), 0, h->ws[0].stream, T);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// bytes the boundary scratch may take ($MCQ_BOUND_BYTES, default 1 GiB)
+static size_t bound_byte_cap()
+{
+    const char* e = getenv("MCQ_BOUND_BYTES");
+    const double v = e ? atof(e) : 0.0;
+    return v >= 1.0 ? (size_t)v : ((size_t)1 << 30);
+}
+
+extern "C" int mcq_bound_dists_device(mcq_handle* h, int tracks, int nmax, const int* n_list, const double* reftrack,
+                                      const double* normvec, int mmax, const int* m_list, const double* raceline, const double* psi,
+                                      double length_veh, double width_veh, const double* length_veh_list, const double* width_veh_list,
+                                      double stepsize_bound, int mode, double* min_dists_out, double* min_dist_out, int* nb_out,
+                                      double* bound_out, int* status_out)
+{
+    const bool len_ok = length_veh_list || (length_veh >= 0.0 && length_veh <= 1.7e308);
+    const bool wid_ok = width_veh_list || (width_veh >= 0.0 && width_veh <= 1.7e308);
+    if (!h || tracks <= 0 || nmax < 3 || mmax < 1 || !reftrack || !normvec || !raceline || !psi || !len_ok || !wid_ok ||
+        !(stepsize_bound > 0.0) || !(stepsize_bound <= 1.7e308) || (mode != MCQ_BOUNDS_ALL && mode != MCQ_BOUNDS_FIRST_ROW) ||
+        !min_dists_out || !min_dist_out || !nb_out || !status_out) {
+        g_err = "mcq_bound_dists_device: bad argument";
+        return MCQ_E_ARG;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    // scratch, in doubles: samples [tracks][2][nbmax][2] | raw boundaries [tracks][2][nmax][2] | running sums [tracks][2][nmax + 1] | side statuses
+    const size_t sides = 2 * (size_t)tracks;
+    const size_t fixed = sides * (size_t)nmax * 2 + sides * ((size_t)nmax + 1) + (size_t)tracks;
+    const size_t cap = bound_byte_cap() / sizeof(double);
+    if (cap < fixed + sides * 2) {
+        g_err = "mcq_bound_dists_device: the boundary scratch would exceed $MCQ_BOUND_BYTES";
+        return MCQ_E_TOO_LARGE;
+    }
+    size_t nbmax = (cap - fixed) / (sides * 2);
+    if (nbmax > MCQ_BOUND_NB_MAX) nbmax = MCQ_BOUND_NB_MAX;
+    const size_t need = (sides * nbmax * 2 + fixed) * sizeof(double);
+    if (need > h->bound_scratch_bytes) {
+        HIP_TRY(hipStreamSynchronize(h->ws[0].stream));
+        (void)hipFree(h->bound_scratch);
+        h->bound_scratch = nullptr;
+        h->bound_scratch_bytes = 0;
+        HIP_TRY(hipMalloc((void**)&h->bound_scratch, need));
+        h->bound_scratch_bytes = need;
+    }
+    McqBound P;
+    memset(&P, 0, sizeof(P));
+    P.tracks = tracks; P.nmax = nmax; P.mmax = mmax; P.nbmax = (int)nbmax; P.mode = mode;
+    P.n_list = n_list; P.m_list = m_list; P.ref = reftrack; P.nv = normvec; P.xy = raceline; P.psi = psi;
+    P.length_veh = length_veh; P.width_veh = width_veh; P.length_list = length_veh_list; P.width_list = width_veh_list;
+    P.step = stepsize_bound;
+    P.samples = h->bound_scratch;
+    P.pts = P.samples + sides * nbmax * 2;
+    P.cum = P.pts + sides * (size_t)nmax * 2;
+    P.side_status = (int*)(P.cum + sides * ((size_t)nmax + 1));
+    P.min_dists = min_dists_out; P.min_dist = min_dist_out; P.nb_out = nb_out; P.bound_out = bound_out; P.status = status_out;
+    hipStream_t st = h->ws[0].stream;
+    hipLaunchKernelGGL(mcq_bound_points_kernel, dim3(2 * tracks), dim3(256), 0, st, P);
+    HIP_TRY(hipGetLastError());
+    const int block = 256 * MCQ_BD_S;
+    hipLaunchKernelGGL(mcq_bound_dists_kernel, dim3((mmax + block - 1) / block, tracks), dim3(256), 0, st, P);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(mcq_bound_min_kernel, dim3(tracks), dim3(256), 0, st, P);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -267,3 +267,65 @@ struct McqVelForms {
 __global__ void mcq_vel_profile_open_kernel(McqVelForms F);
 __global__ void mcq_vel_profile_locgg_kernel(McqVelForms F);
 __global__ void mcq_vel_profile_open_locgg_kernel(McqVelForms F);
+
+/* ---- tph.calc_ax_profile / calc_t_profile, the trajectory rows [s, x, y, psi, kappa, vx, ax] and the limit quantities of check_traj
+ *      [REF main_globaltraj.py:412-421, 502-534; helper_funcs_glob/src/check_traj.py] of a batch of variants (mcq_trajectory_device).
+ *      One wave per variant: the lanes form the elements' lengths, times and accelerations coalesced, lane 0 sums s and t in the order
+ *      of numpy.cumsum / of the velocity kernel's lap-time loop, the limits are wave reductions of exact maxima / minima. ---- */
+struct McqTraj {
+    int batch, m, mmax;
+    const int* m_of_track;   // [tracks] stations of each row, or nullptr (all rows: m)
+    const int* track_of;     // [batch] row a variant uses, or nullptr (row = variant)
+    const double* xy;        // [tracks][mmax][2]
+    const double* psi;       // [tracks][mmax]
+    const double* kappa;     // [tracks][mmax]
+    const double* el;        // [tracks][mmax] (closed: m elements; unclosed: m - 1)
+    const double* vx;        // [batch][mmax]
+    int closed;
+    const double* drag;      // [batch]
+    const double* mass;      // [batch]
+    const double* vmax;      // [batch]
+    const double* ggv;       // [batch][ng][3] or nullptr
+    int ng;
+    const double* axm;       // [batch][nam][2] or nullptr
+    int nam;
+    double curvlim;
+    double* traj;            // [batch][mmax][7] or nullptr
+    double* t_out;           // [batch][mmax + 1] or nullptr
+    double* length;          // [batch]
+    double* limits;          // [batch][MCQ_TRAJ_NLIM]
+    int* flags;              // [batch]
+};
+__global__ void mcq_trajectory_kernel(McqTraj T);
+
+/* ---- check_traj's first block (mcq_bound_dists_device): the two boundaries p + n w_r / p - n w_l, re-sampled by interp_track's rule
+ *      (mcq_bound_points_kernel, a workgroup per track and side), the minimum distance of the vehicle's four corners to every sample per
+ *      station (mcq_bound_dists_kernel, grid (station blocks, tracks): the all-pairs hot path) and the minimum over a track's stations with
+ *      the track's status (mcq_bound_min_kernel, a workgroup per track). ---- */
+#define MCQ_BD_S 2          /* stations per thread of mcq_bound_dists_kernel: a station block is MCQ_BD_S x 256 stations */
+#define MCQ_BD_TILE 256     /* boundary samples per LDS tile */
+struct McqBound {
+    int tracks, nmax, mmax, nbmax, mode;
+    const int* n_list;       // [tracks] or nullptr (all nmax)
+    const int* m_list;       // [tracks] or nullptr (all mmax)
+    const double* ref;       // [tracks][nmax][4]
+    const double* nv;        // [tracks][nmax][2]
+    const double* xy;        // [tracks][mmax][2]
+    const double* psi;       // [tracks][mmax]
+    double length_veh, width_veh;
+    const double* length_list;  // [tracks] or nullptr
+    const double* width_list;   // [tracks] or nullptr
+    double step;
+    double* samples;         // scratch [tracks][2][nbmax][2]
+    double* pts;             // scratch [tracks][2][nmax][2]: the raw boundaries
+    double* cum;             // scratch [tracks][2][nmax + 1]: running sums of their element lengths
+    int* side_status;        // scratch [tracks][2]
+    double* min_dists;       // [tracks][mmax]
+    double* min_dist;        // [tracks]
+    int* nb_out;             // [tracks][2]
+    double* bound_out;       // [tracks][2][nmax][2] or nullptr
+    int* status;             // [tracks]
+};
+__global__ void mcq_bound_points_kernel(McqBound P);
+__global__ void mcq_bound_dists_kernel(McqBound P);
+__global__ void mcq_bound_min_kernel(McqBound P);

@@ -3304,3 +3304,416 @@ __global__ void __launch_bounds__(64) mcq_widen_rows_kernel(const float* rows, c
     }
 }
 
+
+// ---- the finished trajectory (mcq_trajectory_device): tph.calc_ax_profile, the time profile in its stable form, the rows
+//      [s, x, y, psi, kappa, vx, ax] and the limit quantities and verdicts of check_traj [REF main_globaltraj.py:412-421, 502-534;
+//      helper_funcs_glob/src/check_traj.py].  One wave per variant, a chunk of 256 stations at a time: the lanes form l, 2 l / (v_a + v_b) and
+//      ax coalesced, lane 0 runs the two sums over the chunk in LDS -- s in numpy.cumsum's order, t in the order of vel_profile_body's lap-time
+//      loop (the same expression, so the last t is that kernel's lap time bit for bit) --, the lanes write the rows.  Maxima and minima are
+//      exact, so the wave reduction's order does not matter. ----
+#define MCQ_TJ_CH 256
+__global__ void __launch_bounds__(64) mcq_trajectory_kernel(McqTraj T)
+{
+    __shared__ double s_dt[MCQ_TJ_CH], s_l[MCQ_TJ_CH];
+    __shared__ double s_ct, s_cs;
+    const int lane = threadIdx.x, v = blockIdx.x;
+    const size_t mm = (size_t)T.mmax;
+    const int trk = T.track_of ? T.track_of[v] : v;
+    const int m = T.m_of_track ? T.m_of_track[trk] : T.m;
+    const gdouble* vx = (const gdouble*)(T.vx + (size_t)v * mm);
+    gdouble* traj = T.traj ? (gdouble*)(T.traj + (size_t)v * mm * MCQ_TRAJ_COLS) : nullptr;
+    gdouble* tout = T.t_out ? (gdouble*)(T.t_out + (size_t)v * (mm + 1)) : nullptr;
+    gdouble* lim = (gdouble*)(T.limits + (size_t)v * MCQ_TRAJ_NLIM);
+    bool bad = m < 2 || m > T.mmax;
+    if (!bad) {
+        int has_nan = 0;
+        for (int i = lane; i < m; i += 64) {
+            const double a = vx[i];
+            if (a != a) has_nan = 1;
+        }
+        bad = __ballot(has_nan) != 0;
+    }
+    if (bad) {      // the profile's NaN rule: never stale buffer contents
+        if (traj) for (size_t i = lane; i < mm * MCQ_TRAJ_COLS; i += 64) traj[i] = NAN;
+        if (tout) for (size_t i = lane; i < mm + 1; i += 64) tout[i] = NAN;
+        if (lane < MCQ_TRAJ_NLIM) lim[lane] = NAN;
+        if (lane == 0) {
+            ((gdouble*)T.length)[v] = NAN;
+            ((gint*)T.flags)[v] = -1;
+        }
+        return;
+    }
+    const size_t row = (size_t)trk * mm;
+    const gdouble* xy = (const gdouble*)(T.xy + row * 2);
+    const gdouble* psi = (const gdouble*)(T.psi + row);
+    const gdouble* kap = (const gdouble*)(T.kappa + row);
+    const gdouble* el = (const gdouble*)(T.el + row);
+    const int ne = T.closed ? m : m - 1;
+    const double v0 = vx[0], dr = T.drag[v], ms = T.mass[v];
+    if (lane == 0) {
+        s_ct = 0.0;
+        s_cs = 0.0;
+        if (tout) tout[0] = 0.0;
+    }
+    double q_kap = -(double)INFINITY, q_ay = -(double)INFINITY, q_axp = -(double)INFINITY, q_axn = (double)INFINITY,
+           q_tot = -(double)INFINITY, q_vx = -(double)INFINITY;
+    for (int base = 0; base < m; base += MCQ_TJ_CH) {
+        double va_[MCQ_TJ_CH / 64], ax_[MCQ_TJ_CH / 64];
+        __syncthreads();
+        for (int q = 0; q < MCQ_TJ_CH / 64; ++q) {
+            const int j = q * 64 + lane, i = base + j;
+            va_[q] = 0.0;
+            ax_[q] = 0.0;
+            if (i < m) {
+                const double va = vx[i];
+                double l = 0.0, dt = 0.0;
+                if (i < ne) {
+                    const double vb = i + 1 < m ? vx[i + 1] : v0;
+                    l = el[i];
+                    dt = 2.0 * l / (va + vb);
+                    ax_[q] = (vb * vb - va * va) / (2.0 * l);
+                }
+                va_[q] = va;
+                s_l[j] = l;
+                s_dt[j] = dt;
+            }
+        }
+        __syncthreads();
+        if (lane == 0) {
+            double t = s_ct, s = s_cs;
+            const int cnt = m - base < MCQ_TJ_CH ? m - base : MCQ_TJ_CH;
+            int k = 0;
+            for (; k + 8 <= cnt; k += 8) {      // eight at a time through registers: the LDS reads do not wait for the sums
+                double l_[8], d_[8];
+                #pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    l_[u] = s_l[k + u];
+                    d_[u] = s_dt[k + u];
+                }
+                #pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    const double l = l_[u];
+                    l_[u] = s;
+                    s += l;
+                    t += d_[u];
+                    d_[u] = t;
+                }
+                #pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    s_l[k + u] = l_[u];
+                    s_dt[k + u] = d_[u];
+                }
+            }
+            for (; k < cnt; ++k) {
+                const double l = s_l[k];
+                s_l[k] = s;         // station k's s: the sum of the elements before it
+                s += l;
+                t += s_dt[k];
+                s_dt[k] = t;        // the time at the element's end
+            }
+            s_ct = t;
+            s_cs = s;
+        }
+        __syncthreads();
+        for (int q = 0; q < MCQ_TJ_CH / 64; ++q) {
+            const int j = q * 64 + lane, i = base + j;
+            if (i >= m) continue;
+            const double va = va_[q], ax = ax_[q], k = kap[i];
+            if (traj) {
+                gdouble* r = traj + (size_t)i * MCQ_TRAJ_COLS;
+                r[0] = s_l[j];
+                r[1] = xy[2 * (size_t)i];
+                r[2] = xy[2 * (size_t)i + 1];
+                r[3] = psi[i];
+                r[4] = k;
+                r[5] = va;
+                r[6] = ax;
+            }
+            if (tout && i < ne) tout[i + 1] = s_dt[j];
+            const double v2 = va * va;
+            const double ay = k != 0.0 ? v2 / fabs(1.0 / k) : 0.0;
+            const double axw = ax + v2 * dr / ms;
+            const double tot = sqrt(axw * axw + ay * ay);
+            q_kap = fmax(q_kap, fabs(k));
+            q_ay = fmax(q_ay, ay);
+            q_axp = fmax(q_axp, axw);
+            q_axn = fmin(q_axn, axw);
+            q_tot = fmax(q_tot, tot);
+            q_vx = fmax(q_vx, va);
+        }
+    }
+    // rows and times behind the last: written, never stale
+    if (traj) for (size_t i = (size_t)m * MCQ_TRAJ_COLS + lane; i < mm * MCQ_TRAJ_COLS; i += 64) traj[i] = NAN;
+    if (tout) for (size_t i = (size_t)ne + 1 + lane; i < mm + 1; i += 64) tout[i] = NAN;
+    for (int d = 32; d >= 1; d >>= 1) {
+        q_kap = fmax(q_kap, __shfl_xor(q_kap, d));
+        q_ay = fmax(q_ay, __shfl_xor(q_ay, d));
+        q_axp = fmax(q_axp, __shfl_xor(q_axp, d));
+        q_axn = fmin(q_axn, __shfl_xor(q_axn, d));
+        q_tot = fmax(q_tot, __shfl_xor(q_tot, d));
+        q_vx = fmax(q_vx, __shfl_xor(q_vx, d));
+    }
+    __syncthreads();
+    if (lane == 0) {
+        lim[0] = q_kap; lim[1] = q_ay; lim[2] = q_axp; lim[3] = q_axn; lim[4] = q_tot; lim[5] = q_vx;
+        ((gdouble*)T.length)[v] = s_cs;
+        int f = 0;
+        const double mg = MCQ_CHECK_ACC_MARGIN;
+        if (q_kap > T.curvlim) f |= MCQ_CHK_KAPPA;
+        if (T.ggv) {
+            const gdouble* g = (const gdouble*)(T.ggv + (size_t)v * T.ng * 3);
+            double ax_hi = g[1], ay_hi = g[2], nax_lo = -g[1];
+            for (int k = 1; k < T.ng; ++k) {
+                ax_hi = fmax(ax_hi, g[(size_t)k * 3 + 1]);
+                ay_hi = fmax(ay_hi, g[(size_t)k * 3 + 2]);
+                nax_lo = fmin(nax_lo, -g[(size_t)k * 3 + 1]);
+            }
+            if (q_ay > ay_hi + mg) f |= MCQ_CHK_AY;
+            if (q_axp > ax_hi + mg) f |= MCQ_CHK_AX_POS;
+            if (q_axn < nax_lo - mg) f |= MCQ_CHK_AX_NEG;
+            if (q_tot > fmax(ax_hi, ay_hi) + mg) f |= MCQ_CHK_A_TOT;
+        }
+        if (T.axm) {
+            const gdouble* a = (const gdouble*)(T.axm + (size_t)v * T.nam * 2);
+            double hi = a[1];
+            for (int k = 1; k < T.nam; ++k) hi = fmax(hi, a[(size_t)k * 2 + 1]);
+            if (q_axp > hi + mg) f |= MCQ_CHK_MACHINES;
+        }
+        if (q_vx > T.vmax[v] + mg) f |= MCQ_CHK_V_MAX;
+        ((gint*)T.flags)[v] = f;
+    }
+}
+
+// ---- check_traj's first block (mcq_bound_dists_device) [REF helper_funcs_glob/src/check_traj.py:47-70, interp_track.py, calc_min_bound_dists.py].
+//      mcq_bound_points_kernel: a workgroup per track and side (blockIdx.x = 2 track + side, side 0 = right).  The raw boundary into the scratch
+//      (and bound_out); element lengths of the closed polyline, summed 256 at a time through LDS by thread 0 in numpy.cumsum's order;
+//      nb = ceil(total / step) samples kept of numpy.linspace(0, total, nb + 1); per sample a binary search for its element and numpy.interp's
+//      slope * (x - xp_j) + fp_j in each coordinate. ----
+typedef __attribute__((address_space(1))) d2 gd2;
+__device__ __forceinline__ bool bd_finite(double a) { return fabs(a) < (double)INFINITY; }      // (false for a NaN)
+
+__global__ void __launch_bounds__(MCQ_NT) mcq_bound_points_kernel(McqBound P)
+{
+    __shared__ double s_el[MCQ_NT];
+    __shared__ double s_carry;
+    __shared__ int s_bad;
+    const int tid = threadIdx.x, ts = blockIdx.x, t = ts >> 1, side = ts & 1;
+    const size_t nm = (size_t)P.nmax;
+    const int n = P.n_list ? P.n_list[t] : P.nmax;
+    const int m = P.m_list ? P.m_list[t] : P.mmax;
+    gint* st = (gint*)(P.side_status + ts);
+    gint* nbo = (gint*)(P.nb_out + ts);
+    gdouble* bout = P.bound_out ? (gdouble*)(P.bound_out + (size_t)ts * nm * 2) : nullptr;
+    if (tid == 0) {
+        s_bad = 0;
+        s_carry = 0.0;
+    }
+    __syncthreads();
+    if (n < 3 || n > P.nmax || m < 1 || m > P.mmax) {
+        if (bout) for (size_t i = tid; i < nm * 2; i += MCQ_NT) bout[i] = NAN;
+        if (tid == 0) {
+            *st = MCQ_BAD_INPUT;
+            *nbo = 0;
+        }
+        return;
+    }
+    const gdouble* ref = (const gdouble*)(P.ref + (size_t)t * nm * 4);
+    const gdouble* nv = (const gdouble*)(P.nv + (size_t)t * nm * 2);
+    const gdouble* xy = (const gdouble*)(P.xy + (size_t)t * P.mmax * 2);
+    const gdouble* psi = (const gdouble*)(P.psi + (size_t)t * P.mmax);
+    gdouble* pts = (gdouble*)(P.pts + (size_t)ts * nm * 2);
+    gdouble* cum = (gdouble*)(P.cum + (size_t)ts * (nm + 1));
+    gdouble* smp = (gdouble*)(P.samples + (size_t)ts * P.nbmax * 2);
+    int bad = 0;
+    for (int i = tid; i < n; i += MCQ_NT) {
+        const double w = ref[4 * (size_t)i + 2 + side];
+        const double sw = side ? -w : w;
+        const double bx = ref[4 * (size_t)i] + nv[2 * (size_t)i] * sw, by = ref[4 * (size_t)i + 1] + nv[2 * (size_t)i + 1] * sw;
+        if (!bd_finite(bx) || !bd_finite(by)) bad = 1;
+        pts[2 * (size_t)i] = bx;
+        pts[2 * (size_t)i + 1] = by;
+        if (bout) {
+            bout[2 * (size_t)i] = bx;
+            bout[2 * (size_t)i + 1] = by;
+        }
+    }
+    if (bout) for (size_t i = (size_t)n * 2 + tid; i < nm * 2; i += MCQ_NT) bout[i] = NAN;
+    for (int i = tid; i < m; i += MCQ_NT)
+        if (!bd_finite(xy[2 * (size_t)i]) || !bd_finite(xy[2 * (size_t)i + 1]) || !bd_finite(psi[i])) bad = 1;
+    if (tid == 0) {
+        if (P.length_list && !bd_finite(P.length_list[t])) bad = 1;
+        if (P.width_list && !bd_finite(P.width_list[t])) bad = 1;
+        cum[0] = 0.0;
+    }
+    __syncthreads();        // the boundary points are in the scratch for every thread of the workgroup
+    for (int base = 0; base < n; base += MCQ_NT) {
+        const int i = base + tid;
+        if (i < n) {
+            const int j = i + 1 < n ? i + 1 : 0;
+            const double dx = pts[2 * (size_t)j] - pts[2 * (size_t)i], dy = pts[2 * (size_t)j + 1] - pts[2 * (size_t)i + 1];
+            const double e = sqrt(dx * dx + dy * dy);
+            if (!(e > 0.0)) bad = 1;       // numpy.interp has no answer on an element of length 0
+            s_el[tid] = e;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            double c = s_carry;
+            const int cnt = n - base < MCQ_NT ? n - base : MCQ_NT;
+            for (int k = 0; k < cnt; ++k) {
+                c += s_el[k];
+                s_el[k] = c;
+            }
+            s_carry = c;
+        }
+        __syncthreads();
+        if (i < n) cum[(size_t)i + 1] = s_el[tid];
+        __syncthreads();
+    }
+    if (bad) s_bad = 1;
+    __syncthreads();
+    const double total = s_carry;
+    const double cnt = ceil(total / P.step);
+    if (s_bad || !bd_finite(cnt) || !(cnt >= 1.0) || cnt > (double)P.nbmax) {
+        if (tid == 0) {
+            *st = MCQ_BAD_INPUT;
+            *nbo = (!s_bad && cnt >= 1.0 && cnt < 2147483647.0) ? (int)cnt : 0;       // the samples a boundary would need
+        }
+        return;
+    }
+    const int nb = (int)cnt;
+    const double dl = total / (double)nb;           // numpy.linspace's step: (stop - start) / (num - 1)
+    for (int j = tid; j < nb; j += MCQ_NT) {
+        const double x = (double)j * dl;
+        int lo = 0, hi = n - 1;                     // the last k in [0, n - 1] with cum[k] <= x
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (cum[mid] <= x) lo = mid;
+            else hi = mid - 1;
+        }
+        const int k1 = lo + 1 < n ? lo + 1 : 0;
+        const double x0 = cum[lo], den = cum[(size_t)lo + 1] - x0;
+        const double fx = pts[2 * (size_t)lo], fy = pts[2 * (size_t)lo + 1];
+        const double sx = (pts[2 * (size_t)k1] - fx) / den, sy = (pts[2 * (size_t)k1 + 1] - fy) / den;
+        smp[2 * (size_t)j] = sx * (x - x0) + fx;
+        smp[2 * (size_t)j + 1] = sy * (x - x0) + fy;
+    }
+    if (tid == 0) {
+        *st = MCQ_OK;
+        *nbo = nb;
+    }
+}
+
+// mcq_bound_dists_kernel: the all-pairs hot path.  Grid (station blocks, tracks); a station block is MCQ_BD_S x 256 stations, a thread keeping
+// the 4 corners of its MCQ_BD_S stations in registers.  The samples of both boundaries pass through LDS in tiles of MCQ_BD_TILE: every thread
+// loads one sample (16 bytes, contiguous over the workgroup) of the NEXT tile before it consumes the current one and parks it in the other
+// buffer afterwards -- one barrier per tile.  In the inner loop every lane reads the same sample (a broadcast read); per pair: two
+// subtractions, a multiply, a fused multiply-add, a minimum.  The root is taken once per station over the minimum of the squares (sqrt is
+// monotone and correctly rounded), so the result does not depend on tile, grid or order.  Tails (nb % tile, m % block) by predication: no
+// sample behind nb is read.
+__global__ void __launch_bounds__(MCQ_NT) mcq_bound_dists_kernel(McqBound P)
+{
+    __shared__ d2 s_tile[2][MCQ_BD_TILE];
+    const int tid = threadIdx.x, t = blockIdx.y;
+    const int m = P.m_list ? P.m_list[t] : P.mmax;
+    const int i0 = blockIdx.x * (MCQ_NT * MCQ_BD_S);
+    gdouble* out = (gdouble*)(P.min_dists + (size_t)t * P.mmax);
+    const bool ok = P.side_status[2 * t] == MCQ_OK && P.side_status[2 * t + 1] == MCQ_OK;
+    if (!ok || i0 >= m) {       // (uniform over the workgroup)
+        for (int s = 0; s < MCQ_BD_S; ++s) {
+            const int i = i0 + s * MCQ_NT + tid;
+            if (i < P.mmax) out[i] = NAN;
+        }
+        return;
+    }
+    const int nb0 = P.mode == MCQ_BOUNDS_FIRST_ROW ? 1 : P.nb_out[2 * t], nb1 = P.mode == MCQ_BOUNDS_FIRST_ROW ? 1 : P.nb_out[2 * t + 1];
+    const double hl = 0.5 * (P.length_list ? P.length_list[t] : P.length_veh), hw = 0.5 * (P.width_list ? P.width_list[t] : P.width_veh);
+    const gdouble* xy = (const gdouble*)(P.xy + (size_t)t * P.mmax * 2);
+    const gdouble* psi = (const gdouble*)(P.psi + (size_t)t * P.mmax);
+    double cx[MCQ_BD_S][4], cy[MCQ_BD_S][4], best[MCQ_BD_S];
+    for (int s = 0; s < MCQ_BD_S; ++s) {
+        const int i = i0 + s * MCQ_NT + tid;
+        const bool valid = i < m;
+        const double x = valid ? xy[2 * (size_t)i] : 0.0, y = valid ? xy[2 * (size_t)i + 1] : 0.0, a = valid ? psi[i] : 0.0;
+        const double c = cos(a), sn = sin(a);
+        // [cos -sin; sin cos] (ox, oy): front left (-w/2, l/2), front right (w/2, l/2), rear left (-w/2, -l/2), rear right (w/2, -l/2)
+        for (int q = 0; q < 4; ++q) {
+            const double ox = (q & 1) ? hw : -hw, oy = (q & 2) ? -hl : hl;
+            cx[s][q] = x + (c * ox - sn * oy);
+            cy[s][q] = y + (sn * ox + c * oy);
+        }
+        best[s] = (double)INFINITY;
+    }
+    const int tiles0 = (nb0 + MCQ_BD_TILE - 1) / MCQ_BD_TILE, tiles1 = (nb1 + MCQ_BD_TILE - 1) / MCQ_BD_TILE;
+    const int ntiles = tiles0 + tiles1;
+    const d2 zero = {0.0, 0.0};
+    // tile k: side, first sample, samples
+    #define BD_TILE_OF(k, side, first, cnt)                                        \
+        const int side = (k) >= tiles0 ? 1 : 0;                                    \
+        const int first = ((k) - (side ? tiles0 : 0)) * MCQ_BD_TILE;               \
+        const int cnt = (side ? nb1 : nb0) - first < MCQ_BD_TILE ? (side ? nb1 : nb0) - first : MCQ_BD_TILE;
+    d2 nxt = zero;
+    {
+        BD_TILE_OF(0, sd, first, cnt)
+        if (tid < cnt) nxt = *(const gd2*)(P.samples + ((size_t)(2 * t + sd) * P.nbmax + first + tid) * 2);
+        s_tile[0][tid] = nxt;
+    }
+    __syncthreads();
+    for (int k = 0; k < ntiles; ++k) {
+        if (k + 1 < ntiles) {       // the next tile's load is in flight while this one is consumed
+            BD_TILE_OF(k + 1, sd, first, cnt)
+            nxt = zero;
+            if (tid < cnt) nxt = *(const gd2*)(P.samples + ((size_t)(2 * t + sd) * P.nbmax + first + tid) * 2);
+        }
+        BD_TILE_OF(k, sd_, first_, cnt)
+        (void)sd_; (void)first_;
+        const d2* tile = s_tile[k & 1];
+        for (int j = 0; j < cnt; ++j) {
+            const d2 b = tile[j];
+            #pragma unroll
+            for (int s = 0; s < MCQ_BD_S; ++s)
+                #pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const double dx = cx[s][q] - b[0], dy = cy[s][q] - b[1];
+                    best[s] = fmin(best[s], fma(dy, dy, dx * dx));
+                }
+        }
+        if (k + 1 < ntiles) s_tile[(k + 1) & 1][tid] = nxt;
+        __syncthreads();
+    }
+    #undef BD_TILE_OF
+    for (int s = 0; s < MCQ_BD_S; ++s) {
+        const int i = i0 + s * MCQ_NT + tid;
+        if (i < m) out[i] = sqrt(best[s]);
+        else if (i < P.mmax) out[i] = NAN;
+    }
+}
+
+// mcq_bound_min_kernel: the second pass -- a workgroup per track: the track's status from its two sides, the minimum over its m stations (a
+// tree over exact minima: no order to fix).
+__global__ void __launch_bounds__(MCQ_NT) mcq_bound_min_kernel(McqBound P)
+{
+    __shared__ double s_min[MCQ_NT];
+    const int tid = threadIdx.x, t = blockIdx.x;
+    const int m = P.m_list ? P.m_list[t] : P.mmax;
+    const bool ok = P.side_status[2 * t] == MCQ_OK && P.side_status[2 * t + 1] == MCQ_OK;
+    if (!ok) {
+        if (tid == 0) {
+            ((gint*)P.status)[t] = MCQ_BAD_INPUT;
+            ((gdouble*)P.min_dist)[t] = NAN;
+        }
+        return;
+    }
+    const gdouble* md = (const gdouble*)(P.min_dists + (size_t)t * P.mmax);
+    double v = (double)INFINITY;
+    for (int i = tid; i < m; i += MCQ_NT) v = fmin(v, md[i]);
+    s_min[tid] = v;
+    __syncthreads();
+    for (int d = MCQ_NT / 2; d >= 1; d >>= 1) {
+        if (tid < d) s_min[tid] = fmin(s_min[tid], s_min[tid + d]);
+        __syncthreads();
+    }
+    if (tid == 0) {
+        ((gint*)P.status)[t] = MCQ_OK;
+        ((gdouble*)P.min_dist)[t] = s_min[0];
+    }
+}

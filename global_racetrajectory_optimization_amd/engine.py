@@ -118,7 +118,16 @@ EXPORTED_SYMBOLS = ("mcq_create", "mcq_destroy", "mcq_last_error", "mcq_default_
                     "mcq_last_timing", "mcq_timing_begin", "mcq_timing_end", "mcq_workspace_bytes",
                     "mcq_comm_unique_id", "mcq_comm_init", "mcq_comm_allgather", "mcq_comm_wait", "mcq_comm_world", "mcq_comm_destroy",
                     "mcq_les_scalings", "mcq_last_upload_was_direct", "mcq_solve_batch_ends", "mcq_les_scalings_open",
-                    "mcq_raceline_device_ends")
+                    "mcq_raceline_device_ends", "mcq_trajectory_device", "mcq_bound_dists_device")
+
+# include/mcq.h: the columns of a trajectory row, the limit quantities, check_traj's verdict bits and margins, the boundary modes
+TRAJ_COLS = 7
+TRAJ_NLIM = 6
+LIMIT_NAMES = ("kappa_max", "ay_max", "ax_wo_drag_max", "ax_wo_drag_min", "a_tot_max", "vx_max")
+CHECK_ACC_MARGIN = 0.1
+CHECK_DIST_WARN = 1.0
+CHK_KAPPA, CHK_AY, CHK_AX_POS, CHK_AX_NEG, CHK_A_TOT, CHK_MACHINES, CHK_V_MAX = 1, 2, 4, 8, 16, 32, 64
+BOUNDS_ALL, BOUNDS_FIRST_ROW = 0, 1
 
 
 IQP_ROUND_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int))
@@ -216,6 +225,11 @@ def load_library(path=None):
     lib.mcq_raceline_device_ends.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, vp, ctypes.c_double, ctypes.c_int, vp, vp,
                                              vp, vp, vp, vp]
     lib.mcq_raceline_device_ends.restype = ctypes.c_int
+    ci, cd = ctypes.c_int, ctypes.c_double
+    lib.mcq_trajectory_device.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, ci, vp, ci, cd, vp, vp, vp, vp, vp]
+    lib.mcq_trajectory_device.restype = ctypes.c_int
+    lib.mcq_bound_dists_device.argtypes = [vp, ci, ci, vp, vp, vp, ci, vp, vp, vp, cd, cd, vp, vp, cd, ci, vp, vp, vp, vp, vp]
+    lib.mcq_bound_dists_device.restype = ctypes.c_int
     lib.mcq_normals_crossing_device.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, ctypes.c_int, vp]
     lib.mcq_normals_crossing_device.restype = ctypes.c_int
     lib.mcq_device_alloc.argtypes = [vp, ctypes.c_size_t, ctypes.POINTER(vp)]
@@ -894,6 +908,132 @@ class Engine:
                         kappa=self.download(d_k, (bsz, mmax), np.float64),
                         el_lengths=self.download(d_el, (bsz, mmax), np.float64),
                         m=self.download(d_m, (bsz,), np.int32), status=self.download(d_st, (bsz,), np.int32))
+        finally:
+            for p in ptrs:
+                self.free(p)
+
+    def trajectory_device(self, batch, m, mmax, d_m_of_track, d_track_of, d_xy, d_psi, d_kappa, d_el, d_vx, closed, d_drag, d_mass, d_vmax,
+                          d_ggv, n_ggv, d_axm, n_machines, curvlim, d_traj, d_t, d_length, d_limits, d_flags):
+        """mcq_trajectory_device (include/mcq.h) on device pointers; d_m_of_track / d_track_of / d_ggv / d_axm / d_traj / d_t may be None.
+        Asynchronous."""
+        rc = self.lib.mcq_trajectory_device(self.h, int(batch), int(m), int(mmax), d_m_of_track or None, d_track_of or None, d_xy, d_psi,
+                                            d_kappa, d_el, d_vx, 1 if closed else 0, d_drag, d_mass, d_vmax, d_ggv or None, int(n_ggv),
+                                            d_axm or None, int(n_machines), float(curvlim), d_traj or None, d_t or None, d_length,
+                                            d_limits, d_flags)
+        self._check(rc, "mcq_trajectory_device")
+
+    def bound_dists_device(self, tracks, nmax, d_n, d_ref, d_nv, mmax, d_m, d_xy, d_psi, length_veh, width_veh, d_length_list, d_width_list,
+                           stepsize_bound, mode, d_min_dists, d_min_dist, d_nb, d_bound, d_status):
+        """mcq_bound_dists_device (include/mcq.h) on device pointers; d_n / d_m / the two lists / d_bound may be None.  Asynchronous."""
+        rc = self.lib.mcq_bound_dists_device(self.h, int(tracks), int(nmax), d_n or None, d_ref, d_nv, int(mmax), d_m or None, d_xy, d_psi,
+                                             float(length_veh), float(width_veh), d_length_list or None, d_width_list or None,
+                                             float(stepsize_bound), int(mode), d_min_dists, d_min_dist, d_nb, d_bound or None, d_status)
+        self._check(rc, "mcq_bound_dists_device")
+
+    def trajectory_batch(self, race, vx, ggv, ax_max_machines, drag_coeff, m_veh, v_max, curvlim, track_of=None, closed=True):
+        """The finished trajectories of a batch of variants and check_traj's limit tests on them (mcq_trajectory_device)
+        [REF main_globaltraj.py:412-421, 502-534].  race: raceline_batch's dict (xy, psi, kappa, el_lengths, m); vx [batch, mmax]: the profiles of
+        vel_profile_batch on race['kappa'] / race['el_lengths']; ggv [batch, g, 3] or None; ax_max_machines [batch, k, 2] or None; drag_coeff,
+        m_veh, v_max: scalars or [batch]; curvlim: scalar; track_of [batch] (row of race per variant) or None when rows == batch.
+        Returns a dict: traj [batch, mmax, 7] = [s, x, y, psi, kappa, vx, ax] (rows behind a variant's m are NaN), t [batch, mmax + 1]
+        (t[m] for closed rows / t[m - 1] for unclosed ones is vel_profile_batch's lap time, bit for bit), length [batch], limits [batch, 6]
+        (LIMIT_NAMES), flags [batch] (CHK_* bits, -1 for a variant whose row length or profile is unusable)."""
+        xy = np.ascontiguousarray(race["xy"], dtype=np.float64)
+        rows, mmax = xy.shape[0], xy.shape[1]
+        arrs = [np.ascontiguousarray(race[k], dtype=np.float64) for k in ("psi", "kappa", "el_lengths")]
+        for a in arrs:
+            if a.shape != (rows, mmax):
+                raise ValueError("trajectory_batch: race's arrays do not have one shape")
+        ms = np.ascontiguousarray(race["m"], dtype=np.int32)
+        vx = np.ascontiguousarray(vx, dtype=np.float64)
+        if vx.ndim != 2 or vx.shape[1] != mmax:
+            raise ValueError("trajectory_batch: vx must be [batch, %d]" % mmax)
+        bsz = vx.shape[0]
+        if track_of is None and rows != bsz:
+            raise ValueError("trajectory_batch: %d rows for %d variants and no track_of" % (rows, bsz))
+        scal = [np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float64), (bsz,))) for a in (drag_coeff, m_veh, v_max)]
+        ggv = None if ggv is None else np.ascontiguousarray(ggv, dtype=np.float64)
+        axm = None if ax_max_machines is None else np.ascontiguousarray(ax_max_machines, dtype=np.float64)
+        if (ggv is not None and ggv.shape[0] != bsz) or (axm is not None and axm.shape[0] != bsz):
+            raise ValueError("trajectory_batch: ggv / ax_max_machines need one table per variant")
+        tr = None if track_of is None else np.ascontiguousarray(track_of, dtype=np.int32)
+        ptrs = []
+
+        def up(a):
+            p = self.alloc(a.nbytes)
+            ptrs.append(p)
+            self.upload(p, a)
+            return p
+
+        def new(nbytes):
+            p = self.alloc(nbytes)
+            ptrs.append(p)
+            return p
+        try:
+            d_xy, d_psi, d_k, d_el = up(xy), up(arrs[0]), up(arrs[1]), up(arrs[2])
+            d_m, d_vx = up(ms), up(vx)
+            d_s = [up(a) for a in scal]
+            d_g = up(ggv) if ggv is not None else None
+            d_a = up(axm) if axm is not None else None
+            d_t = up(tr) if tr is not None else None
+            d_traj, d_time = new(bsz * mmax * TRAJ_COLS * 8), new(bsz * (mmax + 1) * 8)
+            d_len, d_lim, d_fl = new(bsz * 8), new(bsz * TRAJ_NLIM * 8), new(bsz * 4)
+            self.trajectory_device(bsz, 0, mmax, d_m, d_t, d_xy, d_psi, d_k, d_el, d_vx, closed, d_s[0], d_s[1], d_s[2], d_g,
+                                   ggv.shape[1] if ggv is not None else 0, d_a, axm.shape[1] if axm is not None else 0, curvlim, d_traj,
+                                   d_time, d_len, d_lim, d_fl)
+            return dict(traj=self.download(d_traj, (bsz, mmax, TRAJ_COLS), np.float64), t=self.download(d_time, (bsz, mmax + 1), np.float64),
+                        length=self.download(d_len, (bsz,), np.float64), limits=self.download(d_lim, (bsz, TRAJ_NLIM), np.float64),
+                        flags=self.download(d_fl, (bsz,), np.int32))
+        finally:
+            for p in ptrs:
+                self.free(p)
+
+    def bound_dists_batch(self, reftracks, normvecs, race, length_veh, width_veh, stepsize_bound=1.0, first_row_only=False):
+        """check_traj's first block for a list of tracks (mcq_bound_dists_device) [REF helper_funcs_glob/src/check_traj.py:47-70]: the distance
+        of the vehicle's four corners to the two boundaries re-sampled at stepsize_bound, per station of race (raceline_batch's dict: xy, psi,
+        m; one row per track).  length_veh / width_veh: scalars or one value per track.  first_row_only=True measures against the first sample
+        of each boundary only, which is what the reference's call computes (include/mcq.h: MCQ_BOUNDS_FIRST_ROW).
+        Returns a dict: min_dists [tracks, mmax] (NaN behind a track's m), min_dist [tracks], nb [tracks, 2] (samples per boundary, right
+        first), bound_r / bound_l [tracks, nmax, 2] (the raw boundaries check_traj returns; NaN behind a track's n), status [tracks]."""
+        bsz = len(reftracks)
+        ns = np.array([np.asarray(r).shape[0] for r in reftracks], dtype=np.int32)
+        nmax = max(int(ns.max()), 3)
+        ref = np.zeros((bsz, nmax, 4))
+        nv = np.zeros((bsz, nmax, 2))
+        for k in range(bsz):
+            ref[k, :ns[k]] = np.asarray(reftracks[k], dtype=np.float64)[:, :4]
+            nv[k, :ns[k]] = normvecs[k]
+        xy = np.ascontiguousarray(race["xy"], dtype=np.float64)
+        psi = np.ascontiguousarray(race["psi"], dtype=np.float64)
+        ms = np.ascontiguousarray(race["m"], dtype=np.int32)
+        if xy.shape[0] != bsz or psi.shape != xy.shape[:2] or ms.shape != (bsz,):
+            raise ValueError("bound_dists_batch: race must hold one row per track")
+        mmax = xy.shape[1]
+        lens, wids = np.asarray(length_veh, dtype=np.float64), np.asarray(width_veh, dtype=np.float64)
+        ptrs = []
+
+        def up(a):
+            p = self.alloc(a.nbytes)
+            ptrs.append(p)
+            self.upload(p, a)
+            return p
+
+        def new(nbytes):
+            p = self.alloc(nbytes)
+            ptrs.append(p)
+            return p
+        try:
+            d_ref, d_nv, d_n, d_xy, d_psi, d_m = up(ref), up(nv), up(ns), up(xy), up(psi), up(ms)
+            d_ll = up(np.ascontiguousarray(np.broadcast_to(lens, (bsz,)))) if lens.ndim else None
+            d_wl = up(np.ascontiguousarray(np.broadcast_to(wids, (bsz,)))) if wids.ndim else None
+            d_md, d_mn, d_nb, d_bd, d_st = new(bsz * mmax * 8), new(bsz * 8), new(bsz * 8), new(bsz * 2 * nmax * 16), new(bsz * 4)
+            self.bound_dists_device(bsz, nmax, d_n, d_ref, d_nv, mmax, d_m, d_xy, d_psi, 0.0 if lens.ndim else float(lens),
+                                    0.0 if wids.ndim else float(wids), d_ll, d_wl, stepsize_bound,
+                                    BOUNDS_FIRST_ROW if first_row_only else BOUNDS_ALL, d_md, d_mn, d_nb, d_bd, d_st)
+            bound = self.download(d_bd, (bsz, 2, nmax, 2), np.float64)
+            return dict(min_dists=self.download(d_md, (bsz, mmax), np.float64), min_dist=self.download(d_mn, (bsz,), np.float64),
+                        nb=self.download(d_nb, (bsz, 2), np.int32), bound_r=bound[:, 0].copy(), bound_l=bound[:, 1].copy(),
+                        status=self.download(d_st, (bsz,), np.int32))
         finally:
             for p in ptrs:
                 self.free(p)

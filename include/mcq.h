@@ -371,6 +371,71 @@ int mcq_raceline_device_ends(mcq_handle* h, int batch, int nmax, const int* n_in
                              double* raceline_out, double* psi_out, double* kappa_out, double* el_lengths_out, int* m_out,
                              int* status_out);
 
+/* ---- the finished trajectory and check_traj's verdicts [REF main_globaltraj.py:412-421, 502-534; helper_funcs_glob/src/check_traj.py] ----
+ *
+ * mcq_trajectory_device: tph.calc_ax_profile, the time profile, the rows [s, x, y, psi, kappa, vx, ax] and the seven limit tests of check_traj for a
+ * batch of variants.  All pointers DEVICE pointers.  raceline [tracks][mmax][2], psi / kappa / el_lengths [tracks][mmax]: the outputs of
+ * mcq_raceline_device(_ends), unchanged; m_of_track [tracks] stations per row, or NULL (every row has m); track_of [batch] or NULL (row = variant);
+ * vx [batch][mmax]: the output of mcq_vel_profile_device*; closed: one int per launch, as the field of mcq_vel_forms -- closed rows have m elements, unclosed
+ * rows m - 1; drag_coeff / m_veh / v_max [batch]; ggv [batch][n_ggv][3] or NULL; ax_max_machines [batch][n_machines][2] or NULL; curvlim.
+ *   traj_out [batch][mmax][MCQ_TRAJ_COLS] (or NULL): s = running sum of el_lengths in numpy.cumsum's order, from 0 (the script's s_points);
+ *     ax_i = (v_(i+1)^2 - v_i^2) / (2 l_i), closed rows with v_m := v_0, unclosed rows with a written 0 in row m - 1 (eq_length_output=True).
+ *   t_out [batch][mmax + 1] (or NULL): t_0 = 0, t_(i+1) = t_i + 2 l_i / (v_i + v_(i+1)) -- the stable form of tph.calc_t_profile, summed in the order
+ *     of the velocity kernel, so t_out[m] (closed) / t_out[m - 1] (unclosed) is BITWISE the lap_time_out of mcq_vel_profile_device* on the same arrays.
+ *   length_out [batch]: s after the last element.
+ *   limits_out [batch][MCQ_TRAJ_NLIM]: max |kappa|, max ay, max ax_wo_drag, min ax_wo_drag, max a_tot, max vx over the m stations, with
+ *     ay = vx^2 / |1 / kappa| (0 where kappa is 0), ax_wo_drag = ax + vx^2 drag_coeff / m_veh, a_tot = sqrt(ax_wo_drag^2 + ay^2).
+ *   flags_out [batch]: MCQ_CHK_* bits, each tested as check_traj tests: KAPPA: max |kappa| > curvlim (no margin); AY: > max ggv[:, 2] + margin;
+ *     AX_POS: > max ggv[:, 1] + margin; AX_NEG: < min(-ggv[:, 1]) - margin; A_TOT: > max ggv[:, 1:] + margin; MACHINES: ax_wo_drag > max
+ *     ax_max_machines[:, 1] + margin; V_MAX: vx > v_max + margin; margin = MCQ_CHECK_ACC_MARGIN.  ggv == NULL leaves the four ggv bits 0,
+ *     ax_max_machines == NULL the machine bit.
+ * NaN rule (as for the profile): a row length outside [2, mmax] or a vx row holding a NaN gives NaN rows, NaN times, NaN length and limits and
+ * flags -1.  Rows m .. mmax-1 of traj_out and the entries of t_out behind the last time are NaN: no output keeps stale memory.
+ * Asynchronous on the handle's stream. */
+#define MCQ_TRAJ_COLS 7
+#define MCQ_TRAJ_NLIM 6
+#define MCQ_CHECK_ACC_MARGIN 0.1
+#define MCQ_CHK_KAPPA 1
+#define MCQ_CHK_AY 2
+#define MCQ_CHK_AX_POS 4
+#define MCQ_CHK_AX_NEG 8
+#define MCQ_CHK_A_TOT 16
+#define MCQ_CHK_MACHINES 32
+#define MCQ_CHK_V_MAX 64
+int mcq_trajectory_device(mcq_handle* h, int batch, int m, int mmax, const int* m_of_track, const int* track_of, const double* raceline,
+                          const double* psi, const double* kappa, const double* el_lengths, const double* vx, int closed,
+                          const double* drag_coeff, const double* m_veh, const double* v_max, const double* ggv, int n_ggv,
+                          const double* ax_max_machines, int n_machines, double curvlim, double* traj_out, double* t_out,
+                          double* length_out, double* limits_out, int* flags_out);
+
+/* mcq_bound_dists_device: check_traj's first block -- the minimum distance of the vehicle's four corners to the two track boundaries, per station
+ * and per track.  All pointers DEVICE pointers.  reftrack [tracks][nmax][4], normvec [tracks][nmax][2], n_list [tracks] or NULL (all nmax);
+ * raceline [tracks][mmax][2], psi [tracks][mmax], m_list [tracks] or NULL (all mmax); length_veh / width_veh, or per track length_veh_list /
+ * width_veh_list [tracks] (either may be NULL, then the scalar applies).
+ *   boundaries  bound_r = p + n w_r, bound_l = p - n w_l (bound_out [tracks][2][nmax][2], optional: what check_traj returns; right first);
+ *   re-sampling interp_track's rule for each: closed polyline, element lengths sqrt(dx^2 + dy^2), running sum in numpy.cumsum's order,
+ *               ceil(total / stepsize_bound) + 1 samples of numpy.linspace(0, total), numpy.interp in each coordinate, last sample dropped
+ *               (nb_out [tracks][2]: samples kept per boundary);
+ *   corners     (+-width / 2, +-length / 2) rotated by psi (0 = north, the length along y) and added to the station;
+ *   outputs     min_dists_out [tracks][mmax]: per station the minimum over 4 corners x every sample of both boundaries (entries m .. mmax-1 NaN);
+ *               min_dist_out [tracks]: its minimum over the stations (check_traj warns below MCQ_CHECK_DIST_WARN).
+ * mode: MCQ_BOUNDS_ALL (0) is what calc_min_bound_dists documents.  MCQ_BOUNDS_FIRST_ROW (1) measures against the FIRST sample of each boundary
+ * only -- what the reference's call computes, because it passes interp_track(...)[0], one row, as the boundary [REF helper_funcs_glob/src/check_traj.py:57-60]: a quirk
+ * reproduced on request, not fixed and not the default (nb_out still reports the samples per boundary).
+ * status_out [tracks]: MCQ_BAD_INPUT for n < 3 (or > nmax), m < 1 (or > mmax), non-finite input, a boundary element of length 0 (numpy.interp has
+ * no answer there) or more samples than the handle's scratch holds per boundary: min(MCQ_BOUND_NB_MAX, $MCQ_BOUND_BYTES / (32 tracks)) with
+ * $MCQ_BOUND_BYTES 1 GiB by default (nb_out then reports the samples needed); such a track's distances are NaN.  The scratch grows on demand.
+ * The minimum is taken over squared distances and the root once per station: results are bit-identical whatever the tiling, grid or launch order.
+ * Asynchronous on the handle's stream. */
+#define MCQ_BOUNDS_ALL 0
+#define MCQ_BOUNDS_FIRST_ROW 1
+#define MCQ_CHECK_DIST_WARN 1.0
+#define MCQ_BOUND_NB_MAX 65536
+int mcq_bound_dists_device(mcq_handle* h, int tracks, int nmax, const int* n_list, const double* reftrack, const double* normvec, int mmax,
+                           const int* m_list, const double* raceline, const double* psi, double length_veh, double width_veh,
+                           const double* length_veh_list, const double* width_veh_list, double stepsize_bound, int mode,
+                           double* min_dists_out, double* min_dist_out, int* nb_out, double* bound_out, int* status_out);
+
 /* Host-buffer entry for a UNIFORM batch (every track n waypoints): reftrack [batch][n][4], normvec [batch][n][2] or NULL,
  * scaling [batch][n] or NULL in host memory, results to host memory.  One asynchronous copy per array straight from / to the
  * caller's buffers -- no packing pass; buffers from mcq_host_alloc (pinned) are copied at PCIe speed, pageable ones go through
