@@ -86,6 +86,8 @@ struct mcq_handle {
     size_t vel_scratch_bytes = 0;
     double* bound_scratch = nullptr;    // mcq_bound_dists_device: samples [tracks][2][nbmax][2], raw boundaries, running sums, side statuses
     size_t bound_scratch_bytes = 0;
+    double* spl_scratch = nullptr;      // mcq_spline_approx_device: first guesses, closest parameters, distances, sides [tracks][nmax + 1] each, sample counts
+    size_t spl_scratch_bytes = 0;
     long long gi_bytes = 0;             // ws[0]'s full slots
     size_t gi_none_nmax = 0;           // > 0: no full slot could be had for rings of this many waypoints (beyond the byte cap, or hipMalloc said no) -- not tried again
     double* gis = nullptr;              // SMALL slots (MCQ_ALG_GI: one per resident workgroup): gis_slots x MCQ_GI_SLOT_DOUBLES(gis_nmax, gi_small_qcap(gis_nmax))
@@ -252,6 +254,7 @@ extern "C" void mcq_destroy(mcq_handle* h)
     if (h->cs_out) (void)hipStreamDestroy(h->cs_out);
     (void)hipFree(h->vel_scratch);
     (void)hipFree(h->bound_scratch);
+    (void)hipFree(h->spl_scratch);
     if (h->pin) (void)hipHostFree(h->pin);
     for (int k = 0; k < 5; ++k) if (h->ev[k]) (void)hipEventDestroy(h->ev[k]);
     for (int k = 0; k < 2; ++k) if (h->ev_span[k]) (void)hipEventDestroy(h->ev_span[k]);
@@ -1001,6 +1004,62 @@ extern "C" int mcq_bound_dists_device(mcq_handle* h, int tracks, int nmax, const
     hipLaunchKernelGGL(mcq_bound_dists_kernel, dim3((mmax + block - 1) / block, tracks), dim3(256), 0, st, P);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(mcq_bound_min_kernel, dim3(tracks), dim3(256), 0, st, P);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// tph.spline_approximation behind FITPACK's fit (include/mcq.h): three launches on the handle's stream
+extern "C" int mcq_spline_approx_device(mcq_handle* h, int tracks, int nmax, const int* n_list, const double* track, int k, int nkmax,
+                                        const int* nk_list, const double* knots, const double* coef, double stepsize_reg, int mmax,
+                                        double* reftrack_out, int* m_out, double* closest_t_out, double* dists_out, double* dev_out,
+                                        int* nonmono_out, int* status_out)
+{
+    if (!h || tracks <= 0 || tracks > MCQ_SPL_MAX_TRACKS || nmax < 3 || nmax > MCQ_SPL_MAX_N || !track || k < 1 || k > 5 || nkmax < 2 * k + 2 || !knots || !coef || !(stepsize_reg > 0.0) ||
+        !(stepsize_reg <= 1.7e308) || mmax < 3 || !reftrack_out || !m_out || !status_out) {
+        g_err = "mcq_spline_approx_device: bad argument";
+        return MCQ_E_ARG;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t per = (size_t)tracks * ((size_t)nmax + 1);
+    const size_t need = (4 * per + (size_t)tracks) * sizeof(double);      // (the sample counts take a double's room each)
+    if (need > h->spl_scratch_bytes) {
+        HIP_TRY(hipStreamSynchronize(h->ws[0].stream));
+        (void)hipFree(h->spl_scratch);
+        h->spl_scratch = nullptr;
+        h->spl_scratch_bytes = 0;
+        HIP_TRY(hipMalloc((void**)&h->spl_scratch, need));
+        h->spl_scratch_bytes = need;
+    }
+    McqSpline S;
+    memset(&S, 0, sizeof(S));
+    S.tracks = tracks; S.nmax = nmax; S.k = k; S.nkmax = nkmax; S.mmax = mmax;
+    S.n_list = n_list; S.nk_list = nk_list; S.track = track; S.knots = knots; S.coef = coef; S.step = stepsize_reg;
+    S.tguess = h->spl_scratch;
+    S.ct = S.tguess + per;
+    S.dist = S.ct + per;
+    S.side = S.dist + per;
+    S.npts = (int*)(S.side + per);
+    S.ref_out = reftrack_out; S.m_out = m_out; S.ct_out = closest_t_out; S.dist_out = dists_out; S.dev_out = dev_out;
+    S.nonmono_out = nonmono_out; S.status = status_out;
+    hipStream_t st = h->ws[0].stream;
+    hipLaunchKernelGGL(mcq_spline_length_kernel, dim3(tracks), dim3(256), 0, st, S);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(mcq_spline_search_kernel, dim3((nmax + 1 + 255) / 256, tracks), dim3(256), 0, st, S);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(mcq_spline_finish_kernel, dim3(tracks), dim3(256), 0, st, S);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int mcq_min_width_device(mcq_handle* h, int batch, int nmax, const int* n_list, double* reftrack_io, double min_width,
+                                    int* changed_out)
+{
+    if (!h || batch <= 0 || nmax <= 0 || !reftrack_io || !changed_out || !(min_width == min_width)) {
+        g_err = "mcq_min_width_device: bad argument";
+        return MCQ_E_ARG;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    hipLaunchKernelGGL(mcq_min_width_kernel, dim3(batch), dim3(256), 0, h->ws[0].stream, nmax, n_list, reftrack_io, min_width, changed_out);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -329,3 +329,40 @@ struct McqBound {
 __global__ void mcq_bound_points_kernel(McqBound P);
 __global__ void mcq_bound_dists_kernel(McqBound P);
 __global__ void mcq_bound_min_kernel(McqBound P);
+
+/* ---- tph.spline_approximation behind FITPACK's fit (mcq_spline_approx_device) [REF helper_funcs_glob/src/prep_track.py:39-45]: from the
+ *      B-spline (knots, coefficients) of the smoothed centre line and the raw rows to the prepared rows.  Three launches:
+ *      mcq_spline_length_kernel (a workgroup per track: checks, the closed raw line's running sum -> first guesses, the smoothed line's length
+ *      -> the number of rows), mcq_spline_search_kernel (grid (blocks of 256 raw waypoints, tracks): scipy.optimize.fmin's one-dimensional
+ *      Nelder-Mead search per waypoint, the hot path) and mcq_spline_finish_kernel (a workgroup per track: deviations, widths carried over by
+ *      numpy.interp's rule, the path rows, the NaN padding).  The spline is evaluated as FITPACK's splev / fpbspl do, with the degree a
+ *      compile-time parameter; knots and coefficients are staged in LDS when 3 nk <= MCQ_SPL_LDS doubles and read from HBM otherwise. ---- */
+#define MCQ_SPL_LDS 3072      /* doubles of LDS for a track's knots and coefficients: nk <= 1024 knots are staged (24 KB) */
+#define MCQ_SPL_MAXFUN 200    /* fmin's default budget for one variable: 200 function calls, 200 iterations */
+struct McqSpline {
+    int tracks, nmax, k, nkmax, mmax;
+    const int* n_list;       // [tracks] or nullptr (all nmax)
+    const int* nk_list;      // [tracks] or nullptr (all nkmax)
+    const double* track;     // [tracks][nmax][4] raw rows, not closed
+    const double* knots;     // [tracks][nkmax]
+    const double* coef;      // [tracks][2][nkmax]
+    double step;             // stepsize_reg
+    double* tguess;          // scratch [tracks][nmax + 1]: running sums, then the first guesses
+    double* ct;              // scratch [tracks][nmax + 1]: closest parameters
+    double* dist;            // scratch [tracks][nmax + 1]: distances to the closest points
+    double* side;            // scratch [tracks][nmax + 1]: side of the closest point (entry n is not used)
+    int* npts;               // scratch [tracks]: no_points_reg_cl
+    double* ref_out;         // [tracks][mmax][4]
+    int* m_out;              // [tracks]
+    double* ct_out;          // [tracks][nmax + 1] or nullptr
+    double* dist_out;        // [tracks][nmax + 1] or nullptr
+    double* dev_out;         // [tracks][2] or nullptr
+    int* nonmono_out;        // [tracks] or nullptr
+    int* status;             // [tracks]
+};
+__global__ void mcq_spline_length_kernel(McqSpline S);
+__global__ void mcq_spline_search_kernel(McqSpline S);
+__global__ void mcq_spline_finish_kernel(McqSpline S);
+
+/* prep_track's tail [REF helper_funcs_glob/src/prep_track.py:89-98]: rows narrower than min_width grow by half the deficit on both sides. */
+__global__ void mcq_min_width_kernel(int nmax, const int* n_list, double* ref_all, double min_width, int* changed_out);

@@ -3717,3 +3717,412 @@ __global__ void __launch_bounds__(MCQ_NT) mcq_bound_min_kernel(McqBound P)
         ((gdouble*)P.min_dist)[t] = s_min[0];
     }
 }
+
+// ---- tph.spline_approximation behind FITPACK's fit (mcq_spline_approx_device) [REF helper_funcs_glob/src/prep_track.py:39-45] ----
+// Everything from here to the end of the file is compiled WITHOUT floating-point contraction: scipy.optimize.fmin's simplex points (3 a - 2 b,
+// 1.5 a - 0.5 b, ...), FITPACK's recursion and numpy's expressions are rounded products followed by rounded sums, and the search's decisions
+// are compared bit for bit with theirs.  (The interpreter build has no fused multiply-add to contract to: baseline x86-64, ISO C++.)
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+
+// splev(x, (t, c, K)) with ext = 0 for both coordinates: the knot interval l with t[l] <= x < t[l + 1], clamped to [K, nk - K - 2] (x itself is
+// neither clamped nor wrapped), FITPACK's fpbspl recursion for the K + 1 non-zero B-splines, the sum over c[l - K .. l] in ascending order.
+// Reads t[l - K + 1 .. l + K] and c[l - K .. l]: inside [1, nk - 2] and [0, nk - K - 2] for nk >= 2 K + 2.
+template <int K, typename PT>
+__device__ __forceinline__ void spl_eval(PT t, PT cx, PT cy, int nk, double x, double& sx, double& sy)
+{
+    int lo = K, hi = nk - K - 2;
+    while (lo < hi) {                       // at most log2(nk) + 1 steps
+        const int mid = (lo + hi + 1) >> 1;
+        if (t[mid] <= x) lo = mid;
+        else hi = mid - 1;
+    }
+    const int l = lo;
+    double h[K + 1], hh[K];
+    h[0] = 1.0;
+    #pragma unroll
+    for (int j = 1; j <= K; ++j) {
+        #pragma unroll
+        for (int i = 0; i < j; ++i) hh[i] = h[i];
+        h[0] = 0.0;
+        #pragma unroll
+        for (int i = 0; i < j; ++i) {
+            const double tli = t[l + 1 + i], tlj = t[l + 1 + i - j];
+            if (tli == tlj) {
+                h[i + 1] = 0.0;
+            } else {
+                const double f = hh[i] / (tli - tlj);
+                h[i] = h[i] + f * (tli - x);
+                h[i + 1] = f * (x - tlj);
+            }
+        }
+    }
+    double ax = 0.0, ay = 0.0;
+    #pragma unroll
+    for (int j = 0; j <= K; ++j) {
+        ax = ax + cx[l - K + j] * h[j];
+        ay = ay + cy[l - K + j] * h[j];
+    }
+    sx = ax;
+    sy = ay;
+}
+
+template <int K, typename PT>
+__device__ __forceinline__ double spl_dist(PT t, PT cx, PT cy, int nk, double x, double px, double py)
+{
+    double sx, sy;
+    spl_eval<K>(t, cx, cy, nk, x, sx, sy);
+    return hypot(sx - px, sy - py);
+}
+
+// A track's knots and coefficients into LDS (all threads of the workgroup; returns whether they fit).  lds: [3 nk] = t | cx | cy.
+__device__ __forceinline__ bool spl_stage(const McqSpline& S, int tr, int nk, double* lds)
+{
+    const bool fits = 3 * nk <= MCQ_SPL_LDS;
+    if (fits) {
+        const gdouble* t = (const gdouble*)(S.knots + (size_t)tr * S.nkmax);
+        const gdouble* c = (const gdouble*)(S.coef + (size_t)tr * 2 * S.nkmax);
+        for (int i = threadIdx.x; i < nk; i += MCQ_NT) {
+            lds[i] = t[i];
+            lds[nk + i] = c[i];
+            lds[2 * nk + i] = c[(size_t)S.nkmax + i];
+        }
+    }
+    __syncthreads();
+    return fits;
+}
+
+// BODY<K>(..., t, cx, cy, ...) on the LDS copy or on HBM, for the launch's degree
+#define SPL_CALL(BODY, fits, lds, ...)                                                                               \
+    do {                                                                                                             \
+        const gdouble* gt_ = (const gdouble*)(S.knots + (size_t)tr * S.nkmax);                                       \
+        const gdouble* gc_ = (const gdouble*)(S.coef + (size_t)tr * 2 * S.nkmax);                                    \
+        const double* lt_ = (lds);                                                                                   \
+        switch (S.k) {                                                                                               \
+        case 1: if (fits) BODY<1>(S, tr, n, nk, lt_, lt_ + nk, lt_ + 2 * nk, __VA_ARGS__); else BODY<1>(S, tr, n, nk, gt_, gc_, gc_ + S.nkmax, __VA_ARGS__); break; \
+        case 2: if (fits) BODY<2>(S, tr, n, nk, lt_, lt_ + nk, lt_ + 2 * nk, __VA_ARGS__); else BODY<2>(S, tr, n, nk, gt_, gc_, gc_ + S.nkmax, __VA_ARGS__); break; \
+        case 3: if (fits) BODY<3>(S, tr, n, nk, lt_, lt_ + nk, lt_ + 2 * nk, __VA_ARGS__); else BODY<3>(S, tr, n, nk, gt_, gc_, gc_ + S.nkmax, __VA_ARGS__); break; \
+        case 4: if (fits) BODY<4>(S, tr, n, nk, lt_, lt_ + nk, lt_ + 2 * nk, __VA_ARGS__); else BODY<4>(S, tr, n, nk, gt_, gc_, gc_ + S.nkmax, __VA_ARGS__); break; \
+        default: if (fits) BODY<5>(S, tr, n, nk, lt_, lt_ + nk, lt_ + 2 * nk, __VA_ARGS__); else BODY<5>(S, tr, n, nk, gt_, gc_, gc_ + S.nkmax, __VA_ARGS__); break; \
+        }                                                                                                            \
+    } while (0)
+
+// the chords of the smoothed line between its N samples at numpy.linspace(0, 1, N): this thread's share, chords tid, tid + 256, ... in that order
+template <int K, typename PT>
+__device__ __forceinline__ void spl_length_body(const McqSpline& S, int tr, int n, int nk, PT t, PT cx, PT cy, int N, double& acc)
+{
+    (void)S; (void)tr; (void)n;
+    const double st = 1.0 / (double)(N - 1);
+    double a = 0.0;
+    for (int j = threadIdx.x; j < N - 1; j += MCQ_NT) {
+        const double ta = (double)j * st, tb = j + 1 == N - 1 ? 1.0 : (double)(j + 1) * st;
+        double ax, ay, bx, by;
+        spl_eval<K>(t, cx, cy, nk, ta, ax, ay);
+        spl_eval<K>(t, cx, cy, nk, tb, bx, by);
+        const double dx = bx - ax, dy = by - ay;
+        a = a + sqrt(dx * dx + dy * dy);
+    }
+    acc = a;
+}
+
+__global__ void __launch_bounds__(MCQ_NT) mcq_spline_length_kernel(McqSpline S)
+{
+    __shared__ double s_tc[MCQ_SPL_LDS];
+    __shared__ double s_el[MCQ_NT];
+    __shared__ double s_red[2 * MCQ_NW];
+    __shared__ double s_carry;
+    __shared__ int s_bad;
+    const int tid = threadIdx.x, tr = blockIdx.x;
+    const size_t nm = (size_t)S.nmax;
+    const int n = S.n_list ? S.n_list[tr] : S.nmax;
+    const int nk = S.nk_list ? S.nk_list[tr] : S.nkmax;
+    const int K = S.k;
+    gint* st = (gint*)(S.status + tr);
+    gint* mo = (gint*)(S.m_out + tr);
+    gint* np_ = (gint*)(S.npts + tr);
+    if (tid == 0) {
+        s_bad = 0;
+        s_carry = 0.0;
+    }
+    __syncthreads();
+    if (n < 3 || n > S.nmax || nk < 2 * K + 2 || nk > S.nkmax) {      // (uniform over the workgroup)
+        if (tid == 0) {
+            *st = MCQ_BAD_INPUT;
+            *mo = 0;
+            *np_ = 0;
+        }
+        return;
+    }
+    const gdouble* trk = (const gdouble*)(S.track + (size_t)tr * nm * 4);
+    const gdouble* kt = (const gdouble*)(S.knots + (size_t)tr * S.nkmax);
+    const gdouble* kc = (const gdouble*)(S.coef + (size_t)tr * 2 * S.nkmax);
+    gdouble* cum = (gdouble*)(S.tguess + (size_t)tr * (nm + 1));
+    int bad = 0;
+    for (int i = tid; i < 4 * n; i += MCQ_NT)
+        if (!bd_finite(trk[i])) bad = 1;
+    for (int i = tid; i < nk; i += MCQ_NT) {
+        if (!bd_finite(kt[i])) bad = 1;
+        if (i > 0 && !(kt[i - 1] <= kt[i])) bad = 1;
+        if (i < nk - K - 1 && (!bd_finite(kc[i]) || !bd_finite(kc[(size_t)S.nkmax + i]))) bad = 1;
+    }
+    if (tid == 0) cum[0] = 0.0;
+    for (int base = 0; base < n; base += MCQ_NT) {       // element lengths of the closed raw line, summed in numpy.cumsum's order
+        const int i = base + tid;
+        if (i < n) {
+            const int j = i + 1 < n ? i + 1 : 0;
+            const double dx = trk[4 * (size_t)j] - trk[4 * (size_t)i], dy = trk[4 * (size_t)j + 1] - trk[4 * (size_t)i + 1];
+            s_el[tid] = sqrt(dx * dx + dy * dy);
+        }
+        __syncthreads();
+        if (tid == 0) {
+            double c = s_carry;
+            const int cnt = n - base < MCQ_NT ? n - base : MCQ_NT;
+            for (int k = 0; k < cnt; ++k) {
+                c += s_el[k];
+                s_el[k] = c;
+            }
+            s_carry = c;
+        }
+        __syncthreads();
+        if (i < n) cum[(size_t)i + 1] = s_el[tid];
+        __syncthreads();
+    }
+    if (bad) s_bad = 1;
+    __syncthreads();
+    const double total = s_carry;
+    const double ct = ceil(total);
+    if (s_bad || !(total > 0.0) || !bd_finite(total) || ct > 4194304.0) {        // (2^22 m: the 4 ceil(total) length samples stay a bounded loop)
+        if (tid == 0) {
+            *st = MCQ_BAD_INPUT;
+            *mo = 0;
+            *np_ = 0;
+        }
+        return;
+    }
+    for (int i = tid; i <= n; i += MCQ_NT) cum[i] = cum[i] / total;       // t_guess (entry n: total / total = 1)
+    const bool fits = spl_stage(S, tr, nk, s_tc);
+    const int N = 4 * (int)ct;
+    double acc = 0.0;
+    SPL_CALL(spl_length_body, fits, s_tc, N, acc);
+    const double len = block_reduce_(acc, 0, s_red);
+    const double cnt = ceil(len / S.step) + 1.0;
+    if (tid == 0) {
+        if (!bd_finite(cnt) || cnt > 1073741824.0) {
+            *st = MCQ_BAD_INPUT;
+            *mo = 0;
+            *np_ = 0;
+        } else {
+            const int npts = (int)cnt, m = npts - 1;
+            *np_ = npts;
+            *mo = m;                                     // (the rows needed, also where they exceed mmax)
+            *st = (m > S.mmax || m < 3) ? MCQ_BAD_INPUT : MCQ_OK;
+        }
+    }
+}
+
+// scipy.optimize.fmin(f, x0) for ONE variable with its defaults (xtol = ftol = 1e-4, 200 calls, 200 iterations), f(t) = |s(t) - p|: the
+// simplex is the pair (a, fa) best, (b, fb) worst; every point is formed with scipy's roundings; the pair is re-ordered after every iteration
+// by a stable sort (swap only if fb < fa).  Everything lives in registers.
+template <int K, typename PT>
+__device__ __forceinline__ void spl_search_body(const McqSpline& S, int tr, int n, int nk, PT t, PT cx, PT cy, int i)
+{
+    const size_t nm = (size_t)S.nmax;
+    const gdouble* trk = (const gdouble*)(S.track + (size_t)tr * nm * 4);
+    const int i0 = i < n ? i : 0, i1 = i + 1 < n ? i + 1 : 0;
+    const double px = trk[4 * (size_t)i0], py = trk[4 * (size_t)i0 + 1];
+    const double x0 = ((const gdouble*)S.tguess)[(size_t)tr * (nm + 1) + i];
+    double a = x0, b = x0 != 0.0 ? (1.0 + 0.05) * x0 : 0.00025;
+    double fa = spl_dist<K>(t, cx, cy, nk, a, px, py), fb = spl_dist<K>(t, cx, cy, nk, b, px, py);
+    if (fb < fa) {
+        const double tx = a, tf = fa;
+        a = b; fa = fb; b = tx; fb = tf;
+    }
+    int calls = 2, iters = 1;
+    while (calls < MCQ_SPL_MAXFUN && iters < MCQ_SPL_MAXFUN) {
+        if (fabs(b - a) <= 1e-4 && fabs(fa - fb) <= 1e-4) break;
+        const double xr = 2.0 * a - b;
+        const double fxr = spl_dist<K>(t, cx, cy, nk, xr, px, py);
+        ++calls;
+        bool shrink = false;
+        if (fxr < fa) {
+            const double xe = 3.0 * a - 2.0 * b;
+            const double fxe = spl_dist<K>(t, cx, cy, nk, xe, px, py);
+            ++calls;
+            if (fxe < fxr) { b = xe; fb = fxe; }
+            else { b = xr; fb = fxr; }
+        } else if (fxr < fb) {
+            const double xc = 1.5 * a - 0.5 * b;
+            const double fxc = spl_dist<K>(t, cx, cy, nk, xc, px, py);
+            ++calls;
+            if (fxc <= fxr) { b = xc; fb = fxc; }
+            else shrink = true;
+        } else {
+            const double xcc = 0.5 * a + 0.5 * b;
+            const double fxcc = spl_dist<K>(t, cx, cy, nk, xcc, px, py);
+            ++calls;
+            if (fxcc < fb) { b = xcc; fb = fxcc; }
+            else shrink = true;
+        }
+        if (shrink) {
+            b = a + 0.5 * (b - a);
+            fb = spl_dist<K>(t, cx, cy, nk, b, px, py);
+            ++calls;
+        }
+        ++iters;
+        if (fb < fa) {
+            const double tx = a, tf = fa;
+            a = b; fa = fb; b = tx; fb = tf;
+        }
+    }
+    double sx, sy;
+    spl_eval<K>(t, cx, cy, nk, a, sx, sy);
+    const size_t o = (size_t)tr * (nm + 1) + i;
+    ((gdouble*)S.ct)[o] = a;
+    ((gdouble*)S.dist)[o] = hypot(sx - px, sy - py);
+    // side_of_line(a = track_cl[i], b = track_cl[i + 1], z = closest point): sign((b - a) x (z - a)); entry n is not used (side_n = side_0)
+    const double qx = trk[4 * (size_t)i1], qy = trk[4 * (size_t)i1 + 1];
+    const double cr = (qx - px) * (sy - py) - (qy - py) * (sx - px);
+    ((gdouble*)S.side)[o] = cr > 0.0 ? 1.0 : (cr < 0.0 ? -1.0 : 0.0);
+}
+
+__global__ void __launch_bounds__(MCQ_NT) mcq_spline_search_kernel(McqSpline S)
+{
+    __shared__ double s_tc[MCQ_SPL_LDS];
+    const int tr = blockIdx.y;
+    if (S.status[tr] != MCQ_OK) return;       // (uniform over the workgroup)
+    const int n = S.n_list ? S.n_list[tr] : S.nmax;
+    const int nk = S.nk_list ? S.nk_list[tr] : S.nkmax;
+    if ((int)(blockIdx.x * MCQ_NT) > n) return;
+    const bool fits = spl_stage(S, tr, nk, s_tc);
+    const int i = blockIdx.x * MCQ_NT + threadIdx.x;
+    if (i > n) return;                         // (no barrier behind this point)
+    SPL_CALL(spl_search_body, fits, s_tc, i);
+}
+
+// rows j = tid, tid + 256, ... < m of the prepared track: the path at numpy.linspace(0, 1, m + 1)[j], the widths by numpy.interp's rule over
+// (closest_t, w_new): plain bisection for the last i with closest_t[i] <= x, slope * (x - xp_i) + fp_i, fp[0] / fp[n] outside the range
+template <int K, typename PT>
+__device__ __forceinline__ void spl_rows_body(const McqSpline& S, int tr, int n, int nk, PT t, PT cx, PT cy, int m)
+{
+    const size_t nm = (size_t)S.nmax;
+    const gdouble* trk = (const gdouble*)(S.track + (size_t)tr * nm * 4);
+    const gdouble* ct = (const gdouble*)(S.ct + (size_t)tr * (nm + 1));
+    const gdouble* dist = (const gdouble*)(S.dist + (size_t)tr * (nm + 1));
+    const gdouble* side = (const gdouble*)(S.side + (size_t)tr * (nm + 1));
+    gdouble* out = (gdouble*)(S.ref_out + (size_t)tr * S.mmax * 4);
+    const double st = 1.0 / (double)m;          // linspace's step over no_points_reg_cl = m + 1 samples
+    for (int j = threadIdx.x; j < m; j += MCQ_NT) {
+        const double x = (double)j * st;
+        double sx, sy;
+        spl_eval<K>(t, cx, cy, nk, x, sx, sy);
+        int lo = 0, hi = n;
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (ct[mid] <= x) lo = mid;
+            else hi = mid - 1;
+        }
+        double wr, wl;
+        const int e = x < ct[0] ? 0 : ((x > ct[n] || lo == n) ? n : -1);
+        if (e >= 0 || ct[lo] == x) {
+            const int q = e >= 0 ? e : lo, r = q < n ? q : 0;
+            const double sd = side[r] * dist[q];
+            wr = trk[4 * (size_t)r + 2] + sd;
+            wl = trk[4 * (size_t)r + 3] - sd;
+        } else {
+            const int r0 = lo, r1 = lo + 1 < n ? lo + 1 : 0;
+            const double s0 = side[r0] * dist[lo], s1 = side[r1] * dist[lo + 1];
+            const double a0 = trk[4 * (size_t)r0 + 2] + s0, a1 = trk[4 * (size_t)r1 + 2] + s1;
+            const double b0 = trk[4 * (size_t)r0 + 3] - s0, b1 = trk[4 * (size_t)r1 + 3] - s1;
+            const double den = ct[lo + 1] - ct[lo], dxp = x - ct[lo];
+            wr = (a1 - a0) / den * dxp + a0;
+            wl = (b1 - b0) / den * dxp + b0;
+        }
+        out[4 * (size_t)j] = sx;
+        out[4 * (size_t)j + 1] = sy;
+        out[4 * (size_t)j + 2] = wr;
+        out[4 * (size_t)j + 3] = wl;
+    }
+}
+
+__global__ void __launch_bounds__(MCQ_NT) mcq_spline_finish_kernel(McqSpline S)
+{
+    __shared__ double s_tc[MCQ_SPL_LDS];
+    __shared__ double s_red[2 * MCQ_NW];
+    const int tid = threadIdx.x, tr = blockIdx.x;
+    const size_t nm = (size_t)S.nmax;
+    gdouble* out = (gdouble*)(S.ref_out + (size_t)tr * S.mmax * 4);
+    gdouble* cto = S.ct_out ? (gdouble*)(S.ct_out + (size_t)tr * (nm + 1)) : nullptr;
+    gdouble* dso = S.dist_out ? (gdouble*)(S.dist_out + (size_t)tr * (nm + 1)) : nullptr;
+    if (S.status[tr] != MCQ_OK) {             // (uniform) nothing of this track but NaNs; m_out keeps the rows it would need
+        for (size_t i = tid; i < (size_t)S.mmax * 4; i += MCQ_NT) out[i] = NAN;
+        for (size_t i = tid; i <= nm; i += MCQ_NT) {
+            if (cto) cto[i] = NAN;
+            if (dso) dso[i] = NAN;
+        }
+        if (tid == 0) {
+            if (S.dev_out) {
+                ((gdouble*)S.dev_out)[2 * (size_t)tr] = NAN;
+                ((gdouble*)S.dev_out)[2 * (size_t)tr + 1] = NAN;
+            }
+            if (S.nonmono_out) ((gint*)S.nonmono_out)[tr] = 0;
+        }
+        return;
+    }
+    const int n = S.n_list ? S.n_list[tr] : S.nmax;
+    const int nk = S.nk_list ? S.nk_list[tr] : S.nkmax;
+    const int m = S.npts[tr] - 1;
+    const gdouble* ct = (const gdouble*)(S.ct + (size_t)tr * (nm + 1));
+    const gdouble* dist = (const gdouble*)(S.dist + (size_t)tr * (nm + 1));
+    double sum = 0.0, mx = 0.0, desc = 0.0;
+    for (int i = tid; i <= n; i += MCQ_NT) {
+        const double d = dist[i];
+        sum += d;
+        mx = fmax(mx, fabs(d));
+        if (i < n && ct[i + 1] <= ct[i]) desc += 1.0;
+        if (cto) cto[i] = ct[i];
+        if (dso) dso[i] = d;
+    }
+    for (size_t i = (size_t)n + 1 + tid; i <= nm; i += MCQ_NT) {
+        if (cto) cto[i] = NAN;
+        if (dso) dso[i] = NAN;
+    }
+    block_reduce2_(sum, 0, mx, 2, s_red);
+    desc = block_reduce_(desc, 0, s_red);
+    if (tid == 0) {
+        if (S.dev_out) {
+            ((gdouble*)S.dev_out)[2 * (size_t)tr] = sum / (double)(n + 1);
+            ((gdouble*)S.dev_out)[2 * (size_t)tr + 1] = mx;
+        }
+        if (S.nonmono_out) ((gint*)S.nonmono_out)[tr] = (int)desc;
+    }
+    const bool fits = spl_stage(S, tr, nk, s_tc);
+    SPL_CALL(spl_rows_body, fits, s_tc, m);
+    for (size_t i = (size_t)m * 4 + tid; i < (size_t)S.mmax * 4; i += MCQ_NT) out[i] = NAN;
+}
+#undef SPL_CALL
+
+__global__ void __launch_bounds__(MCQ_NT) mcq_min_width_kernel(int nmax, const int* n_list, double* ref_all, double min_width, int* changed_out)
+{
+    __shared__ int s_any;
+    const int tid = threadIdx.x, tr = blockIdx.x;
+    const int n0 = n_list ? n_list[tr] : nmax;
+    const int n = n0 < 0 ? 0 : (n0 > nmax ? nmax : n0);
+    gdouble* ref = (gdouble*)(ref_all + (size_t)tr * nmax * 4);
+    if (tid == 0) s_any = 0;
+    __syncthreads();
+    int any = 0;
+    for (int i = tid; i < n; i += MCQ_NT) {
+        const double wr = ref[4 * (size_t)i + 2], wl = ref[4 * (size_t)i + 3];
+        const double cur = wr + wl;
+        if (cur < min_width) {
+            const double g = (min_width - cur) / 2.0;
+            ref[4 * (size_t)i + 2] = wr + g;
+            ref[4 * (size_t)i + 3] = wl + g;
+            any = 1;
+        }
+    }
+    if (any) s_any = 1;
+    __syncthreads();
+    if (tid == 0) ((gint*)changed_out)[tr] = s_any;
+}

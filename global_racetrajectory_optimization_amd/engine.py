@@ -118,7 +118,7 @@ EXPORTED_SYMBOLS = ("mcq_create", "mcq_destroy", "mcq_last_error", "mcq_default_
                     "mcq_last_timing", "mcq_timing_begin", "mcq_timing_end", "mcq_workspace_bytes",
                     "mcq_comm_unique_id", "mcq_comm_init", "mcq_comm_allgather", "mcq_comm_wait", "mcq_comm_world", "mcq_comm_destroy",
                     "mcq_les_scalings", "mcq_last_upload_was_direct", "mcq_solve_batch_ends", "mcq_les_scalings_open",
-                    "mcq_raceline_device_ends", "mcq_trajectory_device", "mcq_bound_dists_device")
+                    "mcq_raceline_device_ends", "mcq_trajectory_device", "mcq_bound_dists_device", "mcq_spline_approx_device", "mcq_min_width_device")
 
 # include/mcq.h: the columns of a trajectory row, the limit quantities, check_traj's verdict bits and margins, the boundary modes
 TRAJ_COLS = 7
@@ -230,6 +230,10 @@ def load_library(path=None):
     lib.mcq_trajectory_device.restype = ctypes.c_int
     lib.mcq_bound_dists_device.argtypes = [vp, ci, ci, vp, vp, vp, ci, vp, vp, vp, cd, cd, vp, vp, cd, ci, vp, vp, vp, vp, vp]
     lib.mcq_bound_dists_device.restype = ctypes.c_int
+    lib.mcq_spline_approx_device.argtypes = [vp, ci, ci, vp, vp, ci, ci, vp, vp, vp, cd, ci, vp, vp, vp, vp, vp, vp, vp]
+    lib.mcq_spline_approx_device.restype = ctypes.c_int
+    lib.mcq_min_width_device.argtypes = [vp, ci, ci, vp, vp, cd, vp]
+    lib.mcq_min_width_device.restype = ctypes.c_int
     lib.mcq_normals_crossing_device.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, ctypes.c_int, vp]
     lib.mcq_normals_crossing_device.restype = ctypes.c_int
     lib.mcq_device_alloc.argtypes = [vp, ctypes.c_size_t, ctypes.POINTER(vp)]
@@ -842,6 +846,154 @@ class Engine:
         finally:
             for p in ptrs:
                 self.free(p)
+
+    def spline_approx_device(self, tracks, nmax, d_n, d_track, k, nkmax, d_nk, d_knots, d_coef, stepsize_reg, mmax, d_ref, d_m, d_ct, d_dist,
+                             d_dev, d_nonmono, d_status):
+        """mcq_spline_approx_device (include/mcq.h) on device pointers; d_n / d_nk / d_ct / d_dist / d_dev / d_nonmono may be None.  Asynchronous."""
+        rc = self.lib.mcq_spline_approx_device(self.h, int(tracks), int(nmax), d_n or None, d_track or None, int(k), int(nkmax), d_nk or None,
+                                               d_knots or None, d_coef or None, float(stepsize_reg), int(mmax), d_ref or None, d_m or None,
+                                               d_ct or None, d_dist or None, d_dev or None, d_nonmono or None, d_status or None)
+        self._check(rc, "mcq_spline_approx_device")
+
+    def min_width_device(self, batch, nmax, d_n, d_ref, min_width, d_changed):
+        """mcq_min_width_device (include/mcq.h) on device pointers, in place.  Asynchronous."""
+        self._check(self.lib.mcq_min_width_device(self.h, int(batch), int(nmax), d_n or None, d_ref or None, float(min_width), d_changed or None),
+                    "mcq_min_width_device")
+
+    @staticmethod
+    def pack_tcks(tcks):
+        """[(t, c, k)] of scipy.interpolate.splprep -> (k, nk [B] int32, knots [B, nkmax], coef [B, 2, nkmax]); one degree per launch."""
+        ks = {int(tck[2]) for tck in tcks}
+        if len(ks) != 1:
+            raise ValueError("spline_approx_batch: the splines of one launch must share their degree")
+        nk = np.array([np.asarray(tck[0]).shape[0] for tck in tcks], dtype=np.int32)
+        nkmax = int(nk.max())
+        knots = np.zeros((len(tcks), nkmax))
+        coef = np.zeros((len(tcks), 2, nkmax))
+        for b, (t, c, _) in enumerate(tcks):
+            knots[b, :nk[b]] = np.asarray(t, dtype=np.float64)
+            for q in range(2):
+                cq = np.asarray(c[q], dtype=np.float64)[:nkmax]
+                coef[b, q, :cq.shape[0]] = cq
+        return ks.pop(), nk, knots, coef
+
+    def spline_approx_batch(self, tracks, tcks, stepsize_reg, mmax=None, keep=None):
+        """tph.spline_approximation behind FITPACK's fit for a list of raw tracks ([n_k, 4] rows [x, y, w_r, w_l], not closed) and their
+        smoothing splines (tcks: the (t, c, k) tuples scipy.interpolate.splprep returns; one degree per launch), on the device
+        (mcq_spline_approx_device).  mmax: rows the output holds per track (default: enough for every track of the launch).
+        Returns a dict: reftrack -- list of (m_k, 4) arrays (None where status != 0) --, m [B], closest_t / dists [B, nmax + 1] (NaN behind n_k),
+        dev [B, 2] = mean and maximum deviation, nonmono [B], status [B].
+        keep: a list that receives (d_ref, d_n, mmax) -- the rows stay on the device, padded to mmax, and the caller frees both (prep_track_batch)."""
+        bsz = len(tracks)
+        ns = np.array([np.asarray(r).shape[0] for r in tracks], dtype=np.int32)
+        nmax = max(int(ns.max()), 3)
+        trk = np.zeros((bsz, nmax, 4))
+        for b in range(bsz):
+            trk[b, :ns[b]] = np.asarray(tracks[b], dtype=np.float64)[:, :4]
+        k, nk, knots, coef = self.pack_tcks(tcks)
+        if mmax is None:      # a smoothed line is shorter than its raw one: room for one twice as long (a track that needs more reports its m)
+            el = [float(np.sum(np.hypot(*(np.diff(np.vstack((trk[b, :ns[b], :2], trk[b, :1, :2])), axis=0).T)))) for b in range(bsz)]
+            finite = [e for e in el if np.isfinite(e)]
+            mmax = max(int(2.0 * max(finite + [0.0]) / float(stepsize_reg)) + 8, 8)
+        ptrs = []
+
+        def up(a):
+            q = self.alloc(a.nbytes)
+            ptrs.append(q)
+            self.upload(q, a)
+            return q
+
+        def new(nbytes):
+            q = self.alloc(nbytes)
+            ptrs.append(q)
+            return q
+        try:
+            d_trk, d_n, d_nk, d_kn, d_cf = up(trk), up(ns), up(nk), up(knots), up(coef)
+            d_m, d_ct, d_ds, d_dev, d_nm, d_st = new(bsz * 4), new(bsz * (nmax + 1) * 8), new(bsz * (nmax + 1) * 8), new(bsz * 16), new(bsz * 4), new(bsz * 4)
+            d_ref = new(bsz * mmax * 32)
+            self.spline_approx_device(bsz, nmax, d_n, d_trk, k, knots.shape[1], d_nk, d_kn, d_cf, stepsize_reg, mmax, d_ref, d_m, d_ct, d_ds,
+                                      d_dev, d_nm, d_st)
+            m = self.download(d_m, (bsz,), np.int32)
+            st = self.download(d_st, (bsz,), np.int32)
+            ref = self.download(d_ref, (bsz, mmax, 4), np.float64)
+            out = dict(reftrack=[ref[b, :m[b]].copy() if st[b] == 0 else None for b in range(bsz)], m=m, status=st,
+                       closest_t=self.download(d_ct, (bsz, nmax + 1), np.float64), dists=self.download(d_ds, (bsz, nmax + 1), np.float64),
+                       dev=self.download(d_dev, (bsz, 2), np.float64), nonmono=self.download(d_nm, (bsz,), np.int32))
+            if keep is not None:
+                ptrs.remove(d_ref)
+                ptrs.remove(d_m)
+                keep.extend((d_ref, d_m, mmax))
+            return out
+        finally:
+            for q in ptrs:
+                self.free(q)
+
+    def min_width_batch(self, reftracks, min_width):
+        """prep_track's tail for a list of prepared tracks (mcq_min_width_device): rows narrower than min_width grow by half the deficit on both
+        sides.  Returns (list of [n, 4] arrays, changed [B] int32: 1 where upstream would print its warning)."""
+        bsz = len(reftracks)
+        ns = np.array([np.asarray(r).shape[0] for r in reftracks], dtype=np.int32)
+        nmax = int(ns.max())
+        ref = np.zeros((bsz, nmax, 4))
+        for b in range(bsz):
+            ref[b, :ns[b]] = np.asarray(reftracks[b], dtype=np.float64)[:, :4]
+        d_ref, d_n, d_ch = self.alloc(ref.nbytes), self.alloc(ns.nbytes), self.alloc(bsz * 4)
+        try:
+            self.upload(d_ref, ref)
+            self.upload(d_n, ns)
+            self.min_width_device(bsz, nmax, d_n, d_ref, min_width, d_ch)
+            out = self.download(d_ref, (bsz, nmax, 4), np.float64)
+            return [out[b, :ns[b]].copy() for b in range(bsz)], self.download(d_ch, (bsz,), np.int32)
+        finally:
+            for q in (d_ref, d_n, d_ch):
+                self.free(q)
+
+    def prep_track_batch(self, tracks, k_reg=3, s_reg=10, stepsize_prep=1.0, stepsize_reg=3.0, min_width=None, tcks=None, horizon=10):
+        """prep_track [REF helper_funcs_glob/src/prep_track.py] for a list of raw tracks ([n_k, 4] rows, not closed).  On the host, per track:
+        the linear re-sampling at stepsize_prep and FITPACK's periodic smoothing fit (scipy.interpolate.splprep) -- or the caller's tcks, one
+        (t, c, k) per track.  Then on the device, the rows staying there: mcq_spline_approx_device, mcq_prep_device (normals and scalings of
+        the prepared rows), mcq_normals_crossing_device (on the un-inflated widths, as upstream) and, with min_width, mcq_min_width_device.
+        Returns a dict: reftrack -- list of (m_k, 4) arrays (None where status != 0) --, normvec (m_k, 2), scaling (m_k), crossing [B] (1 / 0,
+        -1 where tph raises), inflated [B] (all 0 without min_width), status [B], m [B], dev [B, 2], nonmono [B], tcks (the splines used: the
+        caller's, or the ones fitted here): reftrack / normvec / scaling are what solve_batch takes."""
+        if tcks is None:
+            from scipy import interpolate
+            from .trajectory_planning_helpers import interp_track as _it
+            tcks = []
+            for trk in tracks:
+                ti = _it.interp_track(track=np.asarray(trk, dtype=np.float64), stepsize=stepsize_prep)
+                cl = np.vstack((ti, ti[0]))
+                tcks.append(interpolate.splprep([cl[:, 0], cl[:, 1]], k=k_reg, s=s_reg, per=1)[0])
+        bsz = len(tracks)
+        keep = []
+        out = self.spline_approx_batch(tracks, tcks, stepsize_reg, keep=keep)
+        d_ref, d_m, mmax = keep
+        ptrs = [d_ref, d_m]
+        try:
+            if np.any(out["status"] != 0):      # a refused track has no rows: the kernels behind must not take its m_out (the rows it would need) for a length
+                self.upload(d_m, np.where(out["status"] == 0, out["m"], 0).astype(np.int32))
+            d_nv, d_sc, d_st, d_cr, d_ch = (self.alloc(bsz * mmax * 16), self.alloc(bsz * mmax * 8), self.alloc(bsz * 4), self.alloc(bsz * 4),
+                                            self.alloc(bsz * 4))
+            ptrs += [d_nv, d_sc, d_st, d_cr, d_ch]
+            self._check(self.lib.mcq_prep_device(self.h, bsz, mmax, d_m, d_ref, d_nv, d_sc, d_st), "mcq_prep_device")
+            self._check(self.lib.mcq_normals_crossing_device(self.h, bsz, mmax, d_m, d_ref, d_nv, int(horizon), d_cr), "mcq_normals_crossing_device")
+            if min_width is not None:
+                self.min_width_device(bsz, mmax, d_m, d_ref, min_width, d_ch)
+            ref = self.download(d_ref, (bsz, mmax, 4), np.float64)
+            nv = self.download(d_nv, (bsz, mmax, 2), np.float64)
+            sc = self.download(d_sc, (bsz, mmax), np.float64)
+            st = np.where(out["status"] != 0, out["status"], self.download(d_st, (bsz,), np.int32))
+            m = out["m"]
+            good = [st[b] == 0 for b in range(bsz)]
+            return dict(reftrack=[ref[b, :m[b]].copy() if good[b] else None for b in range(bsz)],
+                        normvec=[nv[b, :m[b]].copy() if good[b] else None for b in range(bsz)],
+                        scaling=[sc[b, :m[b]].copy() if good[b] else None for b in range(bsz)],
+                        crossing=self.download(d_cr, (bsz,), np.int32),
+                        inflated=self.download(d_ch, (bsz,), np.int32) if min_width is not None else np.zeros(bsz, dtype=np.int32), status=st, m=m,
+                        dev=out["dev"], nonmono=out["nonmono"], tcks=tcks)
+        finally:
+            for q in ptrs:
+                self.free(q)
 
     def raceline_device_ends(self, batch, nmax, d_n, d_ref, d_nv, d_alpha, d_closed, d_psi, stepsize, mmax, d_xy, d_psi_out, d_kappa,
                              d_el, d_m, d_status):

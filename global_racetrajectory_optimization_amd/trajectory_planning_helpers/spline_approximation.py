@@ -2,8 +2,12 @@
 Host-side shim of tph.spline_approximation.spline_approximation -- boundary
 [REF helper_funcs_glob/src/prep_track.py:39-45].  FITPACK smoothing (scipy) + per-point closest-parameter search;
 host only, not part of the GPU hot path.
+
+MCQ_PREP_DEVICE=1 in the environment: everything behind FITPACK's fit runs on the device instead (Engine.spline_approx_batch ->
+mcq_spline_approx_device, include/mcq.h); signature, print line and the default route are unchanged.
 """
 import math
+import os
 
 import numpy as np
 from scipy import interpolate, optimize
@@ -28,6 +32,9 @@ def spline_approximation(track: np.ndarray, k_reg: int = 3, s_reg: int = 10, ste
     dists_cum_cl = np.insert(np.cumsum(el_cl), 0, 0.0)
 
     tck_cl = interpolate.splprep([track_interp_cl[:, 0], track_interp_cl[:, 1]], k=k_reg, s=s_reg, per=1)[0]
+
+    if os.environ.get("MCQ_PREP_DEVICE") == "1":
+        return _on_device(track, tck_cl, stepsize_reg, debug)
 
     no_points_lencalc = math.ceil(dists_cum_cl[-1]) * 4
     path_tmp = np.array(interpolate.splev(np.linspace(0.0, 1.0, no_points_lencalc), tck_cl)).T
@@ -60,3 +67,13 @@ def spline_approximation(track: np.ndarray, k_reg: int = 3, s_reg: int = 10, ste
     w_right_s = np.interp(grid, closest_t, w_right_new)
     w_left_s = np.interp(grid, closest_t, w_left_new)
     return np.column_stack((path_smoothed, w_right_s[:-1], w_left_s[:-1]))
+
+
+def _on_device(track, tck_cl, stepsize_reg, debug):
+    from ..engine import EngineError, default_engine
+    out = default_engine().spline_approx_batch([track], [tck_cl], stepsize_reg)
+    if out["status"][0] != 0:
+        raise EngineError("mcq_spline_approx_device: bad input (status %d, %d rows needed)" % (out["status"][0], out["m"][0]))
+    if debug:
+        print("Spline approximation: mean deviation %.2fm, maximum deviation %.2fm" % (float(out["dev"][0, 0]), float(out["dev"][0, 1])))
+    return out["reftrack"][0]

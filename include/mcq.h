@@ -436,6 +436,48 @@ int mcq_bound_dists_device(mcq_handle* h, int tracks, int nmax, const int* n_lis
                            const double* length_veh_list, const double* width_veh_list, double stepsize_bound, int mode,
                            double* min_dists_out, double* min_dist_out, int* nb_out, double* bound_out, int* status_out);
 
+/* ---- tph.spline_approximation behind FITPACK's fit [REF helper_funcs_glob/src/prep_track.py:39-45]: from the smoothing B-spline of the centre line
+ * (scipy.interpolate.splprep's tck: the one step of prep_track that stays on the host) and the raw rows to the prepared rows.  All pointers
+ * DEVICE pointers; asynchronous on the handle's stream.  Per track:
+ *   closing     track_cl = the n rows and row 0 again; element lengths sqrt(dx^2 + dy^2), running sum in numpy.cumsum's order: total;
+ *               first guesses t_guess_i = cum_i / total, i = 0 .. n.
+ *   evaluation  splev(t, tck) with ext = 0: the interval l with knots[l] <= t < knots[l + 1] clamped to [k, nk - k - 2], t itself neither
+ *               clamped nor wrapped (a parameter below 0 or above 1 is evaluated on the first / last polynomial piece; the search goes there),
+ *               FITPACK's recursion for the k + 1 B-splines.
+ *   length      4 ceil(total) samples at numpy.linspace(0, 1), the sum of the chords (a fixed order: 256 strided partial sums, then a tree);
+ *               no_points_reg_cl = ceil(len_smoothed / stepsize_reg) + 1; m = no_points_reg_cl - 1 rows at numpy.linspace(0, 1,
+ *               no_points_reg_cl), the last one dropped.
+ *   search      per row i of track_cl: scipy.optimize.fmin(|s(t) - p_i|, x0 = t_guess_i) with its defaults, restated for one variable with
+ *               scipy's roundings (second vertex 1.05 x0, or 0.00025 for x0 == 0; at most 200 calls): closest_t_i; dists_i = |s(closest_t_i) - p_i|.
+ *   widths      side_i = sign((p_(i+1) - p_i) x (s(closest_t_i) - p_i)), side_n = side_0; w_r + side dist and w_l - side dist, carried to the
+ *               rows by numpy.interp's rule over closest_t (plain bisection: the last i with closest_t_i <= x; slope * (x - xp_i) + fp_i; the
+ *               first / last value outside the range).  Where closest_t descends numpy's own answer depends on its search heuristic; the
+ *               entry's is the bisection's, and nonmono_out counts the i with closest_t_(i+1) <= closest_t_i.  Not an error (upstream does
+ *               not check either).
+ * status_out: MCQ_BAD_INPUT -- that track's reftrack_out / closest_t_out / dists_out / dev_out NaN, nonmono_out 0 -- for n < 3 or n > nmax, a
+ *   non-finite row, knot or coefficient, nk < 2 k + 2 or nk > nkmax, descending knots, total == 0 (or beyond 2^22 m), m < 3 and m > mmax (m_out
+ *   then reports the m needed, as the raceline entries do; otherwise m_out of a refused track is 0).  The other tracks are not affected.
+ * MCQ_E_ARG: k outside 1 .. 5, nmax < 3, nkmax < 2 k + 2, mmax < 3, stepsize_reg <= 0, NULL where an array is required, more than
+ *   MCQ_SPL_MAX_TRACKS tracks in one launch (the tracks are one axis of the search kernel's grid) or nmax above MCQ_SPL_MAX_N. */
+#define MCQ_SPL_MAX_TRACKS 65535
+#define MCQ_SPL_MAX_N 16777216
+int mcq_spline_approx_device(mcq_handle* h, int tracks,
+        int nmax, const int* n_list, const double* track,      /* [tracks][nmax][4] raw rows [x, y, w_r, w_l], NOT closed; n_list NULL: all nmax */
+        int k, int nkmax, const int* nk_list,                  /* degree 1..5; knots per track (NULL: all nkmax) */
+        const double* knots, const double* coef,               /* [tracks][nkmax], [tracks][2][nkmax] (nk - k - 1 valid per coordinate: splprep's tck) */
+        double stepsize_reg, int mmax,
+        double* reftrack_out,                                  /* [tracks][mmax][4]; rows m_out .. mmax-1 NaN */
+        int* m_out,                                            /* rows written = no_points_reg_cl - 1 (the count needed when it exceeds mmax) */
+        double* closest_t_out, double* dists_out,              /* [tracks][nmax + 1] each, optional (NULL) */
+        double* dev_out,                                       /* [tracks][2] = mean, max of dists_closest (the debug line's two numbers), optional */
+        int* nonmono_out,                                      /* [tracks]: count of i with closest_t[i+1] <= closest_t[i], optional */
+        int* status_out);
+
+/* prep_track's tail [REF helper_funcs_glob/src/prep_track.py:89-98]: where w_r + w_l < min_width both widths of reftrack_io [batch][nmax][4] grow by
+ * half the deficit; changed_out [batch] = 1 if any row of the track changed (upstream's warning), else 0.  n_list [batch] or NULL (all nmax).
+ * A separate entry because prep_track runs the normals-crossing check on the un-inflated widths.  DEVICE pointers; asynchronous. */
+int mcq_min_width_device(mcq_handle* h, int batch, int nmax, const int* n_list, double* reftrack_io, double min_width, int* changed_out);
+
 /* Host-buffer entry for a UNIFORM batch (every track n waypoints): reftrack [batch][n][4], normvec [batch][n][2] or NULL,
  * scaling [batch][n] or NULL in host memory, results to host memory.  One asynchronous copy per array straight from / to the
  * caller's buffers -- no packing pass; buffers from mcq_host_alloc (pinned) are copied at PCIe speed, pageable ones go through
