@@ -47,6 +47,12 @@ struct Staging {
     size_t elems = 0, batch = 0;
 };
 
+// A grow-only device buffer of the handle, reused from call to call (grow(), below HIP_TRY).
+struct Scratch {
+    void* p = nullptr;
+    size_t bytes = 0;
+};
+
 struct mcq_handle {
     int device = 0;
     Workspace ws[2];
@@ -75,7 +81,10 @@ struct mcq_handle {
                             // double), so that a read of memory nothing has written shows up as a wrong result on every box instead of
                             // on the rare one whose recycled memory happens to hold garbage
     bool smem_attr_set = false;
-    double* vel_scratch = nullptr;      // profiles of mcq_vel_profile_device*, [2 nmax][batch] (the lap doubled) or [nmax][batch] (unclosed rows)
+    Scratch vel;                        // profiles of mcq_vel_profile_device*, [2 nmax][batch] (the lap doubled) or [nmax][batch] (unclosed rows)
+    Scratch bound;                      // mcq_bound_dists_device: samples [tracks][2][nbmax][2], raw boundaries, running sums, side statuses
+    Scratch spl;                        // mcq_spline_approx_device: first guesses, closest parameters, distances, sides [tracks][nmax + 1] each, sample counts
+    Scratch ends;                       // per-problem ring / open-chain records of mcq_solve_batch_ends (device)
     mcq_iqp_round_cb iqp_cb = nullptr;  // mcq_iqp_set_round_callback
     void* iqp_cb_user = nullptr;
     void* comm = nullptr;               // ncclComm_t of mcq_comm_init (RCCL, loaded with dlopen)
@@ -83,11 +92,6 @@ struct mcq_handle {
     hipStream_t comm_stream = nullptr;  // the gathers run here: ordered behind the solves by an event, overlapping the NEXT solve
     hipEvent_t comm_ready = nullptr, comm_t0[4] = {nullptr, nullptr, nullptr, nullptr}, comm_done[4] = {nullptr, nullptr, nullptr, nullptr};
     unsigned comm_seq = 0;              // gathers enqueued so far (event ring index)
-    size_t vel_scratch_bytes = 0;
-    double* bound_scratch = nullptr;    // mcq_bound_dists_device: samples [tracks][2][nbmax][2], raw boundaries, running sums, side statuses
-    size_t bound_scratch_bytes = 0;
-    double* spl_scratch = nullptr;      // mcq_spline_approx_device: first guesses, closest parameters, distances, sides [tracks][nmax + 1] each, sample counts
-    size_t spl_scratch_bytes = 0;
     long long gi_bytes = 0;             // ws[0]'s full slots
     size_t gi_none_nmax = 0;           // > 0: no full slot could be had for rings of this many waypoints (beyond the byte cap, or hipMalloc said no) -- not tried again
     double* gis = nullptr;              // SMALL slots (MCQ_ALG_GI: one per resident workgroup): gis_slots x MCQ_GI_SLOT_DOUBLES(gis_nmax, gi_small_qcap(gis_nmax))
@@ -100,8 +104,6 @@ struct mcq_handle {
     hipEvent_t ev_up[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr}, ev_down[2] = {nullptr, nullptr};
     hipEvent_t ev_slice[16] = {};      // mcq_solve_host / mcq_solve_batch in slices: upload / kernel done, per slice
     int last_upload_direct = 0;         // the last host-buffer batch went up without the packing pass (mcq_last_upload_was_direct)
-    mcq_ends* d_ends = nullptr;         // per-problem ring / open-chain records of mcq_solve_batch_ends (device), ends_cap of them
-    size_t ends_cap = 0;
 };
 
 // ---- the one error path of the HIP calls ----------------------------------------------------------------------------------------
@@ -133,6 +135,19 @@ static void drain(mcq_handle* h)
         hipError_t e_ = (expr);                                                                   \
         if (e_ != hipSuccess) { drain(h); return hip_failed(#expr, e_, __FILE__, __LINE__); }     \
     } while (0)
+
+// s holds at least `bytes` afterwards.  A launch in flight on the handle's stream may still read the old buffer: it is waited for before the free.
+// A refused allocation leaves the record empty.
+static int grow(mcq_handle* h, Scratch& s, size_t bytes)
+{
+    if (bytes <= s.bytes) return 0;
+    HIP_TRY(hipStreamSynchronize(h->ws[0].stream));
+    (void)hipFree(s.p);
+    s = Scratch();
+    HIP_TRY(hipMalloc(&s.p, bytes));
+    s.bytes = bytes;
+    return 0;
+}
 
 extern "C" const char* mcq_last_error(void) { return g_err.c_str(); }
 
@@ -241,8 +256,6 @@ extern "C" void mcq_destroy(mcq_handle* h)
     (void)mcq_comm_destroy(h);
     if (h->ws[1].stream) (void)hipStreamSynchronize(h->ws[1].stream);
     for (int k = 0; k < 2; ++k) { free_workspace(h, k); free_staging(h, k); }
-    (void)hipFree(h->d_ends);
-    h->d_ends = nullptr;
     if (h->ws[1].stream) (void)hipStreamDestroy(h->ws[1].stream);
     for (int k = 0; k < 2; ++k) {
         if (h->ev_up[k]) (void)hipEventDestroy(h->ev_up[k]);
@@ -252,9 +265,7 @@ extern "C" void mcq_destroy(mcq_handle* h)
     for (int k = 0; k < 16; ++k) if (h->ev_slice[k]) (void)hipEventDestroy(h->ev_slice[k]);
     if (h->cs_in) (void)hipStreamDestroy(h->cs_in);
     if (h->cs_out) (void)hipStreamDestroy(h->cs_out);
-    (void)hipFree(h->vel_scratch);
-    (void)hipFree(h->bound_scratch);
-    (void)hipFree(h->spl_scratch);
+    for (Scratch* s : {&h->vel, &h->bound, &h->spl, &h->ends}) (void)hipFree(s->p);
     if (h->pin) (void)hipHostFree(h->pin);
     for (int k = 0; k < 5; ++k) if (h->ev[k]) (void)hipEventDestroy(h->ev[k]);
     for (int k = 0; k < 2; ++k) if (h->ev_span[k]) (void)hipEventDestroy(h->ev_span[k]);
@@ -773,14 +784,7 @@ static int vel_profile_launch(mcq_handle* h, int batch, int n, int nmax, const i
     }
     HIP_TRY(hipSetDevice(h->device));
     const size_t need = (size_t)(closed ? 2 : 1) * nmax * batch * sizeof(double);      // the lap doubled, or the row once
-    if (need > h->vel_scratch_bytes) {
-        HIP_TRY(hipStreamSynchronize(h->ws[0].stream));
-        (void)hipFree(h->vel_scratch);
-        h->vel_scratch = nullptr;
-        h->vel_scratch_bytes = 0;
-        HIP_TRY(hipMalloc((void**)&h->vel_scratch, need));
-        h->vel_scratch_bytes = need;
-    }
+    if (int rc = grow(h, h->vel, need)) return rc;
     McqVelForms F;
     memset(&F, 0, sizeof(F));
     McqVel& V = F.V;
@@ -790,7 +794,7 @@ static int vel_profile_launch(mcq_handle* h, int batch, int n, int nmax, const i
     V.ggv = ggv; V.ng = n_ggv; V.axm = ax_max_machines; V.nam = n_machines;
     V.drag = drag_coeff; V.mass = m_veh; V.vmax = v_max; V.dyn_exp = dyn_model_exp;
     V.mu = mu; V.filt_window = filt_window;
-    V.scratch = h->vel_scratch; V.vx_out = vx_out; V.lap_time = lap_time_out;
+    V.scratch = (double*)h->vel.p; V.vx_out = vx_out; V.lap_time = lap_time_out;
     F.loc_gg = loc_gg; F.v_start = v_start; F.v_end = v_end;
     const dim3 grid((batch + 63) / 64), block(64);
     if (closed && !loc_gg) hipLaunchKernelGGL(mcq_vel_profile_kernel, grid, block, 0, h->ws[0].stream, V);
@@ -853,6 +857,18 @@ extern "C" int mcq_vel_profile_device_forms(mcq_handle* h, int batch, int n, int
                               forms->filt_window, forms->closed != 0, forms->loc_gg, forms->v_start, forms->v_end);
 }
 
+// the fields both raceline entries share (Q is zeroed by the caller, with the record it may be part of)
+static void fill_race(McqRace& Q, mcq_handle* h, int batch, int nmax, const int* n_in, const double* reftrack, const double* normvec,
+                      const double* alpha, double stepsize, int mmax, double* raceline_out, double* psi_out, double* kappa_out,
+                      double* el_lengths_out, int* m_out, int* status_out)
+{
+    Q.batch = batch; Q.nmax = nmax; Q.mmax = mmax;
+    Q.n_in = n_in; Q.ref = reftrack; Q.nv = normvec; Q.alpha = alpha; Q.stepsize = stepsize;
+    Q.xy_out = raceline_out; Q.psi_out = psi_out; Q.kappa_out = kappa_out; Q.el_out = el_lengths_out;
+    Q.m_out = m_out; Q.status = status_out;
+    Q.vec = h->ws[0].vec;
+}
+
 extern "C" int mcq_raceline_device(mcq_handle* h, int batch, int nmax, const int* n_in, const double* reftrack,
                                    const double* normvec, const double* alpha, double stepsize, int mmax,
                                    double* raceline_out, double* psi_out, double* kappa_out, double* el_lengths_out,
@@ -868,11 +884,7 @@ extern "C" int mcq_raceline_device(mcq_handle* h, int batch, int nmax, const int
     if (rc) return rc;
     McqRace Q;
     memset(&Q, 0, sizeof(Q));
-    Q.batch = batch; Q.nmax = nmax; Q.mmax = mmax;
-    Q.n_in = n_in; Q.ref = reftrack; Q.nv = normvec; Q.alpha = alpha; Q.stepsize = stepsize;
-    Q.xy_out = raceline_out; Q.psi_out = psi_out; Q.kappa_out = kappa_out; Q.el_out = el_lengths_out;
-    Q.m_out = m_out; Q.status = status_out;
-    Q.vec = h->ws[0].vec;
+    fill_race(Q, h, batch, nmax, n_in, reftrack, normvec, alpha, stepsize, mmax, raceline_out, psi_out, kappa_out, el_lengths_out, m_out, status_out);
     hipLaunchKernelGGL(mcq_raceline_kernel, dim3(batch), dim3(256), 0, h->ws[0].stream, Q);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -903,12 +915,7 @@ extern "C" int mcq_raceline_device_ends(mcq_handle* h, int batch, int nmax, cons
     }
     McqRaceEnds E;
     memset(&E, 0, sizeof(E));
-    McqRace& Q = E.Q;
-    Q.batch = batch; Q.nmax = nmax; Q.mmax = mmax;
-    Q.n_in = n_in; Q.ref = reftrack; Q.nv = normvec; Q.alpha = alpha; Q.stepsize = stepsize;
-    Q.xy_out = raceline_out; Q.psi_out = psi_out; Q.kappa_out = kappa_out; Q.el_out = el_lengths_out;
-    Q.m_out = m_out; Q.status = status_out;
-    Q.vec = h->ws[0].vec;
+    fill_race(E.Q, h, batch, nmax, n_in, reftrack, normvec, alpha, stepsize, mmax, raceline_out, psi_out, kappa_out, el_lengths_out, m_out, status_out);
     E.closed = closed; E.psi = psi;
     hipLaunchKernelGGL(mcq_raceline_ends_kernel, dim3(batch), dim3(256), 0, h->ws[0].stream, E);
     HIP_TRY(hipGetLastError());
@@ -978,21 +985,14 @@ extern "C" int mcq_bound_dists_device(mcq_handle* h, int tracks, int nmax, const
     size_t nbmax = (cap - fixed) / (sides * 2);
     if (nbmax > MCQ_BOUND_NB_MAX) nbmax = MCQ_BOUND_NB_MAX;
     const size_t need = (sides * nbmax * 2 + fixed) * sizeof(double);
-    if (need > h->bound_scratch_bytes) {
-        HIP_TRY(hipStreamSynchronize(h->ws[0].stream));
-        (void)hipFree(h->bound_scratch);
-        h->bound_scratch = nullptr;
-        h->bound_scratch_bytes = 0;
-        HIP_TRY(hipMalloc((void**)&h->bound_scratch, need));
-        h->bound_scratch_bytes = need;
-    }
+    if (int rc = grow(h, h->bound, need)) return rc;
     McqBound P;
     memset(&P, 0, sizeof(P));
     P.tracks = tracks; P.nmax = nmax; P.mmax = mmax; P.nbmax = (int)nbmax; P.mode = mode;
     P.n_list = n_list; P.m_list = m_list; P.ref = reftrack; P.nv = normvec; P.xy = raceline; P.psi = psi;
     P.length_veh = length_veh; P.width_veh = width_veh; P.length_list = length_veh_list; P.width_list = width_veh_list;
     P.step = stepsize_bound;
-    P.samples = h->bound_scratch;
+    P.samples = (double*)h->bound.p;
     P.pts = P.samples + sides * nbmax * 2;
     P.cum = P.pts + sides * (size_t)nmax * 2;
     P.side_status = (int*)(P.cum + sides * ((size_t)nmax + 1));
@@ -1022,19 +1022,12 @@ extern "C" int mcq_spline_approx_device(mcq_handle* h, int tracks, int nmax, con
     HIP_TRY(hipSetDevice(h->device));
     const size_t per = (size_t)tracks * ((size_t)nmax + 1);
     const size_t need = (4 * per + (size_t)tracks) * sizeof(double);      // (the sample counts take a double's room each)
-    if (need > h->spl_scratch_bytes) {
-        HIP_TRY(hipStreamSynchronize(h->ws[0].stream));
-        (void)hipFree(h->spl_scratch);
-        h->spl_scratch = nullptr;
-        h->spl_scratch_bytes = 0;
-        HIP_TRY(hipMalloc((void**)&h->spl_scratch, need));
-        h->spl_scratch_bytes = need;
-    }
+    if (int rc = grow(h, h->spl, need)) return rc;
     McqSpline S;
     memset(&S, 0, sizeof(S));
     S.tracks = tracks; S.nmax = nmax; S.k = k; S.nkmax = nkmax; S.mmax = mmax;
     S.n_list = n_list; S.nk_list = nk_list; S.track = track; S.knots = knots; S.coef = coef; S.step = stepsize_reg;
-    S.tguess = h->spl_scratch;
+    S.tguess = (double*)h->spl.p;
     S.ct = S.tguess + per;
     S.dist = S.ct + per;
     S.side = S.dist + per;
@@ -1997,18 +1990,11 @@ extern "C" int mcq_solve_batch_ends(mcq_handle* h, const mcq_problem* probs, con
         if (o.objective != MCQ_OBJ_MIN_CURV) { g_err = "mcq_solve_batch_ends: open chains have the minimum-curvature objective only"; return MCQ_E_ARG; }
     }
     HIP_TRY(hipSetDevice(h->device));
-    if (h->ends_cap < (size_t)batch) {
-        HIP_TRY(hipStreamSynchronize(h->ws[0].stream));       // (the previous records may still be read by a launch in flight)
-        (void)hipFree(h->d_ends);
-        h->d_ends = nullptr;
-        h->ends_cap = 0;
-        HIP_TRY(hipMalloc((void**)&h->d_ends, (size_t)batch * sizeof(mcq_ends)));
-        h->ends_cap = (size_t)batch;
-    }
+    if (int rc = grow(h, h->ends, (size_t)batch * sizeof(mcq_ends))) return rc;
     // ordered before every launch of the solve (and the copy streams of its slices) by the synchronisation: the caller's array is pageable
-    HIP_TRY(hipMemcpyAsync(h->d_ends, ends, (size_t)batch * sizeof(mcq_ends), hipMemcpyHostToDevice, h->ws[0].stream));
+    HIP_TRY(hipMemcpyAsync(h->ends.p, ends, (size_t)batch * sizeof(mcq_ends), hipMemcpyHostToDevice, h->ws[0].stream));
     HIP_TRY(hipStreamSynchronize(h->ws[0].stream));
-    return solve_batch_impl(h, probs, h->d_ends, batch, opts, alpha_out, curv_err_out, status_out, info_out);
+    return solve_batch_impl(h, probs, (const mcq_ends*)h->ends.p, batch, opts, alpha_out, curv_err_out, status_out, info_out);
 }
 
 // ---- a stream of RESIDENT uniform batches on the handle's two compute streams (include/mcq.h) ---------------------------------------------

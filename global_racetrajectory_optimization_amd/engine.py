@@ -108,18 +108,6 @@ class McqIqpStats(ctypes.Structure):
 
 IQP_TRACE = 16      # MCQ_IQP_TRACE
 
-EXPORTED_SYMBOLS = ("mcq_create", "mcq_destroy", "mcq_last_error", "mcq_default_opts", "mcq_solve_batch", "mcq_solve_host",
-                    "mcq_iqp_device", "mcq_iqp_batch", "mcq_iqp_set_round_callback", "mcq_host_alloc", "mcq_host_free",
-                    "mcq_solve_device", "mcq_solve_device_f32", "mcq_solve_device_f32_rows", "mcq_solve_batch_f32",
-                    "mcq_solve_host_pipelined", "mcq_solve_device_stream", "mcq_solve_device_ragged", "mcq_solve_device_ragged_params", "mcq_prep_device", "mcq_relinearise_device",
-                    "mcq_vel_profile_device", "mcq_vel_profile_device_ragged", "mcq_vel_profile_device_opts", "mcq_vel_profile_device_forms", "mcq_raceline_device", "mcq_normals_crossing_device",
-                    "mcq_device_alloc",
-                    "mcq_device_free", "mcq_copy_to_device", "mcq_copy_to_host", "mcq_sync", "mcq_stream",
-                    "mcq_last_timing", "mcq_timing_begin", "mcq_timing_end", "mcq_workspace_bytes",
-                    "mcq_comm_unique_id", "mcq_comm_init", "mcq_comm_allgather", "mcq_comm_wait", "mcq_comm_world", "mcq_comm_destroy",
-                    "mcq_les_scalings", "mcq_last_upload_was_direct", "mcq_solve_batch_ends", "mcq_les_scalings_open",
-                    "mcq_raceline_device_ends", "mcq_trajectory_device", "mcq_bound_dists_device", "mcq_spline_approx_device", "mcq_min_width_device")
-
 # include/mcq.h: the columns of a trajectory row, the limit quantities, check_traj's verdict bits and margins, the boundary modes
 TRAJ_COLS = 7
 TRAJ_NLIM = 6
@@ -131,6 +119,71 @@ BOUNDS_ALL, BOUNDS_FIRST_ROW = 0, 1
 
 
 IQP_ROUND_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int))
+
+# The C ABI of include/mcq.h, name -> (restype, argtypes), in the order the entries were added: what load_library declares, and
+# EXPORTED_SYMBOLS.  ctypes checks none of it against the library (tests/helper_checks.py counts the header's parameters).
+_vp, _ci, _cd, _sz, _P = ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_size_t, ctypes.POINTER
+_po = _P(McqOpts)
+_SOLVE_DEVICE = [_vp, _ci, _ci, _vp, _vp, _vp, _cd, _cd, _po, _vp, _vp, _vp, _vp]
+_SOLVE_ROWS = [_vp, _ci, _ci, _ci, _vp, _vp, _cd, _cd, _po, _vp, _vp, _vp, _vp]
+_SOLVE_STREAM = [_vp, _ci, _ci, _ci, _vp, _vp, _vp, _cd, _cd, _po, _vp, _vp, _vp]
+_ABI = {
+    "mcq_create": (_ci, [_ci, _P(_vp)]),
+    "mcq_destroy": (None, [_vp]),
+    "mcq_last_error": (ctypes.c_char_p, []),
+    "mcq_default_opts": (None, [_po]),
+    "mcq_solve_batch": (_ci, [_vp, _P(McqProblem), _ci, _po, _dp, _dp, _ip, _P(McqInfo)]),
+    "mcq_solve_host": (_ci, _SOLVE_DEVICE),
+    "mcq_iqp_device": (_ci, [_vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _cd, _cd, _cd, _ci, _cd, _ci, _po, _vp, _vp, _vp, _vp, _vp, _vp,
+                             _P(McqIqpStats)]),
+    "mcq_iqp_batch": (_ci, [_vp, _P(McqProblem), _ci, _cd, _ci, _cd, _ci, _po, _ci, _dp, _dp, _dp, _ip, _dp, _ip, _ip, _dp, _P(McqIqpStats)]),
+    "mcq_iqp_set_round_callback": (_ci, [_vp, IQP_ROUND_CB, _vp]),
+    "mcq_host_alloc": (_ci, [_vp, _sz, _P(_vp)]),
+    "mcq_host_free": (_ci, [_vp, _vp]),
+    "mcq_solve_device": (_ci, _SOLVE_DEVICE),
+    "mcq_solve_device_f32": (_ci, _SOLVE_DEVICE),
+    "mcq_solve_device_f32_rows": (_ci, _SOLVE_ROWS),
+    "mcq_solve_batch_f32": (_ci, _SOLVE_ROWS),
+    "mcq_solve_host_pipelined": (_ci, _SOLVE_STREAM),
+    "mcq_solve_device_stream": (_ci, _SOLVE_STREAM),
+    "mcq_solve_device_ragged": (_ci, [_vp, _ci, _ci, _vp, _vp, _vp, _vp, _cd, _cd, _po, _vp, _vp, _vp, _vp]),
+    "mcq_solve_device_ragged_params": (_ci, [_vp, _ci, _ci, _vp, _vp, _vp, _vp, _cd, _cd, _vp, _vp, _po, _vp, _vp, _vp, _vp]),
+    "mcq_prep_device": (_ci, [_vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp]),
+    "mcq_relinearise_device": (_ci, [_vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _cd, _cd, _vp, _vp, _vp, _vp]),
+    "mcq_vel_profile_device": (_ci, [_vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _cd, _vp, _vp]),
+    "mcq_vel_profile_device_ragged": (_ci, [_vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _cd, _vp, _vp]),
+    "mcq_vel_profile_device_opts": (_ci, [_vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _P(McqVelOpts), _vp, _vp]),
+    "mcq_vel_profile_device_forms": (_ci, [_vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _P(McqVelForms), _vp, _vp]),
+    "mcq_raceline_device": (_ci, [_vp, _ci, _ci, _vp, _vp, _vp, _vp, _cd, _ci, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mcq_normals_crossing_device": (_ci, [_vp, _ci, _ci, _vp, _vp, _vp, _ci, _vp]),
+    "mcq_device_alloc": (_ci, [_vp, _sz, _P(_vp)]),
+    "mcq_device_free": (_ci, [_vp, _vp]),
+    "mcq_copy_to_device": (_ci, [_vp, _vp, _vp, _sz]),
+    "mcq_copy_to_host": (_ci, [_vp, _vp, _vp, _sz]),
+    "mcq_sync": (_ci, [_vp]),
+    "mcq_stream": (_vp, [_vp]),
+    "mcq_last_timing": (_ci, [_vp, _P(ctypes.c_float * 5)]),
+    "mcq_timing_begin": (_ci, [_vp]),
+    "mcq_timing_end": (_ci, [_vp, _P(ctypes.c_float), _ip]),
+    "mcq_workspace_bytes": (ctypes.c_longlong, [_vp]),
+    "mcq_comm_unique_id": (_ci, [ctypes.c_char_p]),
+    "mcq_comm_init": (_ci, [_vp, _ci, _ci, ctypes.c_char_p]),
+    "mcq_comm_allgather": (_ci, [_vp, _vp, _vp, _sz, _ci]),
+    "mcq_comm_wait": (_ci, [_vp, _ci, _P(ctypes.c_float)]),
+    "mcq_comm_world": (_ci, [_vp, _ip, _ip]),
+    "mcq_comm_destroy": (_ci, [_vp]),
+    "mcq_les_scalings": (_ci, [_vp, _ci, _vp, _ci]),
+    "mcq_last_upload_was_direct": (_ci, [_vp]),
+    "mcq_solve_batch_ends": (_ci, [_vp, _P(McqProblem), _P(McqEnds), _ci, _po, _dp, _dp, _ip, _P(McqInfo)]),
+    "mcq_les_scalings_open": (_ci, [_vp, _ci, _vp, _ci]),
+    "mcq_raceline_device_ends": (_ci, [_vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _cd, _ci, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mcq_trajectory_device": (_ci, [_vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _vp, _vp, _vp, _vp, _ci, _vp, _ci, _cd, _vp, _vp, _vp,
+                                    _vp, _vp]),
+    "mcq_bound_dists_device": (_ci, [_vp, _ci, _ci, _vp, _vp, _vp, _ci, _vp, _vp, _vp, _cd, _cd, _vp, _vp, _cd, _ci, _vp, _vp, _vp, _vp, _vp]),
+    "mcq_spline_approx_device": (_ci, [_vp, _ci, _ci, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _cd, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mcq_min_width_device": (_ci, [_vp, _ci, _ci, _vp, _vp, _cd, _vp]),
+}
+EXPORTED_SYMBOLS = tuple(_ABI)
 
 
 class EngineError(RuntimeError):
@@ -144,130 +197,9 @@ def load_library(path=None):
         raise EngineError("MI355X engine library not found at %s -- build it with "
                           "global_racetrajectory_optimization_amd/csrc/build.sh (hipcc, gfx950)" % path)
     lib = ctypes.CDLL(path)
-    vp = ctypes.c_void_p
-    lib.mcq_create.argtypes = [ctypes.c_int, ctypes.POINTER(vp)]
-    lib.mcq_create.restype = ctypes.c_int
-    lib.mcq_destroy.argtypes = [vp]
-    lib.mcq_destroy.restype = None
-    lib.mcq_last_error.argtypes = []
-    lib.mcq_last_error.restype = ctypes.c_char_p
-    lib.mcq_default_opts.argtypes = [ctypes.POINTER(McqOpts)]
-    lib.mcq_default_opts.restype = None
-    lib.mcq_solve_batch.argtypes = [vp, ctypes.POINTER(McqProblem), ctypes.c_int, ctypes.POINTER(McqOpts), _dp, _dp,
-                                    _ip, ctypes.POINTER(McqInfo)]
-    lib.mcq_solve_batch.restype = ctypes.c_int
-    lib.mcq_solve_device.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, ctypes.c_double, ctypes.c_double,
-                                     ctypes.POINTER(McqOpts), vp, vp, vp, vp]
-    lib.mcq_solve_device.restype = ctypes.c_int
-    lib.mcq_solve_host.argtypes = lib.mcq_solve_device.argtypes
-    lib.mcq_solve_host.restype = ctypes.c_int
-    lib.mcq_iqp_device.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, vp, ctypes.c_double, ctypes.c_double,
-                                   ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.POINTER(McqOpts), vp, vp, vp,
-                                   vp, vp, vp, ctypes.POINTER(McqIqpStats)]
-    lib.mcq_iqp_device.restype = ctypes.c_int
-    lib.mcq_iqp_batch.argtypes = [vp, ctypes.POINTER(McqProblem), ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_double,
-                                  ctypes.c_int, ctypes.POINTER(McqOpts), ctypes.c_int, _dp, _dp, _dp, _ip, _dp, _ip, _ip, _dp,
-                                  ctypes.POINTER(McqIqpStats)]
-    lib.mcq_iqp_batch.restype = ctypes.c_int
-    lib.mcq_iqp_set_round_callback.argtypes = [vp, IQP_ROUND_CB, vp]
-    lib.mcq_iqp_set_round_callback.restype = ctypes.c_int
-    lib.mcq_last_upload_was_direct.argtypes = [vp]
-    lib.mcq_last_upload_was_direct.restype = ctypes.c_int
-    lib.mcq_les_scalings.argtypes = [vp, ctypes.c_int, vp, ctypes.c_int]
-    lib.mcq_les_scalings.restype = ctypes.c_int
-    lib.mcq_les_scalings_open.argtypes = [vp, ctypes.c_int, vp, ctypes.c_int]
-    lib.mcq_les_scalings_open.restype = ctypes.c_int
-    lib.mcq_solve_batch_ends.argtypes = [vp, ctypes.POINTER(McqProblem), ctypes.POINTER(McqEnds), ctypes.c_int, ctypes.POINTER(McqOpts), _dp,
-                                         _dp, _ip, ctypes.POINTER(McqInfo)]
-    lib.mcq_solve_batch_ends.restype = ctypes.c_int
-    lib.mcq_host_alloc.argtypes = [vp, ctypes.c_size_t, ctypes.POINTER(vp)]
-    lib.mcq_host_alloc.restype = ctypes.c_int
-    lib.mcq_host_free.argtypes = [vp, vp]
-    lib.mcq_host_free.restype = ctypes.c_int
-    lib.mcq_solve_device_f32.argtypes = lib.mcq_solve_device.argtypes
-    lib.mcq_solve_device_f32.restype = ctypes.c_int
-    lib.mcq_solve_device_f32_rows.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_double, ctypes.c_double,
-                                              ctypes.POINTER(McqOpts), vp, vp, vp, vp]
-    lib.mcq_solve_device_f32_rows.restype = ctypes.c_int
-    lib.mcq_solve_batch_f32.argtypes = lib.mcq_solve_device_f32_rows.argtypes
-    lib.mcq_solve_batch_f32.restype = ctypes.c_int
-    lib.mcq_solve_host_pipelined.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, ctypes.c_double, ctypes.c_double,
-                                             ctypes.POINTER(McqOpts), vp, vp, vp]
-    lib.mcq_solve_host_pipelined.restype = ctypes.c_int
-    lib.mcq_solve_device_stream.argtypes = lib.mcq_solve_host_pipelined.argtypes
-    lib.mcq_solve_device_stream.restype = ctypes.c_int
-    lib.mcq_solve_device_ragged.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, ctypes.c_double,
-                                            ctypes.c_double, ctypes.POINTER(McqOpts), vp, vp, vp, vp]
-    lib.mcq_solve_device_ragged.restype = ctypes.c_int
-    lib.mcq_solve_device_ragged_params.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, ctypes.c_double,
-                                                   ctypes.c_double, vp, vp, ctypes.POINTER(McqOpts), vp, vp, vp, vp]
-    lib.mcq_solve_device_ragged_params.restype = ctypes.c_int
-    lib.mcq_prep_device.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp]
-    lib.mcq_prep_device.restype = ctypes.c_int
-    lib.mcq_relinearise_device.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, ctypes.c_double,
-                                           ctypes.c_double, vp, vp, vp, vp]
-    lib.mcq_relinearise_device.restype = ctypes.c_int
-    lib.mcq_vel_profile_device.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, ctypes.c_int, vp,
-                                           ctypes.c_int, vp, vp, vp, ctypes.c_double, vp, vp]
-    lib.mcq_vel_profile_device.restype = ctypes.c_int
-    lib.mcq_vel_profile_device_ragged.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, ctypes.c_int, vp,
-                                                  ctypes.c_int, vp, vp, vp, ctypes.c_double, vp, vp]
-    lib.mcq_vel_profile_device_ragged.restype = ctypes.c_int
-    lib.mcq_vel_profile_device_opts.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, ctypes.c_int, vp,
-                                                ctypes.c_int, vp, vp, vp, ctypes.POINTER(McqVelOpts), vp, vp]
-    lib.mcq_vel_profile_device_opts.restype = ctypes.c_int
-    lib.mcq_vel_profile_device_forms.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, ctypes.c_int, vp,
-                                                 ctypes.c_int, vp, vp, vp, ctypes.POINTER(McqVelForms), vp, vp]
-    lib.mcq_vel_profile_device_forms.restype = ctypes.c_int
-    lib.mcq_raceline_device.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, ctypes.c_double, ctypes.c_int, vp, vp,
-                                        vp, vp, vp, vp]
-    lib.mcq_raceline_device.restype = ctypes.c_int
-    lib.mcq_raceline_device_ends.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, vp, ctypes.c_double, ctypes.c_int, vp, vp,
-                                             vp, vp, vp, vp]
-    lib.mcq_raceline_device_ends.restype = ctypes.c_int
-    ci, cd = ctypes.c_int, ctypes.c_double
-    lib.mcq_trajectory_device.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, ci, vp, ci, cd, vp, vp, vp, vp, vp]
-    lib.mcq_trajectory_device.restype = ctypes.c_int
-    lib.mcq_bound_dists_device.argtypes = [vp, ci, ci, vp, vp, vp, ci, vp, vp, vp, cd, cd, vp, vp, cd, ci, vp, vp, vp, vp, vp]
-    lib.mcq_bound_dists_device.restype = ctypes.c_int
-    lib.mcq_spline_approx_device.argtypes = [vp, ci, ci, vp, vp, ci, ci, vp, vp, vp, cd, ci, vp, vp, vp, vp, vp, vp, vp]
-    lib.mcq_spline_approx_device.restype = ctypes.c_int
-    lib.mcq_min_width_device.argtypes = [vp, ci, ci, vp, vp, cd, vp]
-    lib.mcq_min_width_device.restype = ctypes.c_int
-    lib.mcq_normals_crossing_device.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, ctypes.c_int, vp]
-    lib.mcq_normals_crossing_device.restype = ctypes.c_int
-    lib.mcq_device_alloc.argtypes = [vp, ctypes.c_size_t, ctypes.POINTER(vp)]
-    lib.mcq_device_alloc.restype = ctypes.c_int
-    lib.mcq_device_free.argtypes = [vp, vp]
-    lib.mcq_device_free.restype = ctypes.c_int
-    lib.mcq_copy_to_device.argtypes = [vp, vp, vp, ctypes.c_size_t]
-    lib.mcq_copy_to_device.restype = ctypes.c_int
-    lib.mcq_copy_to_host.argtypes = [vp, vp, vp, ctypes.c_size_t]
-    lib.mcq_copy_to_host.restype = ctypes.c_int
-    lib.mcq_sync.argtypes = [vp]
-    lib.mcq_sync.restype = ctypes.c_int
-    lib.mcq_stream.argtypes = [vp]
-    lib.mcq_stream.restype = vp
-    lib.mcq_last_timing.argtypes = [vp, ctypes.POINTER(ctypes.c_float * 5)]
-    lib.mcq_last_timing.restype = ctypes.c_int
-    lib.mcq_timing_begin.argtypes = [vp]
-    lib.mcq_timing_begin.restype = ctypes.c_int
-    lib.mcq_timing_end.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int)]
-    lib.mcq_timing_end.restype = ctypes.c_int
-    lib.mcq_workspace_bytes.argtypes = [vp]
-    lib.mcq_workspace_bytes.restype = ctypes.c_longlong
-    lib.mcq_comm_unique_id.argtypes = [ctypes.c_char_p]
-    lib.mcq_comm_unique_id.restype = ctypes.c_int
-    lib.mcq_comm_init.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_char_p]
-    lib.mcq_comm_init.restype = ctypes.c_int
-    lib.mcq_comm_allgather.argtypes = [vp, vp, vp, ctypes.c_size_t, ctypes.c_int]
-    lib.mcq_comm_allgather.restype = ctypes.c_int
-    lib.mcq_comm_wait.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]
-    lib.mcq_comm_wait.restype = ctypes.c_int
-    lib.mcq_comm_world.argtypes = [vp, _ip, _ip]
-    lib.mcq_comm_world.restype = ctypes.c_int
-    lib.mcq_comm_destroy.argtypes = [vp]
-    lib.mcq_comm_destroy.restype = ctypes.c_int
+    for name, (restype, argtypes) in _ABI.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     return lib
 
 
@@ -300,6 +232,61 @@ def increments_to_rows(rows32, origin=None):
     if origin is not None:
         xy = xy + np.asarray(origin, dtype=np.float64)[..., None, :]
     return np.concatenate((xy, r[..., 2:]), axis=-1)
+
+
+def _pad_rows(rows, cols, nmin=0, strict=True):
+    """A ragged list of [n_k, c] arrays as (ns int32 [B], padded float64 [B, max(nmax, nmin), cols]), zeros behind each n_k.  strict: a row
+    with fewer than `cols` columns is numpy's ValueError; strict=False zero-fills its missing columns."""
+    rows = [np.asarray(r, dtype=np.float64)[:, :cols] for r in rows]
+    ns = np.array([r.shape[0] for r in rows], dtype=np.int32)
+    out = np.zeros((len(rows), max(int(ns.max()), nmin), cols))
+    for k, r in enumerate(rows):
+        out[k, :ns[k], :cols if strict else r.shape[1]] = r
+    return ns, out
+
+
+def _pad_like(rows, ns, tail=(), nmin=0):
+    """A second list (normals: tail (2,); alphas: ()) behind the lengths of a packed one, [B, max(nmax, nmin)] + tail: row k must fill ns[k] rows."""
+    out = np.zeros((len(rows), max(int(ns.max()), nmin)) + tail)
+    for k, r in enumerate(rows):
+        out[k, :ns[k]] = r
+    return out
+
+
+class _Scope:
+    """The device allocations of one call (Engine.scope): freed on exit, in allocation order, with or without an exception in flight."""
+
+    def __init__(self, eng):
+        self.eng, self.ptrs = eng, []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        while self.ptrs:
+            self.eng.free(self.ptrs.pop(0))
+
+    def new(self, nbytes):
+        self.ptrs.append(self.eng.alloc(nbytes))
+        return self.ptrs[-1]
+
+    def up(self, a):
+        """Pointer to a device copy of the array (made contiguous); None for None."""
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a)
+        self.eng.upload(self.new(a.nbytes), a)
+        return self.ptrs[-1]
+
+    def adopt(self, ptr):
+        """A pointer another scope released: this one frees it."""
+        self.ptrs.append(ptr)
+        return ptr
+
+    def release(self, ptr):
+        """The pointer leaves the scope: the caller frees it."""
+        self.ptrs.remove(ptr)
+        return ptr
 
 
 class Engine:
@@ -645,31 +632,15 @@ class Engine:
         bsz, n = ref.shape[0], ref.shape[1]
         nv = None if normvec is None else np.ascontiguousarray(normvec, dtype=np.float32)
         sc = None if scaling is None else np.ascontiguousarray(scaling, dtype=np.float32)
-        bufs = []
-
-        def up(a):
-            p = self.alloc(a.nbytes)
-            bufs.append(p)
-            self.upload(p, a)
-            return p
-
-        try:
-            d_ref = up(ref)
-            d_nv = up(nv) if nv is not None else None
-            d_sc = up(sc) if sc is not None else None
-            d_alpha = self.alloc(bsz * n * 4); bufs.append(d_alpha)
-            d_curv = self.alloc(bsz * 8); bufs.append(d_curv)
-            d_status = self.alloc(bsz * 4); bufs.append(d_status)
-            d_info = self.alloc(bsz * ctypes.sizeof(McqInfo)); bufs.append(d_info)
+        with self.scope() as dev:
+            d_ref, d_nv, d_sc = dev.up(ref), dev.up(nv), dev.up(sc)
+            d_alpha, d_curv, d_status, d_info = dev.new(bsz * n * 4), dev.new(bsz * 8), dev.new(bsz * 4), dev.new(bsz * ctypes.sizeof(McqInfo))
             self.solve_device_f32(bsz, n, d_ref, d_nv, d_sc, kappa_bound, w_veh, d_alpha, d_curv, d_status, d_info, **opt_kw)
             self.sync()
             alpha = self.download(d_alpha, (bsz, n), np.float32)
             curv = self.download(d_curv, (bsz,), np.float64)
             status = self.download(d_status, (bsz,), np.int32)
             raw = self.download(d_info, (bsz * ctypes.sizeof(McqInfo),), np.uint8)
-        finally:
-            for p in bufs:
-                self.free(p)
         infos = (McqInfo * bsz).from_buffer_copy(raw.tobytes())
         info = [dict(ipm_iters=i.ipm_iters, as_iters=i.as_iters, n_active_box=i.n_active_box,
                      n_active_kappa=i.n_active_kappa, kappa_max=i.kappa_max, kkt_res=i.kkt_res) for i in infos]
@@ -697,24 +668,15 @@ class Engine:
     def prep_batch(self, reftracks):
         """Unit normals and spline scalings of the closed distance-scaled splines through a list of reference lines
         ([n,>=2] arrays), computed on the device (mcq_prep_device).  Returns (list of [n,2], list of [n])."""
-        bsz = len(reftracks)
-        ns = np.array([r.shape[0] for r in reftracks], dtype=np.int32)
-        nmax = int(ns.max())
-        ref = np.zeros((bsz, nmax, 4))
-        for k, r in enumerate(reftracks):
-            ref[k, :ns[k], :min(4, r.shape[1])] = np.asarray(r, dtype=np.float64)[:, :4]
-        d_ref, d_n = self.alloc(ref.nbytes), self.alloc(ns.nbytes)
-        d_nv, d_sc, d_st = self.alloc(bsz * nmax * 16), self.alloc(bsz * nmax * 8), self.alloc(bsz * 4)
-        try:
-            self.upload(d_ref, ref)
-            self.upload(d_n, ns)
+        ns, ref = _pad_rows(reftracks, 4, strict=False)
+        bsz, nmax = ref.shape[:2]
+        with self.scope() as dev:
+            d_ref, d_n = dev.up(ref), dev.up(ns)
+            d_nv, d_sc, d_st = dev.new(bsz * nmax * 16), dev.new(bsz * nmax * 8), dev.new(bsz * 4)
             self._check(self.lib.mcq_prep_device(self.h, bsz, nmax, d_n, d_ref, d_nv, d_sc, d_st), "mcq_prep_device")
             st = self.download(d_st, (bsz,), np.int32)
             nv = self.download(d_nv, (bsz, nmax, 2), np.float64)
             sc = self.download(d_sc, (bsz, nmax), np.float64)
-        finally:
-            for p in (d_ref, d_n, d_nv, d_sc, d_st):
-                self.free(p)
         if np.any(st != 0):
             raise EngineError("mcq_prep_device: bad input in problem(s) %s" % np.nonzero(st)[0].tolist())
         return [nv[k, :ns[k]].copy() for k in range(bsz)], [sc[k, :ns[k]].copy() for k in range(bsz)]
@@ -775,28 +737,18 @@ class Engine:
                 raise RuntimeError("kappa and mu must have the same length!")
         tr = None if track_of is None else np.ascontiguousarray(track_of, dtype=np.int32)
         nt = None if n_of_track is None else np.ascontiguousarray(n_of_track, dtype=np.int32)
-        ptrs = []
-
-        def up(a):
-            p = self.alloc(a.nbytes)
-            ptrs.append(p)
-            self.upload(p, a)
-            return p
-        try:
+        with self.scope() as dev:
+            up = dev.up
             d_k, d_e, d_a = up(kappa), up(el), up(axm)
-            d_g, n_g = (up(ggv), ggv.shape[1]) if ggv is not None else (None, 0)
+            d_g, n_g = up(ggv), ggv.shape[1] if ggv is not None else 0
             d_s = [up(a) for a in scal]
-            d_t = up(tr) if tr is not None else None
-            d_vx = self.alloc(bsz * n * 8); ptrs.append(d_vx)
-            d_lt = self.alloc(bsz * 8); ptrs.append(d_lt)
-            d_n = up(nt) if nt is not None else None
-            d_mu = up(mu) if mu is not None else None
-            d_lg = up(loc_gg) if loc_gg is not None else None
+            d_t, d_vx, d_lt = up(tr), dev.new(bsz * n * 8), dev.new(bsz * 8)
+            d_n, d_mu, d_lg = up(nt), up(mu), up(loc_gg)
             d_vs = d_ve = None
             if not closed:
-                d_vs = up(np.ascontiguousarray(np.broadcast_to(np.asarray(v_start, dtype=np.float64), (bsz,))))
+                d_vs = up(np.broadcast_to(np.asarray(v_start, dtype=np.float64), (bsz,)))
                 if v_end is not None:
-                    d_ve = up(np.ascontiguousarray(np.broadcast_to(np.asarray(v_end, dtype=np.float64), (bsz,))))
+                    d_ve = up(np.broadcast_to(np.asarray(v_end, dtype=np.float64), (bsz,)))
             if timed:
                 self.timing_begin()
             if not closed or loc_gg is not None:
@@ -819,33 +771,18 @@ class Engine:
             ms = self.timing_end()[0] if timed else None
             res = (self.download(d_vx, (bsz, n), np.float64), self.download(d_lt, (bsz,), np.float64))
             return res + (ms,) if timed else res
-        finally:
-            for p in ptrs:
-                self.free(p)
 
     def normals_crossing_batch(self, reftracks, normvecs, horizon=10):
         """tph.check_normals_crossing of a list of tracks on the device [REF helper_funcs_glob/src/prep_track.py:57-59].
         Returns an int32 array: 1 crossing, 0 none, -1 where tph would raise (horizon >= n)."""
-        bsz = len(reftracks)
-        ns = np.array([np.asarray(r).shape[0] for r in reftracks], dtype=np.int32)
-        nmax = int(ns.max())
-        ref = np.zeros((bsz, nmax, 4))
-        nv = np.zeros((bsz, nmax, 2))
-        for k in range(bsz):
-            ref[k, :ns[k]] = np.asarray(reftracks[k], dtype=np.float64)[:, :4]
-            nv[k, :ns[k]] = normvecs[k]
-        ptrs = []
-        try:
-            for a in (ref, nv, ns):
-                ptrs.append(self.alloc(a.nbytes))
-                self.upload(ptrs[-1], a)
-            ptrs.append(self.alloc(bsz * 4))
-            rc = self.lib.mcq_normals_crossing_device(self.h, bsz, nmax, ptrs[2], ptrs[0], ptrs[1], int(horizon), ptrs[3])
+        ns, ref = _pad_rows(reftracks, 4)
+        nv = _pad_like(normvecs, ns, (2,))
+        bsz, nmax = ref.shape[:2]
+        with self.scope() as dev:
+            d_ref, d_nv, d_n, d_out = dev.up(ref), dev.up(nv), dev.up(ns), dev.new(bsz * 4)
+            rc = self.lib.mcq_normals_crossing_device(self.h, bsz, nmax, d_n, d_ref, d_nv, int(horizon), d_out)
             self._check(rc, "mcq_normals_crossing_device")
-            return self.download(ptrs[3], (bsz,), np.int32)
-        finally:
-            for p in ptrs:
-                self.free(p)
+            return self.download(d_out, (bsz,), np.int32)
 
     def spline_approx_device(self, tracks, nmax, d_n, d_track, k, nkmax, d_nk, d_knots, d_coef, stepsize_reg, mmax, d_ref, d_m, d_ct, d_dist,
                              d_dev, d_nonmono, d_status):
@@ -884,30 +821,15 @@ class Engine:
         Returns a dict: reftrack -- list of (m_k, 4) arrays (None where status != 0) --, m [B], closest_t / dists [B, nmax + 1] (NaN behind n_k),
         dev [B, 2] = mean and maximum deviation, nonmono [B], status [B].
         keep: a list that receives (d_ref, d_n, mmax) -- the rows stay on the device, padded to mmax, and the caller frees both (prep_track_batch)."""
-        bsz = len(tracks)
-        ns = np.array([np.asarray(r).shape[0] for r in tracks], dtype=np.int32)
-        nmax = max(int(ns.max()), 3)
-        trk = np.zeros((bsz, nmax, 4))
-        for b in range(bsz):
-            trk[b, :ns[b]] = np.asarray(tracks[b], dtype=np.float64)[:, :4]
+        ns, trk = _pad_rows(tracks, 4, nmin=3)
+        bsz, nmax = trk.shape[:2]
         k, nk, knots, coef = self.pack_tcks(tcks)
         if mmax is None:      # a smoothed line is shorter than its raw one: room for one twice as long (a track that needs more reports its m)
             el = [float(np.sum(np.hypot(*(np.diff(np.vstack((trk[b, :ns[b], :2], trk[b, :1, :2])), axis=0).T)))) for b in range(bsz)]
             finite = [e for e in el if np.isfinite(e)]
             mmax = max(int(2.0 * max(finite + [0.0]) / float(stepsize_reg)) + 8, 8)
-        ptrs = []
-
-        def up(a):
-            q = self.alloc(a.nbytes)
-            ptrs.append(q)
-            self.upload(q, a)
-            return q
-
-        def new(nbytes):
-            q = self.alloc(nbytes)
-            ptrs.append(q)
-            return q
-        try:
+        with self.scope() as dev:
+            up, new = dev.up, dev.new
             d_trk, d_n, d_nk, d_kn, d_cf = up(trk), up(ns), up(nk), up(knots), up(coef)
             d_m, d_ct, d_ds, d_dev, d_nm, d_st = new(bsz * 4), new(bsz * (nmax + 1) * 8), new(bsz * (nmax + 1) * 8), new(bsz * 16), new(bsz * 4), new(bsz * 4)
             d_ref = new(bsz * mmax * 32)
@@ -920,33 +842,19 @@ class Engine:
                        closest_t=self.download(d_ct, (bsz, nmax + 1), np.float64), dists=self.download(d_ds, (bsz, nmax + 1), np.float64),
                        dev=self.download(d_dev, (bsz, 2), np.float64), nonmono=self.download(d_nm, (bsz,), np.int32))
             if keep is not None:
-                ptrs.remove(d_ref)
-                ptrs.remove(d_m)
-                keep.extend((d_ref, d_m, mmax))
+                keep.extend((dev.release(d_ref), dev.release(d_m), mmax))
             return out
-        finally:
-            for q in ptrs:
-                self.free(q)
 
     def min_width_batch(self, reftracks, min_width):
         """prep_track's tail for a list of prepared tracks (mcq_min_width_device): rows narrower than min_width grow by half the deficit on both
         sides.  Returns (list of [n, 4] arrays, changed [B] int32: 1 where upstream would print its warning)."""
-        bsz = len(reftracks)
-        ns = np.array([np.asarray(r).shape[0] for r in reftracks], dtype=np.int32)
-        nmax = int(ns.max())
-        ref = np.zeros((bsz, nmax, 4))
-        for b in range(bsz):
-            ref[b, :ns[b]] = np.asarray(reftracks[b], dtype=np.float64)[:, :4]
-        d_ref, d_n, d_ch = self.alloc(ref.nbytes), self.alloc(ns.nbytes), self.alloc(bsz * 4)
-        try:
-            self.upload(d_ref, ref)
-            self.upload(d_n, ns)
+        ns, ref = _pad_rows(reftracks, 4)
+        bsz, nmax = ref.shape[:2]
+        with self.scope() as dev:
+            d_ref, d_n, d_ch = dev.up(ref), dev.up(ns), dev.new(bsz * 4)
             self.min_width_device(bsz, nmax, d_n, d_ref, min_width, d_ch)
             out = self.download(d_ref, (bsz, nmax, 4), np.float64)
             return [out[b, :ns[b]].copy() for b in range(bsz)], self.download(d_ch, (bsz,), np.int32)
-        finally:
-            for q in (d_ref, d_n, d_ch):
-                self.free(q)
 
     def prep_track_batch(self, tracks, k_reg=3, s_reg=10, stepsize_prep=1.0, stepsize_reg=3.0, min_width=None, tcks=None, horizon=10):
         """prep_track [REF helper_funcs_glob/src/prep_track.py] for a list of raw tracks ([n_k, 4] rows, not closed).  On the host, per track:
@@ -967,14 +875,11 @@ class Engine:
         bsz = len(tracks)
         keep = []
         out = self.spline_approx_batch(tracks, tcks, stepsize_reg, keep=keep)
-        d_ref, d_m, mmax = keep
-        ptrs = [d_ref, d_m]
-        try:
+        with self.scope() as dev:
+            d_ref, d_m, mmax = dev.adopt(keep[0]), dev.adopt(keep[1]), keep[2]
             if np.any(out["status"] != 0):      # a refused track has no rows: the kernels behind must not take its m_out (the rows it would need) for a length
                 self.upload(d_m, np.where(out["status"] == 0, out["m"], 0).astype(np.int32))
-            d_nv, d_sc, d_st, d_cr, d_ch = (self.alloc(bsz * mmax * 16), self.alloc(bsz * mmax * 8), self.alloc(bsz * 4), self.alloc(bsz * 4),
-                                            self.alloc(bsz * 4))
-            ptrs += [d_nv, d_sc, d_st, d_cr, d_ch]
+            d_nv, d_sc, d_st, d_cr, d_ch = dev.new(bsz * mmax * 16), dev.new(bsz * mmax * 8), dev.new(bsz * 4), dev.new(bsz * 4), dev.new(bsz * 4)
             self._check(self.lib.mcq_prep_device(self.h, bsz, mmax, d_m, d_ref, d_nv, d_sc, d_st), "mcq_prep_device")
             self._check(self.lib.mcq_normals_crossing_device(self.h, bsz, mmax, d_m, d_ref, d_nv, int(horizon), d_cr), "mcq_normals_crossing_device")
             if min_width is not None:
@@ -991,9 +896,6 @@ class Engine:
                         crossing=self.download(d_cr, (bsz,), np.int32),
                         inflated=self.download(d_ch, (bsz,), np.int32) if min_width is not None else np.zeros(bsz, dtype=np.int32), status=st, m=m,
                         dev=out["dev"], nonmono=out["nonmono"], tcks=tcks)
-        finally:
-            for q in ptrs:
-                self.free(q)
 
     def raceline_device_ends(self, batch, nmax, d_n, d_ref, d_nv, d_alpha, d_closed, d_psi, stepsize, mmax, d_xy, d_psi_out, d_kappa,
                              d_el, d_m, d_status):
@@ -1011,34 +913,15 @@ class Engine:
         with psi_s, psi_e (fix_s / fix_e are ignored): that track is an open chain (mcq_raceline_device_ends: the open unit-scaling spline
         with the solver's heading rows, every station kept, the last one being the last raceline point); el_lengths[:m - 1] are its
         elements and el_lengths[m - 1] is 0."""
-        bsz = len(reftracks)
-        ns = np.array([np.asarray(r).shape[0] for r in reftracks], dtype=np.int32)
-        nmax = int(ns.max())
-        ref = np.zeros((bsz, nmax, 4))
-        nv = np.zeros((bsz, nmax, 2))
-        al = np.zeros((bsz, nmax))
-        for k in range(bsz):
-            r = np.asarray(reftracks[k], dtype=np.float64)
-            ref[k, :ns[k], :min(4, r.shape[1])] = r[:, :4]
-            nv[k, :ns[k]] = normvecs[k]
-            al[k, :ns[k]] = alphas[k]
+        ns, ref = _pad_rows(reftracks, 4, strict=False)
+        nv, al = _pad_like(normvecs, ns, (2,)), _pad_like(alphas, ns)
+        bsz, nmax = ref.shape[:2]
         if mmax is None:      # polygon length + the widest shift bounds the raceline length from above generously
             per = [float(np.sum(np.hypot(*np.diff(np.vstack((r[:, :2], r[:1, :2])), axis=0).T)) + 8.0 * np.sum(np.abs(a)))
                    for r, a in zip(reftracks, alphas)]
             mmax = int(max(per) / float(stepsize) * 1.25) + 16
-        ptrs = []
-
-        def up(a):
-            p = self.alloc(a.nbytes)
-            ptrs.append(p)
-            self.upload(p, a)
-            return p
-
-        def new(nbytes):
-            p = self.alloc(nbytes)
-            ptrs.append(p)
-            return p
-        try:
+        with self.scope() as dev:
+            up, new = dev.up, dev.new
             d_ref, d_nv, d_al, d_n = up(ref), up(nv), up(al), up(ns)
             d_xy, d_psi, d_k, d_el = new(bsz * mmax * 16), new(bsz * mmax * 8), new(bsz * mmax * 8), new(bsz * mmax * 8)
             d_m, d_st = new(bsz * 4), new(bsz * 4)
@@ -1060,9 +943,6 @@ class Engine:
                         kappa=self.download(d_k, (bsz, mmax), np.float64),
                         el_lengths=self.download(d_el, (bsz, mmax), np.float64),
                         m=self.download(d_m, (bsz,), np.int32), status=self.download(d_st, (bsz,), np.int32))
-        finally:
-            for p in ptrs:
-                self.free(p)
 
     def trajectory_device(self, batch, m, mmax, d_m_of_track, d_track_of, d_xy, d_psi, d_kappa, d_el, d_vx, closed, d_drag, d_mass, d_vmax,
                           d_ggv, n_ggv, d_axm, n_machines, curvlim, d_traj, d_t, d_length, d_limits, d_flags):
@@ -1109,25 +989,12 @@ class Engine:
         if (ggv is not None and ggv.shape[0] != bsz) or (axm is not None and axm.shape[0] != bsz):
             raise ValueError("trajectory_batch: ggv / ax_max_machines need one table per variant")
         tr = None if track_of is None else np.ascontiguousarray(track_of, dtype=np.int32)
-        ptrs = []
-
-        def up(a):
-            p = self.alloc(a.nbytes)
-            ptrs.append(p)
-            self.upload(p, a)
-            return p
-
-        def new(nbytes):
-            p = self.alloc(nbytes)
-            ptrs.append(p)
-            return p
-        try:
+        with self.scope() as dev:
+            up, new = dev.up, dev.new
             d_xy, d_psi, d_k, d_el = up(xy), up(arrs[0]), up(arrs[1]), up(arrs[2])
             d_m, d_vx = up(ms), up(vx)
             d_s = [up(a) for a in scal]
-            d_g = up(ggv) if ggv is not None else None
-            d_a = up(axm) if axm is not None else None
-            d_t = up(tr) if tr is not None else None
+            d_g, d_a, d_t = up(ggv), up(axm), up(tr)
             d_traj, d_time = new(bsz * mmax * TRAJ_COLS * 8), new(bsz * (mmax + 1) * 8)
             d_len, d_lim, d_fl = new(bsz * 8), new(bsz * TRAJ_NLIM * 8), new(bsz * 4)
             self.trajectory_device(bsz, 0, mmax, d_m, d_t, d_xy, d_psi, d_k, d_el, d_vx, closed, d_s[0], d_s[1], d_s[2], d_g,
@@ -1136,9 +1003,6 @@ class Engine:
             return dict(traj=self.download(d_traj, (bsz, mmax, TRAJ_COLS), np.float64), t=self.download(d_time, (bsz, mmax + 1), np.float64),
                         length=self.download(d_len, (bsz,), np.float64), limits=self.download(d_lim, (bsz, TRAJ_NLIM), np.float64),
                         flags=self.download(d_fl, (bsz,), np.int32))
-        finally:
-            for p in ptrs:
-                self.free(p)
 
     def bound_dists_batch(self, reftracks, normvecs, race, length_veh, width_veh, stepsize_bound=1.0, first_row_only=False):
         """check_traj's first block for a list of tracks (mcq_bound_dists_device) [REF helper_funcs_glob/src/check_traj.py:47-70]: the distance
@@ -1147,14 +1011,9 @@ class Engine:
         of each boundary only, which is what the reference's call computes (include/mcq.h: MCQ_BOUNDS_FIRST_ROW).
         Returns a dict: min_dists [tracks, mmax] (NaN behind a track's m), min_dist [tracks], nb [tracks, 2] (samples per boundary, right
         first), bound_r / bound_l [tracks, nmax, 2] (the raw boundaries check_traj returns; NaN behind a track's n), status [tracks]."""
-        bsz = len(reftracks)
-        ns = np.array([np.asarray(r).shape[0] for r in reftracks], dtype=np.int32)
-        nmax = max(int(ns.max()), 3)
-        ref = np.zeros((bsz, nmax, 4))
-        nv = np.zeros((bsz, nmax, 2))
-        for k in range(bsz):
-            ref[k, :ns[k]] = np.asarray(reftracks[k], dtype=np.float64)[:, :4]
-            nv[k, :ns[k]] = normvecs[k]
+        ns, ref = _pad_rows(reftracks, 4, nmin=3)
+        nv = _pad_like(normvecs, ns, (2,), nmin=3)
+        bsz, nmax = ref.shape[:2]
         xy = np.ascontiguousarray(race["xy"], dtype=np.float64)
         psi = np.ascontiguousarray(race["psi"], dtype=np.float64)
         ms = np.ascontiguousarray(race["m"], dtype=np.int32)
@@ -1162,22 +1021,11 @@ class Engine:
             raise ValueError("bound_dists_batch: race must hold one row per track")
         mmax = xy.shape[1]
         lens, wids = np.asarray(length_veh, dtype=np.float64), np.asarray(width_veh, dtype=np.float64)
-        ptrs = []
-
-        def up(a):
-            p = self.alloc(a.nbytes)
-            ptrs.append(p)
-            self.upload(p, a)
-            return p
-
-        def new(nbytes):
-            p = self.alloc(nbytes)
-            ptrs.append(p)
-            return p
-        try:
+        with self.scope() as dev:
+            up, new = dev.up, dev.new
             d_ref, d_nv, d_n, d_xy, d_psi, d_m = up(ref), up(nv), up(ns), up(xy), up(psi), up(ms)
-            d_ll = up(np.ascontiguousarray(np.broadcast_to(lens, (bsz,)))) if lens.ndim else None
-            d_wl = up(np.ascontiguousarray(np.broadcast_to(wids, (bsz,)))) if wids.ndim else None
+            d_ll = up(np.broadcast_to(lens, (bsz,))) if lens.ndim else None
+            d_wl = up(np.broadcast_to(wids, (bsz,))) if wids.ndim else None
             d_md, d_mn, d_nb, d_bd, d_st = new(bsz * mmax * 8), new(bsz * 8), new(bsz * 8), new(bsz * 2 * nmax * 16), new(bsz * 4)
             self.bound_dists_device(bsz, nmax, d_n, d_ref, d_nv, mmax, d_m, d_xy, d_psi, 0.0 if lens.ndim else float(lens),
                                     0.0 if wids.ndim else float(wids), d_ll, d_wl, stepsize_bound,
@@ -1186,9 +1034,6 @@ class Engine:
             return dict(min_dists=self.download(d_md, (bsz, mmax), np.float64), min_dist=self.download(d_mn, (bsz,), np.float64),
                         nb=self.download(d_nb, (bsz, 2), np.int32), bound_r=bound[:, 0].copy(), bound_l=bound[:, 1].copy(),
                         status=self.download(d_st, (bsz,), np.int32))
-        finally:
-            for p in ptrs:
-                self.free(p)
 
     def relinearise_device(self, batch, nmax, d_n_in, d_ref_in, d_nv_in, d_alpha, d_live, alpha_scale, stepsize,
                            d_ref_out, d_nv_out, d_n_out, d_status):
@@ -1212,6 +1057,10 @@ class Engine:
         self._check(self.lib.mcq_iqp_set_round_callback(self.h, self._iqp_cb, None), "mcq_iqp_set_round_callback")
 
     # ---- device memory plumbing (mcq_device_alloc & co): numpy in, numpy out, raw device pointers as ints ----------------
+    def scope(self):
+        """Context manager owning device allocations: up(array or None) / new(nbytes) give pointers it frees on exit, release(ptr) takes one out."""
+        return _Scope(self)
+
     def alloc(self, nbytes):
         p = ctypes.c_void_p()
         self._check(self.lib.mcq_device_alloc(self.h, int(nbytes), ctypes.byref(p)), "mcq_device_alloc")

@@ -99,19 +99,10 @@ def solve_sharded(problems: list, engine, dist=None, partition: str = "block", *
     # one send buffer per rank, [alpha per x nmax | curv per | status per (int32 in the first half of `per` doubles)]: the engine writes
     # its outputs straight into it, the collective reads it
     count = per * nmax + 2 * per
-    bufs = []
-
-    def dev(arr=None, nbytes=0):
-        p = engine.alloc(arr.nbytes if arr is not None else nbytes)
-        bufs.append(p)
-        if arr is not None:
-            engine.upload(p, arr)
-        return p
-
-    try:
-        d_ref, d_sc, d_n, d_kb, d_wv = dev(ref), dev(sc), dev(ns), dev(kb), dev(wv)
-        d_nv = dev(nv) if with_nv[0] else None
-        d_send = dev(nbytes=8 * count)                      # (mcq_device_alloc zero-fills: empty shards gather zeros)
+    with engine.scope() as dev:
+        d_ref, d_sc, d_n, d_kb, d_wv = dev.up(ref), dev.up(sc), dev.up(ns), dev.up(kb), dev.up(wv)
+        d_nv = dev.up(nv) if with_nv[0] else None
+        d_send = dev.new(8 * count)                         # (mcq_device_alloc zero-fills: empty shards gather zeros)
         d_alpha, d_curv, d_status = d_send, d_send + 8 * per * nmax, d_send + 8 * (per * nmax + per)
         if len(mine) > 0:
             engine.solve_device_ragged_params(per, nmax, d_n, d_ref, d_nv, d_sc, 0.0, 0.0, d_kb, d_wv, d_alpha, d_curv, d_status,
@@ -119,13 +110,10 @@ def solve_sharded(problems: list, engine, dist=None, partition: str = "block", *
         if world == 1 and not use_rccl:
             full = engine.download(d_send, (1, count), np.float64)
         else:
-            d_recv = dev(nbytes=8 * count * world)
+            d_recv = dev.new(8 * count * world)
             engine.comm_allgather(d_send, d_recv, count, engine.DT_F64)       # the single collective of the job: on the handle's COMM stream,
             engine.comm_wait(0)                                               # behind the solve; the receive buffer is complete after this
             full = engine.download(d_recv, (world, count), np.float64)
-    finally:
-        for p in bufs:
-            engine.free(p)
     out_a, out_c, out_s = [None] * bsz, np.zeros(bsz), np.zeros(bsz, dtype=np.int32)
     for r in range(world):
         al = full[r, :per * nmax].reshape(per, nmax)

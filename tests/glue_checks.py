@@ -73,14 +73,8 @@ def relin_device(eng, refs, nvs, alphas, alpha_scale, stepsize, nmax, live=None,
         ref_in[k, :n_in[k]] = refs[k]
         nv_in[k, :n_in[k]] = nvs[k]
         al[k, :n_in[k]] = alphas[k]
-    ptrs = []
-
-    def up(a):
-        p = eng.alloc(a.nbytes)
-        ptrs.append(p)
-        eng.upload(p, a)
-        return p
-    try:
+    with eng.scope() as dev:
+        up = dev.up
         d_n, d_ref, d_nv, d_al = up(n_in), up(ref_in), up(nv_in), up(al)
         d_live = up(np.ascontiguousarray(live, dtype=np.int32)) if live is not None else None
         d_ro, d_no = up(np.full((bsz, nmax, 4), NAN_PATTERN)), up(np.full((bsz, nmax, 2), NAN_PATTERN))
@@ -91,9 +85,6 @@ def relin_device(eng, refs, nvs, alphas, alpha_scale, stepsize, nmax, live=None,
         eng.sync()
         return (eng.download(d_ro, (bsz, nmax, 4), np.float64), eng.download(d_no, (bsz, nmax, 2), np.float64),
                 eng.download(d_m, (bsz,), np.int32), eng.download(d_st, (bsz,), np.int32))
-    finally:
-        for p in ptrs:
-            eng.free(p)
 
 
 def _untouched(a):

@@ -113,14 +113,8 @@ def _device_call(eng, refs, nvs, als, closed, psi, stepsize, mmax):
     ref, nv, al = np.zeros((bsz, nmax, 4)), np.zeros((bsz, nmax, 2)), np.zeros((bsz, nmax))
     for k in range(bsz):
         ref[k, :ns[k]], nv[k, :ns[k]], al[k, :ns[k]] = refs[k], nvs[k], als[k]
-    ptrs = []
-
-    def up(a):
-        p = eng.alloc(a.nbytes)
-        ptrs.append(p)
-        eng.upload(p, a)
-        return p
-    try:
+    with eng.scope() as dev:
+        up = dev.up
         d = [up(a) for a in (ns, ref, nv, al)]
         d_c = up(np.ascontiguousarray(closed, dtype=np.int32)) if closed is not None else None
         d_p = up(np.ascontiguousarray(psi, dtype=np.float64)) if psi is not None else None
@@ -131,9 +125,6 @@ def _device_call(eng, refs, nvs, als, closed, psi, stepsize, mmax):
         return dict(xy=eng.download(d_xy, (bsz, mmax, 2), np.float64), psi=eng.download(d_ps, (bsz, mmax), np.float64),
                     kappa=eng.download(d_k, (bsz, mmax), np.float64), el_lengths=eng.download(d_el, (bsz, mmax), np.float64),
                     m=eng.download(d_m, (bsz,), np.int32), status=eng.download(d_st, (bsz,), np.int32))
-    finally:
-        for p in ptrs:
-            eng.free(p)
 
 
 def check_arguments_and_status(eng, family):

@@ -90,28 +90,6 @@ def check_last_resort(lname, rows, out):
 
 
 # ---- the other entry points ---------------------------------------------------------------------------------------------------------------------
-class _Device:
-    """Device buffers of one check, freed together."""
-
-    def __init__(self, eng):
-        self.eng, self.ptrs = eng, []
-
-    def up(self, a):
-        a = np.ascontiguousarray(a)
-        p = self.eng.alloc(a.nbytes)
-        self.ptrs.append(p)
-        self.eng.upload(p, a)
-        return p
-
-    def out(self, shape, dtype, fill):
-        return self.up(np.full(shape, fill, dtype=dtype))
-
-    def free(self):
-        for p in self.ptrs:
-            self.eng.free(p)
-        self.ptrs = []
-
-
 def _stack(names):
     return np.stack([sc.case(x)[0] for x in names]), np.stack([sc.case(x)[1] for x in names])
 
@@ -149,13 +127,13 @@ def check_entry_points(eng, n, worst):
     # mcq_solve_host
     al, curv, st, info = eng.solve_host(refs, nvs, None, 1.0, sc.W_VEH, objective=SP)
     _expect("solve_host n=%d" % n, base, al, curv, st, [{q: getattr(i, q) for q in INFO_EXACT} for i in info])
-    D = _Device(eng)
-    try:
+    with eng.scope() as D:
         d_ref, d_nv = D.up(refs), D.up(nvs)
         d_n = D.up(np.full(bsz, n, dtype=np.int32))
 
         def outs():
-            return D.out((bsz, n), np.float64, np.nan), D.out(bsz, np.float64, np.nan), D.out(bsz, np.int32, -1), D.out(bsz * isz, np.uint8, 0xFF)
+            return (D.up(np.full((bsz, n), np.nan)), D.up(np.full(bsz, np.nan)), D.up(np.full(bsz, -1, dtype=np.int32)),
+                    D.up(np.full(bsz * isz, 0xFF, dtype=np.uint8)))
 
         def fetch(o):
             eng.sync()
@@ -190,8 +168,6 @@ def check_entry_points(eng, n, worst):
         for s in range(steps):
             got = fetch(os_[s])
             _expect("solve_device_stream n=%d step %d" % (n, s), base, got[0], got[1], got[2], None, rot[s])
-    finally:
-        D.free()
     # mcq_solve_host_pipelined: three steps
     alphas = [np.full((bsz, n), np.nan) for _ in range(steps)]
     curv, st = eng.solve_host_pipelined([refs[r] for r in rot], [nvs[r] for r in rot], None, 1.0, sc.W_VEH, alphas, objective=SP)

@@ -91,17 +91,9 @@ def forms_call(eng, L, closed=True, loc_gg=None, v_start=None, v_end=None, ggv="
     ggv = L["ggv"][o] if isinstance(ggv, str) else ggv
     mu = L["mu"] if isinstance(mu, str) else mu
     fw = L["filt_window"] if isinstance(filt_window, str) else filt_window
-    ptrs = []
-
-    def up(a, dtype=np.float64):
-        if a is None:
-            return None
-        a = np.ascontiguousarray(a, dtype=dtype)
-        p = eng.alloc(a.nbytes)
-        ptrs.append(p)
-        eng.upload(p, a)
-        return p
-    try:
+    with eng.scope() as dev:
+        def up(a, dtype=np.float64):
+            return dev.up(None if a is None else np.asarray(a, dtype=dtype))
         d_vx, d_lt = up(np.full((bsz, nmax), STALE)), up(np.full(bsz, STALE))
         vf = engine.McqVelForms(float(L["exp"]), int(fw or 0), 1 if closed else 0, up(mu), up(loc_gg),
                                 up(None if v_start is None else np.broadcast_to(np.asarray(v_start, dtype=np.float64), (bsz,))),
@@ -114,9 +106,6 @@ def forms_call(eng, L, closed=True, loc_gg=None, v_start=None, v_end=None, ggv="
             return rc, None, None
         eng.sync()
         return rc, eng.download(d_vx, (bsz, nmax), np.float64), eng.download(d_lt, (bsz,), np.float64)
-    finally:
-        for p in ptrs:
-            eng.free(p)
 
 
 def _rows_equal(L, a, b, flip=False):
