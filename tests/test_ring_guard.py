@@ -22,6 +22,8 @@ def test_every_ring_fixture_has_a_spread_entry():
         name = os.path.basename(path)[:-4]
         if name.startswith("open_") or name in ("harness_runs", "ring_spread", "glue_spread"):      # (glue_spread: tests/glue_guard.py's table)
             continue
+        if name == "gi_edges":      # (the Goldfarb-Idnani edge cases carry their spread per case, by the same draws and the same rule:
+            continue                #  tests/gi_cases.guard, held finite and positive by tests/test_gi_ref.py::test_case_is_decided)
         assert name in names, "ring fixture %s has no entry in ring_spread.npz (scripts/make_golden_ring_spread.py)" % name
     # the guard rule of tests/open_ref.py
     for name, what, k in have[:5]:
