@@ -1057,6 +1057,41 @@ extern "C" int mcq_min_width_device(mcq_handle* h, int batch, int nmax, const in
     return 0;
 }
 
+// ---- the export tables (include/mcq.h): the spline lengths per track, then the lookup and the rows per variant; two launches on the handle's stream
+extern "C" int mcq_export_device(mcq_handle* h, int tracks, int nmax, const int* n_list, const double* reftrack, const double* normvec,
+                                 const double* alpha, int batch, int mmax, const int* m_of_track, const int* track_of, const double* traj,
+                                 double* ltpl_out, int* idx_out, double* spline_lengths_out, double* s_ref_out, double* spline_total_out,
+                                 int* status_out)
+{
+    if (!h || tracks <= 0 || batch <= 0 || nmax < 3 || mmax < 2 || !reftrack || !normvec || !alpha || !traj || !ltpl_out ||
+        !spline_total_out || !status_out) {
+        g_err = "mcq_export_device: bad argument";
+        return MCQ_E_ARG;
+    }
+    const size_t nblk = ((size_t)nmax + MCQ_EX_ROWS) / MCQ_EX_ROWS;      // row blocks of a table of nmax + 1 rows
+    if ((size_t)batch * nblk > 0x7fffffffu) {
+        g_err = "mcq_export_device: more row blocks than one launch holds";
+        return MCQ_E_TOO_LARGE;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    int rc = ensure_workspace(h, 0, (size_t)tracks, (size_t)nmax);
+    if (rc) return rc;
+    McqExport X;
+    memset(&X, 0, sizeof(X));
+    X.tracks = tracks; X.nmax = nmax; X.batch = batch; X.mmax = mmax;
+    X.n_list = n_list; X.ref = reftrack; X.nv = normvec; X.alpha = alpha;
+    X.m_of_track = m_of_track; X.track_of = track_of; X.traj = traj;
+    X.vec = h->ws[0].vec;
+    X.ltpl = ltpl_out; X.idx = idx_out; X.len_out = spline_lengths_out; X.s_ref_out = s_ref_out; X.total_out = spline_total_out;
+    X.status = status_out;
+    hipStream_t st = h->ws[0].stream;
+    hipLaunchKernelGGL(mcq_export_s_kernel, dim3(tracks), dim3(256), 0, st, X);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(mcq_export_rows_kernel, dim3((unsigned)((size_t)batch * nblk)), dim3(256), 0, st, X);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // ---- device memory plumbing for callers that keep data resident between calls without a second HIP runtime in the
 //      process (the Python IQP driver): plain allocate / free / copy on the handle's device and stream ------------------
 extern "C" int mcq_device_alloc(mcq_handle* h, size_t bytes, void** out)

@@ -366,3 +366,31 @@ __global__ void mcq_spline_finish_kernel(McqSpline S);
 
 /* prep_track's tail [REF helper_funcs_glob/src/prep_track.py:89-98]: rows narrower than min_width grow by half the deficit on both sides. */
 __global__ void mcq_min_width_kernel(int nmax, const int* n_list, double* ref_all, double min_width, int* changed_out);
+
+/* ---- the export tables (mcq_export_device) [REF main_globaltraj.py:502-552, helper_funcs_glob/src/export_traj_ltpl.py:35-63].  Two launches:
+ *      mcq_export_s_kernel (a workgroup per TRACK: the raceline's own spline lengths at the reference waypoints and their running sum -- the front
+ *      half of mcq_raceline_kernel, kept in the slab's slots 6 / 7 for the second launch) and mcq_export_rows_kernel (a workgroup per variant and row block:
+ *      per waypoint the nearest station of the variant's s column, then the table, a lane per output element). ---- */
+#define MCQ_EX_RPT 4        /* table rows a thread of mcq_export_rows_kernel looks up */
+#define MCQ_EX_ROWS (256 * MCQ_EX_RPT)      /* table rows per workgroup: every workgroup reads the variant's whole s column, so fewer, larger row
+                                             * blocks read it less often (measured at config 4's shape: 4.10 ms with 256 rows, 2.47 ms with 1024; docs/NOTEBOOK.md "Export tables") */
+#define MCQ_EX_TILE 1024    /* stations of the s column per LDS tile */
+struct McqExport {
+    int tracks, nmax, batch, mmax;
+    const int* n_list;       // [tracks] or nullptr (all nmax)
+    const double* ref;       // [tracks][nmax][4]
+    const double* nv;        // [tracks][nmax][2]
+    const double* alpha;     // [tracks][nmax]
+    const int* m_of_track;   // [tracks] or nullptr (all mmax)
+    const int* track_of;     // [batch] or nullptr (row = variant)
+    const double* traj;      // [batch][mmax][MCQ_TRAJ_COLS]
+    double* vec;             // workspace, [tracks][MCQ_NVEC][nmax] (the solver's vector slab)
+    double* ltpl;            // [batch][nmax + 1][MCQ_LTPL_COLS]
+    int* idx;                // [batch][nmax] or nullptr
+    double* len_out;         // [tracks][nmax] or nullptr
+    double* s_ref_out;       // [tracks][nmax + 1] or nullptr
+    double* total_out;       // [tracks]
+    int* status;             // [batch]
+};
+__global__ void mcq_export_s_kernel(McqExport X);
+__global__ void mcq_export_rows_kernel(McqExport X);

@@ -4126,3 +4126,178 @@ __global__ void __launch_bounds__(MCQ_NT) mcq_min_width_kernel(int nmax, const i
     __syncthreads();
     if (tid == 0) ((gint*)changed_out)[tr] = s_any;
 }
+
+// ---- the export tables (mcq_export_device) [REF main_globaltraj.py:502-552, helper_funcs_glob/src/export_traj_ltpl.py:35-63].
+//      mcq_export_s_kernel: a workgroup per track.  relin_front with alpha_scale 1 -- the statements mcq_raceline_kernel runs, so spline_lengths and
+//      their running sum are that kernel's bits -- leaves LEN / CUM in the slab's slots 6 / 7, where mcq_export_rows_kernel reads them; the station
+//      count relin_front derives from its stepsize is not used (the constant 1).  A refused track (a non-finite input among its n waypoints, a total
+//      that is not finite) marks itself with a NaN in CUM[n - 1]; a track whose n is out of range is recognised by every reader from n itself. ----
+__device__ __forceinline__ bool ex_finite(double a) { return fabs(a) < (double)INFINITY; }      // (false for a NaN)
+
+__global__ void __launch_bounds__(MCQ_NT) mcq_export_s_kernel(McqExport X)
+{
+    __shared__ double relin_lds[RELIN_LDS];
+    __shared__ int s_bad;
+    const int tid = threadIdx.x, tr = blockIdx.x;
+    const size_t nm = (size_t)X.nmax;
+    const int n = X.n_list ? X.n_list[tr] : X.nmax;
+    const gdouble* ref = (const gdouble*)(X.ref + (size_t)tr * nm * 4);
+    const gdouble* nv = (const gdouble*)(X.nv + (size_t)tr * nm * 2);
+    const gdouble* al = (const gdouble*)(X.alpha + (size_t)tr * nm);
+    gdouble* vec = (gdouble*)(X.vec + (size_t)tr * nm * MCQ_NVEC);
+    gdouble* LEN = vec + 6 * nm;
+    gdouble* CUM = vec + 7 * nm;
+    gdouble* lo = X.len_out ? (gdouble*)(X.len_out + (size_t)tr * nm) : nullptr;
+    gdouble* so = X.s_ref_out ? (gdouble*)(X.s_ref_out + (size_t)tr * (nm + 1)) : nullptr;
+    const bool range = n >= 3 && n <= X.nmax;
+    if (tid == 0) s_bad = 0;
+    __syncthreads();
+    if (range) {
+        int bad = 0;
+        for (int i = tid; i < n; i += MCQ_NT) {
+            const bool ok = ex_finite(ref[4 * (size_t)i]) && ex_finite(ref[4 * (size_t)i + 1]) && ex_finite(ref[4 * (size_t)i + 2]) &&
+                            ex_finite(ref[4 * (size_t)i + 3]) && ex_finite(nv[2 * (size_t)i]) && ex_finite(nv[2 * (size_t)i + 1]) && ex_finite(al[i]);
+            if (!ok) bad = 1;
+        }
+        if (bad) s_bad = 1;
+    }
+    __syncthreads();
+    double total = NAN;
+    bool good = range && s_bad == 0;
+    if (good) {
+        relin_front(ref, nv, al, n, 1.0, 1.0, vec, nm, total, relin_lds);
+        good = ex_finite(total);
+    }
+    if (!good) {
+        if (range && tid == 0) CUM[n - 1] = NAN;
+        if (lo) for (size_t i = tid; i < nm; i += MCQ_NT) lo[i] = NAN;
+        if (so) for (size_t i = tid; i < nm + 1; i += MCQ_NT) so[i] = NAN;
+        if (tid == 0) ((gdouble*)X.total_out)[tr] = NAN;
+        return;
+    }
+    if (lo) for (size_t i = tid; i < nm; i += MCQ_NT) lo[i] = i < (size_t)n ? LEN[i] : NAN;
+    if (so) for (size_t i = tid; i < nm + 1; i += MCQ_NT) so[i] = i == 0 ? 0.0 : (i <= (size_t)n ? CUM[i - 1] : NAN);
+    if (tid == 0) ((gdouble*)X.total_out)[tr] = total;
+}
+
+// ---- mcq_export_rows_kernel: a workgroup per (variant, block of MCQ_EX_ROWS table rows), the row block the fast index.  Every workgroup passes the variant's whole s column through
+//      LDS, MCQ_EX_TILE stations at a time (the column sits at a stride of MCQ_TRAJ_COLS doubles): that is the check of the column -- no NaN, never
+//      descending; the verdict belongs to the whole table, so every row block needs it -- and, tile by tile, the count lo_i = #{j : s_j < s_ref_i}
+//      of the block's rows by bisection in the tile.  The counts add up over the tiles, so lo_i -- and with it idx_i -- is the same whatever the
+//      tile size; then numpy.argmin's first-minimum rule on the candidates lo - 1 / lo (include/mcq.h).  The table is written a lane per output
+//      ELEMENT, consecutive lanes consecutive doubles (a lane per row would store at a stride of 96 B); row n is row 0 with the total in column 7,
+//      and is looked up as row 0. ----
+__global__ void __launch_bounds__(MCQ_NT) mcq_export_rows_kernel(McqExport X)
+{
+    __shared__ double s_tile[MCQ_EX_TILE + 1];
+    __shared__ double s_q[MCQ_EX_ROWS];
+    __shared__ int s_idx[MCQ_EX_ROWS];
+    __shared__ int s_bad;
+    const int tid = threadIdx.x;
+    const unsigned nblk = ((unsigned)X.nmax + MCQ_EX_ROWS) / MCQ_EX_ROWS;                   // row blocks of a table of nmax + 1 rows
+    const int b = (int)(blockIdx.x / nblk), rb = (int)(blockIdx.x - (unsigned)b * nblk);    // (one axis: a batch is not bounded by 65535)
+    const int r0 = rb * MCQ_EX_ROWS;
+    const size_t nm = (size_t)X.nmax, mm = (size_t)X.mmax;
+    const int rows_all = X.nmax + 1;
+    const int rcnt = rows_all - r0 < MCQ_EX_ROWS ? rows_all - r0 : MCQ_EX_ROWS;          // table rows of this block
+    gdouble* out = (gdouble*)(X.ltpl + ((size_t)b * (nm + 1) + (size_t)r0) * MCQ_LTPL_COLS);
+    gint* iout = X.idx ? (gint*)(X.idx + (size_t)b * nm) : nullptr;
+    const int trk = X.track_of ? X.track_of[b] : b;
+    bool bad = trk < 0 || trk >= X.tracks;
+    int n = 0, m = 0;
+    if (!bad) {
+        n = X.n_list ? X.n_list[trk] : X.nmax;
+        m = X.m_of_track ? X.m_of_track[trk] : X.mmax;
+        bad = n < 3 || n > X.nmax || m < 2 || m > X.mmax;
+    }
+    const size_t t0 = bad ? 0 : (size_t)trk;
+    const gdouble* CUM = (const gdouble*)(X.vec + t0 * nm * MCQ_NVEC + 7 * nm);
+    const gdouble* col = (const gdouble*)(X.traj + (size_t)b * mm * MCQ_TRAJ_COLS);
+    double total = NAN;
+    if (!bad) {
+        total = CUM[n - 1];
+        bad = !ex_finite(total);
+    }
+    if (tid == 0) s_bad = 0;
+    // this thread's rows (MCQ_EX_RPT of them, MCQ_NT apart) and their queries: s_ref of the row (row n asks for s_ref_0)
+    bool has[MCQ_EX_RPT];
+    double q[MCQ_EX_RPT];
+    int lo[MCQ_EX_RPT];
+    #pragma unroll
+    for (int u = 0; u < MCQ_EX_RPT; ++u) {
+        const int lr = u * MCQ_NT + tid, r = r0 + lr;
+        has[u] = !bad && lr < rcnt && r <= n;
+        const int w = has[u] ? (r == n ? 0 : r) : 0;            // the waypoint the row belongs to
+        q[u] = (has[u] && w > 0) ? CUM[w - 1] : 0.0;
+        lo[u] = 0;
+    }
+    if (!bad) {
+        for (int j0 = 0; j0 < m; j0 += MCQ_EX_TILE) {
+            const int cnt = m - j0 < MCQ_EX_TILE ? m - j0 : MCQ_EX_TILE;
+            const int halo = j0 + cnt < m ? cnt + 1 : cnt;      // one station of the next tile: the pair across the tile's edge
+            __syncthreads();
+            for (int j = tid; j < halo; j += MCQ_NT) s_tile[j] = col[(size_t)(j0 + j) * MCQ_TRAJ_COLS];
+            __syncthreads();
+            int wrong = 0;
+            for (int j = tid; j < cnt; j += MCQ_NT) {
+                const double a = s_tile[j];
+                if (a != a) wrong = 1;
+                if (j + 1 < halo && a > s_tile[j + 1]) wrong = 1;
+            }
+            if (wrong) s_bad = 1;
+            #pragma unroll
+            for (int u = 0; u < MCQ_EX_RPT; ++u) {
+                if (!has[u]) continue;
+                int a = 0, e = cnt;                             // first entry of the tile that is not below q
+                while (a < e) {
+                    const int mid = (a + e) >> 1;
+                    if (s_tile[mid] < q[u]) a = mid + 1; else e = mid;
+                }
+                lo[u] += a;
+            }
+        }
+    }
+    __syncthreads();
+    bad = bad || s_bad != 0;
+    if (bad) {      // the whole table NaN, every idx -1: never stale buffer contents
+        for (int e = tid; e < rcnt * MCQ_LTPL_COLS; e += MCQ_NT) out[e] = NAN;
+        if (iout) for (int i = tid; i < MCQ_EX_ROWS; i += MCQ_NT) if (r0 + i < X.nmax) iout[r0 + i] = -1;
+        if (rb == 0 && tid == 0) ((gint*)X.status)[b] = MCQ_BAD_INPUT;
+        return;
+    }
+    #pragma unroll
+    for (int u = 0; u < MCQ_EX_RPT; ++u) {
+        const int lr = u * MCQ_NT + tid, r = r0 + lr;
+        int idx = -1;
+        if (has[u]) {
+            const double qq = q[u];
+            const int c1 = lo[u] - 1, c2 = lo[u];
+            if (c1 < 0) idx = c2;
+            else if (c2 >= m) idx = c1;
+            else idx = fabs(col[(size_t)c1 * MCQ_TRAJ_COLS] - qq) <= fabs(col[(size_t)c2 * MCQ_TRAJ_COLS] - qq) ? c1 : c2;
+            while (idx > 0 && fabs(col[(size_t)(idx - 1) * MCQ_TRAJ_COLS] - qq) == fabs(col[(size_t)idx * MCQ_TRAJ_COLS] - qq)) --idx;
+        }
+        s_idx[lr] = idx;
+        s_q[lr] = (has[u] && r == n) ? total : q[u];
+        if (iout && lr < rcnt && r < X.nmax) iout[r] = r < n ? idx : -1;
+    }
+    __syncthreads();
+    const gdouble* ref = (const gdouble*)(X.ref + (size_t)trk * nm * 4);
+    const gdouble* nv = (const gdouble*)(X.nv + (size_t)trk * nm * 2);
+    const gdouble* al = (const gdouble*)(X.alpha + (size_t)trk * nm);
+    for (int e = tid; e < rcnt * MCQ_LTPL_COLS; e += MCQ_NT) {
+        const int lr = e / MCQ_LTPL_COLS, c = e - lr * MCQ_LTPL_COLS;
+        const int row = r0 + lr;
+        double v = NAN;
+        if (row <= n) {
+            const size_t wp = row == n ? 0 : (size_t)row;
+            if (c < 4) v = ref[4 * wp + c];
+            else if (c < 6) v = nv[2 * wp + (c - 4)];
+            else if (c == 6) v = al[wp];
+            else if (c == 7) v = s_q[lr];
+            else v = col[(size_t)s_idx[lr] * MCQ_TRAJ_COLS + (c - 5)];      // columns 8 .. 11 <- psi, kappa, vx, ax (3 .. 6)
+        }
+        out[e] = v;
+    }
+    if (rb == 0 && tid == 0) ((gint*)X.status)[b] = MCQ_OK;
+}

@@ -116,6 +116,7 @@ CHECK_ACC_MARGIN = 0.1
 CHECK_DIST_WARN = 1.0
 CHK_KAPPA, CHK_AY, CHK_AX_POS, CHK_AX_NEG, CHK_A_TOT, CHK_MACHINES, CHK_V_MAX = 1, 2, 4, 8, 16, 32, 64
 BOUNDS_ALL, BOUNDS_FIRST_ROW = 0, 1
+LTPL_COLS = 12      # MCQ_LTPL_COLS: x_ref, y_ref, w_r, w_l, n_x, n_y, alpha, s_ref, psi, kappa, vx, ax
 
 
 IQP_ROUND_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int))
@@ -182,6 +183,7 @@ _ABI = {
     "mcq_bound_dists_device": (_ci, [_vp, _ci, _ci, _vp, _vp, _vp, _ci, _vp, _vp, _vp, _cd, _cd, _vp, _vp, _cd, _ci, _vp, _vp, _vp, _vp, _vp]),
     "mcq_spline_approx_device": (_ci, [_vp, _ci, _ci, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _cd, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mcq_min_width_device": (_ci, [_vp, _ci, _ci, _vp, _vp, _cd, _vp]),
+    "mcq_export_device": (_ci, [_vp, _ci, _ci, _vp, _vp, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 EXPORTED_SYMBOLS = tuple(_ABI)
 
@@ -251,6 +253,25 @@ def _pad_like(rows, ns, tail=(), nmin=0):
     for k, r in enumerate(rows):
         out[k, :ns[k]] = r
     return out
+
+
+def export_result(tab, idx, lens, s_ref, total, status, ns, ms, tr, tj):
+    """Engine.export_batch's host piece: the padded outputs of mcq_export_device cut to lists (ns [tracks], ms [tracks], tr [batch] = track_of,
+    tj = the padded trajectories), and the closed race tables."""
+    tracks = len(ns)
+    in_range = lambda t: 0 <= t < tracks        # noqa: E731
+    n_of = [min(max(int(ns[t]), 0), tab.shape[1] - 1) if in_range(t) else 0 for t in tr]
+    m_of = [min(max(int(ms[t]), 0), tj.shape[1]) if in_range(t) else 0 for t in tr]
+    race_cl = []
+    for v, t in enumerate(tr):
+        rows = tj[v, :m_of[v]]
+        last = rows[:1].copy() if m_of[v] else np.full((1, tj.shape[2]), np.nan)
+        last[0, 0] = total[t] if (in_range(t) and status[v] == 0) else np.nan
+        race_cl.append(np.vstack((rows, last)))
+    return dict(ltpl=[tab[v, :n_of[v] + 1].copy() for v in range(len(tr))], idx=[idx[v, :n_of[v]].copy() for v in range(len(tr))],
+                spline_lengths=[lens[t, :max(min(int(ns[t]), lens.shape[1]), 0)].copy() for t in range(tracks)],
+                s_ref=[s_ref[t, :max(min(int(ns[t]), lens.shape[1]), 0) + 1].copy() for t in range(tracks)],
+                spline_total=total, status=status, race_cl=race_cl)
 
 
 class _Scope:
@@ -1034,6 +1055,64 @@ class Engine:
             return dict(min_dists=self.download(d_md, (bsz, mmax), np.float64), min_dist=self.download(d_mn, (bsz,), np.float64),
                         nb=self.download(d_nb, (bsz, 2), np.int32), bound_r=bound[:, 0].copy(), bound_l=bound[:, 1].copy(),
                         status=self.download(d_st, (bsz,), np.int32))
+
+    def export_device(self, tracks, nmax, d_n, d_ref, d_nv, d_alpha, batch, mmax, d_m_of_track, d_track_of, d_traj, d_ltpl, d_idx, d_lengths,
+                      d_s_ref, d_total, d_status):
+        """mcq_export_device (include/mcq.h) on device pointers; d_n / d_m_of_track / d_track_of / d_idx / d_lengths / d_s_ref may be None.
+        Asynchronous."""
+        rc = self.lib.mcq_export_device(self.h, int(tracks), int(nmax), d_n or None, d_ref, d_nv, d_alpha, int(batch), int(mmax),
+                                        d_m_of_track or None, d_track_of or None, d_traj, d_ltpl, d_idx or None, d_lengths or None,
+                                        d_s_ref or None, d_total, d_status)
+        self._check(rc, "mcq_export_device")
+
+    def export_batch(self, reftracks, normvecs, alphas, traj, track_of=None):
+        """The EXPORT block for a batch of variants (mcq_export_device) [REF main_globaltraj.py:502-552, helper_funcs_glob/src/
+        export_traj_ltpl.py:35-63]: the local planner's table and the closed race table.  reftracks [n_k, 4], normvecs [n_k, 2], alphas [n_k]: one
+        entry per track; traj: trajectory_batch's dict (traj [batch, mmax, 7]; m [tracks] -- when absent, the rows that are not NaN are counted) or
+        the padded array itself; track_of [batch] (track per variant) or None when tracks == batch.
+        Returns a dict of lists / arrays: ltpl (per variant an (n + 1, 12) array: upstream's traj_ltpl_cl; export.write_traj_ltpl writes its first
+        n rows, as upstream does), idx (per variant [n]), spline_lengths (per track [n]), s_ref (per track [n + 1]), spline_total [tracks],
+        status [batch], race_cl (per variant (m + 1, 7): the trajectory's rows, then row 0 again with s = spline_total).
+        NOTE: upstream closes the race table with numpy.sum(spline_lengths); spline_total is the running sum's last value (numpy.cumsum's order),
+        so the two differ in the last bits.  A refused variant (status MCQ_BAD_INPUT) has NaN tables and idx -1."""
+        ns, ref = _pad_rows(reftracks, 4, nmin=3)
+        nv, al = _pad_like(normvecs, ns, (2,), nmin=3), _pad_like(alphas, ns, nmin=3)
+        tracks, nmax = ref.shape[:2]
+        ms = None
+        if isinstance(traj, dict):
+            ms = traj.get("m")
+            traj = traj["traj"]
+        tj = np.ascontiguousarray(traj, dtype=np.float64)
+        if tj.ndim != 3 or tj.shape[2] != TRAJ_COLS:
+            raise ValueError("export_batch: traj must be [batch, mmax, %d]" % TRAJ_COLS)
+        bsz, mmax = tj.shape[:2]
+        if track_of is None and tracks != bsz:
+            raise ValueError("export_batch: %d tracks for %d variants and no track_of" % (tracks, bsz))
+        tr = np.arange(bsz, dtype=np.int32) if track_of is None else np.ascontiguousarray(track_of, dtype=np.int32)
+        if tr.shape != (bsz,):
+            raise ValueError("export_batch: track_of must be [batch]")
+        if ms is None:      # rows behind a variant's m are NaN (trajectory_batch): the stations of a track are those of its first variant
+            ms = np.zeros(tracks, dtype=np.int32)
+            for v in range(bsz - 1, -1, -1):
+                if 0 <= tr[v] < tracks:
+                    ms[tr[v]] = int(np.sum(~np.isnan(tj[v, :, 1])))
+        ms = np.ascontiguousarray(ms, dtype=np.int32)
+        if ms.shape != (tracks,):
+            raise ValueError("export_batch: m must hold one count per track")
+        with self.scope() as dev:
+            up, new = dev.up, dev.new
+            d_ref, d_nv, d_al, d_n = up(ref), up(nv), up(al), up(ns)
+            d_m, d_t, d_tj = up(ms), up(tr), up(tj)
+            d_tab, d_idx = new(bsz * (nmax + 1) * LTPL_COLS * 8), new(bsz * nmax * 4)
+            d_len, d_s, d_tot, d_st = new(tracks * nmax * 8), new(tracks * (nmax + 1) * 8), new(tracks * 8), new(bsz * 4)
+            self.export_device(tracks, nmax, d_n, d_ref, d_nv, d_al, bsz, mmax, d_m, d_t, d_tj, d_tab, d_idx, d_len, d_s, d_tot, d_st)
+            tab = self.download(d_tab, (bsz, nmax + 1, LTPL_COLS), np.float64)
+            idx = self.download(d_idx, (bsz, nmax), np.int32)
+            lens = self.download(d_len, (tracks, nmax), np.float64)
+            s_ref = self.download(d_s, (tracks, nmax + 1), np.float64)
+            total = self.download(d_tot, (tracks,), np.float64)
+            status = self.download(d_st, (bsz,), np.int32)
+        return export_result(tab, idx, lens, s_ref, total, status, ns, ms, tr, tj)
 
     def relinearise_device(self, batch, nmax, d_n_in, d_ref_in, d_nv_in, d_alpha, d_live, alpha_scale, stepsize,
                            d_ref_out, d_nv_out, d_n_out, d_status):

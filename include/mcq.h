@@ -478,6 +478,39 @@ int mcq_spline_approx_device(mcq_handle* h, int tracks,
  * A separate entry because prep_track runs the normals-crossing check on the un-inflated widths.  DEVICE pointers; asynchronous. */
 int mcq_min_width_device(mcq_handle* h, int batch, int nmax, const int* n_list, double* reftrack_io, double min_width, int* changed_out);
 
+/* ---- the export tables [REF main_globaltraj.py:502-552, helper_funcs_glob/src/export_traj_ltpl.py:35-63]: the local planner's rows and the
+ * total that closes the race table, the last stage of the post-QP flow.  All pointers DEVICE pointers; asynchronous on the handle's stream; rings
+ * only (the reference's export always closes its table; a chain has no definition upstream).
+ * Per track of n waypoints (n_list [tracks] or NULL: all nmax): the raceline points P_i = p_i + alpha_i n_i, the closed cubic spline through them
+ *   with unit scalings, spline_lengths_i from 15 points / 14 chords per segment (tph.calc_spline_lengths: what tph.create_raceline returns as
+ *   spline_lengths_opt), s_ref_0 = 0 and s_ref_(i+1) their running sum in numpy.cumsum's order, spline_total = s_ref_n.  These are the bits
+ *   mcq_raceline_device forms internally for the same inputs, and they do not depend on which other tracks are in the launch.
+ *   NOTE: upstream closes the race table with numpy.sum(spline_lengths) (pairwise summation); this entry has the running sum's last value.  The
+ *   two differ in the last bits.
+ * Per variant b (track_of [batch] or NULL: row = variant; m_of_track [tracks] stations of the track's trajectories or NULL: all mmax), on
+ *   traj [batch][mmax][MCQ_TRAJ_COLS], the traj_out of mcq_trajectory_device:
+ *   lookup  idx_i = numpy.argmin(|traj[b][0..m-1][0] - s_ref_i|), i = 0 .. n-1, first minimum; only the m stations are searched and the table is
+ *           not wrapped (upstream's behaviour: the last waypoints may be nearer to the lap's end than to any station).  On the non-decreasing s
+ *           column this is: lo = count of j with s_j < s_ref_i; of the candidates lo - 1 and lo the one that exists, or the nearer one (the lower
+ *           at equal distance); then downwards while the station below is at the same distance.
+ *   rows    ltpl_out [batch][nmax + 1][MCQ_LTPL_COLS]: row i <= n-1 = [x_ref, y_ref, w_r, w_l, n_x, n_y, alpha, s_ref_i, psi, kappa, vx, ax] -- the
+ *           first seven bit-for-bit copies of the inputs, the last four bit-for-bit copies of traj[b][idx_i][3..6]; row n = row 0 with column 7
+ *           = spline_total (upstream's traj_ltpl_cl; the FILE upstream writes holds the first n rows only); rows n+1 .. nmax NaN.
+ *           idx_out [batch][nmax] (optional): idx_i, entries n .. nmax-1 are -1.
+ *   spline_lengths_out [tracks][nmax] (optional; NaN behind n), s_ref_out [tracks][nmax + 1] (optional; s_ref_0 .. s_ref_n, NaN behind),
+ *   spline_total_out [tracks].
+ * status_out [batch]: MCQ_OK, or MCQ_BAD_INPUT for n < 3 or n > nmax, m < 2 or m > mmax, a track_of entry outside the tracks, a non-finite reftrack /
+ *   normvec / alpha entry among the n (or a raceline whose length is not finite), a NaN among the m entries of the s column (the trajectory entry's
+ *   NaN rule arrives here as such) or an s column that descends somewhere.  That variant's whole table is NaN and its idx -1; the other variants are
+ *   not affected.  A refused TRACK has NaN spline_lengths_out / s_ref_out / spline_total_out.  No output keeps stale memory.
+ * MCQ_E_ARG: nmax < 3, mmax < 2, batch or tracks <= 0, NULL where an array is required; MCQ_E_TOO_LARGE: batch x ceil((nmax + 1) / 1024) beyond 2^31 - 1
+ *   (the second launch's grid).  Indices and copies: identical whatever the grid or order. */
+#define MCQ_LTPL_COLS 12
+int mcq_export_device(mcq_handle* h, int tracks, int nmax, const int* n_list, const double* reftrack, const double* normvec,
+                      const double* alpha, int batch, int mmax, const int* m_of_track, const int* track_of, const double* traj,
+                      double* ltpl_out, int* idx_out, double* spline_lengths_out, double* s_ref_out, double* spline_total_out,
+                      int* status_out);
+
 /* Host-buffer entry for a UNIFORM batch (every track n waypoints): reftrack [batch][n][4], normvec [batch][n][2] or NULL,
  * scaling [batch][n] or NULL in host memory, results to host memory.  One asynchronous copy per array straight from / to the
  * caller's buffers -- no packing pass; buffers from mcq_host_alloc (pinned) are copied at PCIe speed, pageable ones go through
