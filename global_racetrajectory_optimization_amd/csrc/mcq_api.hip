@@ -83,6 +83,7 @@ struct mcq_handle {
     bool smem_attr_set = false;
     Scratch vel;                        // profiles of mcq_vel_profile_device*, [2 nmax][batch] (the lap doubled) or [nmax][batch] (unclosed rows)
     Scratch bound;                      // mcq_bound_dists_device: samples [tracks][2][nbmax][2], raw boundaries, running sums, side statuses
+    Scratch fit;                        // mcq_spline_fit_device: running sums, closed points, parameters, the per-track work area
     Scratch spl;                        // mcq_spline_approx_device: first guesses, closest parameters, distances, sides [tracks][nmax + 1] each, sample counts
     Scratch ends;                       // per-problem ring / open-chain records of mcq_solve_batch_ends (device)
     mcq_iqp_round_cb iqp_cb = nullptr;  // mcq_iqp_set_round_callback
@@ -265,7 +266,7 @@ extern "C" void mcq_destroy(mcq_handle* h)
     for (int k = 0; k < 16; ++k) if (h->ev_slice[k]) (void)hipEventDestroy(h->ev_slice[k]);
     if (h->cs_in) (void)hipStreamDestroy(h->cs_in);
     if (h->cs_out) (void)hipStreamDestroy(h->cs_out);
-    for (Scratch* s : {&h->vel, &h->bound, &h->spl, &h->ends}) (void)hipFree(s->p);
+    for (Scratch* s : {&h->vel, &h->bound, &h->fit, &h->spl, &h->ends}) (void)hipFree(s->p);
     if (h->pin) (void)hipHostFree(h->pin);
     for (int k = 0; k < 5; ++k) if (h->ev[k]) (void)hipEventDestroy(h->ev[k]);
     for (int k = 0; k < 2; ++k) if (h->ev_span[k]) (void)hipEventDestroy(h->ev_span[k]);
@@ -1004,6 +1005,41 @@ extern "C" int mcq_bound_dists_device(mcq_handle* h, int tracks, int nmax, const
     hipLaunchKernelGGL(mcq_bound_dists_kernel, dim3((mmax + block - 1) / block, tracks), dim3(256), 0, st, P);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(mcq_bound_min_kernel, dim3(tracks), dim3(256), 0, st, P);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// FITPACK's periodic smoothing fit (include/mcq.h): one launch on the handle's stream, a workgroup per track
+extern "C" int mcq_spline_fit_device(mcq_handle* h, int tracks, int nmax, const int* n_list, const double* track, double stepsize_prep, int mimax,
+                                     int k, double s, int nkmax, int* nk_out, double* knots_out, double* coef_out, double* fp_out, int* ier_out,
+                                     int* mi_out, double* pts_out, int* status_out)
+{
+    if (!h || tracks <= 0 || tracks > MCQ_SPL_MAX_TRACKS || nmax < 3 || nmax > MCQ_SPL_MAX_N || mimax < 2 || mimax > MCQ_SPL_MAX_N || !track ||
+        k < 1 || k > 5 || !(s >= 0.0) || !(s <= 1.7e308) || nkmax < 2 * k + 2 || nkmax > MCQ_SPL_MAX_N + 10 || !(stepsize_prep == stepsize_prep) ||
+        !nk_out || !knots_out || !coef_out || !ier_out || !status_out) {
+        g_err = "mcq_spline_fit_device: bad argument";
+        return MCQ_E_ARG;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t nm = (size_t)nmax, mm = (size_t)mimax, nk = (size_t)nkmax;
+    // per track: B-splines [mimax][k + 1], residuals [mimax], two triangles [(2 k + 5) nkmax], coefficients [nkmax][2], jump rows [nkmax][k + 2],
+    // fpint [nkmax + 2], then the ints: intervals [mimax], nrdata [nkmax + 2], row marks [mimax]; at the end the segments' reduced rows
+    // [mimax][k + 1] and their right-hand sides [mimax][2]
+    const size_t work_per = mm * (k + 2) + 2 * (size_t)(2 * k + 5) * nk + 2 * nk + nk * (k + 2) + nk + 2 + (2 * mm + nk + 2 + 1) / 2 + 1 + mm * (k + 3);
+    const size_t per = nm + 1 + 3 * mm + work_per;
+    if (int rc = grow(h, h->fit, (size_t)tracks * per * sizeof(double))) return rc;
+    McqFit P;
+    memset(&P, 0, sizeof(P));
+    P.tracks = tracks; P.nmax = nmax; P.mimax = mimax; P.k = k; P.nkmax = nkmax;
+    P.n_list = n_list; P.track = track; P.step = stepsize_prep; P.s = s;
+    P.cum = (double*)h->fit.p;
+    P.pts = P.cum + (size_t)tracks * (nm + 1);
+    P.u = P.pts + (size_t)tracks * mm * 2;
+    P.work = P.u + (size_t)tracks * mm;
+    P.work_per = work_per;
+    P.nk_out = nk_out; P.knots_out = knots_out; P.coef_out = coef_out; P.fp_out = fp_out; P.ier_out = ier_out; P.mi_out = mi_out;
+    P.pts_out = pts_out; P.status = status_out;
+    hipLaunchKernelGGL(mcq_spline_fit_kernel, dim3(tracks), dim3(256), 0, h->ws[0].stream, P);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -364,6 +364,32 @@ __global__ void mcq_spline_length_kernel(McqSpline S);
 __global__ void mcq_spline_search_kernel(McqSpline S);
 __global__ void mcq_spline_finish_kernel(McqSpline S);
 
+/* ---- FITPACK's periodic smoothing fit (mcq_spline_fit_device; csrc/mcq_fit.inc): one launch, a workgroup per track -- interp_track's
+ *      re-sampling, the chord-length parameter, fpclos.  The triangle of the periodic system takes (2 k + 5) doubles per distinct coefficient
+ *      (band k + 2, border k + 1, two right-hand sides); it lives in LDS while that is at most MCQ_FIT_LDS doubles (k = 3: n <= 565 knots) and
+ *      in the handle's scratch beyond, with the same statements and the same bits. ---- */
+#define MCQ_FIT_LDS 6144      /* doubles of LDS for a fit's triangle (48 KB) */
+struct McqFit {
+    int tracks, nmax, mimax, k, nkmax;
+    const int* n_list;       // [tracks] or nullptr (all nmax)
+    const double* track;     // [tracks][nmax][4] raw rows, not closed
+    double step, s;          // stepsize_prep (<= 0: no re-sampling), smoothing factor
+    double* cum;             // scratch [tracks][nmax + 1]: running sums of the raw line
+    double* pts;             // scratch [tracks][mimax][2]: the closed points that are fitted
+    double* u;               // scratch [tracks][mimax]: their parameter
+    double* work;            // scratch [tracks][work_per]: B-splines, residuals, triangles, coefficients, jump rows, fpknot's tables, the segments' reduced rows
+    size_t work_per;         // doubles per track
+    int* nk_out;             // [tracks]
+    double* knots_out;       // [tracks][nkmax]
+    double* coef_out;        // [tracks][2][nkmax]
+    double* fp_out;          // [tracks] or nullptr
+    int* ier_out;            // [tracks]
+    int* mi_out;             // [tracks] or nullptr
+    double* pts_out;         // [tracks][mimax][2] or nullptr
+    int* status;             // [tracks]
+};
+__global__ void mcq_spline_fit_kernel(McqFit P);
+
 /* prep_track's tail [REF helper_funcs_glob/src/prep_track.py:89-98]: rows narrower than min_width grow by half the deficit on both sides. */
 __global__ void mcq_min_width_kernel(int nmax, const int* n_list, double* ref_all, double min_width, int* changed_out);
 

@@ -182,6 +182,7 @@ _ABI = {
                                     _vp, _vp]),
     "mcq_bound_dists_device": (_ci, [_vp, _ci, _ci, _vp, _vp, _vp, _ci, _vp, _vp, _vp, _cd, _cd, _vp, _vp, _cd, _ci, _vp, _vp, _vp, _vp, _vp]),
     "mcq_spline_approx_device": (_ci, [_vp, _ci, _ci, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _cd, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mcq_spline_fit_device": (_ci, [_vp, _ci, _ci, _vp, _vp, _cd, _ci, _ci, _cd, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mcq_min_width_device": (_ci, [_vp, _ci, _ci, _vp, _vp, _cd, _vp]),
     "mcq_export_device": (_ci, [_vp, _ci, _ci, _vp, _vp, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
@@ -835,26 +836,32 @@ class Engine:
                 coef[b, q, :cq.shape[0]] = cq
         return ks.pop(), nk, knots, coef
 
-    def spline_approx_batch(self, tracks, tcks, stepsize_reg, mmax=None, keep=None):
+    def spline_approx_batch(self, tracks, tcks, stepsize_reg, mmax=None, keep=None, resident=None):
         """tph.spline_approximation behind FITPACK's fit for a list of raw tracks ([n_k, 4] rows [x, y, w_r, w_l], not closed) and their
         smoothing splines (tcks: the (t, c, k) tuples scipy.interpolate.splprep returns; one degree per launch), on the device
         (mcq_spline_approx_device).  mmax: rows the output holds per track (default: enough for every track of the launch).
         Returns a dict: reftrack -- list of (m_k, 4) arrays (None where status != 0) --, m [B], closest_t / dists [B, nmax + 1] (NaN behind n_k),
         dev [B, 2] = mean and maximum deviation, nonmono [B], status [B].
-        keep: a list that receives (d_ref, d_n, mmax) -- the rows stay on the device, padded to mmax, and the caller frees both (prep_track_batch)."""
+        keep: a list that receives (d_ref, d_n, mmax) -- the rows stay on the device, padded to mmax, and the caller frees both (prep_track_batch).
+        resident: (k, nkmax, d_nk, d_knots, d_coef) as Engine.spline_fit_batch(keep=...) leaves them on the device, instead of tcks (then None)."""
         ns, trk = _pad_rows(tracks, 4, nmin=3)
         bsz, nmax = trk.shape[:2]
-        k, nk, knots, coef = self.pack_tcks(tcks)
+        if resident is None:
+            k, nk, knots, coef = self.pack_tcks(tcks)
+            nkmax = knots.shape[1]
+        else:
+            k, nkmax = int(resident[0]), int(resident[1])
         if mmax is None:      # a smoothed line is shorter than its raw one: room for one twice as long (a track that needs more reports its m)
             el = [float(np.sum(np.hypot(*(np.diff(np.vstack((trk[b, :ns[b], :2], trk[b, :1, :2])), axis=0).T)))) for b in range(bsz)]
             finite = [e for e in el if np.isfinite(e)]
             mmax = max(int(2.0 * max(finite + [0.0]) / float(stepsize_reg)) + 8, 8)
         with self.scope() as dev:
             up, new = dev.up, dev.new
-            d_trk, d_n, d_nk, d_kn, d_cf = up(trk), up(ns), up(nk), up(knots), up(coef)
+            d_trk, d_n = up(trk), up(ns)
+            d_nk, d_kn, d_cf = (up(nk), up(knots), up(coef)) if resident is None else resident[2:5]
             d_m, d_ct, d_ds, d_dev, d_nm, d_st = new(bsz * 4), new(bsz * (nmax + 1) * 8), new(bsz * (nmax + 1) * 8), new(bsz * 16), new(bsz * 4), new(bsz * 4)
             d_ref = new(bsz * mmax * 32)
-            self.spline_approx_device(bsz, nmax, d_n, d_trk, k, knots.shape[1], d_nk, d_kn, d_cf, stepsize_reg, mmax, d_ref, d_m, d_ct, d_ds,
+            self.spline_approx_device(bsz, nmax, d_n, d_trk, k, nkmax, d_nk, d_kn, d_cf, stepsize_reg, mmax, d_ref, d_m, d_ct, d_ds,
                                       d_dev, d_nm, d_st)
             m = self.download(d_m, (bsz,), np.int32)
             st = self.download(d_st, (bsz,), np.int32)
@@ -864,6 +871,55 @@ class Engine:
                        dev=self.download(d_dev, (bsz, 2), np.float64), nonmono=self.download(d_nm, (bsz,), np.int32))
             if keep is not None:
                 keep.extend((dev.release(d_ref), dev.release(d_m), mmax))
+            return out
+
+    def spline_fit_device(self, tracks, nmax, d_n, d_track, stepsize_prep, mimax, k, s, nkmax, d_nk, d_knots, d_coef, d_fp, d_ier, d_mi, d_pts,
+                          d_status):
+        """mcq_spline_fit_device (include/mcq.h) on device pointers; d_n / d_fp / d_mi / d_pts may be None.  Asynchronous."""
+        rc = self.lib.mcq_spline_fit_device(self.h, int(tracks), int(nmax), d_n or None, d_track or None, float(stepsize_prep), int(mimax), int(k),
+                                            float(s), int(nkmax), d_nk or None, d_knots or None, d_coef or None, d_fp or None, d_ier or None,
+                                            d_mi or None, d_pts or None, d_status or None)
+        self._check(rc, "mcq_spline_fit_device")
+
+    def spline_fit_batch(self, tracks, k=3, s=10, stepsize_prep=1.0, nest=None, keep=None, mimax=None, points=False):
+        """FITPACK's periodic smoothing fit -- scipy.interpolate.splprep(..., k=k, s=s, per=1) behind interp_track's re-sampling at stepsize_prep,
+        as tph.spline_approximation runs them -- for a list of raw tracks ([n_k, >= 2] rows, not closed) on the device (mcq_spline_fit_device).
+        stepsize_prep <= 0: the raw rows are closed and fitted as they are.  nest: FITPACK's knot budget (default: scipy's, mi + 2 k of the
+        longest track).  Returns a dict: tcks -- scipy-shaped (t, [cx, cy], k), None where status != 0 --, nk, fp, ier, mi, status [B] (and pts,
+        the closed points that were fitted, with points=True).
+        keep: a list that receives (k, nkmax, d_nk, d_knots, d_coef) -- the splines stay on the device in mcq_spline_approx_device's layout and
+        the caller frees the three pointers (prep_track_batch)."""
+        ns, trk = _pad_rows([np.asarray(t, dtype=np.float64)[:, :2] for t in tracks], 2, nmin=3)
+        trk = np.concatenate((trk, np.zeros_like(trk)), axis=2)
+        bsz, nmax = trk.shape[:2]
+        if mimax is None:
+            if stepsize_prep > 0.0:
+                el = [float(np.sum(np.hypot(*(np.diff(np.vstack((trk[b, :ns[b], :2], trk[b, :1, :2])), axis=0).T)))) for b in range(bsz)]
+                finite = [e for e in el if np.isfinite(e)]
+                mimax = max(int(np.ceil(max(finite + [0.0]) / float(stepsize_prep))) + 3, 4)
+            else:
+                mimax = nmax + 1
+        nkmax = int(nest) if nest is not None else mimax + 2 * int(k)
+        with self.scope() as dev:
+            up, new = dev.up, dev.new
+            d_trk, d_n = up(trk), up(ns)
+            d_nk, d_kn, d_cf = new(bsz * 4), new(bsz * nkmax * 8), new(bsz * 2 * nkmax * 8)
+            d_fp, d_ier, d_mi, d_st = new(bsz * 8), new(bsz * 4), new(bsz * 4), new(bsz * 4)
+            d_pts = new(bsz * mimax * 16) if points else None
+            self.spline_fit_device(bsz, nmax, d_n, d_trk, stepsize_prep, mimax, k, s, nkmax, d_nk, d_kn, d_cf, d_fp, d_ier, d_mi, d_pts, d_st)
+            nk = self.download(d_nk, (bsz,), np.int32)
+            st = self.download(d_st, (bsz,), np.int32)
+            kn = self.download(d_kn, (bsz, nkmax), np.float64)
+            cf = self.download(d_cf, (bsz, 2, nkmax), np.float64)
+            out = dict(tcks=[(kn[b, :nk[b]].copy(), [cf[b, 0, :nk[b] - k - 1].copy(), cf[b, 1, :nk[b] - k - 1].copy()], int(k)) if st[b] == 0 else None
+                             for b in range(bsz)],
+                       nk=nk, fp=self.download(d_fp, (bsz,), np.float64), ier=self.download(d_ier, (bsz,), np.int32),
+                       mi=self.download(d_mi, (bsz,), np.int32), status=st, knots=kn, coef=cf)
+            if points:
+                pts = self.download(d_pts, (bsz, mimax, 2), np.float64)
+                out["pts"] = [pts[b, :out["mi"][b]].copy() if st[b] == 0 else None for b in range(bsz)]
+            if keep is not None:
+                keep.extend((int(k), nkmax, dev.release(d_nk), dev.release(d_kn), dev.release(d_cf)))
             return out
 
     def min_width_batch(self, reftracks, min_width):
@@ -877,15 +933,25 @@ class Engine:
             out = self.download(d_ref, (bsz, nmax, 4), np.float64)
             return [out[b, :ns[b]].copy() for b in range(bsz)], self.download(d_ch, (bsz,), np.int32)
 
-    def prep_track_batch(self, tracks, k_reg=3, s_reg=10, stepsize_prep=1.0, stepsize_reg=3.0, min_width=None, tcks=None, horizon=10):
+    def prep_track_batch(self, tracks, k_reg=3, s_reg=10, stepsize_prep=1.0, stepsize_reg=3.0, min_width=None, tcks=None, horizon=10, fit="host"):
         """prep_track [REF helper_funcs_glob/src/prep_track.py] for a list of raw tracks ([n_k, 4] rows, not closed).  On the host, per track:
         the linear re-sampling at stepsize_prep and FITPACK's periodic smoothing fit (scipy.interpolate.splprep) -- or the caller's tcks, one
         (t, c, k) per track.  Then on the device, the rows staying there: mcq_spline_approx_device, mcq_prep_device (normals and scalings of
         the prepared rows), mcq_normals_crossing_device (on the un-inflated widths, as upstream) and, with min_width, mcq_min_width_device.
         Returns a dict: reftrack -- list of (m_k, 4) arrays (None where status != 0) --, normvec (m_k, 2), scaling (m_k), crossing [B] (1 / 0,
         -1 where tph raises), inflated [B] (all 0 without min_width), status [B], m [B], dev [B, 2], nonmono [B], tcks (the splines used: the
-        caller's, or the ones fitted here): reftrack / normvec / scaling are what solve_batch takes."""
-        if tcks is None:
+        caller's, or the ones fitted here): reftrack / normvec / scaling are what solve_batch takes.
+        fit="device": the re-sampling and the fit run on the device as well (mcq_spline_fit_device) and the launches are chained -- the spline
+        stays on the device between the fit and mcq_spline_approx_device; tcks are its download, None for a track whose fit was refused, which
+        is refused as a whole (status MCQ_BAD_INPUT) while the others go on; fit_ier [B] holds FITPACK's ier."""
+        if fit not in ("host", "device"):
+            raise ValueError("prep_track_batch: fit must be 'host' or 'device'")
+        resident, fitted = None, None
+        if tcks is None and fit == "device":
+            resident = []
+            fitted = self.spline_fit_batch(tracks, k=k_reg, s=s_reg, stepsize_prep=stepsize_prep, keep=resident)
+            tcks = fitted["tcks"]
+        elif tcks is None:
             from scipy import interpolate
             from .trajectory_planning_helpers import interp_track as _it
             tcks = []
@@ -895,7 +961,14 @@ class Engine:
                 tcks.append(interpolate.splprep([cl[:, 0], cl[:, 1]], k=k_reg, s=s_reg, per=1)[0])
         bsz = len(tracks)
         keep = []
-        out = self.spline_approx_batch(tracks, tcks, stepsize_reg, keep=keep)
+        if resident is None:
+            out = self.spline_approx_batch(tracks, tcks, stepsize_reg, keep=keep)
+        else:       # (a refused fit left nk = 0 and NaN knots: mcq_spline_approx_device refuses that track by itself)
+            try:
+                out = self.spline_approx_batch(tracks, None, stepsize_reg, keep=keep, resident=resident)
+            finally:
+                for ptr in resident[2:5]:
+                    self.free(ptr)
         with self.scope() as dev:
             d_ref, d_m, mmax = dev.adopt(keep[0]), dev.adopt(keep[1]), keep[2]
             if np.any(out["status"] != 0):      # a refused track has no rows: the kernels behind must not take its m_out (the rows it would need) for a length
@@ -916,7 +989,7 @@ class Engine:
                         scaling=[sc[b, :m[b]].copy() if good[b] else None for b in range(bsz)],
                         crossing=self.download(d_cr, (bsz,), np.int32),
                         inflated=self.download(d_ch, (bsz,), np.int32) if min_width is not None else np.zeros(bsz, dtype=np.int32), status=st, m=m,
-                        dev=out["dev"], nonmono=out["nonmono"], tcks=tcks)
+                        dev=out["dev"], nonmono=out["nonmono"], tcks=tcks, **({} if fitted is None else dict(fit_ier=fitted["ier"], fit_fp=fitted["fp"])))
 
     def raceline_device_ends(self, batch, nmax, d_n, d_ref, d_nv, d_alpha, d_closed, d_psi, stepsize, mmax, d_xy, d_psi_out, d_kappa,
                              d_el, d_m, d_status):

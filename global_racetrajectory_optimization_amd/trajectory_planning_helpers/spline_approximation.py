@@ -5,6 +5,8 @@ host only, not part of the GPU hot path.
 
 MCQ_PREP_DEVICE=1 in the environment: everything behind FITPACK's fit runs on the device instead (Engine.spline_approx_batch ->
 mcq_spline_approx_device, include/mcq.h); signature, print line and the default route are unchanged.
+MCQ_FIT_DEVICE=1: the re-sampling and FITPACK's fit run on the device as well (Engine.spline_fit_batch -> mcq_spline_fit_device) and the spline
+stays there for the entry behind it (this implies MCQ_PREP_DEVICE's route); FITPACK's ier 1, 2 and 3 arrive as the RuntimeWarning scipy issues.
 """
 import math
 import os
@@ -23,6 +25,9 @@ def _dist_to_p(t_glob, tck, p):
 
 def spline_approximation(track: np.ndarray, k_reg: int = 3, s_reg: int = 10, stepsize_prep: float = 1.0,
                          stepsize_reg: float = 3.0, debug: bool = False) -> np.ndarray:
+    if os.environ.get("MCQ_FIT_DEVICE") == "1":
+        return _fit_on_device(track, k_reg, s_reg, stepsize_prep, stepsize_reg, debug)
+
     track_interp = _it.interp_track(track=track, stepsize=stepsize_prep)
     track_interp_cl = np.vstack((track_interp, track_interp[0]))
 
@@ -72,6 +77,39 @@ def spline_approximation(track: np.ndarray, k_reg: int = 3, s_reg: int = 10, ste
 def _on_device(track, tck_cl, stepsize_reg, debug):
     from ..engine import EngineError, default_engine
     out = default_engine().spline_approx_batch([track], [tck_cl], stepsize_reg)
+    if out["status"][0] != 0:
+        raise EngineError("mcq_spline_approx_device: bad input (status %d, %d rows needed)" % (out["status"][0], out["m"][0]))
+    if debug:
+        print("Spline approximation: mean deviation %.2fm, maximum deviation %.2fm" % (float(out["dev"][0, 0]), float(out["dev"][0, 1])))
+    return out["reftrack"][0]
+
+
+_IER_MESSAGES = {
+    1: "The required storage space exceeds the available storage space. Probable causes: data (x,y) size is too small or smoothing parameter"
+       "\ns is too small (fp>s).",
+    2: "A theoretically impossible result when finding a smoothing spline\nwith fp = s. Probable cause: s too small. (abs(fp-s)/s>0.001)",
+    3: "The maximal number of iterations (20) allowed for finding smoothing\nspline with fp=s has been reached. Probable cause: s too small."
+       "\n(abs(fp-s)/s>0.001)",
+}
+
+
+def _fit_on_device(track, k_reg, s_reg, stepsize_prep, stepsize_reg, debug):
+    import warnings
+    from ..engine import EngineError, default_engine
+    eng = default_engine()
+    track = np.asarray(track, dtype=np.float64)
+    resident = []
+    fit = eng.spline_fit_batch([track], k=k_reg, s=s_reg, stepsize_prep=stepsize_prep, keep=resident)
+    try:
+        if fit["status"][0] != 0:
+            raise EngineError("mcq_spline_fit_device: bad input (status %d, %d samples needed)" % (fit["status"][0], fit["mi"][0]))
+        if int(fit["ier"][0]) in _IER_MESSAGES:
+            warnings.warn(RuntimeWarning(_IER_MESSAGES[int(fit["ier"][0])] + "\tk=%d n=%d m=%d fp=%f s=%f" % (
+                k_reg, fit["nk"][0], fit["mi"][0], fit["fp"][0], s_reg)), stacklevel=3)
+        out = eng.spline_approx_batch([track], None, stepsize_reg, resident=resident)
+    finally:
+        for ptr in resident[2:5]:
+            eng.free(ptr)
     if out["status"][0] != 0:
         raise EngineError("mcq_spline_approx_device: bad input (status %d, %d rows needed)" % (out["status"][0], out["m"][0]))
     if debug:

@@ -473,6 +473,39 @@ int mcq_spline_approx_device(mcq_handle* h, int tracks,
         int* nonmono_out,                                      /* [tracks]: count of i with closest_t[i+1] <= closest_t[i], optional */
         int* status_out);
 
+/* ---- FITPACK's periodic smoothing fit, the step in front of mcq_spline_approx_device [REF helper_funcs_glob/src/prep_track.py:39-45]: what
+ * scipy.interpolate.splprep([x, y], k = k_reg, s = s_reg, per = 1) computes inside tph.spline_approximation (FITPACK's clocur / fpclos) with
+ * interp_track's linear re-sampling at stepsize_prep in front of it.  nk_out / knots_out / coef_out have the layout mcq_spline_approx_device
+ * reads (nk_list / knots / coef), so raw rows become prepared rows without a host round trip.  All pointers DEVICE pointers; asynchronous on
+ * the handle's stream; the scratch is the handle's and grows on demand.  Per track:
+ *   re-sampling interp_track's rule (see mcq_bound_dists_device): closed polyline, element lengths, running sum in numpy.cumsum's order,
+ *               ceil(total / stepsize_prep) + 1 samples of numpy.linspace(0, total), numpy.interp per coordinate, the last sample dropped; then
+ *               sample 0 is appended again: mi closed points.  stepsize_prep <= 0: the raw rows themselves are closed and fitted (mi = n + 1).
+ *   parameter   u_0 = 0, u_i = u_(i-1) + sqrt(dx^2 + dy^2), each divided by u_(mi-1), u_(mi-1) = 1 (scipy's u, bit for bit).
+ *   fit         fpclos with unit weights, iopt = 0, tol = 0.001, maxit = 20, nest = nkmax on the mi - 1 distinct points: s = 0 the
+ *               interpolating periodic spline (ier -1); otherwise knots are added at data parameters by fpknot's rule, starting from the
+ *               constant (ier -2 if that is within s) and u[(mi + 1) / 2 - 1], until the least-squares spline's fp is at most s; then the
+ *               smoothing spline with |fp - s| < 0.001 s by fprati's rational search for p (ier 0; 1: nkmax knots do not suffice, the
+ *               least-squares spline of that stage is returned; 2 / 3: the search failed / took more than 20 rounds, the last spline is
+ *               returned, as scipy returns it with a warning).  The interior knots are bitwise elements of u.  The triangularisation is
+ *               by Givens rotations as FITPACK's (no normal equations), on one layout for both stages; the observations of a knot interval
+ *               are reduced sixteen at a time to k + 1 rows before they enter it; fp is the sum of the squared residuals in the points' order.  Coefficients and fp agree with scipy's to roundings, not bitwise.
+ *   outputs     nk_out = n; knots_out[0 .. n-1]; coef_out[d][0 .. n-k-2] with the last k equal to the first k (scipy's tck); entries behind
+ *               are NaN; fp_out, ier_out FITPACK's values; mi_out (optional) the closed sample count, or the count needed when it exceeds
+ *               mimax; pts_out (optional) [tracks][mimax][2] the closed points that were fitted, NaN behind mi.
+ * status_out [tracks]: MCQ_BAD_INPUT -- nk_out 0, ier_out 10, every other output of the track NaN, the other tracks unaffected -- for n < 3 or
+ *   n > nmax, a non-finite row, mi <= k, mi > mimax, a zero-length element (u is not strictly increasing), total == 0.
+ * MCQ_E_ARG: k outside 1 .. 5, s < 0 or not finite, nkmax < 2 k + 2, nmax < 3, mimax < 2, NULL where an array is required, more than
+ *   MCQ_SPL_MAX_TRACKS tracks in one launch.  No output keeps stale memory. */
+int mcq_spline_fit_device(mcq_handle* h, int tracks,
+        int nmax, const int* n_list, const double* track,   /* [tracks][nmax][4] raw rows, NOT closed; n_list NULL: all nmax */
+        double stepsize_prep, int mimax,                    /* re-sampling step; samples a track may take (closed count) */
+        int k, double s, int nkmax,                         /* degree 1..5, smoothing factor >= 0, nkmax = FITPACK's nest */
+        int* nk_out, double* knots_out, double* coef_out,   /* [tracks], [tracks][nkmax], [tracks][2][nkmax] */
+        double* fp_out, int* ier_out, int* mi_out,          /* [tracks] each; fp_out / mi_out optional */
+        double* pts_out,                                    /* [tracks][mimax][2], optional */
+        int* status_out);
+
 /* prep_track's tail [REF helper_funcs_glob/src/prep_track.py:89-98]: where w_r + w_l < min_width both widths of reftrack_io [batch][nmax][4] grow by
  * half the deficit; changed_out [batch] = 1 if any row of the track changed (upstream's warning), else 0.  n_list [batch] or NULL (all nmax).
  * A separate entry because prep_track runs the normals-crossing check on the un-inflated widths.  DEVICE pointers; asynchronous. */
