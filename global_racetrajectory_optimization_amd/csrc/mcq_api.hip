@@ -1128,6 +1128,172 @@ extern "C" int mcq_export_device(mcq_handle* h, int tracks, int nmax, const int*
     return 0;
 }
 
+// ---- friction maps (include/mcq.h): one map = one device allocation holding the index; the two entries need no temporaries of their own ----
+struct mcq_fmap {
+    McqFmap F;
+    void* dev = nullptr;
+    size_t bytes = 0;
+};
+#define MCQ_FMAP_MAX_BINS (1 << 22)
+
+// NOTE: an edge is o + k * side in two roundings, here and in fric_edge (csrc/mcq_fric.inc, compiled without contraction).  This translation
+// unit's host code is baseline x86-64, which has no fused multiply-add to contract to.
+static inline double fmap_edge(double o, double side, int k) { return o + (double)k * side; }
+
+static int fmap_bin(double c, double o, double side, int nb)
+{
+    const double t = std::floor((c - o) / side);
+    int k = t >= (double)(nb - 1) ? nb - 1 : (t > 0.0 ? (int)t : 0);
+    while (k > 0 && c < fmap_edge(o, side, k)) --k;                 // the quotient's rounding against the edges the kernels measure from
+    while (k < nb - 1 && c > fmap_edge(o, side, k + 1)) ++k;
+    return k;
+}
+
+extern "C" int mcq_fmap_create(mcq_handle* h, int cells, const double* xy_host, const double* mue_host, double bin_side, mcq_fmap** out)
+{
+    if (!h || cells < 1 || !xy_host || !mue_host || !out) {
+        g_err = "mcq_fmap_create: bad argument";
+        return MCQ_E_ARG;
+    }
+    *out = nullptr;
+    double x0 = INFINITY, x1 = -INFINITY, y0 = INFINITY, y1 = -INFINITY;
+    for (int c = 0; c < cells; ++c) {
+        const double x = xy_host[2 * (size_t)c], y = xy_host[2 * (size_t)c + 1];
+        if (!(std::isfinite(x) && std::isfinite(y))) {
+            g_err = "mcq_fmap_create: a cell coordinate is not finite";
+            return MCQ_E_ARG;
+        }
+        x0 = std::min(x0, x); x1 = std::max(x1, x); y0 = std::min(y0, y); y1 = std::max(y1, y);
+    }
+    const double wx = x1 - x0, wy = y1 - y0;
+    if (!(std::isfinite(wx) && std::isfinite(wy))) {
+        g_err = "mcq_fmap_create: the cells' bounding box is not finite";
+        return MCQ_E_ARG;
+    }
+    double side = bin_side;
+    if (!(side > 0.0) || !std::isfinite(side)) {        // automatic: a cell per bin on average over the box
+        side = std::sqrt(wx * wy / (double)cells);
+        if (!(side > 0.0) || !std::isfinite(side)) side = std::max(wx, wy) / (double)cells;     // a degenerate box: all cells on one line ...
+        if (!(side > 0.0) || !std::isfinite(side)) side = 1.0;                                  // ... or at one point
+    }
+    // a degenerate axis has one bin; the bin count is capped by growing the side
+    for (;;) {
+        const double bx = std::floor(wx / side) + 1.0, by = std::floor(wy / side) + 1.0;
+        if (bx * by <= (double)MCQ_FMAP_MAX_BINS) break;
+        side *= 2.0;
+    }
+    const int nbx = (int)std::floor(wx / side) + 1, nby = (int)std::floor(wy / side) + 1;
+    const size_t nb = (size_t)nbx * nby;
+    // one allocation: sxy [cells][2], mue [cells], bin_start [nb + 1], sidx [cells]
+    const size_t off_mue = (size_t)cells * 2 * sizeof(double), off_bs = off_mue + (size_t)cells * sizeof(double);
+    const size_t off_idx = off_bs + (nb + 1) * sizeof(int), bytes = off_idx + (size_t)cells * sizeof(int);
+    std::vector<double> img((bytes + 7) / 8);
+    char* base = (char*)img.data();
+    double* sxy = (double*)base;
+    double* mue = (double*)(base + off_mue);
+    int* bs = (int*)(base + off_bs);
+    int* sidx = (int*)(base + off_idx);
+    std::vector<int> bin_of(cells);
+    for (size_t b = 0; b <= nb; ++b) bs[b] = 0;
+    for (int c = 0; c < cells; ++c) {
+        bin_of[c] = fmap_bin(xy_host[2 * (size_t)c + 1], y0, side, nby) * nbx + fmap_bin(xy_host[2 * (size_t)c], x0, side, nbx);
+        ++bs[bin_of[c] + 1];
+    }
+    for (size_t b = 0; b < nb; ++b) bs[b + 1] += bs[b];
+    {
+        std::vector<int> fill(bs, bs + nb);
+        for (int c = 0; c < cells; ++c) {       // a counting sort: within a bin the cells keep their original order
+            const int at = fill[bin_of[c]]++;
+            sxy[2 * (size_t)at] = xy_host[2 * (size_t)c];
+            sxy[2 * (size_t)at + 1] = xy_host[2 * (size_t)c + 1];
+            sidx[at] = c;
+        }
+    }
+    memcpy(mue, mue_host, (size_t)cells * sizeof(double));
+    HIP_TRY(hipSetDevice(h->device));
+    mcq_fmap* m = new mcq_fmap();
+    hipError_t e = hipMalloc(&m->dev, bytes);
+    if (e == hipSuccess) e = hipMemcpy(m->dev, base, bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(m->dev);
+        delete m;
+        return hip_failed("mcq_fmap_create: hipMalloc / hipMemcpy", e, __FILE__, __LINE__);
+    }
+    m->bytes = bytes;
+    char* d = (char*)m->dev;
+    m->F.cells = cells; m->F.nbx = nbx; m->F.nby = nby;
+    m->F.x0 = x0; m->F.y0 = y0; m->F.side = side;
+    m->F.sxy = (const double*)d; m->F.mue = (const double*)(d + off_mue);
+    m->F.bin_start = (const int*)(d + off_bs); m->F.sidx = (const int*)(d + off_idx);
+    *out = m;
+    return 0;
+}
+
+extern "C" int mcq_fmap_destroy(mcq_handle* h, mcq_fmap* fmap)
+{
+    if (!h) { g_err = "mcq_fmap_destroy: bad argument"; return MCQ_E_ARG; }
+    if (!fmap) return 0;
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->ws[0].stream));      // a launch in flight may still read the map
+    (void)hipFree(fmap->dev);
+    delete fmap;
+    return 0;
+}
+
+extern "C" int mcq_fmap_info(const mcq_fmap* fmap, int* cells, int* bins_x, int* bins_y, double* bin_side, long long* device_bytes)
+{
+    if (!fmap) { g_err = "mcq_fmap_info: bad argument"; return MCQ_E_ARG; }
+    if (cells) *cells = fmap->F.cells;
+    if (bins_x) *bins_x = fmap->F.nbx;
+    if (bins_y) *bins_y = fmap->F.nby;
+    if (bin_side) *bin_side = fmap->F.side;
+    if (device_bytes) *device_bytes = (long long)fmap->bytes;
+    return 0;
+}
+
+extern "C" int mcq_fmap_query_device(mcq_handle* h, const mcq_fmap* fmap, int count, const double* xy, double* mue_out, int* idx_out,
+                                     double* dist_out)
+{
+    if (!h || !fmap || count < 0 || (count > 0 && (!xy || !mue_out))) {
+        g_err = "mcq_fmap_query_device: bad argument";
+        return MCQ_E_ARG;
+    }
+    if (count == 0) return 0;
+    HIP_TRY(hipSetDevice(h->device));
+    hipLaunchKernelGGL(mcq_fmap_query_kernel, dim3((unsigned)(((size_t)count + 255) / 256)), dim3(256), 0, h->ws[0].stream, fmap->F, count, xy,
+                       mue_out, idx_out, dist_out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int mcq_friction_grid_device(mcq_handle* h, const mcq_fmap* fmap, int tracks, int nmax, const int* n_list, const double* reftrack,
+                                        const double* normvec, double width_opt, const double* width_list, double wheelbase_front,
+                                        double wheelbase_rear, double dn, int jmax, double* n_out, int* cnt_out, double* mue_out, int* idx_out,
+                                        double* w_mue_out, int* status_out)
+{
+    if (!h || !fmap || tracks <= 0 || nmax < 1 || !(dn > 0.0) || !std::isfinite(dn) || jmax < 1 || !reftrack || !normvec || !n_out || !cnt_out ||
+        !mue_out || !status_out) {
+        g_err = "mcq_friction_grid_device: bad argument";
+        return MCQ_E_ARG;
+    }
+    const size_t nblk = ((size_t)nmax + MCQ_FG_ROWS) / MCQ_FG_ROWS;
+    if ((size_t)tracks * nblk > 0x7fffffffu) {
+        g_err = "mcq_friction_grid_device: more row blocks than one launch holds";
+        return MCQ_E_TOO_LARGE;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    McqFricGrid G;
+    memset(&G, 0, sizeof(G));
+    G.F = fmap->F;
+    G.tracks = tracks; G.nmax = nmax; G.jmax = jmax;
+    G.n_list = n_list; G.ref = reftrack; G.nv = normvec;
+    G.width = width_opt; G.width_list = width_list; G.wbf = wheelbase_front; G.wbr = wheelbase_rear; G.dn = dn;
+    G.n_out = n_out; G.cnt_out = cnt_out; G.mue_out = mue_out; G.idx_out = idx_out; G.w_out = w_mue_out; G.status = status_out;
+    hipLaunchKernelGGL(mcq_friction_grid_kernel, dim3((unsigned)((size_t)tracks * nblk)), dim3(256), 0, h->ws[0].stream, G);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // ---- device memory plumbing for callers that keep data resident between calls without a second HIP runtime in the
 //      process (the Python IQP driver): plain allocate / free / copy on the handle's device and stream ------------------
 extern "C" int mcq_device_alloc(mcq_handle* h, size_t bytes, void** out)

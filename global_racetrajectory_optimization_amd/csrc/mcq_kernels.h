@@ -420,3 +420,35 @@ struct McqExport {
 };
 __global__ void mcq_export_s_kernel(McqExport X);
 __global__ void mcq_export_rows_kernel(McqExport X);
+
+/* ---- friction maps (mcq_fmap_create, mcq_fmap_query_device, mcq_friction_grid_device; csrc/mcq_fric.inc) [REF opt_mintime_traj/src/
+ *      friction_map_interface.py, extract_friction_coeffs.py, approx_friction_map.py].  McqFmap is the device view of one map: a uniform grid of bins
+ *      over the cells' bounding box in CSR form, built and uploaded once by mcq_fmap_create. ---- */
+struct McqFmap {
+    int cells, nbx, nby;
+    double x0, y0, side;     // lower corner of the box, side of a bin: bin k of an axis starts at x0 + k * side (two roundings)
+    const int* bin_start;    // [nbx * nby + 1]: bin iy * nbx + ix holds the sorted cells bin_start[.] .. bin_start[. + 1] - 1
+    const double* sxy;       // [cells][2] coordinates, sorted by bin (within a bin: by original index)
+    const int* sidx;         // [cells] original index of a sorted cell
+    const double* mue;       // [cells] in ORIGINAL order
+};
+__global__ void mcq_fmap_query_kernel(McqFmap F, int count, const double* xy, double* mue_out, int* idx_out, double* dist_out);
+
+#define MCQ_FG_ROWS 4        /* rows of a track per workgroup of mcq_friction_grid_kernel: a wave each */
+struct McqFricGrid {
+    McqFmap F;
+    int tracks, nmax, jmax;
+    const int* n_list;       // [tracks] or nullptr (all nmax)
+    const double* ref;       // [tracks][nmax][4]
+    const double* nv;        // [tracks][nmax][2]
+    double width;            // width_opt where width_list is nullptr
+    const double* width_list;   // [tracks] or nullptr
+    double wbf, wbr, dn;
+    double* n_out;           // [tracks][nmax + 1][jmax]
+    int* cnt_out;            // [tracks][nmax + 1]
+    double* mue_out;         // [tracks][4][nmax + 1][jmax]
+    int* idx_out;            // [tracks][4][nmax + 1][jmax] or nullptr
+    double* w_out;           // [tracks][4][nmax + 1][2] or nullptr
+    int* status;             // [tracks]
+};
+__global__ void mcq_friction_grid_kernel(McqFricGrid G);

@@ -4106,6 +4106,8 @@ __global__ void __launch_bounds__(MCQ_NT) mcq_spline_finish_kernel(McqSpline S)
 // tests/conftest.py) and bench.py's source_sha.  An edit to mcq_fit.inc alone neither rebuilds tests/emu/libmcq_emu.so nor changes the hash that
 // ties profiles to sources -- until both lists name it, touch this file as well (build.sh itself always compiles everything).
 #include "mcq_fit.inc"
+// (the same holds for mcq_fric.inc: the friction maps' kernels)
+#include "mcq_fric.inc"
 
 __global__ void __launch_bounds__(MCQ_NT) mcq_min_width_kernel(int nmax, const int* n_list, double* ref_all, double min_width, int* changed_out)
 {

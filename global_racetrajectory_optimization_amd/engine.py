@@ -10,6 +10,7 @@ Mirrors the reference-side interface for the hot path:
     Engine.solve_device(...)       -> device-resident batch entry (bench, IQP driver, multi-GPU shards)
 """
 import ctypes
+import math
 import os
 
 import numpy as np
@@ -185,6 +186,11 @@ _ABI = {
     "mcq_spline_fit_device": (_ci, [_vp, _ci, _ci, _vp, _vp, _cd, _ci, _ci, _cd, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mcq_min_width_device": (_ci, [_vp, _ci, _ci, _vp, _vp, _cd, _vp]),
     "mcq_export_device": (_ci, [_vp, _ci, _ci, _vp, _vp, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mcq_fmap_create": (_ci, [_vp, _ci, _vp, _vp, _cd, _P(_vp)]),
+    "mcq_fmap_destroy": (_ci, [_vp, _vp]),
+    "mcq_fmap_info": (_ci, [_vp, _ip, _ip, _ip, _dp, _P(ctypes.c_longlong)]),
+    "mcq_fmap_query_device": (_ci, [_vp, _vp, _ci, _vp, _vp, _vp, _vp]),
+    "mcq_friction_grid_device": (_ci, [_vp, _vp, _ci, _ci, _vp, _vp, _vp, _cd, _vp, _cd, _cd, _cd, _ci, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 EXPORTED_SYMBOLS = tuple(_ABI)
 
@@ -311,6 +317,37 @@ class _Scope:
         return ptr
 
 
+class FrictionMap:
+    """A friction map resident on an engine's device (mcq_fmap_create): Engine.friction_map makes it, close() or the context manager frees it, and
+    the engine's close() frees whatever is still open.  info: cells, bins_x, bins_y, bin_side, device_bytes."""
+
+    def __init__(self, eng, ptr, mue):
+        self.eng, self.ptr = eng, ptr
+        self.mue = mue          # the host's copy, in the cells' order
+        c, bx, by, side, nbytes = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_double(), ctypes.c_longlong()
+        eng._check(eng.lib.mcq_fmap_info(ptr, ctypes.byref(c), ctypes.byref(bx), ctypes.byref(by), ctypes.byref(side), ctypes.byref(nbytes)),
+                   "mcq_fmap_info")
+        self.info = dict(cells=c.value, bins_x=bx.value, bins_y=by.value, bin_side=side.value, device_bytes=nbytes.value)
+
+    def close(self):
+        if self.ptr and getattr(self.eng, "h", None):
+            self.eng._check(self.eng.lib.mcq_fmap_destroy(self.eng.h, self.ptr), "mcq_fmap_destroy")
+        if self in getattr(self.eng, "_fmaps", []):
+            self.eng._fmaps.remove(self)
+        self.ptr = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _live(self):
+        if not self.ptr:
+            raise EngineError("the friction map has been closed")
+        return self.ptr
+
+
 class Engine:
     """One handle == one GPU + one HIP stream + its device workspace.  One host thread at a time."""
 
@@ -330,6 +367,8 @@ class Engine:
 
     def close(self):
         if getattr(self, "h", None):
+            for fm in list(getattr(self, "_fmaps", [])):
+                fm.close()
             for p in getattr(self, "_pinned", []):
                 self.lib.mcq_host_free(self.h, p)
             self._pinned = []
@@ -1186,6 +1225,99 @@ class Engine:
             total = self.download(d_tot, (tracks,), np.float64)
             status = self.download(d_st, (bsz,), np.int32)
         return export_result(tab, idx, lens, s_ref, total, status, ns, ms, tr, tj)
+
+    # ---- friction maps (include/mcq.h "friction maps"; the reference's names on top of these: friction.py) ----------------------------------
+    def friction_map(self, cells, mue, bin_side=None):
+        """A FrictionMap of cells [c, 2] with mue [c] (NaN: a cell without data), resident on the device (mcq_fmap_create).  bin_side None: automatic."""
+        xy = np.ascontiguousarray(cells, dtype=np.float64)
+        mu = np.ascontiguousarray(mue, dtype=np.float64).reshape(-1)
+        if xy.ndim != 2 or xy.shape[1] != 2 or mu.shape[0] != xy.shape[0]:
+            raise ValueError("friction_map: cells must be [c, 2] and mue [c]")
+        p = ctypes.c_void_p()
+        rc = self.lib.mcq_fmap_create(self.h, xy.shape[0], xy.ctypes.data, mu.ctypes.data, float(bin_side) if bin_side else 0.0, ctypes.byref(p))
+        self._check(rc, "mcq_fmap_create")
+        fm = FrictionMap(self, p.value, mu.copy())
+        if not hasattr(self, "_fmaps"):
+            self._fmaps = []
+        self._fmaps.append(fm)
+        return fm
+
+    def friction_query_device(self, fmap, count, d_xy, d_mue, d_idx=None, d_dist=None):
+        """mcq_fmap_query_device on device pointers: d_xy [count][2] -> d_mue [count] (d_idx, d_dist optional).  Asynchronous.  On raceline_batch's
+        resident xy [batch][mmax][2] with count = batch * mmax, d_mue IS the mu [batch][mmax] of mcq_vel_profile_device_opts: padding rows that
+        are NaN going in are NaN coming out (the raceline entry itself leaves the rows behind m unwritten, and the profile entries do not read
+        them)."""
+        rc = self.lib.mcq_fmap_query_device(self.h, fmap._live(), int(count), d_xy, d_mue, d_idx or None, d_dist or None)
+        self._check(rc, "mcq_fmap_query_device")
+
+    def friction_query_batch(self, fmap, points, want_idx=False, want_dist=False):
+        """The friction under points [..., 2]: mue [...] of the nearest cell each (lowest index among exact ties), or a tuple (mue, idx, dist) with
+        the entries asked for.  A point that is not finite: NaN, -1, NaN."""
+        pts = np.ascontiguousarray(points, dtype=np.float64)
+        if pts.ndim < 1 or pts.shape[-1] != 2:
+            raise ValueError("friction_query_batch: points must be [..., 2]")
+        shape, count = pts.shape[:-1], int(pts.size // 2)
+        fmap._live()
+        if count == 0:
+            res = (np.empty(shape), np.empty(shape, dtype=np.int32), np.empty(shape))
+        else:
+            with self.scope() as dev:
+                d_xy, d_mu = dev.up(pts), dev.new(count * 8)
+                d_i, d_d = dev.new(count * 4) if want_idx else None, dev.new(count * 8) if want_dist else None
+                self.friction_query_device(fmap, count, d_xy, d_mu, d_i, d_d)
+                res = (self.download(d_mu, shape, np.float64), self.download(d_i, shape, np.int32) if want_idx else None,
+                       self.download(d_d, shape, np.float64) if want_dist else None)
+        out = (res[0],) + ((res[1],) if want_idx else ()) + ((res[2],) if want_dist else ())
+        return out if len(out) > 1 else out[0]
+
+    def friction_grid_device(self, fmap, tracks, nmax, d_n, d_ref, d_nv, width_opt, d_width, wheelbase_front, wheelbase_rear, dn, jmax, d_n_out,
+                             d_cnt, d_mue, d_idx, d_w, d_status):
+        """mcq_friction_grid_device (include/mcq.h) on device pointers; d_n / d_width / d_idx / d_w may be None.  Asynchronous."""
+        rc = self.lib.mcq_friction_grid_device(self.h, fmap._live(), int(tracks), int(nmax), d_n or None, d_ref, d_nv, float(width_opt),
+                                               d_width or None, float(wheelbase_front), float(wheelbase_rear), float(dn), int(jmax), d_n_out,
+                                               d_cnt, d_mue, d_idx or None, d_w or None, d_status)
+        self._check(rc, "mcq_friction_grid_device")
+
+    @staticmethod
+    def friction_jmax(reftracks, widths, dn):
+        """The largest count of lateral positions over the finite rows of a list of tracks: Python's own floors, as the kernel takes them."""
+        jmax = 1
+        for r, w in zip(reftracks, widths):
+            for wr, wl in np.asarray(r, dtype=np.float64)[:, 2:4].tolist():
+                q = ((wr - 0.5 * w - 0.5) / dn, (wl - 0.5 * w - 0.5) / dn)
+                if all(math.isfinite(v) and abs(v) < 1e9 for v in q):
+                    jmax = max(jmax, math.floor(q[0]) + math.floor(q[1]) + 1)
+        return jmax
+
+    def friction_grid_batch(self, fmap, reftracks, normvecs, width_opt, wheelbase_front, wheelbase_rear, dn, fit=True, jmax=None, want_idx=False):
+        """extract_friction_coeffs and the linear approx_friction_map of a list of (ragged) tracks in one launch (mcq_friction_grid_device).
+        reftracks [n_k, 4], normvecs [n_k, 2]; width_opt: a scalar or one value per track; jmax None: from the widths, on the host.
+        Returns a dict of padded arrays: n [tracks, nmax + 1, jmax], cnt [tracks, nmax + 1], mue [tracks, 4, nmax + 1, jmax] (fl, fr, rl, rr),
+        w_mue [tracks, 4, nmax + 1, 2] (slope, intercept; fit=False: None), idx (want_idx), status [tracks], rows [tracks] = n_k + 1."""
+        ns, ref = _pad_rows(reftracks, 4)
+        nv = _pad_like(normvecs, ns, (2,))
+        tracks, nmax = ref.shape[:2]
+        wl = None if np.ndim(width_opt) == 0 else np.ascontiguousarray(width_opt, dtype=np.float64)
+        if wl is not None and wl.shape != (tracks,):
+            raise ValueError("friction_grid_batch: width_opt must be a scalar or hold one width per track")
+        w0 = float(width_opt) if wl is None else 0.0
+        if jmax is None:
+            jmax = self.friction_jmax(reftracks, [w0] * tracks if wl is None else wl.tolist(), float(dn))
+        jmax, rows = int(jmax), nmax + 1
+        with self.scope() as dev:
+            up, new = dev.up, dev.new
+            d_ref, d_nv, d_n, d_wl = up(ref), up(nv), up(ns), up(wl)
+            d_no, d_cnt, d_mu = new(tracks * rows * jmax * 8), new(tracks * rows * 4), new(tracks * 4 * rows * jmax * 8)
+            d_ix = new(tracks * 4 * rows * jmax * 4) if want_idx else None
+            d_w = new(tracks * 4 * rows * 2 * 8) if fit else None
+            d_st = new(tracks * 4)
+            self.friction_grid_device(fmap, tracks, nmax, d_n, d_ref, d_nv, w0, d_wl, wheelbase_front, wheelbase_rear, dn, jmax, d_no, d_cnt,
+                                      d_mu, d_ix, d_w, d_st)
+            return dict(n=self.download(d_no, (tracks, rows, jmax), np.float64), cnt=self.download(d_cnt, (tracks, rows), np.int32),
+                        mue=self.download(d_mu, (tracks, 4, rows, jmax), np.float64),
+                        w_mue=self.download(d_w, (tracks, 4, rows, 2), np.float64) if fit else None,
+                        idx=self.download(d_ix, (tracks, 4, rows, jmax), np.int32) if want_idx else None,
+                        status=self.download(d_st, (tracks,), np.int32), rows=ns + 1)
 
     def relinearise_device(self, batch, nmax, d_n_in, d_ref_in, d_nv_in, d_alpha, d_live, alpha_scale, stepsize,
                            d_ref_out, d_nv_out, d_n_out, d_status):

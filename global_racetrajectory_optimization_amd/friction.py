@@ -1,0 +1,107 @@
+"""Friction maps behind the reference's names [REF opt_mintime_traj/src/friction_map_interface.py, extract_friction_coeffs.py,
+approx_friction_map.py]: the same argument names, return shapes and error behaviour, on the engine's device entries (include/mcq.h "friction
+maps": mcq_fmap_create, mcq_fmap_query_device, mcq_friction_grid_device).
+
+  load_friction_map(tpamap_path, tpadata_path)          the two files as (cells [c, 2], mue [c]); a cell without data is NaN
+  FrictionMapInterface(tpamap_path, tpadata_path)       .get_friction_singlepos(positions) -> [k, 1]
+  extract_friction_coeffs(...)                          -> n, mue_fl, mue_fr, mue_rl, mue_rr: lists with one entry per row of the closed track
+  approx_friction_map(...)                              -> w_mue_fl, w_mue_fr, w_mue_rl, w_mue_rr, center_dist for var_friction == "linear"
+
+Differences from the reference, all stated in include/mcq.h: among cells at exactly the same distance the lowest index is taken (scipy's cKDTree
+documents no rule); a row of exactly one lateral position has a NaN line where numpy.polyfit returns a minimum-norm answer with a RankWarning;
+var_friction == "gauss" (an sklearn pipeline whose parity would mean restating its SVD solver) raises NotImplementedError.  plot_debug is ignored.
+Every function takes an `engine` keyword (default: engine.default_engine())."""
+import json
+
+import numpy as np
+
+from . import engine as _engine
+
+
+def load_friction_map(tpamap_path, tpadata_path):
+    """(cells [c, 2], mue [c]): the map file as numpy.loadtxt reads it (comments '#', delimiter ';'), the data file's keys as ints, each value a
+    list of one number (ValueError otherwise); a cell the data file does not name has mue NaN."""
+    cells = np.loadtxt(tpamap_path, comments='#', delimiter=';').reshape(-1, 2)
+    with open(tpadata_path, 'r') as fh:
+        data = json.load(fh)
+    mue = np.full(cells.shape[0], np.nan)
+    for k, v in data.items():
+        i = int(k)
+        if not isinstance(v, list) or len(v) != 1 or isinstance(v[0], (list, dict, str, bool)) or v[0] is None:
+            raise ValueError("tpadata entry %r: expected a list of one number, got %r" % (k, v))
+        if not 0 <= i < cells.shape[0]:
+            raise ValueError("tpadata entry %r names no cell of the map (%d cells)" % (k, cells.shape[0]))
+        mue[i] = float(v[0])
+    return cells, mue
+
+
+class FrictionMapInterface:
+    """The reference's class on a device-resident map."""
+
+    def __init__(self, tpamap_path, tpadata_path, engine=None):
+        self.engine = engine or _engine.default_engine()
+        self.fmap = self.engine.friction_map(*load_friction_map(tpamap_path, tpadata_path))
+
+    def close(self):
+        self.fmap.close()
+
+    def get_friction_singlepos(self, positions):
+        """[[mue_0], [mue_1], ...] for positions [[x_0, y_0], ...]; numpy.asarray([]) for an empty input; KeyError (the cell's index) where the
+        nearest cell has no data, as the reference's dict lookup raises."""
+        positions = np.asarray(positions, dtype=np.float64)
+        if positions.size == 0:
+            return np.asarray([])
+        mue, idx = self.engine.friction_query_batch(self.fmap, positions.reshape(-1, 2), want_idx=True)
+        _raise_missing(mue, idx)
+        return mue.reshape(-1, 1)
+
+
+def _raise_missing(mue, idx):
+    miss = np.isnan(mue) & (idx >= 0)
+    if np.any(miss):
+        raise KeyError(int(idx[miss][0]))
+
+
+def _grid(reftrack, normvectors, tpamap_path, tpadata_path, pars, dn, fit, engine):
+    eng = engine or _engine.default_engine()
+    reftrack, normvectors = np.asarray(reftrack, dtype=np.float64), np.asarray(normvectors, dtype=np.float64)
+    width = pars["optim_opts"]["width_opt"]
+    wb_f = pars["vehicle_params_mintime"]["wheelbase_front"]
+    wb_r = pars["vehicle_params_mintime"]["wheelbase_rear"]
+    cells, mue = load_friction_map(tpamap_path, tpadata_path)
+    with eng.friction_map(cells, mue) as fmap:
+        g = eng.friction_grid_batch(fmap, [reftrack], [normvectors], float(width), wb_f, wb_r, float(dn), fit=fit, want_idx=True)
+    if g["status"][0] != 0:
+        raise ValueError("friction grid: the track was refused (a row that is not finite?)")
+    rows = int(g["rows"][0])
+    cnt = g["cnt"][0, :rows]
+    if np.any(cnt < 0):     # numpy.linspace's own words
+        raise ValueError("Number of samples, %d, must be non-negative." % int(cnt[cnt < 0][0]))
+    for w in range(4):
+        for i in range(rows):
+            _raise_missing(g["mue"][0, w, i, :cnt[i]], g["idx"][0, w, i, :cnt[i]])
+    return g, rows, cnt
+
+
+def extract_friction_coeffs(reftrack, normvectors, tpamap_path, tpadata_path, pars, dn, print_debug=False, plot_debug=False, engine=None):
+    """n, mue_fl, mue_fr, mue_rl, mue_rr: lists of len(reftrack) + 1 entries; n[i] is [cnt_i], mue_x[i] is [cnt_i, 1] (numpy.asarray([]) for an
+    empty row, as the reference's interface returns for an empty input)."""
+    g, rows, cnt = _grid(reftrack, normvectors, tpamap_path, tpadata_path, pars, dn, False, engine)
+    n = [g["n"][0, i, :cnt[i]].copy() for i in range(rows)]
+    mue = [[g["mue"][0, w, i, :cnt[i]].reshape(-1, 1).copy() if cnt[i] else np.asarray([]) for i in range(rows)] for w in range(4)]
+    return n, mue[0], mue[1], mue[2], mue[3]
+
+
+def approx_friction_map(reftrack, normvectors, tpamap_path, tpadata_path, pars, dn, n_gauss=0, print_debug=False, plot_debug=False, engine=None):
+    """w_mue_fl, w_mue_fr, w_mue_rl, w_mue_rr [rows, 2] (slope, intercept per row: numpy.polyfit's order) and center_dist [rows, 1] (zeros) for
+    pars["optim_opts"]["var_friction"] == "linear"."""
+    method = pars["optim_opts"]["var_friction"]
+    if method == "gauss":
+        raise NotImplementedError("var_friction 'gauss' (regression with Gaussian basis functions) is not available on the device")
+    if method != "linear":
+        raise ValueError('Unknown method for friction map approximation!')
+    g, rows, cnt = _grid(reftrack, normvectors, tpamap_path, tpadata_path, pars, dn, True, engine)
+    if np.any(cnt == 0):    # numpy.polyfit's own words
+        raise TypeError("expected non-empty vector for x")
+    w = [g["w_mue"][0, k, :rows].copy() for k in range(4)]
+    return w[0], w[1], w[2], w[3], np.zeros((rows, 1))

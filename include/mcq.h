@@ -544,6 +544,54 @@ int mcq_export_device(mcq_handle* h, int tracks, int nmax, const int* n_list, co
                       double* ltpl_out, int* idx_out, double* spline_lengths_out, double* s_ref_out, double* spline_total_out,
                       int* status_out);
 
+/* ---- friction maps [REF opt_mintime_traj/src/friction_map_interface.py, extract_friction_coeffs.py, approx_friction_map.py]: what produces the
+ * `mu` of mcq_vel_opts / mcq_vel_forms, and the reference's grids of friction along the normals with their lines.
+ * A map is one object, resident on the handle's device: cells points (any point set -- no lattice is assumed) with a friction value each.
+ * mcq_fmap_create builds the index on the host (deterministic, O(cells)) and uploads it once: a uniform grid of bins of side bin_side over the
+ *   cells' bounding box in CSR form (bin_start [bins_x * bins_y + 1], the cells' coordinates and original indices sorted by bin, mue in original
+ *   order).  bin_side <= 0: automatic, sqrt(box area / cells); more than 2^22 bins: the side is doubled until they fit.  A degenerate box (all
+ *   cells on one line or at one point) has one bin along that axis.  xy_host [cells][2], mue_host [cells]: HOST memory, read before the call
+ *   returns.  MCQ_E_ARG: cells < 1, a cell coordinate that is not finite, NULL.  A NaN in mue is allowed and handed through by the lookups.
+ * mcq_fmap_destroy waits for the handle's stream first; NULL is a success.  mcq_fmap_info: any pointer may be NULL.
+ *
+ * mcq_fmap_query_device: the nearest cell of each of count points.  DEVICE pointers; asynchronous on the handle's stream.
+ *   The lookup is EXACT: for any finite query, wherever it lies, idx is a cell of minimum computed squared distance dx * dx + dy * dy (double,
+ *   every operation rounded on its own).  TIE RULE (the engine's own; scipy's cKDTree documents none): among cells at exactly equal computed
+ *   squared distance, the lowest original index -- duplicated cells included.  A query far outside the box is slow (the whole grid may be
+ *   scanned) and correct.
+ *   mue_out [count] = mue[idx], bits unchanged (a NaN there is handed through); idx_out [count] (optional); dist_out [count] (optional) = the
+ *   square root of the minimum.  A query that is not finite: idx -1, mue NaN, dist NaN.  count == 0: success without a launch.
+ *
+ * mcq_friction_grid_device: extract_friction_coeffs and approx_friction_map(var_friction = "linear") for a batch of tracks in one launch.
+ *   reftrack [tracks][nmax][4], normvec [tracks][nmax][2], n_list [tracks] or NULL (all nmax); width_list [tracks] or NULL (width_opt for all).
+ *   A track of n waypoints has n + 1 rows: row n is row 0 again, as the reference closes it.  Per row, with w_r, w_l the row's widths:
+ *   cnt_out [tracks][nmax + 1] = num_right + num_left + 1, num_x = floor((w_x - 0.5 * width - 0.5) / dn): Python's operations, bit for bit its
+ *     decisions ((5.0 - 1.7 - 0.5) / 0.1 is 27.999999999999996 and floors to 27);
+ *   n_out [tracks][nmax + 1][jmax] = numpy.linspace(-dn * num_right, dn * num_left, cnt): j * step + start with the product and the sum rounded
+ *     separately, the last entry the stop value itself -- numpy's bits;
+ *   mue_out [tracks][4][nmax + 1][jmax]: the wheels fl, fr, rl, rr at (p +- wheelbase * tang) - (n_j +- 0.5 * width) * normvec with
+ *     tang = (-n_y, n_x), the reference's four expressions rounded as numpy rounds them, looked up as mcq_fmap_query_device does;
+ *     idx_out (optional), same shape: the cells;
+ *   w_mue_out [tracks][4][nmax + 1][2] (optional): slope, then intercept of the least-squares line through (n_j, mue_j), numpy.polyfit(n, mue, 1)'s
+ *     order, from centred sums taken in one fixed order: bit-identical whatever the grid, the launch's company or the order of the tracks.
+ *   Entries beyond a row's count, rows beyond n and every output of a refused track are NaN (idx -1, cnt 0).
+ *   DEVIATIONS from the reference, both stated: a row whose count is <= 0 has cnt_out equal to that count and NaN outputs, and the track stays
+ *     MCQ_OK (numpy.linspace raises for a negative number, and the reference fails in polyfit for an empty row); a row of exactly one position
+ *     delivers its mue and a NaN line (numpy returns a minimum-norm answer with a RankWarning).
+ *   status_out [tracks]: MCQ_OK, or MCQ_BAD_INPUT for n < 1 or n > nmax, a row (or a width or wheelbase) that is not finite -- cnt_out 0 -- or
+ *     a count above jmax -- cnt_out then reports the counts the track needs, as the raceline entries report m.  Other tracks are not affected.
+ *   MCQ_E_ARG: dn <= 0 or not finite, jmax < 1, nmax < 1, tracks <= 0, NULL where an array is required; MCQ_E_TOO_LARGE: tracks x
+ *     ceil((nmax + 1) / 4) beyond 2^31 - 1 (the launch's grid).  The entry needs no temporaries. */
+typedef struct mcq_fmap mcq_fmap;
+int mcq_fmap_create(mcq_handle* h, int cells, const double* xy_host, const double* mue_host, double bin_side, mcq_fmap** fmap_out);
+int mcq_fmap_destroy(mcq_handle* h, mcq_fmap* fmap);
+int mcq_fmap_info(const mcq_fmap* fmap, int* cells, int* bins_x, int* bins_y, double* bin_side, long long* device_bytes);
+int mcq_fmap_query_device(mcq_handle* h, const mcq_fmap* fmap, int count, const double* xy, double* mue_out, int* idx_out, double* dist_out);
+int mcq_friction_grid_device(mcq_handle* h, const mcq_fmap* fmap, int tracks, int nmax, const int* n_list, const double* reftrack,
+                             const double* normvec, double width_opt, const double* width_list, double wheelbase_front, double wheelbase_rear,
+                             double dn, int jmax, double* n_out, int* cnt_out, double* mue_out, int* idx_out, double* w_mue_out,
+                             int* status_out);
+
 /* Host-buffer entry for a UNIFORM batch (every track n waypoints): reftrack [batch][n][4], normvec [batch][n][2] or NULL,
  * scaling [batch][n] or NULL in host memory, results to host memory.  One asynchronous copy per array straight from / to the
  * caller's buffers -- no packing pass; buffers from mcq_host_alloc (pinned) are copied at PCIe speed, pageable ones go through
