@@ -1294,6 +1294,65 @@ extern "C" int mcq_friction_grid_device(mcq_handle* h, const mcq_fmap* fmap, int
     return 0;
 }
 
+extern "C" int mcq_friction_gauss_device(mcq_handle* h, int tracks, int nmax, int jmax, const double* n_out, const int* cnt_out,
+                                         const double* mue_out, const int* status, int n_gauss, double rcond, double* w_gauss_out,
+                                         double* center_dist_out, int* rank_out, int* sweeps_out)
+{
+    if (!h || tracks <= 0 || nmax < 1 || jmax < 1 || n_gauss < 1 || n_gauss > 15 || std::isnan(rcond) || !n_out || !cnt_out || !mue_out || !status ||
+        !w_gauss_out || !center_dist_out) {
+        g_err = "mcq_friction_gauss_device: bad argument";
+        return MCQ_E_ARG;
+    }
+    const int N = 2 * n_gauss + 1;
+    const size_t row_bytes = mcq_fgs_row_doubles(jmax, N) * sizeof(double);
+    if (row_bytes > MCQ_FGS_LDS) {
+        g_err = "mcq_friction_gauss_device: one row's matrix does not fit into 64 KB of LDS";
+        return MCQ_E_TOO_LARGE;
+    }
+    const int rows_wg = (int)std::min<size_t>(MCQ_FGS_ROWS, MCQ_FGS_LDS / row_bytes);
+    const size_t nblk = ((size_t)nmax + rows_wg) / rows_wg;
+    if ((size_t)tracks * nblk > 0x7fffffffu) {
+        g_err = "mcq_friction_gauss_device: more row blocks than one launch holds";
+        return MCQ_E_TOO_LARGE;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    McqFricGauss G;
+    memset(&G, 0, sizeof(G));
+    G.tracks = tracks; G.nmax = nmax; G.jmax = jmax; G.n_gauss = n_gauss; G.N = N; G.rows_wg = rows_wg; G.rcond = rcond;
+    G.n = n_out; G.cnt = cnt_out; G.mue = mue_out; G.status = status;
+    G.w_out = w_gauss_out; G.cd_out = center_dist_out; G.rank_out = rank_out; G.sweeps_out = sweeps_out;
+    hipLaunchKernelGGL(mcq_friction_gauss_kernel, dim3((unsigned)((size_t)tracks * nblk)), dim3(64 * rows_wg), rows_wg * row_bytes, h->ws[0].stream, G);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int mcq_friction_model_device(mcq_handle* h, int tracks, int nmax, int qmax, const double* q, const int* qcnt, int model,
+                                         const double* weights, int n_gauss, int centres, const double* center_dist, const double* n_out,
+                                         const int* cnt_out, int jmax, double* mue_out)
+{
+    const bool gauss = model == MCQ_FRIC_GAUSS, fit = gauss && centres == MCQ_FRIC_CENTRES_FIT;
+    if (!h || tracks <= 0 || nmax < 1 || qmax < 1 || !q || !weights || !mue_out || (model != MCQ_FRIC_LINEAR && !gauss) ||
+        (gauss && (n_gauss < 1 || n_gauss > 15 || !center_dist || (centres != MCQ_FRIC_CENTRES_FIT && centres != MCQ_FRIC_CENTRES_MINTIME))) ||
+        (fit && (!n_out || !cnt_out || jmax < 1))) {
+        g_err = "mcq_friction_model_device: bad argument";
+        return MCQ_E_ARG;
+    }
+    const size_t total = (size_t)tracks * ((size_t)nmax + 1) * qmax, nblk = (total + 255) / 256;
+    if (nblk > 0x7fffffffu) {
+        g_err = "mcq_friction_model_device: more positions than one launch holds";
+        return MCQ_E_TOO_LARGE;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    McqFricModel M;
+    memset(&M, 0, sizeof(M));
+    M.tracks = tracks; M.nmax = nmax; M.qmax = qmax; M.jmax = jmax; M.model = model; M.centres = centres; M.n_gauss = n_gauss;
+    M.N = gauss ? 2 * n_gauss + 1 : 0;
+    M.q = q; M.qcnt = qcnt; M.w = weights; M.cd = center_dist; M.n = n_out; M.cnt = cnt_out; M.mue_out = mue_out;
+    hipLaunchKernelGGL(mcq_friction_model_kernel, dim3((unsigned)nblk), dim3(256), 0, h->ws[0].stream, M);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // ---- device memory plumbing for callers that keep data resident between calls without a second HIP runtime in the
 //      process (the Python IQP driver): plain allocate / free / copy on the handle's device and stream ------------------
 extern "C" int mcq_device_alloc(mcq_handle* h, size_t bytes, void** out)

@@ -197,3 +197,290 @@ __global__ void __launch_bounds__(MCQ_NT) mcq_friction_grid_kernel(McqFricGrid G
         w[1] = c > 1 ? mm - slope * mn : NAN;
     }
 }
+
+// ---- the Gaussian-basis fit and the models' evaluation (mcq_friction_gauss_device, mcq_friction_model_device; include/mcq.h)
+//      [REF opt_mintime_traj/src/approx_friction_map.py:102-127 and its GaussianFeatures, opt_mintime.py:733-747].  Per row the minimum-norm
+//      least-squares solution of the centred cnt x N system, N = 2 n_gauss + 1, by a one-sided Jacobi (Hestenes) decomposition: plane rotations
+//      from the right make the columns of A orthogonal and are accumulated in V, so that A_end = U S and x = V S^+ U^T b; the Gram matrix, whose
+//      condition is the square of an already large one, is never formed.
+//
+//      Lanes (DESIGN.md "Gaussian friction fit"): a wave per row.  Lane l owns the samples j = l, l + 64, ... of every column of A (column-major
+//      in LDS, stride jmax) and, where l < N, row l of V (V[k * N + l]).  A rotation of the pair (p, q) therefore touches only a lane's own
+//      entries, and the one thing lanes exchange is the pair's three inner products: every lane stores its partial sums (over its samples, rising)
+//      into one of two alternating buffers, and after a wave barrier EVERY lane adds the first min(cnt, 64) partials in rising lane order -- one
+//      order, all lanes hold the same bits, every branch on them is uniform.  The pairs are taken one after another in the row-cyclic order
+//      (0,1) (0,2) .. (0,N-1) (1,2) .. (N-2,N-1).  Nothing depends on which rows share the workgroup.
+//
+//      A pair is rotated while its columns are not orthogonal to sqrt(cnt) eps AND both lie above 2^-20 of the cut rcond * (the largest column
+//      norm seen so far): the columns of a structurally rank-deficient row (cnt <= N) that converge to zero never pass the first test, and frozen
+//      that far below the cut they leave the rank to the problem, not to the sweep that happened to cross the cut. ----
+#define MCQ_FGS_SWEEPS 40       /* a row that has not settled by then delivers NaN and rank -1 */
+
+// the sum of one value per lane over the lanes 0 .. nl-1 in rising order, the same bits in every lane
+__device__ __forceinline__ double fgs_wsum(double* part, int lane, int nl, double v)
+{
+    part[lane] = v;
+    __builtin_amdgcn_wave_barrier();
+    double s = 0.0;
+    for (int l = 0; l < nl; ++l) s += part[l];
+    __builtin_amdgcn_wave_barrier();
+    return s;
+}
+
+// exp(x) to about half a unit in the last place (0.53 at worst over 4e6 arguments in [-120, 0] against long double, on the host).  The weights
+// carry the features' rounding times the problem's conditioning, so the feature is formed as the host's exp forms it, not to the device library's one unit:
+// x = k ln2 + r with ln2 in two pieces (k * LN2_HI and the difference are exact), exp(r) = 1 + r + r^2 / 2 + tail, the tail (below 0.008, a
+// polynomial to r^14 in plain double) and the low pieces added first, the leading three terms through two exact sums, one final rounding.
+// KEEP THESE TWO FUNCTIONS INSIDE THE CONTRACTION-OFF SECTION (mcq_kernels.hip includes this file behind `#pragma clang fp contract(off)`), and
+// build them without fast-math: fgs_two_sum's error term is exact only while every sum is rounded on its own, r_hi is exact only because
+// kd * LN2_HI is a plain exact product followed by an exact difference, and the low pieces mean what the comments say only while no product is
+// fused into the sum next to it (the one fma is asked for by name).  Moved elsewhere the function still compiles and silently returns other
+// bits; tests/fgauss_checks.py (check_model, "a feature alone") holds it to 0.55 units in the last place on the device and on the interpreter.
+__device__ __forceinline__ void fgs_two_sum(double a, double b, double& s, double& e)
+{
+    s = a + b;
+    const double bb = s - a;
+    e = (a - (s - bb)) + (b - bb);
+}
+
+__device__ __forceinline__ double fgs_exp(double x)
+{
+    if (!(x > -745.0)) return x < 0.0 ? 0.0 : x;           // (underflow; a NaN stays)
+    if (x > 709.0) return INFINITY;
+    const double kd = rint(x * 1.4426950408889634);
+    const double r_hi = x - kd * 6.93147180369123816490e-01;        // LN2_HI: 21 bits below its leading one are zero, |k| < 2^11
+    const double r_lo = -(kd * 1.90821492927058770002e-10);         // LN2_LO
+    const double r = r_hi + r_lo;
+    double p = 1.0 / 87178291200.0;                                 // 1 / 14!
+    p = p * r + 1.0 / 6227020800.0;
+    p = p * r + 1.0 / 479001600.0;
+    p = p * r + 1.0 / 39916800.0;
+    p = p * r + 1.0 / 3628800.0;
+    p = p * r + 1.0 / 362880.0;
+    p = p * r + 1.0 / 40320.0;
+    p = p * r + 1.0 / 5040.0;
+    p = p * r + 1.0 / 720.0;
+    p = p * r + 1.0 / 120.0;
+    p = p * r + 1.0 / 24.0;
+    p = p * r + 1.0 / 6.0;
+    const double tail = ((r * r) * r) * p;
+    const double s_hi = r_hi * r_hi, s_lo = fma(r_hi, r_hi, -s_hi);         // r_hi^2 in two pieces (an fma asked for by name; nothing is contracted)
+    const double sq_lo = (0.5 * s_lo + r_hi * r_lo) + 0.5 * (r_lo * r_lo);  // r^2 / 2 = 0.5 s_hi + sq_lo
+    double h1, l1, h2, l2;
+    fgs_two_sum(1.0, r_hi, h1, l1);
+    fgs_two_sum(h1, 0.5 * s_hi, h2, l2);
+    return ldexp(h2 + ((((l1 + l2) + r_lo) + sq_lo) + tail), (int)kd);
+}
+
+// numpy.linspace(start, stop, num)[k] for num >= 2: k * step + start in two roundings, the last entry the stop value itself
+__device__ __forceinline__ double fgs_linspace(double start, double stop, double step, int num, int k) { return k == num - 1 ? stop : (double)k * step + start; }
+
+__global__ void __launch_bounds__(MCQ_NT) mcq_friction_gauss_kernel(McqFricGauss G)
+{
+    HIP_DYNAMIC_SHARED(double, fgs_lds)
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int N = G.N, jmax = G.jmax, P1 = N + 1;
+    const int nblk = (G.nmax + G.rows_wg) / G.rows_wg;
+    const int t = blockIdx.x / nblk, row = (blockIdx.x % nblk) * G.rows_wg + wv;
+    if (row > G.nmax) return;           // (the whole wave; the kernel has no workgroup barrier)
+    double* A = fgs_lds + (size_t)wv * ((size_t)N * ((size_t)jmax + N + 6) + MCQ_FGS_PART);       // (mcq_fgs_row_doubles) [N][jmax]
+    double* V = A + (size_t)N * jmax;                                   // [N][N]: V[k * N + i] = entry i of column k
+    double* cm = V + N * N;                                             // [N] column means of the features
+    double* s2 = cm + N;                                                // [N] squared singular values
+    double* Z = s2 + N;                                                 // [4][N] U^T b / S per wheel (0 where the singular value is cut)
+    double* part = Z + 4 * N;                                           // [MCQ_FGS_PART]
+    const size_t ro = (size_t)t * (G.nmax + 1) + row;
+    const size_t wstride = (size_t)(G.nmax + 1) * jmax;
+    const int cnt = G.cnt[ro];
+    const int c = (G.status[t] == MCQ_OK && cnt >= 1 && cnt <= jmax) ? cnt : 0;
+    double* w_row = G.w_out + ((size_t)t * 4 * (G.nmax + 1) + row) * P1;             // wheel w: + w * (nmax + 1) * P1
+    const size_t w_wheel = (size_t)(G.nmax + 1) * P1;
+    if (c < 2) {        // no row, or one position (the reference's width is 0 and its features NaN)
+        for (int i = lane; i < 4 * P1; i += 64) w_row[(size_t)(i / P1) * w_wheel + i % P1] = NAN;
+        if (lane == 0) {
+            G.cd_out[ro] = c == 1 ? 0.0 : NAN;
+            if (G.rank_out) G.rank_out[ro] = 0;
+            if (G.sweeps_out) G.sweeps_out[ro] = 0;
+        }
+        return;
+    }
+    const double* n_row = G.n + ro * jmax;
+    const double* m_row = G.mue + (size_t)t * 4 * wstride + (size_t)row * jmax;
+    const int nl = c < 64 ? c : 64;
+    const double n0 = n_row[0], n1 = n_row[c - 1];
+    const double cstep = (n1 - n0) / (double)(N - 1);
+    const double width = 2.0 * (fgs_linspace(n0, n1, cstep, N, 1) - n0);
+    // features, their column means, the centred columns; V = I
+    for (int k = 0; k < N; ++k) {
+        const double ck = fgs_linspace(n0, n1, cstep, N, k);
+        double s = 0.0;
+        for (int j = lane; j < c; j += 64) {
+            const double arg = (n_row[j] - ck) / width;
+            const double f = fgs_exp(-0.5 * (arg * arg));
+            A[(size_t)k * jmax + j] = f;
+            s += f;
+        }
+        const double mean = fgs_wsum(part, lane, nl, s) / (double)c;
+        for (int j = lane; j < c; j += 64) A[(size_t)k * jmax + j] -= mean;
+        if (lane == 0) cm[k] = mean;
+        if (lane < N) V[k * N + lane] = lane == k ? 1.0 : 0.0;
+    }
+    const double rc = G.rcond > 0.0 ? G.rcond : (double)(c > N ? c : N) * 2.220446049250313e-16;
+    const double tol = 2.220446049250313e-16 * sqrt((double)c);
+    double smax2 = 0.0;
+    int sweeps = 0, buf = 0;
+    bool settled = false;
+    while (!settled && sweeps < MCQ_FGS_SWEEPS) {
+        settled = true;
+        ++sweeps;
+        for (int p = 0; p < N - 1; ++p) {
+            for (int q = p + 1; q < N; ++q) {
+                double* ap = A + (size_t)p * jmax;
+                double* aq = A + (size_t)q * jmax;
+                double pa = 0.0, pb = 0.0, pg = 0.0;
+                for (int j = lane; j < c; j += 64) {
+                    const double x = ap[j], y = aq[j];
+                    pa += x * x; pb += y * y; pg += x * y;
+                }
+                double* pp = part + buf * 192;
+                buf ^= 1;
+                pp[lane] = pa; pp[64 + lane] = pb; pp[128 + lane] = pg;
+                __builtin_amdgcn_wave_barrier();
+                double alpha = 0.0, beta = 0.0, gamma = 0.0;
+                for (int l = 0; l < nl; ++l) { alpha += pp[l]; beta += pp[64 + l]; gamma += pp[128 + l]; }
+                smax2 = fmax(smax2, fmax(alpha, beta));
+                const double cut2 = ((rc * rc) * smax2) * 0x1p-40;
+                if (!(alpha > cut2 && beta > cut2)) continue;           // a column 2^-20 below the cut-off: the pair counts as settled
+                if (!(fabs(gamma) > tol * sqrt(alpha * beta))) continue;
+                settled = false;
+                const double zeta = (beta - alpha) / (2.0 * gamma);
+                const double tn = (zeta < 0.0 ? -1.0 : 1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+                const double cs = 1.0 / sqrt(1.0 + tn * tn), sn = cs * tn;
+                for (int j = lane; j < c; j += 64) {
+                    const double x = ap[j], y = aq[j];
+                    ap[j] = cs * x - sn * y;
+                    aq[j] = sn * x + cs * y;
+                }
+                if (lane < N) {
+                    const double x = V[p * N + lane], y = V[q * N + lane];
+                    V[p * N + lane] = cs * x - sn * y;
+                    V[q * N + lane] = sn * x + cs * y;
+                }
+            }
+        }
+    }
+    __builtin_amdgcn_wave_barrier();
+    if (lane == 0) {
+        G.cd_out[ro] = (n1 - n0) / (double)(2 * G.n_gauss);
+        if (G.sweeps_out) G.sweeps_out[ro] = sweeps;
+    }
+    if (!settled) {
+        for (int i = lane; i < 4 * P1; i += 64) w_row[(size_t)(i / P1) * w_wheel + i % P1] = NAN;
+        if (lane == 0 && G.rank_out) G.rank_out[ro] = -1;
+        return;
+    }
+    // the singular values, the cut, the rank
+    double sig_max = 0.0;
+    for (int k = 0; k < N; ++k) {
+        double s = 0.0;
+        for (int j = lane; j < c; j += 64) { const double x = A[(size_t)k * jmax + j]; s += x * x; }
+        const double v = fgs_wsum(part, lane, nl, s);
+        if (lane == 0) s2[k] = v;
+        sig_max = fmax(sig_max, sqrt(v));
+    }
+    __builtin_amdgcn_wave_barrier();
+    const double thr = rc * sig_max;
+    int rank = 0;
+    for (int k = 0; k < N; ++k) rank += sqrt(s2[k]) > thr ? 1 : 0;
+    if (lane == 0 && G.rank_out) G.rank_out[ro] = rank;
+    // the four right-hand sides: their means, U^T b / S = A_k . b / s2_k
+    double mb[4];
+    for (int w = 0; w < 4; ++w) {
+        double s = 0.0;
+        for (int j = lane; j < c; j += 64) s += m_row[w * wstride + j];
+        mb[w] = fgs_wsum(part, lane, nl, s) / (double)c;
+    }
+    for (int k = 0; k < N; ++k) {
+        const double* ak = A + (size_t)k * jmax;
+        double s[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int j = lane; j < c; j += 64) {
+            const double x = ak[j];
+            for (int w = 0; w < 4; ++w) s[w] += x * (m_row[w * wstride + j] - mb[w]);
+        }
+        for (int w = 0; w < 4; ++w) part[w * 64 + lane] = s[w];
+        __builtin_amdgcn_wave_barrier();
+        if (lane < 4) {
+            double g = 0.0;
+            for (int l = 0; l < nl; ++l) g += part[lane * 64 + l];
+            const double v = s2[k];
+            Z[lane * N + k] = sqrt(v) > thr ? g / v : 0.0 * g;         // (0 * g: a NaN right-hand side stays NaN)
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+    // x = V z, entry i by lane i, over the columns in rising order; then the intercept
+    double x[4] = {0.0, 0.0, 0.0, 0.0};
+    if (lane < N) {
+        for (int k = 0; k < N; ++k) {
+            const double v = V[k * N + lane];
+            for (int w = 0; w < 4; ++w) x[w] += v * Z[w * N + k];
+        }
+        for (int w = 0; w < 4; ++w) {
+            w_row[(size_t)w * w_wheel + lane] = x[w];
+            part[w * 64 + lane] = cm[lane] * x[w];
+        }
+    }
+    __builtin_amdgcn_wave_barrier();
+    if (lane < 4) {
+        double d = 0.0;
+        for (int i = 0; i < N; ++i) d += part[lane * 64 + i];
+        w_row[(size_t)lane * w_wheel + N] = mb[lane] - d;
+    }
+}
+
+// a thread per (track, row, position): the four wheels' models at q
+__global__ void __launch_bounds__(MCQ_NT) mcq_friction_model_kernel(McqFricModel M)
+{
+    const size_t e = (size_t)blockIdx.x * MCQ_NT + threadIdx.x;
+    const size_t rows = (size_t)M.nmax + 1, total = (size_t)M.tracks * rows * M.qmax;
+    if (e >= total) return;
+    const int j = (int)(e % M.qmax);
+    const size_t ro = e / M.qmax;              // t * rows + row
+    const size_t t = ro / rows, row = ro % rows;
+    double* out = M.mue_out + (t * 4 * rows + row) * M.qmax + j;           // wheel w: + w * rows * qmax
+    const size_t ostride = rows * M.qmax;
+    const int P = M.model == MCQ_FRIC_LINEAR ? 2 : M.N + 1;
+    const double* w = M.w + (t * 4 * rows + row) * P;
+    const size_t wstride = rows * P;
+    const int qc = M.qcnt ? M.qcnt[ro] : M.qmax;
+    if (j >= qc) {
+        for (int k = 0; k < 4; ++k) out[k * ostride] = NAN;
+        return;
+    }
+    const double q = M.q[ro * M.qmax + j];
+    if (M.model == MCQ_FRIC_LINEAR) {
+        for (int k = 0; k < 4; ++k) out[k * ostride] = w[k * wstride] * q + w[k * wstride + 1];
+        return;
+    }
+    const int N = M.N;
+    const double cd = M.cd[ro];
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    if (M.centres == MCQ_FRIC_CENTRES_FIT) {
+        const int c = M.cnt[ro];
+        const bool have = c >= 2 && c <= M.jmax;
+        const double n0 = have ? M.n[ro * M.jmax] : NAN, n1 = have ? M.n[ro * M.jmax + c - 1] : NAN;
+        const double width = 2.0 * ((cd + n0) - n0);
+        for (int k = 0; k < N; ++k) {
+            const double arg = (q - fgs_linspace(n0, n1, cd, N, k)) / width;
+            const double f = fgs_exp(-0.5 * (arg * arg));
+            for (int v = 0; v < 4; ++v) acc[v] += f * w[v * wstride + k];
+        }
+    } else {
+        const double sigma = 2.0 * cd;
+        for (int k = 0; k < N; ++k) {
+            const double d = q - (double)(k - M.n_gauss) * cd;
+            const double f = fgs_exp(-(d * d) / (2.0 * (sigma * sigma)));
+            for (int v = 0; v < 4; ++v) acc[v] += f * w[v * wstride + k];
+        }
+    }
+    for (int v = 0; v < 4; ++v) out[v * ostride] = acc[v] + w[v * wstride + N];
+}

@@ -452,3 +452,35 @@ struct McqFricGrid {
     int* status;             // [tracks]
 };
 __global__ void mcq_friction_grid_kernel(McqFricGrid G);
+
+/* the Gaussian-basis fit on the grid kernel's outputs (mcq_friction_gauss_device) and the evaluation of either model (mcq_friction_model_device).
+ * A row of the fit keeps its centred cnt x N matrix, V and its small vectors in LDS: fgs_row_doubles doubles; rows_wg rows (waves) share a workgroup. */
+#define MCQ_FGS_PART 384        /* doubles of a row's exchange buffers: two buffers of three sums, or one of four wheels (64 lanes each) */
+#define MCQ_FGS_ROWS 4          /* most rows per workgroup */
+#define MCQ_FGS_LDS 65536       /* bytes a workgroup may take */
+static inline size_t mcq_fgs_row_doubles(int jmax, int N) { return (size_t)N * ((size_t)jmax + N + 6) + MCQ_FGS_PART; }
+struct McqFricGauss {
+    int tracks, nmax, jmax, n_gauss, N, rows_wg;
+    double rcond;            // <= 0: max(cnt, N) * DBL_EPSILON
+    const double* n;         // [tracks][nmax + 1][jmax]
+    const int* cnt;          // [tracks][nmax + 1]
+    const double* mue;       // [tracks][4][nmax + 1][jmax]
+    const int* status;       // [tracks]
+    double* w_out;           // [tracks][4][nmax + 1][N + 1]
+    double* cd_out;          // [tracks][nmax + 1]
+    int* rank_out;           // [tracks][nmax + 1] or nullptr
+    int* sweeps_out;         // [tracks][nmax + 1] or nullptr
+};
+__global__ void mcq_friction_gauss_kernel(McqFricGauss G);
+
+struct McqFricModel {
+    int tracks, nmax, qmax, jmax, model, centres, n_gauss, N;
+    const double* q;         // [tracks][nmax + 1][qmax]
+    const int* qcnt;         // [tracks][nmax + 1] or nullptr (all qmax)
+    const double* w;         // [tracks][4][nmax + 1][P]
+    const double* cd;        // [tracks][nmax + 1] (Gaussian model)
+    const double* n;         // [tracks][nmax + 1][jmax] (MCQ_FRIC_CENTRES_FIT)
+    const int* cnt;          // [tracks][nmax + 1] (MCQ_FRIC_CENTRES_FIT)
+    double* mue_out;         // [tracks][4][nmax + 1][qmax]
+};
+__global__ void mcq_friction_model_kernel(McqFricModel M);

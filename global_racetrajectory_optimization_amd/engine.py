@@ -118,6 +118,8 @@ CHECK_DIST_WARN = 1.0
 CHK_KAPPA, CHK_AY, CHK_AX_POS, CHK_AX_NEG, CHK_A_TOT, CHK_MACHINES, CHK_V_MAX = 1, 2, 4, 8, 16, 32, 64
 BOUNDS_ALL, BOUNDS_FIRST_ROW = 0, 1
 LTPL_COLS = 12      # MCQ_LTPL_COLS: x_ref, y_ref, w_r, w_l, n_x, n_y, alpha, s_ref, psi, kappa, vx, ax
+FRIC_LINEAR, FRIC_GAUSS = 0, 1                      # MCQ_FRIC_*: the model mcq_friction_model_device evaluates
+FRIC_CENTRES_FIT, FRIC_CENTRES_MINTIME = 0, 1       # MCQ_FRIC_CENTRES_*: where the Gaussian model's bumps sit
 
 
 IQP_ROUND_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int))
@@ -191,6 +193,8 @@ _ABI = {
     "mcq_fmap_info": (_ci, [_vp, _ip, _ip, _ip, _dp, _P(ctypes.c_longlong)]),
     "mcq_fmap_query_device": (_ci, [_vp, _vp, _ci, _vp, _vp, _vp, _vp]),
     "mcq_friction_grid_device": (_ci, [_vp, _vp, _ci, _ci, _vp, _vp, _vp, _cd, _vp, _cd, _cd, _cd, _ci, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mcq_friction_gauss_device": (_ci, [_vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _ci, _cd, _vp, _vp, _vp, _vp]),
+    "mcq_friction_model_device": (_ci, [_vp, _ci, _ci, _ci, _vp, _vp, _ci, _vp, _ci, _ci, _vp, _vp, _vp, _ci, _vp]),
 }
 EXPORTED_SYMBOLS = tuple(_ABI)
 
@@ -1289,11 +1293,20 @@ class Engine:
                     jmax = max(jmax, math.floor(q[0]) + math.floor(q[1]) + 1)
         return jmax
 
-    def friction_grid_batch(self, fmap, reftracks, normvecs, width_opt, wheelbase_front, wheelbase_rear, dn, fit=True, jmax=None, want_idx=False):
+    def friction_grid_batch(self, fmap, reftracks, normvecs, width_opt, wheelbase_front, wheelbase_rear, dn, fit=True, jmax=None, want_idx=False,
+                            n_gauss=5, rcond=None):
         """extract_friction_coeffs and the linear approx_friction_map of a list of (ragged) tracks in one launch (mcq_friction_grid_device).
         reftracks [n_k, 4], normvecs [n_k, 2]; width_opt: a scalar or one value per track; jmax None: from the widths, on the host.
         Returns a dict of padded arrays: n [tracks, nmax + 1, jmax], cnt [tracks, nmax + 1], mue [tracks, 4, nmax + 1, jmax] (fl, fr, rl, rr),
-        w_mue [tracks, 4, nmax + 1, 2] (slope, intercept; fit=False: None), idx (want_idx), status [tracks], rows [tracks] = n_k + 1."""
+        w_mue [tracks, 4, nmax + 1, 2] (slope, intercept; fit=False: None), idx (want_idx), status [tracks], rows [tracks] = n_k + 1.
+        fit="gauss": the Gaussian-basis fit on the resident grids instead of the lines (mcq_friction_gauss_device; n_gauss bumps on each side,
+        rcond None: sklearn's cut-off) -- w_mue is None and the dict also holds w_gauss [tracks, 4, nmax + 1, 2 n_gauss + 2] (weights, then the
+        intercept), center_dist [tracks, nmax + 1], rank and sweeps [tracks, nmax + 1].  n_gauss and rcond are read only with fit="gauss";
+        there an n_gauss outside 1 .. 15 or a jmax whose row does not fit into 64 KB of LDS is a ValueError before anything is launched."""
+        gauss = isinstance(fit, str)
+        if gauss and fit != "gauss":
+            raise ValueError("friction_grid_batch: fit must be True, False or 'gauss'")
+        fit = bool(fit) and not gauss
         ns, ref = _pad_rows(reftracks, 4)
         nv = _pad_like(normvecs, ns, (2,))
         tracks, nmax = ref.shape[:2]
@@ -1304,6 +1317,12 @@ class Engine:
         if jmax is None:
             jmax = self.friction_jmax(reftracks, [w0] * tracks if wl is None else wl.tolist(), float(dn))
         jmax, rows = int(jmax), nmax + 1
+        if gauss:       # what mcq_friction_gauss_device would refuse, before the grid is launched for nothing
+            n_gauss = int(n_gauss)
+            if not 1 <= n_gauss <= 15:
+                raise ValueError("friction_grid_batch: n_gauss must be 1 .. 15, got %d" % n_gauss)
+            if jmax >= 1 and 8 * ((2 * n_gauss + 1) * (jmax + 2 * n_gauss + 7) + 384) > 65536:
+                raise ValueError("friction_grid_batch: a row of jmax %d at n_gauss %d does not fit into 64 KB of LDS" % (jmax, n_gauss))
         with self.scope() as dev:
             up, new = dev.up, dev.new
             d_ref, d_nv, d_n, d_wl = up(ref), up(nv), up(ns), up(wl)
@@ -1313,11 +1332,76 @@ class Engine:
             d_st = new(tracks * 4)
             self.friction_grid_device(fmap, tracks, nmax, d_n, d_ref, d_nv, w0, d_wl, wheelbase_front, wheelbase_rear, dn, jmax, d_no, d_cnt,
                                       d_mu, d_ix, d_w, d_st)
-            return dict(n=self.download(d_no, (tracks, rows, jmax), np.float64), cnt=self.download(d_cnt, (tracks, rows), np.int32),
-                        mue=self.download(d_mu, (tracks, 4, rows, jmax), np.float64),
-                        w_mue=self.download(d_w, (tracks, 4, rows, 2), np.float64) if fit else None,
-                        idx=self.download(d_ix, (tracks, 4, rows, jmax), np.int32) if want_idx else None,
-                        status=self.download(d_st, (tracks,), np.int32), rows=ns + 1)
+            out = dict(n=self.download(d_no, (tracks, rows, jmax), np.float64), cnt=self.download(d_cnt, (tracks, rows), np.int32),
+                       mue=self.download(d_mu, (tracks, 4, rows, jmax), np.float64),
+                       w_mue=self.download(d_w, (tracks, 4, rows, 2), np.float64) if fit else None,
+                       idx=self.download(d_ix, (tracks, 4, rows, jmax), np.int32) if want_idx else None,
+                       status=self.download(d_st, (tracks,), np.int32), rows=ns + 1)
+            if gauss:
+                P = 2 * int(n_gauss) + 2
+                d_wg, d_cd, d_rk, d_sw = new(tracks * 4 * rows * max(P, 1) * 8), new(tracks * rows * 8), new(tracks * rows * 4), new(tracks * rows * 4)
+                self.friction_gauss_device(tracks, nmax, jmax, d_no, d_cnt, d_mu, d_st, n_gauss, rcond, d_wg, d_cd, d_rk, d_sw)
+                out.update(w_gauss=self.download(d_wg, (tracks, 4, rows, P), np.float64), center_dist=self.download(d_cd, (tracks, rows), np.float64),
+                           rank=self.download(d_rk, (tracks, rows), np.int32), sweeps=self.download(d_sw, (tracks, rows), np.int32))
+            return out
+
+    def friction_gauss_device(self, tracks, nmax, jmax, d_n, d_cnt, d_mue, d_status, n_gauss, rcond, d_w_gauss, d_center_dist, d_rank=None,
+                              d_sweeps=None):
+        """mcq_friction_gauss_device (include/mcq.h) on the device pointers mcq_friction_grid_device filled; rcond None: sklearn's cut-off;
+        d_rank / d_sweeps may be None.  Asynchronous."""
+        rc = self.lib.mcq_friction_gauss_device(self.h, int(tracks), int(nmax), int(jmax), d_n, d_cnt, d_mue, d_status, int(n_gauss),
+                                                0.0 if rcond is None else float(rcond), d_w_gauss, d_center_dist, d_rank or None, d_sweeps or None)
+        self._check(rc, "mcq_friction_gauss_device")
+
+    def friction_model_device(self, tracks, nmax, qmax, d_q, d_qcnt, model, d_w, d_mue_out, n_gauss=0, centres=FRIC_CENTRES_FIT, d_center_dist=None,
+                              d_n=None, d_cnt=None, jmax=0):
+        """mcq_friction_model_device (include/mcq.h) on device pointers: model FRIC_LINEAR (d_w [tracks][4][nmax + 1][2]) or FRIC_GAUSS (d_w
+        [tracks][4][nmax + 1][2 n_gauss + 2], d_center_dist; with FRIC_CENTRES_FIT also the grid's d_n, d_cnt, jmax).  Asynchronous."""
+        rc = self.lib.mcq_friction_model_device(self.h, int(tracks), int(nmax), int(qmax), d_q, d_qcnt or None, int(model), d_w, int(n_gauss),
+                                                int(centres), d_center_dist or None, d_n or None, d_cnt or None, int(jmax), d_mue_out)
+        self._check(rc, "mcq_friction_model_device")
+
+    def friction_model_batch(self, q, weights, model=None, center_dist=None, n=None, cnt=None, qcnt=None, centres=FRIC_CENTRES_FIT):
+        """A fitted model at lateral positions: q [tracks, rows, qmax] (qcnt [tracks, rows] positions per row, None: all) with weights
+        [tracks, 4, rows, P] -> mue [tracks, 4, rows, qmax].  model None: FRIC_LINEAR for P == 2, else FRIC_GAUSS with n_gauss = (P - 2) / 2 and
+        center_dist [tracks, rows]; FRIC_CENTRES_FIT also takes the grid's n [tracks, rows, jmax] and cnt [tracks, rows]."""
+        q = np.ascontiguousarray(q, dtype=np.float64)
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        if q.ndim != 3 or w.ndim != 4 or w.shape[:3] != (q.shape[0], 4, q.shape[1]) or q.shape[1] < 2:
+            raise ValueError("friction_model_batch: q must be [tracks, rows, qmax] (rows >= 2) and weights [tracks, 4, rows, P]")
+        tracks, rows, qmax = q.shape
+        P = w.shape[3]
+        model = (FRIC_LINEAR if P == 2 else FRIC_GAUSS) if model is None else int(model)
+        n_gauss, jmax = 0, 0
+        if model == FRIC_GAUSS:
+            if P < 4 or P % 2 or center_dist is None:
+                raise ValueError("friction_model_batch: the Gaussian model takes weights [.., 2 n_gauss + 2] and center_dist")
+            n_gauss = (P - 2) // 2
+            center_dist = np.ascontiguousarray(center_dist, dtype=np.float64)
+            if center_dist.shape != (tracks, rows):
+                raise ValueError("friction_model_batch: center_dist must be [tracks, rows]")
+            if centres == FRIC_CENTRES_FIT:
+                if n is None or cnt is None:
+                    raise ValueError("friction_model_batch: FRIC_CENTRES_FIT takes the grid's n and cnt")
+                n, cnt = np.ascontiguousarray(n, dtype=np.float64), np.ascontiguousarray(cnt, dtype=np.int32)
+                if n.ndim != 3 or n.shape[:2] != (tracks, rows) or cnt.shape != (tracks, rows):
+                    raise ValueError("friction_model_batch: n must be [tracks, rows, jmax] and cnt [tracks, rows]")
+                jmax = n.shape[2]
+            else:
+                n = cnt = None
+        elif P != 2:
+            raise ValueError("friction_model_batch: the linear model takes weights [.., 2]")
+        else:
+            center_dist = n = cnt = None
+        if qcnt is not None:
+            qcnt = np.ascontiguousarray(qcnt, dtype=np.int32)
+            if qcnt.shape != (tracks, rows):
+                raise ValueError("friction_model_batch: qcnt must be [tracks, rows]")
+        with self.scope() as dev:
+            d_out = dev.new(tracks * 4 * rows * qmax * 8)
+            self.friction_model_device(tracks, rows - 1, qmax, dev.up(q), dev.up(qcnt), model, dev.up(w), d_out, n_gauss, centres,
+                                       dev.up(center_dist), dev.up(n), dev.up(cnt), jmax)
+            return self.download(d_out, (tracks, 4, rows, qmax), np.float64)
 
     def relinearise_device(self, batch, nmax, d_n_in, d_ref_in, d_nv_in, d_alpha, d_live, alpha_scale, stepsize,
                            d_ref_out, d_nv_out, d_n_out, d_status):

@@ -6,12 +6,18 @@ maps": mcq_fmap_create, mcq_fmap_query_device, mcq_friction_grid_device).
   FrictionMapInterface(tpamap_path, tpadata_path)       .get_friction_singlepos(positions) -> [k, 1]
   extract_friction_coeffs(...)                          -> n, mue_fl, mue_fr, mue_rl, mue_rr: lists with one entry per row of the closed track
   approx_friction_map(...)                              -> w_mue_fl, w_mue_fr, w_mue_rl, w_mue_rr, center_dist for var_friction == "linear"
+  approx_friction_map_gauss(...)                        the same five for var_friction == "gauss": [rows, 2 n_gauss + 2] each, center_dist [rows, 1]
+  eval_friction_model(q, w_mue_fl, ..., center_dist)    either model at lateral positions (mcq_friction_model_device)
 
 Differences from the reference, all stated in include/mcq.h: among cells at exactly the same distance the lowest index is taken (scipy's cKDTree
-documents no rule); a row of exactly one lateral position has a NaN line where numpy.polyfit returns a minimum-norm answer with a RankWarning;
-var_friction == "gauss" (an sklearn pipeline whose parity would mean restating its SVD solver) raises NotImplementedError.  plot_debug is ignored.
+documents no rule); a row of exactly one lateral position has a NaN line where numpy.polyfit returns a minimum-norm answer with a RankWarning.
+var_friction == "gauss" (an sklearn pipeline of Gaussian features and a LinearRegression) is approx_friction_map_gauss: the minimum-norm solution
+under sklearn's cut-off from a one-sided Jacobi decomposition on the device (mcq_friction_gauss_device) -- equal to sklearn's to the problem's
+conditioning, not bit for bit.  approx_friction_map itself raises NotImplementedError for "gauss" unless MCQ_GAUSS_DEVICE=1 is set in the
+environment (read at every call, like MCQ_PREP_DEVICE and MCQ_FIT_DEVICE); then it calls approx_friction_map_gauss.  plot_debug is ignored.
 Every function takes an `engine` keyword (default: engine.default_engine())."""
 import json
+import os
 
 import numpy as np
 
@@ -62,7 +68,7 @@ def _raise_missing(mue, idx):
         raise KeyError(int(idx[miss][0]))
 
 
-def _grid(reftrack, normvectors, tpamap_path, tpadata_path, pars, dn, fit, engine):
+def _grid(reftrack, normvectors, tpamap_path, tpadata_path, pars, dn, fit, engine, n_gauss=5):
     eng = engine or _engine.default_engine()
     reftrack, normvectors = np.asarray(reftrack, dtype=np.float64), np.asarray(normvectors, dtype=np.float64)
     width = pars["optim_opts"]["width_opt"]
@@ -70,7 +76,7 @@ def _grid(reftrack, normvectors, tpamap_path, tpadata_path, pars, dn, fit, engin
     wb_r = pars["vehicle_params_mintime"]["wheelbase_rear"]
     cells, mue = load_friction_map(tpamap_path, tpadata_path)
     with eng.friction_map(cells, mue) as fmap:
-        g = eng.friction_grid_batch(fmap, [reftrack], [normvectors], float(width), wb_f, wb_r, float(dn), fit=fit, want_idx=True)
+        g = eng.friction_grid_batch(fmap, [reftrack], [normvectors], float(width), wb_f, wb_r, float(dn), fit=fit, want_idx=True, n_gauss=n_gauss)
     if g["status"][0] != 0:
         raise ValueError("friction grid: the track was refused (a row that is not finite?)")
     rows = int(g["rows"][0])
@@ -97,7 +103,10 @@ def approx_friction_map(reftrack, normvectors, tpamap_path, tpadata_path, pars, 
     pars["optim_opts"]["var_friction"] == "linear"."""
     method = pars["optim_opts"]["var_friction"]
     if method == "gauss":
-        raise NotImplementedError("var_friction 'gauss' (regression with Gaussian basis functions) is not available on the device")
+        if os.environ.get("MCQ_GAUSS_DEVICE") == "1":
+            return approx_friction_map_gauss(reftrack, normvectors, tpamap_path, tpadata_path, pars, dn, n_gauss, print_debug, plot_debug, engine=engine)
+        raise NotImplementedError("var_friction 'gauss' (regression with Gaussian basis functions) runs on the device with MCQ_GAUSS_DEVICE=1 in "
+                                  "the environment, or through approx_friction_map_gauss")
     if method != "linear":
         raise ValueError('Unknown method for friction map approximation!')
     g, rows, cnt = _grid(reftrack, normvectors, tpamap_path, tpadata_path, pars, dn, True, engine)
@@ -105,3 +114,48 @@ def approx_friction_map(reftrack, normvectors, tpamap_path, tpadata_path, pars, 
         raise TypeError("expected non-empty vector for x")
     w = [g["w_mue"][0, k, :rows].copy() for k in range(4)]
     return w[0], w[1], w[2], w[3], np.zeros((rows, 1))
+
+
+def approx_friction_map_gauss(reftrack, normvectors, tpamap_path, tpadata_path, pars, dn, n_gauss, print_debug=False, plot_debug=False, engine=None):
+    """w_mue_fl, w_mue_fr, w_mue_rl, w_mue_rr [rows, 2 n_gauss + 2] (the weights of the 2 n_gauss + 1 Gaussian bumps, then the intercept) and
+    center_dist [rows, 1]: the reference's var_friction == "gauss" (mcq_friction_gauss_device).  ValueError where the reference fails: n_gauss
+    outside 1 .. 15, a row of fewer than two lateral positions (its features are NaN and sklearn raises), a row that did not settle."""
+    n_gauss = int(n_gauss)
+    if not 1 <= n_gauss <= 15:
+        raise ValueError("approx_friction_map_gauss: n_gauss must be 1 .. 15, got %d" % n_gauss)
+    g, rows, cnt = _grid(reftrack, normvectors, tpamap_path, tpadata_path, pars, dn, "gauss", engine, n_gauss)
+    if np.any(cnt <= 1):
+        i = int(np.flatnonzero(cnt <= 1)[0])
+        raise ValueError("approx_friction_map_gauss: row %d has %d lateral position(s); the Gaussian basis needs two" % (i, int(cnt[i])))
+    if np.any(g["rank"][0, :rows] < 0):
+        raise ValueError("approx_friction_map_gauss: row %d did not settle" % int(np.flatnonzero(g["rank"][0, :rows] < 0)[0]))
+    w = [g["w_gauss"][0, k, :rows].copy() for k in range(4)]
+    return w[0], w[1], w[2], w[3], g["center_dist"][0, :rows].reshape(-1, 1).copy()
+
+
+def eval_friction_model(q, w_mue_fl, w_mue_fr, w_mue_rl, w_mue_rr, center_dist=None, mintime=True, n=None, engine=None):
+    """mue_fl, mue_fr, mue_rl, mue_rr [rows, k] at the lateral positions q [rows, k] (or [rows]: one per row) of either model's weights
+    [rows, P]: P == 2 the lines (slope * q + intercept), else the Gaussian model with center_dist [rows, 1].  mintime=True places the bumps as
+    the reference's consumer does (numpy.linspace(-n_gauss, n_gauss, N) * center_dist, sigma = 2 center_dist [REF opt_mintime.py:733-747]);
+    mintime=False as the fit did, which takes n: extract_friction_coeffs' list of positions.  The two agree only for rows symmetric about 0."""
+    eng = engine or _engine.default_engine()
+    w = np.stack([np.asarray(a, dtype=np.float64) for a in (w_mue_fl, w_mue_fr, w_mue_rl, w_mue_rr)])[None]        # [1, 4, rows, P]
+    rows = w.shape[2]
+    q = np.asarray(q, dtype=np.float64)
+    flat = q.ndim == 1
+    q = q.reshape(rows, -1)[None]
+    kw = {}
+    if w.shape[3] != 2:
+        if center_dist is None:
+            raise ValueError("eval_friction_model: the Gaussian model takes center_dist")
+        kw = dict(center_dist=np.asarray(center_dist, dtype=np.float64).reshape(1, rows), centres=_engine.FRIC_CENTRES_MINTIME)
+        if not mintime:
+            if n is None or len(n) != rows:
+                raise ValueError("eval_friction_model: mintime=False takes the rows' positions n")
+            cnt = np.array([len(r) for r in n], dtype=np.int32)
+            n_pad = np.full((rows, max(int(cnt.max()), 1)), np.nan)
+            for i, r in enumerate(n):
+                n_pad[i, :cnt[i]] = r
+            kw.update(centres=_engine.FRIC_CENTRES_FIT, n=n_pad[None], cnt=cnt[None])
+    out = eng.friction_model_batch(q, w, **kw)[0]
+    return tuple(out[k, :, 0].copy() if flat else out[k].copy() for k in range(4))

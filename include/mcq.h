@@ -592,6 +592,57 @@ int mcq_friction_grid_device(mcq_handle* h, const mcq_fmap* fmap, int tracks, in
                              double dn, int jmax, double* n_out, int* cnt_out, double* mue_out, int* idx_out, double* w_mue_out,
                              int* status_out);
 
+/* mcq_friction_gauss_device: approx_friction_map(var_friction = "gauss") [REF opt_mintime_traj/src/approx_friction_map.py:102-127, GaussianFeatures]
+ *   on what mcq_friction_grid_device left on the device -- n_out, cnt_out, mue_out, status_out with the same tracks, nmax, jmax; nothing is looked
+ *   up again.  DEVICE pointers; asynchronous on the handle's stream.  Per row of cnt positions and per wheel, N = 2 n_gauss + 1 Gaussian bumps and an
+ *   intercept, as sklearn 1.7's dense LinearRegression(fit_intercept = True) behind the reference's features computes them:
+ *   centres  numpy.linspace(n[0], n[cnt - 1], N): k * step + start in two roundings, the last entry the stop value itself;
+ *   width    2.0 * (c[1] - c[0]);   features  exp(-0.5 * ((n_j - c_k) / width)^2);
+ *   centring the features' column means and the mean of the wheel's friction are subtracted;
+ *   solve    the minimum-norm least-squares solution of the centred cnt x N system: every singular value <= rcond * sigma_max counts as zero;
+ *            rcond <= 0: sklearn's own max(cnt, N) * DBL_EPSILON.  The singular values come from a one-sided Jacobi (Hestenes) decomposition of the
+ *            centred matrix itself -- no Gram matrix -- with one fixed pair order and fixed summation orders: a row's bits do not depend on the
+ *            launch's company, the order of the tracks or the grid.  The four wheels share the decomposition.
+ *   intercept mean(mue) - mean(features) . weights.
+ *   w_gauss_out [tracks][4][nmax + 1][N + 1]: the N weights, then the intercept (the reference's column order);
+ *   center_dist_out [tracks][nmax + 1] = (n[cnt - 1] - n[0]) / (2 * n_gauss), the reference's bits;
+ *   rank_out [tracks][nmax + 1] (optional): singular values above the cut; sweeps_out (optional), same shape: Jacobi sweeps taken.
+ *   Where the weights are not unique to working precision (a singular value within rounding of the cut) the answer is one of the two ranks';
+ *   where they are, they agree with sklearn's to the conditioning of the problem (sigma_min / sigma_max is about 6e-7 at n_gauss = 5).
+ *   EDGES: cnt == 1: NaN weights, center_dist 0, rank 0 (the reference's width is 0, its features are NaN and sklearn raises);
+ *     cnt <= 0, rows beyond n, every row of a track the grid call refused: NaN weights, NaN center_dist, rank 0;
+ *     a NaN among one wheel's friction values: that wheel's weights are NaN, the other three are not affected;
+ *     a row that has not settled after 40 sweeps: NaN weights, rank -1 (none is known);
+ *     outputs are always overwritten.
+ *   MCQ_E_ARG: n_gauss < 1 or > 15 (the reference divides by 2 * n_gauss and indexes centers_[1]), rcond NaN, jmax < 1, nmax < 1, tracks <= 0,
+ *     NULL where an array is required; MCQ_E_TOO_LARGE: a single row -- N * (jmax + N + 6) + 384 doubles of LDS -- beyond 64 KB, or more
+ *     workgroups than one launch holds.  Rows per workgroup (a wave each, at most 4) are chosen from jmax and N so that a workgroup stays within
+ *     64 KB.  The entry needs no temporaries.
+ *
+ * mcq_friction_model_device: a fitted model at lateral positions q [tracks][nmax + 1][qmax] (qcnt [tracks][nmax + 1] positions per row, or
+ *   NULL: all qmax) -> mue_out [tracks][4][nmax + 1][qmax].  weights [tracks][4][nmax + 1][P]:
+ *   MCQ_FRIC_LINEAR  P = 2, slope then intercept (w_mue_out): slope * q + intercept in two roundings; center_dist, n, cnt are not read;
+ *   MCQ_FRIC_GAUSS   P = N + 1 (w_gauss_out): sum over k in rising order of feature_k * w_k, then + intercept, with the centres of
+ *     MCQ_FRIC_CENTRES_FIT      n[0] + k * center_dist in linspace's form (the last centre is n[cnt - 1] itself; n = n_out, cnt = cnt_out,
+ *                               jmax their stride), width 2 * (c[1] - c[0]): what the fitted pipeline's predict evaluates;
+ *     MCQ_FRIC_CENTRES_MINTIME  numpy.linspace(-n_gauss, n_gauss, N) * center_dist, sigma = 2 * center_dist, exp(-(q - c_k)^2 / (2 sigma^2)):
+ *                               what the reference's only consumer evaluates [REF opt_mintime_traj/src/opt_mintime.py:733-747]; n, cnt not read.
+ *     The two forms agree only where a row's positions are symmetric about 0 (n[0] = -n[cnt - 1]): the consumer places the bumps around 0,
+ *     the fit around the middle of the row.
+ *   A NaN weight gives NaN (so does a row without a fit); entries beyond qcnt are NaN.  Outputs are always overwritten.
+ *   MCQ_E_ARG: an unknown model or centre form, n_gauss outside 1 .. 15 for the Gaussian model, qmax < 1, nmax < 1, tracks <= 0, jmax < 1 with
+ *     MCQ_FRIC_CENTRES_FIT, NULL where an array is required; MCQ_E_TOO_LARGE: more workgroups than one launch holds. */
+#define MCQ_FRIC_LINEAR 0
+#define MCQ_FRIC_GAUSS 1
+#define MCQ_FRIC_CENTRES_FIT 0
+#define MCQ_FRIC_CENTRES_MINTIME 1
+int mcq_friction_gauss_device(mcq_handle* h, int tracks, int nmax, int jmax, const double* n_out, const int* cnt_out, const double* mue_out,
+                              const int* status, int n_gauss, double rcond, double* w_gauss_out, double* center_dist_out, int* rank_out,
+                              int* sweeps_out);
+int mcq_friction_model_device(mcq_handle* h, int tracks, int nmax, int qmax, const double* q, const int* qcnt, int model, const double* weights,
+                              int n_gauss, int centres, const double* center_dist, const double* n_out, const int* cnt_out, int jmax,
+                              double* mue_out);
+
 /* Host-buffer entry for a UNIFORM batch (every track n waypoints): reftrack [batch][n][4], normvec [batch][n][2] or NULL,
  * scaling [batch][n] or NULL in host memory, results to host memory.  One asynchronous copy per array straight from / to the
  * caller's buffers -- no packing pass; buffers from mcq_host_alloc (pinned) are copied at PCIe speed, pageable ones go through
