@@ -86,6 +86,8 @@ struct mcq_handle {
     Scratch fit;                        // mcq_spline_fit_device: running sums, closed points, parameters, the per-track work area
     Scratch spl;                        // mcq_spline_approx_device: first guesses, closest parameters, distances, sides [tracks][nmax + 1] each, sample counts
     Scratch ends;                       // per-problem ring / open-chain records of mcq_solve_batch_ends (device)
+    Scratch fgen;                       // mcq_points_in_path_device / mcq_friction_gen_device: polygons, kept vertices, contours, their counts
+    Scratch fgen_pts;                   // mcq_friction_gen_device: the grid points' flags and the blocks' counts (sized after the boundaries' launch)
     mcq_iqp_round_cb iqp_cb = nullptr;  // mcq_iqp_set_round_callback
     void* iqp_cb_user = nullptr;
     void* comm = nullptr;               // ncclComm_t of mcq_comm_init (RCCL, loaded with dlopen)
@@ -266,7 +268,7 @@ extern "C" void mcq_destroy(mcq_handle* h)
     for (int k = 0; k < 16; ++k) if (h->ev_slice[k]) (void)hipEventDestroy(h->ev_slice[k]);
     if (h->cs_in) (void)hipStreamDestroy(h->cs_in);
     if (h->cs_out) (void)hipStreamDestroy(h->cs_out);
-    for (Scratch* s : {&h->vel, &h->bound, &h->fit, &h->spl, &h->ends}) (void)hipFree(s->p);
+    for (Scratch* s : {&h->vel, &h->bound, &h->fit, &h->spl, &h->ends, &h->fgen, &h->fgen_pts}) (void)hipFree(s->p);
     if (h->pin) (void)hipHostFree(h->pin);
     for (int k = 0; k < 5; ++k) if (h->ev[k]) (void)hipEventDestroy(h->ev[k]);
     for (int k = 0; k < 2; ++k) if (h->ev_span[k]) (void)hipEventDestroy(h->ev_span[k]);
@@ -1350,6 +1352,115 @@ extern "C" int mcq_friction_model_device(mcq_handle* h, int tracks, int nmax, in
     M.q = q; M.qcnt = qcnt; M.w = weights; M.cd = center_dist; M.n = n_out; M.cnt = cnt_out; M.mue_out = mue_out;
     hipLaunchKernelGGL(mcq_friction_model_kernel, dim3((unsigned)nblk), dim3(256), 0, h->ws[0].stream, M);
     HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---- friction map generation (include/mcq.h; csrc/mcq_fgen.inc) ----
+static inline size_t up8(size_t bytes) { return (bytes + 7) & ~(size_t)7; }
+
+extern "C" int mcq_points_in_path_device(mcq_handle* h, int paths, int vmax, const int* v_list, const double* verts, const double* radius, int count,
+                                         const double* xy, unsigned char* inside_out, int* status_out, double* contour_out, int* contour_count_out)
+{
+    if (!h || paths <= 0 || vmax < 1 || count < 0 || !verts || !radius || !status_out || (count > 0 && (!xy || !inside_out)) ||
+        (contour_out == nullptr) != (contour_count_out == nullptr)) {
+        g_err = "mcq_points_in_path_device: bad argument";
+        return MCQ_E_ARG;
+    }
+    const size_t blocks = ((size_t)count + 255) / 256;
+    if (paths > 65535) {        // (count is an int: its blocks of 256 points fit the first axis)
+        g_err = "mcq_points_in_path_device: more paths than one launch holds";
+        return MCQ_E_TOO_LARGE;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    // scratch: kept [paths][vmax][2] | contours [paths][2 vmax][2] (unless the caller takes them) | flags [paths][vmax] | counts [paths]
+    const size_t pv = (size_t)paths * vmax;
+    const size_t b_kept = pv * 2 * sizeof(double), b_cont = contour_out ? 0 : pv * 4 * sizeof(double), b_flag = up8(pv * sizeof(int));
+    if (int rc = grow(h, h->fgen, b_kept + b_cont + b_flag + up8((size_t)paths * sizeof(int)))) return rc;
+    char* base = (char*)h->fgen.p;
+    McqContour C;
+    memset(&C, 0, sizeof(C));
+    C.paths = paths; C.vmax = vmax; C.v_list = v_list; C.verts = verts; C.radius = radius; C.status = status_out;
+    C.kept = (double*)base;
+    C.cont = contour_out ? contour_out : (double*)(base + b_kept);
+    C.flag = (int*)(base + b_kept + b_cont);
+    C.ccount = contour_count_out ? contour_count_out : (int*)(base + b_kept + b_cont + b_flag);
+    hipStream_t st = h->ws[0].stream;
+    hipLaunchKernelGGL(mcq_fgen_contour_kernel, dim3(paths), dim3(256), 0, st, C);
+    HIP_TRY(hipGetLastError());
+    if (count == 0) return 0;
+    hipLaunchKernelGGL(mcq_fgen_points_kernel, dim3((unsigned)blocks, paths), dim3(256), 0, st, C, count, xy, inside_out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int mcq_friction_gen_device(mcq_handle* h, int tracks, int nmax, const int* n_list, const double* reftrack, double cellwidth,
+                                       const int* inside_right, int cmax, double* bound_r_out, double* bound_l_out, double* grid_out,
+                                       int* count_out, double* cells_out, int* status_out)
+{
+    if (!h || tracks <= 0 || nmax < 3 || !(cellwidth > 0.0) || !std::isfinite(cellwidth) || !reftrack || !grid_out || !status_out ||
+        (cells_out && (cmax < 0 || !count_out))) {
+        g_err = "mcq_friction_gen_device: bad argument";
+        return MCQ_E_ARG;
+    }
+    if (tracks > 32767) {       // (tracks lie along the second axis of the all-pairs and scatter launches)
+        g_err = "mcq_friction_gen_device: more tracks than one launch holds";
+        return MCQ_E_TOO_LARGE;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    // scratch, per track: polygons [2][2 nmax][2] | kept, the same | contours [2][4 nmax][2] | radii [2] || flags [2][2 nmax] | counts, contour counts, nx ny [2] each
+    const size_t tn = (size_t)tracks * nmax, t2 = (size_t)tracks * 2;
+    const size_t b_poly = tn * 8 * sizeof(double), b_cont = tn * 16 * sizeof(double), b_rad = t2 * sizeof(double), b_flag = up8(tn * 4 * sizeof(int));
+    const size_t b_cnt = up8(t2 * sizeof(int));
+    if (int rc = grow(h, h->fgen, 2 * b_poly + b_cont + b_rad + b_flag + 3 * b_cnt)) return rc;
+    char* base = (char*)h->fgen.p;
+    McqFgen G;
+    memset(&G, 0, sizeof(G));
+    G.tracks = tracks; G.nmax = nmax; G.cmax = cells_out ? cmax : 0; G.cw = cellwidth;
+    G.n_list = n_list; G.ref = reftrack; G.inside_right = inside_right;
+    G.bound_r = bound_r_out; G.bound_l = bound_l_out; G.grid = grid_out; G.count = count_out; G.cells = cells_out; G.status = status_out;
+    G.poly = (double*)base;
+    double* kept = (double*)(base + b_poly);
+    G.cont = (double*)(base + 2 * b_poly);
+    G.prad = (double*)(base + 2 * b_poly + b_cont);
+    int* flag = (int*)(base + 2 * b_poly + b_cont + b_rad);
+    G.pcount = (int*)((char*)flag + b_flag);
+    G.ccount = (int*)((char*)G.pcount + b_cnt);
+    G.rec = (int*)((char*)G.ccount + b_cnt);
+    hipStream_t st = h->ws[0].stream;
+    hipLaunchKernelGGL(mcq_fgen_bounds_kernel, dim3(tracks), dim3(256), 0, st, G);
+    HIP_TRY(hipGetLastError());
+    if (!count_out) return 0;       // boundaries, grids and status only
+    McqContour C;
+    memset(&C, 0, sizeof(C));
+    C.paths = 2 * tracks; C.vmax = 2 * nmax; C.v_list = G.pcount; C.verts = G.poly; C.radius = G.prad;
+    C.kept = kept; C.flag = flag; C.cont = G.cont; C.ccount = G.ccount;
+    hipLaunchKernelGGL(mcq_fgen_contour_kernel, dim3(2 * tracks), dim3(256), 0, st, C);
+    HIP_TRY(hipGetLastError());
+    // the one wait: the grids' sizes decide the launches that follow
+    std::vector<int> rec(t2);
+    HIP_TRY(hipMemcpyAsync(rec.data(), G.rec, t2 * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    size_t maxblk = 0;
+    for (int t = 0; t < tracks; ++t) {
+        const size_t items = (size_t)rec[2 * t] * (((size_t)rec[2 * t + 1] + MCQ_FGEN_PPT - 1) / MCQ_FGEN_PPT);
+        maxblk = std::max(maxblk, (items + 255) / 256);
+    }
+    // (MCQ_FGEN_GRID bounds a track at 2^31 - 1 points: at most 2^21 blocks of 256 items, within a launch's first axis)
+    const size_t b_bits = up8((size_t)tracks * maxblk * 256);
+    if (int rc = grow(h, h->fgen_pts, b_bits + (size_t)tracks * std::max<size_t>(maxblk, 1) * sizeof(int))) return rc;
+    G.maxblk = (int)maxblk;
+    G.bits = (unsigned char*)h->fgen_pts.p;
+    G.bcount = (int*)((char*)h->fgen_pts.p + b_bits);
+    if (maxblk > 0) {
+        hipLaunchKernelGGL(mcq_fgen_mask_kernel, dim3((unsigned)maxblk, tracks), dim3(256), 0, st, G);
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(mcq_fgen_scan_kernel, dim3(tracks), dim3(256), 0, st, G);
+    HIP_TRY(hipGetLastError());
+    if (maxblk > 0 && cells_out && cmax > 0) {
+        hipLaunchKernelGGL(mcq_fgen_scatter_kernel, dim3((unsigned)maxblk, tracks), dim3(256), 0, st, G);
+        HIP_TRY(hipGetLastError());
+    }
     return 0;
 }
 

@@ -484,3 +484,48 @@ struct McqFricModel {
     double* mue_out;         // [tracks][4][nmax + 1][qmax]
 };
 __global__ void mcq_friction_model_kernel(McqFricModel M);
+
+/* ---- friction map generation (mcq_points_in_path_device, mcq_friction_gen_device; csrc/mcq_fgen.inc) [REF main_gen_frictionmap.py,
+ *      frictionmap/src/reftrack_functions.py]: matplotlib's contains_points with a radius -- agg's contour, then the crossing test -- on the
+ *      reference's boundaries and grid. ---- */
+#define MCQ_FGEN_TILE 512       /* contour vertices per LDS tile of the crossing test */
+#define MCQ_FGEN_PPT 4          /* grid points (one x, consecutive y) per thread of mcq_fgen_mask_kernel: the edge's terms that do not depend on y are shared */
+struct McqContour {
+    int paths, vmax;
+    const int* v_list;       // [paths] or nullptr (all vmax)
+    const double* verts;     // [paths][vmax][2]
+    const double* radius;    // [paths]
+    double* kept;            // scratch [paths][vmax][2]: the vertices that are not within 1e-14 of their predecessor
+    int* flag;               // scratch [paths][vmax]
+    double* cont;            // [paths][2 vmax][2]
+    int* ccount;             // [paths]
+    int* status;             // [paths] or nullptr
+};
+__global__ void mcq_fgen_contour_kernel(McqContour C);
+__global__ void mcq_fgen_points_kernel(McqContour C, int count, const double* xy, unsigned char* inside_out);
+
+struct McqFgen {
+    int tracks, nmax, cmax, maxblk;
+    double cw;
+    const int* n_list;       // [tracks] or nullptr (all nmax)
+    const double* ref;       // [tracks][nmax][4]
+    const int* inside_right; // [tracks] or nullptr (all right)
+    double* bound_r;         // [tracks][nmax][2] or nullptr
+    double* bound_l;
+    double* grid;            // [tracks][6]
+    int* count;              // [tracks]
+    double* cells;           // [tracks][cmax][2] or nullptr
+    int* status;             // [tracks]
+    double* poly;            // scratch [tracks][2][2 nmax][2]: the polygons to test (closed: outside, inside; open: one of 2 n vertices)
+    int* pcount;             // [tracks][2]
+    double* prad;            // [tracks][2]
+    double* cont;            // [tracks][2][4 nmax][2]: their contours (McqContour with paths = 2 tracks, vmax = 2 nmax)
+    int* ccount;             // [tracks][2]
+    int* rec;                // [tracks][2]: nx, ny (0 for a refused track)
+    unsigned char* bits;     // [tracks][maxblk * 256]: per item the on-track flags of its MCQ_FGEN_PPT points
+    int* bcount;             // [tracks][maxblk]: cells per block of 256 items, then their running sum
+};
+__global__ void mcq_fgen_bounds_kernel(McqFgen G);
+__global__ void mcq_fgen_mask_kernel(McqFgen G);
+__global__ void mcq_fgen_scan_kernel(McqFgen G);
+__global__ void mcq_fgen_scatter_kernel(McqFgen G);

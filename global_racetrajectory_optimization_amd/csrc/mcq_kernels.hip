@@ -4108,6 +4108,8 @@ __global__ void __launch_bounds__(MCQ_NT) mcq_spline_finish_kernel(McqSpline S)
 #include "mcq_fit.inc"
 // (the same holds for mcq_fric.inc: the friction maps' kernels)
 #include "mcq_fric.inc"
+// (and for mcq_fgen.inc: the generation of a friction map's cells)
+#include "mcq_fgen.inc"
 
 __global__ void __launch_bounds__(MCQ_NT) mcq_min_width_kernel(int nmax, const int* n_list, double* ref_all, double min_width, int* changed_out)
 {

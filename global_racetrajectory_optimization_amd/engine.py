@@ -120,6 +120,7 @@ BOUNDS_ALL, BOUNDS_FIRST_ROW = 0, 1
 LTPL_COLS = 12      # MCQ_LTPL_COLS: x_ref, y_ref, w_r, w_l, n_x, n_y, alpha, s_ref, psi, kappa, vx, ax
 FRIC_LINEAR, FRIC_GAUSS = 0, 1                      # MCQ_FRIC_*: the model mcq_friction_model_device evaluates
 FRIC_CENTRES_FIT, FRIC_CENTRES_MINTIME = 0, 1       # MCQ_FRIC_CENTRES_*: where the Gaussian model's bumps sit
+FGEN_NONFINITE, FGEN_FEW, FGEN_OVERFLOW, FGEN_GRID = 1, 2, 4, 8     # MCQ_FGEN_*: the status bits of the friction-map generation
 
 
 IQP_ROUND_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int))
@@ -195,6 +196,8 @@ _ABI = {
     "mcq_friction_grid_device": (_ci, [_vp, _vp, _ci, _ci, _vp, _vp, _vp, _cd, _vp, _cd, _cd, _cd, _ci, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mcq_friction_gauss_device": (_ci, [_vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _ci, _cd, _vp, _vp, _vp, _vp]),
     "mcq_friction_model_device": (_ci, [_vp, _ci, _ci, _ci, _vp, _vp, _ci, _vp, _ci, _ci, _vp, _vp, _vp, _ci, _vp]),
+    "mcq_points_in_path_device": (_ci, [_vp, _ci, _ci, _vp, _vp, _vp, _ci, _vp, _vp, _vp, _vp, _vp]),
+    "mcq_friction_gen_device": (_ci, [_vp, _ci, _ci, _vp, _vp, _cd, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 EXPORTED_SYMBOLS = tuple(_ABI)
 
@@ -1402,6 +1405,90 @@ class Engine:
             self.friction_model_device(tracks, rows - 1, qmax, dev.up(q), dev.up(qcnt), model, dev.up(w), d_out, n_gauss, centres,
                                        dev.up(center_dist), dev.up(n), dev.up(cnt), jmax)
             return self.download(d_out, (tracks, 4, rows, qmax), np.float64)
+
+    # ---- friction map generation (include/mcq.h "friction map generation"; the reference's names on top of these: friction.py) -------------
+    def contains_points_device(self, paths, vmax, d_v, d_verts, d_radius, count, d_xy, d_inside, d_status, d_contour=None, d_contour_count=None):
+        """mcq_points_in_path_device on device pointers: d_verts [paths][vmax][2], d_v [paths] or None, d_radius [paths], d_xy [count][2] ->
+        d_inside [paths][count] bytes, d_status [paths]; d_contour [paths][2 vmax][2] and d_contour_count [paths]: both or neither.  Asynchronous."""
+        rc = self.lib.mcq_points_in_path_device(self.h, int(paths), int(vmax), d_v or None, d_verts, d_radius, int(count), d_xy or None,
+                                                d_inside or None, d_status, d_contour or None, d_contour_count or None)
+        self._check(rc, "mcq_points_in_path_device")
+
+    def contains_points_batch(self, paths, points, radius=0.0, want_contours=False):
+        """matplotlib's Path(v).contains_points(points, radius=r) for a list of polygons [v_k, 2] and one point set [count, 2], on the device:
+        inside bool [paths, count] and status int32 [paths] (FGEN_* bits) -- with want_contours also the list of polygons [c_k, 2] the crossing
+        test ran on (agg's contour at radius / 2; the path itself for radius 0).  radius: a scalar or one per path."""
+        verts = [np.asarray(v, dtype=np.float64).reshape(-1, 2) for v in paths]
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 2)
+        if not verts:
+            raise ValueError("contains_points_batch: no paths")
+        k, count = len(verts), pts.shape[0]
+        vs = np.array([v.shape[0] for v in verts], dtype=np.int32)
+        vmax = max(int(vs.max()), 1)
+        pad = np.zeros((k, vmax, 2))
+        for i, v in enumerate(verts):
+            pad[i, :vs[i]] = v
+        rad = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, dtype=np.float64), (k,)))
+        with self.scope() as dev:
+            d_in, d_st = dev.new(max(k * count, 1)), dev.new(k * 4)
+            d_c, d_cc = (dev.new(k * vmax * 32), dev.new(k * 4)) if want_contours else (None, None)
+            self.contains_points_device(k, vmax, dev.up(vs), dev.up(pad), dev.up(rad), count, dev.up(pts) if count else None, d_in if count else None,
+                                        d_st, d_c, d_cc)
+            inside = self.download(d_in, (k, count), np.uint8).astype(bool) if count else np.zeros((k, 0), dtype=bool)
+            status = self.download(d_st, (k,), np.int32)
+            if not want_contours:
+                return inside, status
+            cc, c = self.download(d_cc, (k,), np.int32), self.download(d_c, (k, 2 * vmax, 2), np.float64)
+        return inside, status, [c[i, :cc[i]].copy() for i in range(k)]
+
+    def friction_gen_device(self, tracks, nmax, d_n, d_ref, cellwidth, d_inside_right, cmax, d_bound_r, d_bound_l, d_grid, d_count, d_cells, d_status):
+        """mcq_friction_gen_device (include/mcq.h) on device pointers; d_n / d_inside_right / d_bound_r / d_bound_l / d_cells may be None (d_cells
+        None: counts only; d_count None as well: boundaries, grids and status only, one asynchronous launch).  With d_count it waits once for the
+        boundaries' launch; the launches after it are asynchronous."""
+        rc = self.lib.mcq_friction_gen_device(self.h, int(tracks), int(nmax), d_n or None, d_ref, float(cellwidth), d_inside_right or None, int(cmax),
+                                              d_bound_r or None, d_bound_l or None, d_grid, d_count or None, d_cells or None, d_status)
+        self._check(rc, "mcq_friction_gen_device")
+
+    def track_boundaries_batch(self, reftracks):
+        """The reference's calc_trackboundaries for a list of (ragged) tracks [n_k, 4]: (bound_right, bound_left: lists of [n_k, 2], status
+        [tracks]) from mcq_friction_gen_device's boundaries-only form (count_out NULL): one launch, no grid point tested.  A waypoint whose
+        neighbours coincide has NaN rows there and FGEN_NONFINITE; a track with a non-finite waypoint or width, or with FGEN_FEW, has all rows NaN."""
+        ns, ref = _pad_rows(reftracks, 4, nmin=3)
+        tracks, nmax = ref.shape[:2]
+        with self.scope() as dev:
+            d_br, d_bl, d_grid, d_st = dev.new(tracks * nmax * 16), dev.new(tracks * nmax * 16), dev.new(tracks * 48), dev.new(tracks * 4)
+            self.friction_gen_device(tracks, nmax, dev.up(ns), dev.up(ref), 1.0, None, 0, d_br, d_bl, d_grid, None, None, d_st)
+            br, bl = self.download(d_br, (tracks, nmax, 2), np.float64), self.download(d_bl, (tracks, nmax, 2), np.float64)
+            status = self.download(d_st, (tracks,), np.int32) & ~FGEN_GRID      # (the grid of the 1 m cell asked for is not the caller's)
+        return [br[t, :ns[t]].copy() for t in range(tracks)], [bl[t, :ns[t]].copy() for t in range(tracks)], status
+
+    def friction_gen_batch(self, reftracks, cellwidth_m, inside_trackbound="right", cmax=None):
+        """The reference's main_gen_frictionmap for a list of (ragged) tracks [n_k, 4] = x, y, w_right, w_left: a counting call, then the cells
+        into buffers of the largest count (cmax given: one call, a track with more cells is cut and carries FGEN_OVERFLOW).  inside_trackbound:
+        "right" / "left", or one of them per track.  Returns a dict: cells (a list of [count_k, 2] in the reference's order), counts [tracks],
+        grids [tracks, 6] = x0, x1, y0, y1, nx, ny, bound_right / bound_left (lists of [n_k, 2]), status [tracks] (FGEN_* bits; a refused track
+        has no cells)."""
+        sides = [inside_trackbound] * len(reftracks) if isinstance(inside_trackbound, str) else list(inside_trackbound)
+        if len(sides) != len(reftracks) or any(s not in ("right", "left") for s in sides):
+            raise ValueError("friction_gen_batch: inside_trackbound must be 'right' or 'left', or one of them per track")
+        ns, ref = _pad_rows(reftracks, 4, nmin=3)
+        tracks, nmax = ref.shape[:2]
+        with self.scope() as dev:
+            d_ref, d_n, d_side = dev.up(ref), dev.up(ns), dev.up(np.array([s == "right" for s in sides], dtype=np.int32))
+            d_br, d_bl, d_grid = dev.new(tracks * nmax * 16), dev.new(tracks * nmax * 16), dev.new(tracks * 48)
+            d_cnt, d_st = dev.new(tracks * 4), dev.new(tracks * 4)
+            if cmax is None:
+                self.friction_gen_device(tracks, nmax, d_n, d_ref, cellwidth_m, d_side, 0, None, None, d_grid, d_cnt, None, d_st)
+                cmax = int(self.download(d_cnt, (tracks,), np.int32).max())
+            cmax = int(cmax)
+            d_cells = dev.new(tracks * max(cmax, 1) * 16)
+            self.friction_gen_device(tracks, nmax, d_n, d_ref, cellwidth_m, d_side, cmax, d_br, d_bl, d_grid, d_cnt, d_cells, d_st)
+            counts, status = self.download(d_cnt, (tracks,), np.int32), self.download(d_st, (tracks,), np.int32)
+            cells = self.download(d_cells, (tracks, max(cmax, 1), 2), np.float64)
+            br, bl = self.download(d_br, (tracks, nmax, 2), np.float64), self.download(d_bl, (tracks, nmax, 2), np.float64)
+            grids = self.download(d_grid, (tracks, 6), np.float64)
+        return dict(cells=[cells[t, :min(int(counts[t]), cmax)].copy() for t in range(tracks)], counts=counts, grids=grids,
+                    bound_right=[br[t, :ns[t]].copy() for t in range(tracks)], bound_left=[bl[t, :ns[t]].copy() for t in range(tracks)], status=status)
 
     def relinearise_device(self, batch, nmax, d_n_in, d_ref_in, d_nv_in, d_alpha, d_live, alpha_scale, stepsize,
                            d_ref_out, d_nv_out, d_n_out, d_status):

@@ -8,6 +8,10 @@ maps": mcq_fmap_create, mcq_fmap_query_device, mcq_friction_grid_device).
   approx_friction_map(...)                              -> w_mue_fl, w_mue_fr, w_mue_rl, w_mue_rr, center_dist for var_friction == "linear"
   approx_friction_map_gauss(...)                        the same five for var_friction == "gauss": [rows, 2 n_gauss + 2] each, center_dist [rows, 1]
   eval_friction_model(q, w_mue_fl, ..., center_dist)    either model at lateral positions (mcq_friction_model_device)
+  check_isclosed_refline(refline), calc_trackboundaries(reftrack)       [REF frictionmap/src/reftrack_functions.py], the latter on the device
+  gen_friction_map(reftrack, cellwidth_m, initial_mue, inside_trackbound)   -> (cells, mue): the reference's main_gen_frictionmap.py
+                                                        (mcq_friction_gen_device), cell for cell matplotlib's contains_points verdicts
+  write_friction_map(cells, mue, tpamap_path, tpadata_path)             the two files that script writes, byte for byte
 
 Differences from the reference, all stated in include/mcq.h: among cells at exactly the same distance the lowest index is taken (scipy's cKDTree
 documents no rule); a row of exactly one lateral position has a NaN line where numpy.polyfit returns a minimum-norm answer with a RankWarning.
@@ -17,6 +21,7 @@ conditioning, not bit for bit.  approx_friction_map itself raises NotImplemented
 environment (read at every call, like MCQ_PREP_DEVICE and MCQ_FIT_DEVICE); then it calls approx_friction_map_gauss.  plot_debug is ignored.
 Every function takes an `engine` keyword (default: engine.default_engine())."""
 import json
+import math
 import os
 
 import numpy as np
@@ -159,3 +164,69 @@ def eval_friction_model(q, w_mue_fl, w_mue_fr, w_mue_rl, w_mue_rr, center_dist=N
             kw.update(centres=_engine.FRIC_CENTRES_FIT, n=n_pad[None], cnt=cnt[None])
     out = eng.friction_model_batch(q, w, **kw)[0]
     return tuple(out[k, :, 0].copy() if flat else out[k].copy() for k in range(4))
+
+
+# ---- generating a map [REF main_gen_frictionmap.py, frictionmap/src/reftrack_functions.py] ---------------------------------------------------------
+def check_isclosed_refline(refline):
+    """True where the last point of the reference line [n, 2] lies within 10 m of the first: the track is a circuit."""
+    refline = np.asarray(refline, dtype=np.float64)
+    return math.sqrt((refline[-1, 0] - refline[0, 0]) ** 2 + (refline[-1, 1] - refline[0, 1]) ** 2) <= 10.0
+
+
+def _gen(reftrack, cellwidth_m, inside_trackbound, engine):
+    eng = engine or _engine.default_engine()
+    reftrack = np.asarray(reftrack, dtype=np.float64)
+    if reftrack.ndim != 2 or reftrack.shape[1] < 4:
+        raise ValueError("reftrack must be [n, 4]: x_m, y_m, trackwidth_right_m, trackwidth_left_m")
+    if inside_trackbound not in ("right", "left"):
+        raise ValueError("inside_trackbound must be 'right' or 'left'")
+    g = eng.friction_gen_batch([reftrack], float(cellwidth_m), inside_trackbound)
+    st = int(g["status"][0])
+    if st & _engine.FGEN_FEW:
+        raise ValueError("the reference track needs at least 3 waypoints")
+    if st & _engine.FGEN_NONFINITE:
+        raise ValueError("the reference track, or a boundary derived from it, is not finite (a NaN, or a waypoint whose neighbours coincide)")
+    if st & _engine.FGEN_GRID:
+        raise ValueError("the grid has more than 2^31 - 1 points at this cell width")
+    return g
+
+
+def calc_trackboundaries(reftrack, engine=None):
+    """(track_boundary_right, track_boundary_left), [n, 2] each, of reftrack [n, 4] = x_m, y_m, trackwidth_right_m, trackwidth_left_m: the
+    reference's bits, from the boundaries-only form of mcq_friction_gen_device (Engine.track_boundaries_batch: no grid, no cells).  As in the
+    reference, a waypoint whose neighbours coincide (a zero gradient) has NaN rows and nothing is raised (a NaN's sign bit is the device's).  Differences: a NaN or infinite entry
+    anywhere makes EVERY row NaN (numpy keeps the rows the entry does not reach), and fewer than 3 waypoints is a ValueError."""
+    eng = engine or _engine.default_engine()
+    reftrack = np.asarray(reftrack, dtype=np.float64)
+    if reftrack.ndim != 2 or reftrack.shape[1] < 4:
+        raise ValueError("reftrack must be [n, 4]: x_m, y_m, trackwidth_right_m, trackwidth_left_m")
+    right, left, status = eng.track_boundaries_batch([reftrack])
+    if int(status[0]) & _engine.FGEN_FEW:
+        raise ValueError("the reference track needs at least 3 waypoints")
+    return right[0], left[0]
+
+
+def gen_friction_map(reftrack, cellwidth_m, initial_mue, inside_trackbound="right", engine=None):
+    """(cells [c, 2], mue [c]) of the reference's script: the points of its grid that lie on the track or within 1.1 cell widths of it, in its
+    order, each with initial_mue.  inside_trackbound ('right' / 'left') matters for circuits only -- with the wrong one the map is EMPTY, as
+    the reference's is (the offset's side follows the boundary's orientation).  ValueError for a track the entry refuses."""
+    if not float(cellwidth_m) > 0.0 or not math.isfinite(float(cellwidth_m)):
+        raise ValueError("cellwidth_m must be positive")
+    cells = _gen(reftrack, cellwidth_m, inside_trackbound, engine)["cells"][0]
+    return cells, np.full(cells.shape[0], float(initial_mue))
+
+
+def write_friction_map(cells, mue, tpamap_path, tpadata_path):
+    """The reference's two files, byte for byte: '*_tpamap.csv' (numpy.savetxt, '%0.4f', ';', header 'x_m;y_m') and '*_tpadata.json'
+    ({"i": [mue_i], ...} with the separators (',', ': ')).  The reference writes the JSON's keys in the order of its cKDTree's index array, a
+    by-product of the tree's build; the same tree is built here for the same order (the content does not depend on it).  load_friction_map
+    reads the files back."""
+    from scipy.spatial import cKDTree
+    cells, mue = np.asarray(cells, dtype=np.float64).reshape(-1, 2), np.asarray(mue, dtype=np.float64).reshape(-1)
+    if mue.shape[0] != cells.shape[0]:
+        raise ValueError("write_friction_map: cells must be [c, 2] and mue [c]")
+    with open(tpamap_path, 'wb') as fh:
+        np.savetxt(fh, cells, fmt='%0.4f', delimiter=';', header='x_m;y_m')
+    order = cKDTree(cells).indices.tolist() if cells.shape[0] else []
+    with open(tpadata_path, 'w') as fh:
+        json.dump({str(i): [float(mue[i])] for i in order}, fh, separators=(',', ': '))

@@ -643,6 +643,63 @@ int mcq_friction_model_device(mcq_handle* h, int tracks, int nmax, int qmax, con
                               int n_gauss, int centres, const double* center_dist, const double* n_out, const int* cnt_out, int jmax,
                               double* mue_out);
 
+/* ---- friction map generation [REF main_gen_frictionmap.py, frictionmap/src/reftrack_functions.py]: the producer of the maps the entries above
+ * consume -- the cells of a square grid that lie on a track or within 1.1 cell widths of it.  DEVICE pointers, launches on the handle's stream.
+ *
+ * mcq_points_in_path_device: matplotlib's Path(verts).contains_points(xy, radius = r) for a batch of closed polygons and one set of points.
+ *   verts [paths][vmax][2], v_list [paths] or NULL (all vmax), radius [paths], xy [count][2] -> inside_out [paths][count], one byte (0 / 1) each.
+ *   With r != 0 matplotlib does not test the polygon: it tests agg's CONTOUR of it, offset by r / 2, on the side the polygon's ORIENTATION and
+ *   the sign of r select.  Restated here operation by operation (fp64, no fused multiply-add), so that the verdicts are matplotlib's exactly:
+ *   vertices  one within 1e-14 of the previous KEPT one is dropped, then trailing ones within 1e-14 of the first; prev / next are cyclic;
+ *   join      per kept vertex v1 between v0 and v2, w = r / 2: the segments' offsets (dx, dy) = w * (delta y, delta x) / length; with
+ *             cp = (v2.x - v1.x)(v1.y - v0.y) - (v2.y - v1.y)(v1.x - v0.x), an INNER join where |cp| > 1e-14 and cp has w's sign: a miter reverted
+ *             beyond max(min(len1, len2) / |w|, 1.01) half widths; otherwise an OUTER join: a miter cut beyond 4 half widths.  The miter point is
+ *             the intersection of the two offset lines (given up where |den| < 1e-30); a join contributes one point or two;
+ *   crossing  per edge (x0, y0) -> (x1, y1) of that polygon, the closing one included: toggle where (y0 >= ty) != (y1 >= ty) and
+ *             ((y1 - ty)(x0 - x1) >= (x1 - tx)(y0 - y1)) == (y1 >= ty).  radius 0: the path itself, no vertex dropped.
+ *   A path of fewer than 3 vertices, or fewer than 2 kept ones: False everywhere (matplotlib's answer).  A point that is not finite: False.
+ *   contour_out [paths][2 * vmax][2] and contour_count_out [paths] (both optional, both or neither): the polygon the crossing test ran on;
+ *   rows beyond the count are not written.  count == 0 (xy and inside_out may be NULL): only the contours.
+ *   status_out [paths]: 0, MCQ_FGEN_NONFINITE (a vertex or radius that is not finite: False everywhere, count 0 -- matplotlib would split the path
+ *   at a NaN; here it is refused) or MCQ_FGEN_FEW (v_list outside 0 .. vmax).
+ *   MCQ_E_ARG: paths <= 0, vmax < 1, count < 0, NULL where an array is required; MCQ_E_TOO_LARGE: more than 65535 paths (they lie along the launch's second axis).
+ *   Asynchronous.  Temporaries: the handle's scratch, 7 doubles per vertex.
+ *
+ * mcq_friction_gen_device: the reference's script for a batch of tracks, reftrack [tracks][nmax][4] = x, y, w_right, w_left; n_list [tracks] or
+ *   NULL (all nmax).  Per track:
+ *   closed    where the last waypoint lies within 10 m of the first; the differences of numpy.gradient on the line (closed: cyclic; open: one-sided
+ *             at the ends), the normal (gy, -gx) / sqrt(gy^2 + gx^2), right = p + normal * w_right, left = p - normal * w_left:
+ *             bound_r_out, bound_l_out [tracks][nmax][2] (optional), the reference's calc_trackboundaries bit for bit;
+ *   grid      d = ceil(max w_right + max w_left + 5), x0 = floor(min x - d), x1 = ceil(max x + d), y likewise; the axes are numpy.arange(x0, x1 + 0.1,
+ *             cellwidth)'s own values: ceil((x1 + 0.1 - x0) / cellwidth) entries, entry i = x0 + i * ((x0 + cellwidth) - x0) (entry 1 the sum
+ *             itself); points x-major, y inner.  grid_out [tracks][6] = x0, x1, y0, y1, nx, ny as doubles;
+ *   cells     closed: contains(outside boundary, +-1.1 cellwidth) and not contains(inside boundary, -+1.1 cellwidth), the signs as the reference
+ *             picks them from inside_right [tracks] (nonzero: the right boundary is the inner one; NULL: all right); open: the one polygon
+ *             (left, right reversed) at radius -1.1 cellwidth.  `contains` is mcq_points_in_path_device's.  count_out [tracks] = cells found;
+ *             cells_out [tracks][cmax][2] (optional) = their coordinates in the order of coordinates[bool_OnTrack]; rows beyond the count are not
+ *             written.  cells_out NULL: counts only (cmax is not read).  count > cmax: the first cmax cells, the true count, MCQ_FGEN_OVERFLOW.
+ *             count_out NULL (then cells_out must be NULL too): boundaries, grids and status only -- one launch, no wait, no grid point tested.
+ *   status_out [tracks], bits: MCQ_FGEN_NONFINITE (a waypoint, width or boundary point that is not finite -- a waypoint whose neighbours coincide
+ *   has a zero gradient and gives one; matplotlib would split the path at a NaN, here the track is REFUSED with count 0), MCQ_FGEN_FEW (n < 3 or
+ *   n > nmax), MCQ_FGEN_OVERFLOW, MCQ_FGEN_GRID (more than 2^31 - 1 grid points).  A refused track has count 0, nx = ny = 0 (MCQ_FGEN_GRID keeps
+ *   its range and counts), its boundary rows NaN (a zero gradient: as computed), and does not affect the others; a track's bytes do not depend on
+ *   the launch's company, its position in the batch or nmax / cmax.  Boundary rows beyond n are not written.
+ *   MCQ_E_ARG: cellwidth <= 0 or not finite, nmax < 3, tracks <= 0, cmax < 0 (with cells_out), cells_out without count_out, NULL where an
+ *   array is required; MCQ_E_TOO_LARGE: more than 32767 tracks (they lie along the launches' second axis) -- the only case: a track's
+ *   item blocks are bounded by MCQ_FGEN_GRID.
+ *   With count_out the entry WAITS ONCE, for the boundaries' launch, and reads 2 ints per track back: the grids' sizes decide the launches and temporaries that
+ *   follow (the handle's scratch: 34 doubles per waypoint and about 0.26 bytes per grid point of the largest track, times tracks); those launches are
+ *   asynchronous. */
+#define MCQ_FGEN_NONFINITE 1
+#define MCQ_FGEN_FEW 2
+#define MCQ_FGEN_OVERFLOW 4
+#define MCQ_FGEN_GRID 8
+int mcq_points_in_path_device(mcq_handle* h, int paths, int vmax, const int* v_list, const double* verts, const double* radius, int count,
+                              const double* xy, unsigned char* inside_out, int* status_out, double* contour_out, int* contour_count_out);
+int mcq_friction_gen_device(mcq_handle* h, int tracks, int nmax, const int* n_list, const double* reftrack, double cellwidth,
+                            const int* inside_right, int cmax, double* bound_r_out, double* bound_l_out, double* grid_out, int* count_out,
+                            double* cells_out, int* status_out);
+
 /* Host-buffer entry for a UNIFORM batch (every track n waypoints): reftrack [batch][n][4], normvec [batch][n][2] or NULL,
  * scaling [batch][n] or NULL in host memory, results to host memory.  One asynchronous copy per array straight from / to the
  * caller's buffers -- no packing pass; buffers from mcq_host_alloc (pinned) are copied at PCIe speed, pageable ones go through
