@@ -625,6 +625,14 @@ extern "C" int mcq_solve_device_f32(mcq_handle* h, int batch, int n, const float
     return narrow_launch(h, s.alpha, alpha_out, elems);
 }
 
+// one wave per track (mcq_widen_rows_kernel): fp64 rows [x, y, w_r, w_l] from float rows in either layout
+static int widen_rows_launch(mcq_handle* h, int batch, int n, int layout, const float* d_rows, const double* d_origin, double* d_out)
+{
+    hipLaunchKernelGGL(mcq_widen_rows_kernel, dim3((unsigned)batch), dim3(64), 0, h->ws[0].stream, d_rows, d_origin, d_out, n, layout);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // fp32 rows in either layout (include/mcq.h: MCQ_F32_ABSOLUTE / MCQ_F32_INCREMENTS), device-resident: the rows are rebuilt as fp64
 // [x, y, w_r, w_l] in the handle's staging buffer (mcq_widen_rows_kernel: running sums in fp64, closure defect spread over the
 // ring), normals and scalings are derived on the device, alpha is narrowed on the way out.
@@ -632,10 +640,10 @@ static int solve_f32_rows(mcq_handle* h, int batch, int n, int layout, const flo
                           double w_veh, const mcq_opts& o, float* d_alpha_out, double* curv_err_out, int* status_out, mcq_info* info_out)
 {
     const size_t elems = (size_t)batch * n;
-    hipLaunchKernelGGL(mcq_widen_rows_kernel, dim3((unsigned)batch), dim3(64), 0, h->ws[0].stream, d_rows, d_origin, h->stage[0].ref, n, layout);
-    HIP_TRY(hipGetLastError());
+    int rc = widen_rows_launch(h, batch, n, layout, d_rows, d_origin, h->stage[0].ref);
+    if (rc) return rc;
     McqBatch B = make_batch(batch, n, nullptr, h->stage[0].ref, nullptr, nullptr, h->stage[0].alpha, curv_err_out, status_out, info_out, kappa_bound, w_veh);
-    int rc = launch(h, B, o);
+    rc = launch(h, B, o);
     if (rc) return rc;
     return narrow_launch(h, h->stage[0].alpha, d_alpha_out, elems);
 }
@@ -656,6 +664,37 @@ extern "C" int mcq_solve_device_f32_rows(mcq_handle* h, int batch, int n, int la
     rc = ensure_staging(h, 0, (size_t)batch, (size_t)n);
     if (rc) return rc;
     return solve_f32_rows(h, batch, n, layout, reftrack, origin, kappa_bound, w_veh, o, alpha_out, curv_err_out, status_out, info_out);
+}
+
+// The pieces of the fp32 boundary on their own (include/mcq.h): the launches of the entries above through the same helpers.
+extern "C" int mcq_f32_rows_device(mcq_handle* h, int batch, int n, int layout, const float* reftrack, const double* origin, double* reftrack_out)
+{
+    if (!h || batch <= 0 || n <= 0 || !reftrack || !reftrack_out || (layout != MCQ_F32_ABSOLUTE && layout != MCQ_F32_INCREMENTS)) {
+        g_err = "mcq_f32_rows_device: bad argument";
+        return MCQ_E_ARG;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    return widen_rows_launch(h, batch, n, layout, reftrack, origin, reftrack_out);
+}
+
+extern "C" int mcq_f32_widen_device(mcq_handle* h, size_t count, const float* src, double* dst)
+{
+    if (!h || count == 0 || !src || !dst) {
+        g_err = "mcq_f32_widen_device: bad argument";
+        return MCQ_E_ARG;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    return widen_launch(h, src, dst, count);
+}
+
+extern "C" int mcq_f32_narrow_device(mcq_handle* h, size_t count, const double* src, float* dst)
+{
+    if (!h || count == 0 || !src || !dst) {
+        g_err = "mcq_f32_narrow_device: bad argument";
+        return MCQ_E_ARG;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    return narrow_launch(h, src, dst, count);
 }
 
 extern "C" int mcq_solve_device_ragged(mcq_handle* h, int batch, int nmax, const int* n_list, const double* reftrack,

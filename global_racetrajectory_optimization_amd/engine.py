@@ -198,6 +198,9 @@ _ABI = {
     "mcq_friction_model_device": (_ci, [_vp, _ci, _ci, _ci, _vp, _vp, _ci, _vp, _ci, _ci, _vp, _vp, _vp, _ci, _vp]),
     "mcq_points_in_path_device": (_ci, [_vp, _ci, _ci, _vp, _vp, _vp, _ci, _vp, _vp, _vp, _vp, _vp]),
     "mcq_friction_gen_device": (_ci, [_vp, _ci, _ci, _vp, _vp, _cd, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mcq_f32_rows_device": (_ci, [_vp, _ci, _ci, _ci, _vp, _vp, _vp]),
+    "mcq_f32_widen_device": (_ci, [_vp, _sz, _vp, _vp]),
+    "mcq_f32_narrow_device": (_ci, [_vp, _sz, _vp, _vp]),
 }
 EXPORTED_SYMBOLS = tuple(_ABI)
 
@@ -240,7 +243,10 @@ def rows_to_increments(reftrack):
 def increments_to_rows(rows32, origin=None):
     """What the device rebuilds from MCQ_F32_INCREMENTS rows (mcq_widen_rows_kernel), in numpy: fp64 running sum from the origin with
     the closure defect of the float increments spread evenly over the ring.  For tests and for callers that want the reference
-    line the engine saw."""
+    line the engine saw.  Equal to the device's rows up to rounding, not bit for bit: the cumsum rounds once per waypoint where the
+    kernel's slices round ceil(n / 64) times, so x, y stand within (2 n + 12) 2^-53 (max|origin| + 2 max_col sum |increment|) of the exact
+    rebuild (tests/f32_ref.py: host_guard; the device meets the same bound with 3 ceil(n / 64) + 12).  The device's own rows:
+    Engine.f32_rows_device."""
     r = np.asarray(rows32, dtype=np.float64)
     n = r.shape[-2]
     d = r[..., :2] - r[..., :2].mean(axis=-2, keepdims=True)
@@ -597,6 +603,21 @@ class Engine:
         rc = self.lib.mcq_solve_device_f32_rows(self.h, int(batch), int(n), int(layout), d_rows, d_origin or None, float(kappa_bound),
                                                 float(w_veh), ctypes.byref(opts), d_alpha, d_curv, d_status, d_info or None)
         self._check(rc, "mcq_solve_device_f32_rows")
+
+    def f32_rows_device(self, batch, n, layout, d_rows, d_origin, d_reftrack_out):
+        """The fp64 rows [batch, n, 4] solve_device_f32_rows solves, without the solve (mcq_f32_rows_device: the same launch): d_rows
+        [batch, n, 4] float32 in `layout`, d_origin [batch, 2] float64 or None.  Input and output must not overlap.  Asynchronous."""
+        rc = self.lib.mcq_f32_rows_device(self.h, int(batch), int(n), int(layout), d_rows, d_origin or None, d_reftrack_out)
+        self._check(rc, "mcq_f32_rows_device")
+
+    def f32_widen_device(self, count, d_src, d_dst):
+        """d_dst[i] = float64(d_src[i]) for count float32 values on the device (mcq_f32_widen_device; exact).  Asynchronous."""
+        self._check(self.lib.mcq_f32_widen_device(self.h, int(count), d_src, d_dst), "mcq_f32_widen_device")
+
+    def f32_narrow_device(self, count, d_src, d_dst):
+        """d_dst[i] = float32(d_src[i]) for count float64 values on the device, rounded to nearest even as alpha is on the way out of the
+        fp32 entries (mcq_f32_narrow_device).  Asynchronous."""
+        self._check(self.lib.mcq_f32_narrow_device(self.h, int(count), d_src, d_dst), "mcq_f32_narrow_device")
 
     def solve_batch_f32(self, rows32, origin, kappa_bound, w_veh, layout=F32_INCREMENTS, **opt_kw):
         """Host-buffer fp32 entry (mcq_solve_batch_f32): rows32 [B, n, 4] float32 in `layout`, origin [B, 2] float64 or None.

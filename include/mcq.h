@@ -232,6 +232,18 @@ int mcq_solve_batch_f32(mcq_handle* h, int batch, int n, int layout, const float
                         double kappa_bound, double w_veh, const mcq_opts* opts, float* alpha_out, double* curv_err_out,
                         int* status_out, mcq_info* info_out);
 
+/* The pieces of the fp32 boundary on their own: the very launches the three entries above make, on DEVICE pointers, asynchronous on the
+ * handle's stream.  Input and output must not overlap.  MCQ_E_ARG for a null handle or pointer (origin may be NULL), batch <= 0, n <= 0,
+ * count == 0 or a layout other than the two above.
+ * mcq_f32_rows_device: what mcq_solve_device_f32_rows does before its solver launch -- reftrack_out [batch][n][4] double = the rows the
+ *   engine sees (x, y rebuilt or origin added per `layout`, the widths widened): input for mcq_prep_device, mcq_raceline_device,
+ *   mcq_export_device.  No solver workspace is touched: any n.
+ * mcq_f32_widen_device / mcq_f32_narrow_device: dst[i] = (double)src[i] (exact) / dst[i] = (float)src[i] (round to nearest even, as
+ *   alpha on the way out), count values: any fp64 result at half the bytes before an all-gather. */
+int mcq_f32_rows_device(mcq_handle* h, int batch, int n, int layout, const float* reftrack, const double* origin, double* reftrack_out);
+int mcq_f32_widen_device(mcq_handle* h, size_t count, const float* src, double* dst);
+int mcq_f32_narrow_device(mcq_handle* h, size_t count, const double* src, float* dst);
+
 /* The front half of prep_track on the device [REF helper_funcs_glob/src/prep_track.py:48-51]: unit normals (pointing
  * right) and spline scalings s_i = l_i / l_{i+1} of the closed distance-scaled cubic spline through the reference line --
  * what tph.calc_splines(path) returns as normvec_normalized and encodes in its matrix.  reftrack [batch][nmax][4],
