@@ -152,6 +152,21 @@ static int grow(mcq_handle* h, Scratch& s, size_t bytes)
     return 0;
 }
 
+// The regions of one Scratch buffer, stated once: a *_layout function below adds them in their order from the shapes alone, the entry grows
+// the buffer to `bytes` and takes the pointers with at(), the regions numbered from 0 in the order of the comment above their layout function.
+// A region's bytes are rounded up to `pad` (8: a double may follow ints).
+struct Arena {
+    size_t off[8], align[8], n = 0, bytes = 0;
+    template <class T> Arena& add(size_t count, size_t pad = 8)
+    {
+        off[n] = bytes;
+        align[n++] = alignof(T);
+        bytes += (count * sizeof(T) + pad - 1) / pad * pad;
+        return *this;
+    }
+    template <class T> T* at(void* base, int region) const { return (T*)((char*)base + off[region]); }
+};
+
 extern "C" const char* mcq_last_error(void) { return g_err.c_str(); }
 
 extern "C" void mcq_default_opts(mcq_opts* o)
@@ -1001,6 +1016,12 @@ static size_t bound_byte_cap()
     return v >= 1.0 ? (size_t)v : ((size_t)1 << 30);
 }
 
+// samples [tracks][2][nbmax][2] | raw boundaries [tracks][2][nmax][2] | running sums [tracks][2][nmax + 1] | side statuses [tracks][2]
+static Arena bound_layout(size_t tracks, size_t nmax, size_t nbmax)
+{
+    return Arena().add<double>(2 * tracks * nbmax * 2).add<double>(2 * tracks * nmax * 2).add<double>(2 * tracks * (nmax + 1)).add<int>(2 * tracks);
+}
+
 extern "C" int mcq_bound_dists_device(mcq_handle* h, int tracks, int nmax, const int* n_list, const double* reftrack,
                                       const double* normvec, int mmax, const int* m_list, const double* raceline, const double* psi,
                                       double length_veh, double width_veh, const double* length_veh_list, const double* width_veh_list,
@@ -1016,9 +1037,9 @@ extern "C" int mcq_bound_dists_device(mcq_handle* h, int tracks, int nmax, const
         return MCQ_E_ARG;
     }
     HIP_TRY(hipSetDevice(h->device));
-    // scratch, in doubles: samples [tracks][2][nbmax][2] | raw boundaries [tracks][2][nmax][2] | running sums [tracks][2][nmax + 1] | side statuses
+    // what the scratch holds in doubles next to the samples: they take what $MCQ_BOUND_BYTES leaves
     const size_t sides = 2 * (size_t)tracks;
-    const size_t fixed = sides * (size_t)nmax * 2 + sides * ((size_t)nmax + 1) + (size_t)tracks;
+    const size_t fixed = bound_layout(tracks, nmax, 0).bytes / sizeof(double);
     const size_t cap = bound_byte_cap() / sizeof(double);
     if (cap < fixed + sides * 2) {
         g_err = "mcq_bound_dists_device: the boundary scratch would exceed $MCQ_BOUND_BYTES";
@@ -1026,18 +1047,16 @@ extern "C" int mcq_bound_dists_device(mcq_handle* h, int tracks, int nmax, const
     }
     size_t nbmax = (cap - fixed) / (sides * 2);
     if (nbmax > MCQ_BOUND_NB_MAX) nbmax = MCQ_BOUND_NB_MAX;
-    const size_t need = (sides * nbmax * 2 + fixed) * sizeof(double);
-    if (int rc = grow(h, h->bound, need)) return rc;
+    const Arena a = bound_layout(tracks, nmax, nbmax);
+    if (int rc = grow(h, h->bound, a.bytes)) return rc;
     McqBound P;
     memset(&P, 0, sizeof(P));
     P.tracks = tracks; P.nmax = nmax; P.mmax = mmax; P.nbmax = (int)nbmax; P.mode = mode;
     P.n_list = n_list; P.m_list = m_list; P.ref = reftrack; P.nv = normvec; P.xy = raceline; P.psi = psi;
     P.length_veh = length_veh; P.width_veh = width_veh; P.length_list = length_veh_list; P.width_list = width_veh_list;
     P.step = stepsize_bound;
-    P.samples = (double*)h->bound.p;
-    P.pts = P.samples + sides * nbmax * 2;
-    P.cum = P.pts + sides * (size_t)nmax * 2;
-    P.side_status = (int*)(P.cum + sides * ((size_t)nmax + 1));
+    P.samples = a.at<double>(h->bound.p, 0); P.pts = a.at<double>(h->bound.p, 1); P.cum = a.at<double>(h->bound.p, 2);
+    P.side_status = a.at<int>(h->bound.p, 3);
     P.min_dists = min_dists_out; P.min_dist = min_dist_out; P.nb_out = nb_out; P.bound_out = bound_out; P.status = status_out;
     hipStream_t st = h->ws[0].stream;
     hipLaunchKernelGGL(mcq_bound_points_kernel, dim3(2 * tracks), dim3(256), 0, st, P);
@@ -1048,6 +1067,20 @@ extern "C" int mcq_bound_dists_device(mcq_handle* h, int tracks, int nmax, const
     hipLaunchKernelGGL(mcq_bound_min_kernel, dim3(tracks), dim3(256), 0, st, P);
     HIP_TRY(hipGetLastError());
     return 0;
+}
+
+// doubles per track of the fit's work area: B-splines [mimax][k + 1], residuals [mimax], two triangles [(2 k + 5) nkmax], coefficients [nkmax][2],
+// jump rows [nkmax][k + 2], fpint [nkmax + 2], then the ints: intervals [mimax], nrdata [nkmax + 2], row marks [mimax]; at the end the segments'
+// reduced rows [mimax][k + 1] and their right-hand sides [mimax][2]
+static size_t fit_work_per(size_t mm, size_t k, size_t nk)
+{
+    return mm * (k + 2) + 2 * (2 * k + 5) * nk + 2 * nk + nk * (k + 2) + nk + 2 + (2 * mm + nk + 2 + 1) / 2 + 1 + mm * (k + 3);
+}
+
+// running sums [tracks][nmax + 1] | closed points [tracks][mimax][2] | parameters [tracks][mimax] | work areas [tracks][fit_work_per]
+static Arena fit_layout(size_t tracks, size_t nmax, size_t mimax, size_t k, size_t nkmax)
+{
+    return Arena().add<double>(tracks * (nmax + 1)).add<double>(tracks * mimax * 2).add<double>(tracks * mimax).add<double>(tracks * fit_work_per(mimax, k, nkmax));
 }
 
 // FITPACK's periodic smoothing fit (include/mcq.h): one launch on the handle's stream, a workgroup per track
@@ -1062,27 +1095,26 @@ extern "C" int mcq_spline_fit_device(mcq_handle* h, int tracks, int nmax, const 
         return MCQ_E_ARG;
     }
     HIP_TRY(hipSetDevice(h->device));
-    const size_t nm = (size_t)nmax, mm = (size_t)mimax, nk = (size_t)nkmax;
-    // per track: B-splines [mimax][k + 1], residuals [mimax], two triangles [(2 k + 5) nkmax], coefficients [nkmax][2], jump rows [nkmax][k + 2],
-    // fpint [nkmax + 2], then the ints: intervals [mimax], nrdata [nkmax + 2], row marks [mimax]; at the end the segments' reduced rows
-    // [mimax][k + 1] and their right-hand sides [mimax][2]
-    const size_t work_per = mm * (k + 2) + 2 * (size_t)(2 * k + 5) * nk + 2 * nk + nk * (k + 2) + nk + 2 + (2 * mm + nk + 2 + 1) / 2 + 1 + mm * (k + 3);
-    const size_t per = nm + 1 + 3 * mm + work_per;
-    if (int rc = grow(h, h->fit, (size_t)tracks * per * sizeof(double))) return rc;
+    const Arena a = fit_layout(tracks, nmax, mimax, k, nkmax);
+    if (int rc = grow(h, h->fit, a.bytes)) return rc;
     McqFit P;
     memset(&P, 0, sizeof(P));
     P.tracks = tracks; P.nmax = nmax; P.mimax = mimax; P.k = k; P.nkmax = nkmax;
     P.n_list = n_list; P.track = track; P.step = stepsize_prep; P.s = s;
-    P.cum = (double*)h->fit.p;
-    P.pts = P.cum + (size_t)tracks * (nm + 1);
-    P.u = P.pts + (size_t)tracks * mm * 2;
-    P.work = P.u + (size_t)tracks * mm;
-    P.work_per = work_per;
+    P.cum = a.at<double>(h->fit.p, 0); P.pts = a.at<double>(h->fit.p, 1); P.u = a.at<double>(h->fit.p, 2); P.work = a.at<double>(h->fit.p, 3);
+    P.work_per = fit_work_per(mimax, k, nkmax);
     P.nk_out = nk_out; P.knots_out = knots_out; P.coef_out = coef_out; P.fp_out = fp_out; P.ier_out = ier_out; P.mi_out = mi_out;
     P.pts_out = pts_out; P.status = status_out;
     hipLaunchKernelGGL(mcq_spline_fit_kernel, dim3(tracks), dim3(256), 0, h->ws[0].stream, P);
     HIP_TRY(hipGetLastError());
     return 0;
+}
+
+// first guesses | closest parameters | distances | sides, [tracks][nmax + 1] each | sample counts [tracks] (they take a double's room each)
+static Arena spl_layout(size_t tracks, size_t nmax)
+{
+    const size_t per = tracks * (nmax + 1);
+    return Arena().add<double>(per).add<double>(per).add<double>(per).add<double>(per).add<int>(2 * tracks);
 }
 
 // tph.spline_approximation behind FITPACK's fit (include/mcq.h): three launches on the handle's stream
@@ -1097,18 +1129,14 @@ extern "C" int mcq_spline_approx_device(mcq_handle* h, int tracks, int nmax, con
         return MCQ_E_ARG;
     }
     HIP_TRY(hipSetDevice(h->device));
-    const size_t per = (size_t)tracks * ((size_t)nmax + 1);
-    const size_t need = (4 * per + (size_t)tracks) * sizeof(double);      // (the sample counts take a double's room each)
-    if (int rc = grow(h, h->spl, need)) return rc;
+    const Arena a = spl_layout(tracks, nmax);
+    if (int rc = grow(h, h->spl, a.bytes)) return rc;
     McqSpline S;
     memset(&S, 0, sizeof(S));
     S.tracks = tracks; S.nmax = nmax; S.k = k; S.nkmax = nkmax; S.mmax = mmax;
     S.n_list = n_list; S.nk_list = nk_list; S.track = track; S.knots = knots; S.coef = coef; S.step = stepsize_reg;
-    S.tguess = (double*)h->spl.p;
-    S.ct = S.tguess + per;
-    S.dist = S.ct + per;
-    S.side = S.dist + per;
-    S.npts = (int*)(S.side + per);
+    S.tguess = a.at<double>(h->spl.p, 0); S.ct = a.at<double>(h->spl.p, 1); S.dist = a.at<double>(h->spl.p, 2); S.side = a.at<double>(h->spl.p, 3);
+    S.npts = a.at<int>(h->spl.p, 4);
     S.ref_out = reftrack_out; S.m_out = m_out; S.ct_out = closest_t_out; S.dist_out = dists_out; S.dev_out = dev_out;
     S.nonmono_out = nonmono_out; S.status = status_out;
     hipStream_t st = h->ws[0].stream;
@@ -1395,7 +1423,24 @@ extern "C" int mcq_friction_model_device(mcq_handle* h, int tracks, int nmax, in
 }
 
 // ---- friction map generation (include/mcq.h; csrc/mcq_fgen.inc) ----
-static inline size_t up8(size_t bytes) { return (bytes + 7) & ~(size_t)7; }
+// kept [paths][vmax][2] | contours [paths][2 vmax][2] (own: none when the caller takes them) | flags [paths][vmax] | counts [paths]
+static Arena path_layout(size_t paths, size_t vmax, bool own_contours)
+{
+    return Arena().add<double>(paths * vmax * 2).add<double>(own_contours ? paths * vmax * 4 : 0).add<int>(paths * vmax).add<int>(paths);
+}
+
+// per track: polygons [2][2 nmax][2] | kept, the same | contours [2][4 nmax][2] | radii [2] || flags [2][2 nmax] | counts, contour counts, nx ny [2] each
+static Arena fgen_layout(size_t tracks, size_t nmax)
+{
+    const size_t tn = tracks * nmax, t2 = tracks * 2;
+    return Arena().add<double>(tn * 8).add<double>(tn * 8).add<double>(tn * 16).add<double>(t2).add<int>(tn * 4).add<int>(t2).add<int>(t2).add<int>(t2);
+}
+
+// the grid points' flags [tracks][maxblk][256] | the blocks' counts [tracks][maxblk] (one per track where there is no block)
+static Arena fgen_pts_layout(size_t tracks, size_t maxblk)
+{
+    return Arena().add<unsigned char>(tracks * maxblk * 256).add<int>(tracks * std::max<size_t>(maxblk, 1), sizeof(int));
+}
 
 extern "C" int mcq_points_in_path_device(mcq_handle* h, int paths, int vmax, const int* v_list, const double* verts, const double* radius, int count,
                                          const double* xy, unsigned char* inside_out, int* status_out, double* contour_out, int* contour_count_out)
@@ -1411,18 +1456,16 @@ extern "C" int mcq_points_in_path_device(mcq_handle* h, int paths, int vmax, con
         return MCQ_E_TOO_LARGE;
     }
     HIP_TRY(hipSetDevice(h->device));
-    // scratch: kept [paths][vmax][2] | contours [paths][2 vmax][2] (unless the caller takes them) | flags [paths][vmax] | counts [paths]
-    const size_t pv = (size_t)paths * vmax;
-    const size_t b_kept = pv * 2 * sizeof(double), b_cont = contour_out ? 0 : pv * 4 * sizeof(double), b_flag = up8(pv * sizeof(int));
-    if (int rc = grow(h, h->fgen, b_kept + b_cont + b_flag + up8((size_t)paths * sizeof(int)))) return rc;
-    char* base = (char*)h->fgen.p;
+    const Arena a = path_layout(paths, vmax, !contour_out);
+    if (int rc = grow(h, h->fgen, a.bytes)) return rc;
+    void* base = h->fgen.p;
     McqContour C;
     memset(&C, 0, sizeof(C));
     C.paths = paths; C.vmax = vmax; C.v_list = v_list; C.verts = verts; C.radius = radius; C.status = status_out;
-    C.kept = (double*)base;
-    C.cont = contour_out ? contour_out : (double*)(base + b_kept);
-    C.flag = (int*)(base + b_kept + b_cont);
-    C.ccount = contour_count_out ? contour_count_out : (int*)(base + b_kept + b_cont + b_flag);
+    C.kept = a.at<double>(base, 0);
+    C.cont = contour_out ? contour_out : a.at<double>(base, 1);
+    C.flag = a.at<int>(base, 2);
+    C.ccount = contour_count_out ? contour_count_out : a.at<int>(base, 3);
     hipStream_t st = h->ws[0].stream;
     hipLaunchKernelGGL(mcq_fgen_contour_kernel, dim3(paths), dim3(256), 0, st, C);
     HIP_TRY(hipGetLastError());
@@ -1446,25 +1489,17 @@ extern "C" int mcq_friction_gen_device(mcq_handle* h, int tracks, int nmax, cons
         return MCQ_E_TOO_LARGE;
     }
     HIP_TRY(hipSetDevice(h->device));
-    // scratch, per track: polygons [2][2 nmax][2] | kept, the same | contours [2][4 nmax][2] | radii [2] || flags [2][2 nmax] | counts, contour counts, nx ny [2] each
-    const size_t tn = (size_t)tracks * nmax, t2 = (size_t)tracks * 2;
-    const size_t b_poly = tn * 8 * sizeof(double), b_cont = tn * 16 * sizeof(double), b_rad = t2 * sizeof(double), b_flag = up8(tn * 4 * sizeof(int));
-    const size_t b_cnt = up8(t2 * sizeof(int));
-    if (int rc = grow(h, h->fgen, 2 * b_poly + b_cont + b_rad + b_flag + 3 * b_cnt)) return rc;
-    char* base = (char*)h->fgen.p;
+    const size_t t2 = (size_t)tracks * 2;
+    const Arena a = fgen_layout(tracks, nmax);
+    if (int rc = grow(h, h->fgen, a.bytes)) return rc;
+    void* base = h->fgen.p;
     McqFgen G;
     memset(&G, 0, sizeof(G));
     G.tracks = tracks; G.nmax = nmax; G.cmax = cells_out ? cmax : 0; G.cw = cellwidth;
     G.n_list = n_list; G.ref = reftrack; G.inside_right = inside_right;
     G.bound_r = bound_r_out; G.bound_l = bound_l_out; G.grid = grid_out; G.count = count_out; G.cells = cells_out; G.status = status_out;
-    G.poly = (double*)base;
-    double* kept = (double*)(base + b_poly);
-    G.cont = (double*)(base + 2 * b_poly);
-    G.prad = (double*)(base + 2 * b_poly + b_cont);
-    int* flag = (int*)(base + 2 * b_poly + b_cont + b_rad);
-    G.pcount = (int*)((char*)flag + b_flag);
-    G.ccount = (int*)((char*)G.pcount + b_cnt);
-    G.rec = (int*)((char*)G.ccount + b_cnt);
+    G.poly = a.at<double>(base, 0); G.cont = a.at<double>(base, 2); G.prad = a.at<double>(base, 3);
+    G.pcount = a.at<int>(base, 5); G.ccount = a.at<int>(base, 6); G.rec = a.at<int>(base, 7);
     hipStream_t st = h->ws[0].stream;
     hipLaunchKernelGGL(mcq_fgen_bounds_kernel, dim3(tracks), dim3(256), 0, st, G);
     HIP_TRY(hipGetLastError());
@@ -1472,7 +1507,7 @@ extern "C" int mcq_friction_gen_device(mcq_handle* h, int tracks, int nmax, cons
     McqContour C;
     memset(&C, 0, sizeof(C));
     C.paths = 2 * tracks; C.vmax = 2 * nmax; C.v_list = G.pcount; C.verts = G.poly; C.radius = G.prad;
-    C.kept = kept; C.flag = flag; C.cont = G.cont; C.ccount = G.ccount;
+    C.kept = a.at<double>(base, 1); C.flag = a.at<int>(base, 4); C.cont = G.cont; C.ccount = G.ccount;
     hipLaunchKernelGGL(mcq_fgen_contour_kernel, dim3(2 * tracks), dim3(256), 0, st, C);
     HIP_TRY(hipGetLastError());
     // the one wait: the grids' sizes decide the launches that follow
@@ -1485,11 +1520,11 @@ extern "C" int mcq_friction_gen_device(mcq_handle* h, int tracks, int nmax, cons
         maxblk = std::max(maxblk, (items + 255) / 256);
     }
     // (MCQ_FGEN_GRID bounds a track at 2^31 - 1 points: at most 2^21 blocks of 256 items, within a launch's first axis)
-    const size_t b_bits = up8((size_t)tracks * maxblk * 256);
-    if (int rc = grow(h, h->fgen_pts, b_bits + (size_t)tracks * std::max<size_t>(maxblk, 1) * sizeof(int))) return rc;
+    const Arena ap = fgen_pts_layout(tracks, maxblk);
+    if (int rc = grow(h, h->fgen_pts, ap.bytes)) return rc;
     G.maxblk = (int)maxblk;
-    G.bits = (unsigned char*)h->fgen_pts.p;
-    G.bcount = (int*)((char*)h->fgen_pts.p + b_bits);
+    G.bits = ap.at<unsigned char>(h->fgen_pts.p, 0);
+    G.bcount = ap.at<int>(h->fgen_pts.p, 1);
     if (maxblk > 0) {
         hipLaunchKernelGGL(mcq_fgen_mask_kernel, dim3((unsigned)maxblk, tracks), dim3(256), 0, st, G);
         HIP_TRY(hipGetLastError());
@@ -1613,31 +1648,50 @@ static int ensure_pin(mcq_handle* h, size_t bytes)
     return 0;
 }
 
-// ---- the n spline scalings out of the dense matrix the reference passes (include/mcq.h); host code, no GPU ----------------------------------
-extern "C" int mcq_les_scalings(const double* A, int n, double* s_out, int check)
+// fn(t, i0, i1) for the nthreads sub-ranges [i0, i1) of [lo, hi): sub-range 0 on the caller, the others on threads of their own -- and those no
+// thread could be had for on the caller as well, behind its own.  Returns when all are done.
+template <class F> static void fan_out(int lo, int hi, int nthreads, F fn)
 {
-    if (!A || !s_out || n < 3) { g_err = "mcq_les_scalings: bad argument"; return MCQ_E_ARG; }
-    const size_t m = (size_t)4 * n;
-    for (int i = 0; i + 1 < n; ++i) s_out[i] = -A[((size_t)4 * i + 2) * m + 4 * i + 5];
-    s_out[n - 1] = A[(m - 2) * m + 1];
+    auto run = [=](int t) { fn(t, lo + (int)((long long)(hi - lo) * t / nthreads), lo + (int)((long long)(hi - lo) * (t + 1) / nthreads)); };
+    std::vector<std::thread> th;
+    int taken = 1;          // sub-ranges 0 .. taken - 1 have a thread (0: this one)
+    try {
+        for (; taken < nthreads; ++taken) th.emplace_back(run, taken);
+    } catch (...) {}
+    run(0);
+    for (int t = taken; t < nthreads; ++t) run(t);
+    for (auto& t : th) t.join();
+}
+
+// ---- the n spline scalings out of the dense matrix the reference passes (include/mcq.h); host code, no GPU ----------------------------------
+// closed: calc_splines' closed system through n waypoints, [4n][4n]; open: its open system, [4(n-1)][4(n-1)] with 12 n - 15 non-zeros, whose
+// last block holds the two heading rows and whose s_out ends in two ones.
+static int les_scalings(const double* A, int n, double* s_out, int check, bool closed)
+{
+    const char* name = closed ? "mcq_les_scalings" : "mcq_les_scalings_open";
+    if (!A || !s_out || n < 3) { g_err = std::string(name) + ": bad argument"; return MCQ_E_ARG; }
+    const int ns = closed ? n : n - 1;          // splines
+    const size_t m = (size_t)4 * ns;
+    for (int i = 0; i + 1 < ns; ++i) s_out[i] = -A[((size_t)4 * i + 2) * m + 4 * i + 5];
+    if (closed) s_out[n - 1] = A[(m - 2) * m + 1];
+    else s_out[n - 2] = s_out[n - 1] = 1.0;
     if (!check) return 0;
-    // Row by row: the entries the closed-spline system has in that row, at their values (the wrap-around rows carry the
+    // Row by row: the entries the system has in that row, at their values (the closed system's wrap-around rows carry the
     // opposite sign), and NOTHING else -- a row's non-zeros are counted while it streams through.
     // one thread per 16 MB of matrix, 32 at most (512 MB at n = 2000: 3.4 ms on 8 threads of the bench host, memory-bound); $MCQ_PACK_THREADS overrides
     int nthreads = (int)std::min<size_t>(32, std::max<size_t>(1, (m * m * sizeof(double)) >> 24));
     if (const char* e = getenv("MCQ_PACK_THREADS")) nthreads = atoi(e);
     const int hw = (int)std::thread::hardware_concurrency();
     if (hw > 0 && nthreads > hw) nthreads = hw;
-    if (nthreads > n) nthreads = n;
+    if (nthreads > ns) nthreads = ns;
     if (nthreads < 1) nthreads = 1;
     std::vector<long long> bad((size_t)nthreads, -1);          // first offending (row * m + column) of a thread's blocks
     auto rel = [](double a, double b) { return fabs(a - b) <= 1e-12 * fabs(b); };
-    auto scan = [&](int t) {
-        const int i0 = (int)((long long)n * t / nthreads), i1 = (int)((long long)n * (t + 1) / nthreads);
+    fan_out(0, ns, nthreads, [&](int t, int i0, int i1) {
         for (int i = i0; i < i1 && bad[t] < 0; ++i) {
             const size_t j = (size_t)4 * i;
-            const bool last = i == n - 1;
-            const double s = s_out[i];
+            const bool last = i == ns - 1;
+            const double s = last && !closed ? 1.0 : s_out[i];
             if (!(s > 0.0) || !std::isfinite(s)) { bad[t] = (long long)((j + 2) * m + (last ? 1 : j + 5)); break; }
             for (int r = 0; r < 4; ++r) {
                 const double* row = A + (j + r) * m;
@@ -1646,28 +1700,21 @@ extern "C" int mcq_les_scalings(const double* A, int n, double* s_out, int check
                 bool ok;
                 if (r == 0) ok = nz == 1 && row[j] == 1.0;
                 else if (r == 1) ok = nz == 4 && row[j] == 1.0 && row[j + 1] == 1.0 && row[j + 2] == 1.0 && row[j + 3] == 1.0;
-                else if (r == 2) ok = nz == 4 && (last ? (row[j + 1] == -1.0 && row[j + 2] == -2.0 && row[j + 3] == -3.0 && row[1] == s)
-                                                       : (row[j + 1] == 1.0 && row[j + 2] == 2.0 && row[j + 3] == 3.0 && row[j + 5] == -s));
-                else ok = nz == 3 && (last ? (row[j + 2] == -2.0 && row[j + 3] == -6.0 && rel(row[2], 2.0 * s * s))
-                                           : (row[j + 2] == 2.0 && row[j + 3] == 6.0 && rel(-row[j + 6], 2.0 * s * s)));
+                else if (r == 2 && !last) ok = nz == 4 && row[j + 1] == 1.0 && row[j + 2] == 2.0 && row[j + 3] == 3.0 && row[j + 5] == -s;
+                else if (r == 2) ok = closed ? nz == 4 && row[j + 1] == -1.0 && row[j + 2] == -2.0 && row[j + 3] == -3.0 && row[1] == s
+                                             : nz == 1 && row[1] == 1.0;                                        // heading at the start
+                else if (!last) ok = nz == 3 && row[j + 2] == 2.0 && row[j + 3] == 6.0 && rel(-row[j + 6], 2.0 * s * s);
+                else ok = nz == 3 && (closed ? row[j + 2] == -2.0 && row[j + 3] == -6.0 && rel(row[2], 2.0 * s * s)
+                                             : row[j + 1] == 1.0 && row[j + 2] == 2.0 && row[j + 3] == 3.0);    // ... at the end
                 if (!ok) { bad[t] = (long long)((j + r) * m); break; }
             }
         }
-    };
-    if (nthreads > 1) {
-        std::vector<std::thread> th;
-        int taken = 1;
-        try {
-            for (; taken < nthreads; ++taken) th.emplace_back(scan, taken);
-        } catch (...) {}
-        scan(0);
-        for (int t = taken; t < nthreads; ++t) scan(t);
-        for (auto& t : th) t.join();
-    } else scan(0);
+    });
     for (int t = 0; t < nthreads; ++t) {
         if (bad[t] >= 0) {
             char buf[160];
-            snprintf(buf, sizeof buf, "mcq_les_scalings: row %lld of A does not have the structure of calc_splines' closed-spline system", bad[t] / (long long)m);
+            snprintf(buf, sizeof buf, "%s: row %lld of A does not have the structure of calc_splines' %s-spline system", name, bad[t] / (long long)m,
+                     closed ? "closed" : "open");
             g_err = buf;
             return MCQ_E_ARG;
         }
@@ -1675,65 +1722,9 @@ extern "C" int mcq_les_scalings(const double* A, int n, double* s_out, int check
     return 0;
 }
 
-// ---- the same for the open system through n waypoints: [4(n-1)][4(n-1)], 12 n - 15 non-zeros (include/mcq.h) -----------------------------
-extern "C" int mcq_les_scalings_open(const double* A, int n, double* s_out, int check)
-{
-    if (!A || !s_out || n < 3) { g_err = "mcq_les_scalings_open: bad argument"; return MCQ_E_ARG; }
-    const int ns = n - 1;                       // splines
-    const size_t m = (size_t)4 * ns;
-    for (int i = 0; i + 1 < ns; ++i) s_out[i] = -A[((size_t)4 * i + 2) * m + 4 * i + 5];
-    s_out[n - 2] = s_out[n - 1] = 1.0;
-    if (!check) return 0;
-    int nthreads = (int)std::min<size_t>(32, std::max<size_t>(1, (m * m * sizeof(double)) >> 24));
-    if (const char* e = getenv("MCQ_PACK_THREADS")) nthreads = atoi(e);
-    const int hw = (int)std::thread::hardware_concurrency();
-    if (hw > 0 && nthreads > hw) nthreads = hw;
-    if (nthreads > ns) nthreads = ns;
-    if (nthreads < 1) nthreads = 1;
-    std::vector<long long> bad((size_t)nthreads, -1);
-    auto rel = [](double a, double b) { return fabs(a - b) <= 1e-12 * fabs(b); };
-    auto scan = [&](int t) {
-        const int i0 = (int)((long long)ns * t / nthreads), i1 = (int)((long long)ns * (t + 1) / nthreads);
-        for (int i = i0; i < i1 && bad[t] < 0; ++i) {
-            const size_t j = (size_t)4 * i;
-            const bool last = i == ns - 1;
-            const double s = last ? 1.0 : s_out[i];
-            if (!(s > 0.0) || !std::isfinite(s)) { bad[t] = (long long)((j + 2) * m + j + 5); break; }
-            for (int r = 0; r < 4; ++r) {
-                const double* row = A + (j + r) * m;
-                size_t nz = 0;
-                for (size_t c = 0; c < m; ++c) nz += row[c] != 0.0;
-                bool ok;
-                if (r == 0) ok = nz == 1 && row[j] == 1.0;
-                else if (r == 1) ok = nz == 4 && row[j] == 1.0 && row[j + 1] == 1.0 && row[j + 2] == 1.0 && row[j + 3] == 1.0;
-                else if (r == 2) ok = last ? (nz == 1 && row[1] == 1.0)                                     // heading at the start
-                                           : (nz == 4 && row[j + 1] == 1.0 && row[j + 2] == 2.0 && row[j + 3] == 3.0 && row[j + 5] == -s);
-                else ok = last ? (nz == 3 && row[j + 1] == 1.0 && row[j + 2] == 2.0 && row[j + 3] == 3.0)   // ... at the end
-                               : (nz == 3 && row[j + 2] == 2.0 && row[j + 3] == 6.0 && rel(-row[j + 6], 2.0 * s * s));
-                if (!ok) { bad[t] = (long long)((j + r) * m); break; }
-            }
-        }
-    };
-    if (nthreads > 1) {
-        std::vector<std::thread> th;
-        int taken = 1;
-        try {
-            for (; taken < nthreads; ++taken) th.emplace_back(scan, taken);
-        } catch (...) {}
-        scan(0);
-        for (int t = taken; t < nthreads; ++t) scan(t);
-        for (auto& t : th) t.join();
-    } else scan(0);
-    for (int t = 0; t < nthreads; ++t) {
-        if (bad[t] >= 0) {
-            char buf[160];
-            snprintf(buf, sizeof buf, "mcq_les_scalings_open: row %lld of A does not have the structure of calc_splines' open-spline system", bad[t] / (long long)m);
-            g_err = buf;
-            return MCQ_E_ARG;
-        }
-    }
-    return 0;
-}
+extern "C" int mcq_les_scalings(const double* A, int n, double* s_out, int check) { return les_scalings(A, n, s_out, check, true); }
+
+extern "C" int mcq_les_scalings_open(const double* A, int n, double* s_out, int check) { return les_scalings(A, n, s_out, check, false); }
 
 extern "C" int mcq_host_alloc(mcq_handle* h, size_t bytes, void** out)
 {
@@ -2328,17 +2319,7 @@ static int pack_and_upload(mcq_handle* h, const mcq_problem* probs, int batch, s
     }
     for (int ck = 0; ck < nchunks; ++ck) {
         const int b0 = (int)((long long)batch * ck / nchunks), b1 = (int)((long long)batch * (ck + 1) / nchunks);
-        if (nthreads > 1) {
-            auto sub = [&](int t) { return b0 + (int)((long long)(b1 - b0) * t / nthreads); };
-            std::vector<std::thread> th;
-            int taken = 1;          // sub-ranges 0 .. taken - 1 have a thread (0: this one)
-            try {
-                for (; taken < nthreads; ++taken) th.emplace_back(pack_range, sub(taken), sub(taken + 1));
-            } catch (...) {}        // (no more threads to be had: their sub-ranges are packed here)
-            pack_range(sub(0), sub(1));
-            for (int t = taken; t < nthreads; ++t) pack_range(sub(t), sub(t + 1));
-            for (auto& t : th) t.join();
-        } else pack_range(b0, b1);
+        fan_out(b0, b1, nthreads, [&](int, int r0, int r1) { pack_range(r0, r1); });
         const size_t off = (size_t)b0 * nmax, cnt = (size_t)(b1 - b0) * nmax;
         HIP_TRY_DRAIN(hipMemcpyAsync(s.ref + off * 4, P.ref + off * 4, cnt * 4 * sizeof(double), hipMemcpyHostToDevice, up));
         if (with_nv) HIP_TRY_DRAIN(hipMemcpyAsync(s.nv + off * 2, P.nv + off * 2, cnt * 2 * sizeof(double), hipMemcpyHostToDevice, up));

@@ -275,6 +275,24 @@ def _pad_like(rows, ns, tail=(), nmin=0):
     return out
 
 
+def _closed_length(xy):
+    """The length of the closed polygon through the rows of xy [n, 2]."""
+    return float(np.sum(np.hypot(*np.diff(np.vstack((xy, xy[:1])), axis=0).T)))
+
+
+def _per_variant(bsz, *values):
+    """Scalars or [bsz] sequences as contiguous float64 arrays [bsz] each."""
+    return [np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float64), (bsz,))) for a in values]
+
+
+INFO_FIELDS = tuple(f[0] for f in McqInfo._fields_)
+
+
+def _info_dicts(infos, fields=INFO_FIELDS):
+    """A sequence of McqInfo records as dicts of the named fields."""
+    return [{f: list(getattr(i, f)) if f == "ticks" else getattr(i, f) for f in fields} for i in infos]
+
+
 def export_result(tab, idx, lens, s_ref, total, status, ns, ms, tr, tj):
     """Engine.export_batch's host piece: the padded outputs of mcq_export_device cut to lists (ns [tracks], ms [tracks], tr [batch] = track_of,
     tj = the padded trajectories), and the closed race tables."""
@@ -298,7 +316,7 @@ class _Scope:
     """The device allocations of one call (Engine.scope): freed on exit, in allocation order, with or without an exception in flight."""
 
     def __init__(self, eng):
-        self.eng, self.ptrs = eng, []
+        self.eng, self.ptrs, self.extent = eng, [], {}      # extent: pointer -> (shape, dtype) of what out / up / adopt put behind it
 
     def __enter__(self):
         return self
@@ -311,22 +329,36 @@ class _Scope:
         self.ptrs.append(self.eng.alloc(nbytes))
         return self.ptrs[-1]
 
+    def out(self, shape, dtype=np.float64, floor=0):
+        """Pointer to a zero-filled array of that shape (an int: [shape]) and dtype, at least `floor` bytes; get(pointer) fetches it."""
+        ptr = self.new(max(int(np.prod(shape)) * np.dtype(dtype).itemsize, floor))
+        self.extent[ptr] = (shape, dtype)
+        return ptr
+
+    def get(self, ptr):
+        """The array behind a pointer of out, up or adopt(ptr, shape), as the device holds it now."""
+        return self.eng.download(ptr, *self.extent[ptr])
+
     def up(self, a):
         """Pointer to a device copy of the array (made contiguous); None for None."""
         if a is None:
             return None
         a = np.ascontiguousarray(a)
         self.eng.upload(self.new(a.nbytes), a)
+        self.extent[self.ptrs[-1]] = (a.shape, a.dtype)
         return self.ptrs[-1]
 
-    def adopt(self, ptr):
-        """A pointer another scope released: this one frees it."""
+    def adopt(self, ptr, shape=None, dtype=np.float64):
+        """A pointer another scope released: this one frees it.  shape: what get(ptr) fetches."""
         self.ptrs.append(ptr)
+        if shape is not None:
+            self.extent[ptr] = (shape, dtype)
         return ptr
 
     def release(self, ptr):
         """The pointer leaves the scope: the caller frees it."""
         self.ptrs.remove(ptr)
+        self.extent.pop(ptr, None)
         return ptr
 
 
@@ -463,11 +495,7 @@ class Engine:
         for ref, _, _ in keep:
             out.append(alpha[off:off + ref.shape[0]].copy())
             off += ref.shape[0]
-        infos = [dict(ipm_iters=i.ipm_iters, as_iters=i.as_iters, n_active_box=i.n_active_box,
-                      n_active_kappa=i.n_active_kappa, kappa_max=i.kappa_max, kkt_res=i.kkt_res,
-                      ticks=list(i.ticks), refine_rounds=i.refine_rounds, second_attempt=i.second_attempt,
-                      f32_factorisations=i.f32_factorisations, gi_iters=i.gi_iters) for i in info]
-        return out, curv, status, infos
+        return out, curv, status, _info_dicts(info)
 
     # ------------------------------------------------------------------------------------------------------------------
     def solve_device(self, batch, n, d_reftrack, d_normvec, d_scaling, kappa_bound, w_veh, d_alpha, d_curv, d_status,
@@ -671,7 +699,7 @@ class Engine:
                 seg = xy - np.roll(xy, -1, axis=1)
                 lengths = np.sqrt(np.einsum("bnk,bnk->bn", seg, seg)).sum(axis=1)
             else:
-                lengths = np.array([np.hypot(np.diff(r[:, 0], append=r[0, 0]), np.diff(r[:, 1], append=r[0, 1])).sum() for r in refs])
+                lengths = np.array([_closed_length(r[:, :2]) for r in refs])
             finite = lengths[np.isfinite(lengths)]          # (a track with non-finite rows is reported by the engine: status 4)
             longest = float(finite.max()) if finite.size else 0.0
             nmax = max(refs.shape[1] if stacked else max(r.shape[0] for r in refs), int(np.ceil(1.3 * longest / stepsize_interp)) + 16)
@@ -723,17 +751,12 @@ class Engine:
         sc = None if scaling is None else np.ascontiguousarray(scaling, dtype=np.float32)
         with self.scope() as dev:
             d_ref, d_nv, d_sc = dev.up(ref), dev.up(nv), dev.up(sc)
-            d_alpha, d_curv, d_status, d_info = dev.new(bsz * n * 4), dev.new(bsz * 8), dev.new(bsz * 4), dev.new(bsz * ctypes.sizeof(McqInfo))
+            d_alpha, d_curv, d_status = dev.out((bsz, n), np.float32), dev.out(bsz), dev.out(bsz, np.int32)
+            d_info = dev.out((bsz, ctypes.sizeof(McqInfo)), np.uint8)
             self.solve_device_f32(bsz, n, d_ref, d_nv, d_sc, kappa_bound, w_veh, d_alpha, d_curv, d_status, d_info, **opt_kw)
             self.sync()
-            alpha = self.download(d_alpha, (bsz, n), np.float32)
-            curv = self.download(d_curv, (bsz,), np.float64)
-            status = self.download(d_status, (bsz,), np.int32)
-            raw = self.download(d_info, (bsz * ctypes.sizeof(McqInfo),), np.uint8)
-        infos = (McqInfo * bsz).from_buffer_copy(raw.tobytes())
-        info = [dict(ipm_iters=i.ipm_iters, as_iters=i.as_iters, n_active_box=i.n_active_box,
-                     n_active_kappa=i.n_active_kappa, kappa_max=i.kappa_max, kkt_res=i.kkt_res) for i in infos]
-        return alpha, curv, status, info
+            alpha, curv, status, raw = dev.get(d_alpha), dev.get(d_curv), dev.get(d_status), dev.get(d_info)
+        return alpha, curv, status, _info_dicts((McqInfo * bsz).from_buffer_copy(raw.tobytes()), INFO_FIELDS[:6])
 
     def solve_device_ragged(self, batch, nmax, d_n, d_reftrack, d_normvec, d_scaling, kappa_bound, w_veh, d_alpha,
                             d_curv, d_status, d_info=None, **opt_kw):
@@ -761,11 +784,9 @@ class Engine:
         bsz, nmax = ref.shape[:2]
         with self.scope() as dev:
             d_ref, d_n = dev.up(ref), dev.up(ns)
-            d_nv, d_sc, d_st = dev.new(bsz * nmax * 16), dev.new(bsz * nmax * 8), dev.new(bsz * 4)
+            d_nv, d_sc, d_st = dev.out((bsz, nmax, 2)), dev.out((bsz, nmax)), dev.out(bsz, np.int32)
             self._check(self.lib.mcq_prep_device(self.h, bsz, nmax, d_n, d_ref, d_nv, d_sc, d_st), "mcq_prep_device")
-            st = self.download(d_st, (bsz,), np.int32)
-            nv = self.download(d_nv, (bsz, nmax, 2), np.float64)
-            sc = self.download(d_sc, (bsz, nmax), np.float64)
+            st, nv, sc = dev.get(d_st), dev.get(d_nv), dev.get(d_sc)
         if np.any(st != 0):
             raise EngineError("mcq_prep_device: bad input in problem(s) %s" % np.nonzero(st)[0].tolist())
         return [nv[k, :ns[k]].copy() for k in range(bsz)], [sc[k, :ns[k]].copy() for k in range(bsz)]
@@ -806,7 +827,7 @@ class Engine:
         if ggv is not None:
             ggv = np.ascontiguousarray(ggv, dtype=np.float64)
         bsz, n = (ggv if ggv is not None else axm).shape[0], kappa.shape[1]
-        scal = [np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float64), (bsz,))) for a in (drag_coeff, m_veh, v_max)]
+        scal = _per_variant(bsz, drag_coeff, m_veh, v_max)
         # what tph.calc_vel_profile raises on (the kernel itself flags such a variant with lap_time = NaN)
         if ggv is not None and np.any(ggv[:, -1, 0] < scal[2]):
             raise RuntimeError("ggv has to cover the entire velocity range of the car (i.e. >= v_max)!")
@@ -831,13 +852,13 @@ class Engine:
             d_k, d_e, d_a = up(kappa), up(el), up(axm)
             d_g, n_g = up(ggv), ggv.shape[1] if ggv is not None else 0
             d_s = [up(a) for a in scal]
-            d_t, d_vx, d_lt = up(tr), dev.new(bsz * n * 8), dev.new(bsz * 8)
+            d_t, d_vx, d_lt = up(tr), dev.out((bsz, n)), dev.out(bsz)
             d_n, d_mu, d_lg = up(nt), up(mu), up(loc_gg)
             d_vs = d_ve = None
             if not closed:
-                d_vs = up(np.broadcast_to(np.asarray(v_start, dtype=np.float64), (bsz,)))
+                d_vs = up(_per_variant(bsz, v_start)[0])
                 if v_end is not None:
-                    d_ve = up(np.broadcast_to(np.asarray(v_end, dtype=np.float64), (bsz,)))
+                    d_ve = up(_per_variant(bsz, v_end)[0])
             if timed:
                 self.timing_begin()
             if not closed or loc_gg is not None:
@@ -858,7 +879,7 @@ class Engine:
                                                      d_s[0], d_s[1], d_s[2], float(dyn_model_exp), d_vx, d_lt)
             self._check(rc, "mcq_vel_profile_device")
             ms = self.timing_end()[0] if timed else None
-            res = (self.download(d_vx, (bsz, n), np.float64), self.download(d_lt, (bsz,), np.float64))
+            res = (dev.get(d_vx), dev.get(d_lt))
             return res + (ms,) if timed else res
 
     def normals_crossing_batch(self, reftracks, normvecs, horizon=10):
@@ -868,10 +889,10 @@ class Engine:
         nv = _pad_like(normvecs, ns, (2,))
         bsz, nmax = ref.shape[:2]
         with self.scope() as dev:
-            d_ref, d_nv, d_n, d_out = dev.up(ref), dev.up(nv), dev.up(ns), dev.new(bsz * 4)
+            d_ref, d_nv, d_n, d_out = dev.up(ref), dev.up(nv), dev.up(ns), dev.out(bsz, np.int32)
             rc = self.lib.mcq_normals_crossing_device(self.h, bsz, nmax, d_n, d_ref, d_nv, int(horizon), d_out)
             self._check(rc, "mcq_normals_crossing_device")
-            return self.download(d_out, (bsz,), np.int32)
+            return dev.get(d_out)
 
     def spline_approx_device(self, tracks, nmax, d_n, d_track, k, nkmax, d_nk, d_knots, d_coef, stepsize_reg, mmax, d_ref, d_m, d_ct, d_dist,
                              d_dev, d_nonmono, d_status):
@@ -919,26 +940,22 @@ class Engine:
         else:
             k, nkmax = int(resident[0]), int(resident[1])
         if mmax is None:      # a smoothed line is shorter than its raw one: room for one twice as long (a track that needs more reports its m)
-            el = [float(np.sum(np.hypot(*(np.diff(np.vstack((trk[b, :ns[b], :2], trk[b, :1, :2])), axis=0).T)))) for b in range(bsz)]
-            finite = [e for e in el if np.isfinite(e)]
+            finite = [e for e in (_closed_length(trk[b, :ns[b], :2]) for b in range(bsz)) if np.isfinite(e)]
             mmax = max(int(2.0 * max(finite + [0.0]) / float(stepsize_reg)) + 8, 8)
         with self.scope() as dev:
-            up, new = dev.up, dev.new
+            up, out, get = dev.up, dev.out, dev.get
             d_trk, d_n = up(trk), up(ns)
             d_nk, d_kn, d_cf = (up(nk), up(knots), up(coef)) if resident is None else resident[2:5]
-            d_m, d_ct, d_ds, d_dev, d_nm, d_st = new(bsz * 4), new(bsz * (nmax + 1) * 8), new(bsz * (nmax + 1) * 8), new(bsz * 16), new(bsz * 4), new(bsz * 4)
-            d_ref = new(bsz * mmax * 32)
+            d_m, d_ct, d_ds, d_dev, d_nm, d_st = out(bsz, np.int32), out((bsz, nmax + 1)), out((bsz, nmax + 1)), out((bsz, 2)), out(bsz, np.int32), out(bsz, np.int32)
+            d_ref = out((bsz, mmax, 4))
             self.spline_approx_device(bsz, nmax, d_n, d_trk, k, nkmax, d_nk, d_kn, d_cf, stepsize_reg, mmax, d_ref, d_m, d_ct, d_ds,
                                       d_dev, d_nm, d_st)
-            m = self.download(d_m, (bsz,), np.int32)
-            st = self.download(d_st, (bsz,), np.int32)
-            ref = self.download(d_ref, (bsz, mmax, 4), np.float64)
-            out = dict(reftrack=[ref[b, :m[b]].copy() if st[b] == 0 else None for b in range(bsz)], m=m, status=st,
-                       closest_t=self.download(d_ct, (bsz, nmax + 1), np.float64), dists=self.download(d_ds, (bsz, nmax + 1), np.float64),
-                       dev=self.download(d_dev, (bsz, 2), np.float64), nonmono=self.download(d_nm, (bsz,), np.int32))
+            m, st, ref = get(d_m), get(d_st), get(d_ref)
+            res = dict(reftrack=[ref[b, :m[b]].copy() if st[b] == 0 else None for b in range(bsz)], m=m, status=st,
+                       closest_t=get(d_ct), dists=get(d_ds), dev=get(d_dev), nonmono=get(d_nm))
             if keep is not None:
                 keep.extend((dev.release(d_ref), dev.release(d_m), mmax))
-            return out
+            return res
 
     def spline_fit_device(self, tracks, nmax, d_n, d_track, stepsize_prep, mimax, k, s, nkmax, d_nk, d_knots, d_coef, d_fp, d_ier, d_mi, d_pts,
                           d_status):
@@ -961,33 +978,28 @@ class Engine:
         bsz, nmax = trk.shape[:2]
         if mimax is None:
             if stepsize_prep > 0.0:
-                el = [float(np.sum(np.hypot(*(np.diff(np.vstack((trk[b, :ns[b], :2], trk[b, :1, :2])), axis=0).T)))) for b in range(bsz)]
-                finite = [e for e in el if np.isfinite(e)]
+                finite = [e for e in (_closed_length(trk[b, :ns[b], :2]) for b in range(bsz)) if np.isfinite(e)]
                 mimax = max(int(np.ceil(max(finite + [0.0]) / float(stepsize_prep))) + 3, 4)
             else:
                 mimax = nmax + 1
         nkmax = int(nest) if nest is not None else mimax + 2 * int(k)
         with self.scope() as dev:
-            up, new = dev.up, dev.new
+            up, out, get = dev.up, dev.out, dev.get
             d_trk, d_n = up(trk), up(ns)
-            d_nk, d_kn, d_cf = new(bsz * 4), new(bsz * nkmax * 8), new(bsz * 2 * nkmax * 8)
-            d_fp, d_ier, d_mi, d_st = new(bsz * 8), new(bsz * 4), new(bsz * 4), new(bsz * 4)
-            d_pts = new(bsz * mimax * 16) if points else None
+            d_nk, d_kn, d_cf = out(bsz, np.int32), out((bsz, nkmax)), out((bsz, 2, nkmax))
+            d_fp, d_ier, d_mi, d_st = out(bsz), out(bsz, np.int32), out(bsz, np.int32), out(bsz, np.int32)
+            d_pts = out((bsz, mimax, 2)) if points else None
             self.spline_fit_device(bsz, nmax, d_n, d_trk, stepsize_prep, mimax, k, s, nkmax, d_nk, d_kn, d_cf, d_fp, d_ier, d_mi, d_pts, d_st)
-            nk = self.download(d_nk, (bsz,), np.int32)
-            st = self.download(d_st, (bsz,), np.int32)
-            kn = self.download(d_kn, (bsz, nkmax), np.float64)
-            cf = self.download(d_cf, (bsz, 2, nkmax), np.float64)
-            out = dict(tcks=[(kn[b, :nk[b]].copy(), [cf[b, 0, :nk[b] - k - 1].copy(), cf[b, 1, :nk[b] - k - 1].copy()], int(k)) if st[b] == 0 else None
+            nk, st, kn, cf = get(d_nk), get(d_st), get(d_kn), get(d_cf)
+            res = dict(tcks=[(kn[b, :nk[b]].copy(), [cf[b, 0, :nk[b] - k - 1].copy(), cf[b, 1, :nk[b] - k - 1].copy()], int(k)) if st[b] == 0 else None
                              for b in range(bsz)],
-                       nk=nk, fp=self.download(d_fp, (bsz,), np.float64), ier=self.download(d_ier, (bsz,), np.int32),
-                       mi=self.download(d_mi, (bsz,), np.int32), status=st, knots=kn, coef=cf)
+                       nk=nk, fp=get(d_fp), ier=get(d_ier), mi=get(d_mi), status=st, knots=kn, coef=cf)
             if points:
-                pts = self.download(d_pts, (bsz, mimax, 2), np.float64)
-                out["pts"] = [pts[b, :out["mi"][b]].copy() if st[b] == 0 else None for b in range(bsz)]
+                pts = get(d_pts)
+                res["pts"] = [pts[b, :res["mi"][b]].copy() if st[b] == 0 else None for b in range(bsz)]
             if keep is not None:
                 keep.extend((int(k), nkmax, dev.release(d_nk), dev.release(d_kn), dev.release(d_cf)))
-            return out
+            return res
 
     def min_width_batch(self, reftracks, min_width):
         """prep_track's tail for a list of prepared tracks (mcq_min_width_device): rows narrower than min_width grow by half the deficit on both
@@ -995,10 +1007,10 @@ class Engine:
         ns, ref = _pad_rows(reftracks, 4)
         bsz, nmax = ref.shape[:2]
         with self.scope() as dev:
-            d_ref, d_n, d_ch = dev.up(ref), dev.up(ns), dev.new(bsz * 4)
+            d_ref, d_n, d_ch = dev.up(ref), dev.up(ns), dev.out(bsz, np.int32)
             self.min_width_device(bsz, nmax, d_n, d_ref, min_width, d_ch)
-            out = self.download(d_ref, (bsz, nmax, 4), np.float64)
-            return [out[b, :ns[b]].copy() for b in range(bsz)], self.download(d_ch, (bsz,), np.int32)
+            out = dev.get(d_ref)
+            return [out[b, :ns[b]].copy() for b in range(bsz)], dev.get(d_ch)
 
     def prep_track_batch(self, tracks, k_reg=3, s_reg=10, stepsize_prep=1.0, stepsize_reg=3.0, min_width=None, tcks=None, horizon=10, fit="host"):
         """prep_track [REF helper_funcs_glob/src/prep_track.py] for a list of raw tracks ([n_k, 4] rows, not closed).  On the host, per track:
@@ -1037,25 +1049,23 @@ class Engine:
                 for ptr in resident[2:5]:
                     self.free(ptr)
         with self.scope() as dev:
-            d_ref, d_m, mmax = dev.adopt(keep[0]), dev.adopt(keep[1]), keep[2]
+            mmax = keep[2]
+            d_ref, d_m = dev.adopt(keep[0], (bsz, mmax, 4)), dev.adopt(keep[1])
             if np.any(out["status"] != 0):      # a refused track has no rows: the kernels behind must not take its m_out (the rows it would need) for a length
                 self.upload(d_m, np.where(out["status"] == 0, out["m"], 0).astype(np.int32))
-            d_nv, d_sc, d_st, d_cr, d_ch = dev.new(bsz * mmax * 16), dev.new(bsz * mmax * 8), dev.new(bsz * 4), dev.new(bsz * 4), dev.new(bsz * 4)
+            d_nv, d_sc, d_st, d_cr, d_ch = dev.out((bsz, mmax, 2)), dev.out((bsz, mmax)), dev.out(bsz, np.int32), dev.out(bsz, np.int32), dev.out(bsz, np.int32)
             self._check(self.lib.mcq_prep_device(self.h, bsz, mmax, d_m, d_ref, d_nv, d_sc, d_st), "mcq_prep_device")
             self._check(self.lib.mcq_normals_crossing_device(self.h, bsz, mmax, d_m, d_ref, d_nv, int(horizon), d_cr), "mcq_normals_crossing_device")
             if min_width is not None:
                 self.min_width_device(bsz, mmax, d_m, d_ref, min_width, d_ch)
-            ref = self.download(d_ref, (bsz, mmax, 4), np.float64)
-            nv = self.download(d_nv, (bsz, mmax, 2), np.float64)
-            sc = self.download(d_sc, (bsz, mmax), np.float64)
-            st = np.where(out["status"] != 0, out["status"], self.download(d_st, (bsz,), np.int32))
+            ref, nv, sc = dev.get(d_ref), dev.get(d_nv), dev.get(d_sc)
+            st = np.where(out["status"] != 0, out["status"], dev.get(d_st))
             m = out["m"]
             good = [st[b] == 0 for b in range(bsz)]
             return dict(reftrack=[ref[b, :m[b]].copy() if good[b] else None for b in range(bsz)],
                         normvec=[nv[b, :m[b]].copy() if good[b] else None for b in range(bsz)],
                         scaling=[sc[b, :m[b]].copy() if good[b] else None for b in range(bsz)],
-                        crossing=self.download(d_cr, (bsz,), np.int32),
-                        inflated=self.download(d_ch, (bsz,), np.int32) if min_width is not None else np.zeros(bsz, dtype=np.int32), status=st, m=m,
+                        crossing=dev.get(d_cr), inflated=dev.get(d_ch) if min_width is not None else np.zeros(bsz, dtype=np.int32), status=st, m=m,
                         dev=out["dev"], nonmono=out["nonmono"], tcks=tcks, **({} if fitted is None else dict(fit_ier=fitted["ier"], fit_fp=fitted["fp"])))
 
     def raceline_device_ends(self, batch, nmax, d_n, d_ref, d_nv, d_alpha, d_closed, d_psi, stepsize, mmax, d_xy, d_psi_out, d_kappa,
@@ -1078,14 +1088,13 @@ class Engine:
         nv, al = _pad_like(normvecs, ns, (2,)), _pad_like(alphas, ns)
         bsz, nmax = ref.shape[:2]
         if mmax is None:      # polygon length + the widest shift bounds the raceline length from above generously
-            per = [float(np.sum(np.hypot(*np.diff(np.vstack((r[:, :2], r[:1, :2])), axis=0).T)) + 8.0 * np.sum(np.abs(a)))
-                   for r, a in zip(reftracks, alphas)]
+            per = [float(_closed_length(r[:, :2]) + 8.0 * np.sum(np.abs(a))) for r, a in zip(reftracks, alphas)]
             mmax = int(max(per) / float(stepsize) * 1.25) + 16
         with self.scope() as dev:
-            up, new = dev.up, dev.new
+            up, out, get = dev.up, dev.out, dev.get
             d_ref, d_nv, d_al, d_n = up(ref), up(nv), up(al), up(ns)
-            d_xy, d_psi, d_k, d_el = new(bsz * mmax * 16), new(bsz * mmax * 8), new(bsz * mmax * 8), new(bsz * mmax * 8)
-            d_m, d_st = new(bsz * 4), new(bsz * 4)
+            d_xy, d_psi, d_k, d_el = out((bsz, mmax, 2)), out((bsz, mmax)), out((bsz, mmax)), out((bsz, mmax))
+            d_m, d_st = out(bsz, np.int32), out(bsz, np.int32)
             if ends is None:
                 rc = self.lib.mcq_raceline_device(self.h, bsz, nmax, d_n, d_ref, d_nv, d_al, float(stepsize), int(mmax), d_xy,
                                                   d_psi, d_k, d_el, d_m, d_st)
@@ -1100,10 +1109,7 @@ class Engine:
                         heads[k] = (float(e["psi_s"]), float(e["psi_e"]))
                 self.raceline_device_ends(bsz, nmax, d_n, d_ref, d_nv, d_al, up(closed), up(heads), stepsize, mmax, d_xy, d_psi, d_k,
                                           d_el, d_m, d_st)
-            return dict(xy=self.download(d_xy, (bsz, mmax, 2), np.float64), psi=self.download(d_psi, (bsz, mmax), np.float64),
-                        kappa=self.download(d_k, (bsz, mmax), np.float64),
-                        el_lengths=self.download(d_el, (bsz, mmax), np.float64),
-                        m=self.download(d_m, (bsz,), np.int32), status=self.download(d_st, (bsz,), np.int32))
+            return dict(xy=get(d_xy), psi=get(d_psi), kappa=get(d_k), el_lengths=get(d_el), m=get(d_m), status=get(d_st))
 
     def trajectory_device(self, batch, m, mmax, d_m_of_track, d_track_of, d_xy, d_psi, d_kappa, d_el, d_vx, closed, d_drag, d_mass, d_vmax,
                           d_ggv, n_ggv, d_axm, n_machines, curvlim, d_traj, d_t, d_length, d_limits, d_flags):
@@ -1144,26 +1150,24 @@ class Engine:
         bsz = vx.shape[0]
         if track_of is None and rows != bsz:
             raise ValueError("trajectory_batch: %d rows for %d variants and no track_of" % (rows, bsz))
-        scal = [np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float64), (bsz,))) for a in (drag_coeff, m_veh, v_max)]
+        scal = _per_variant(bsz, drag_coeff, m_veh, v_max)
         ggv = None if ggv is None else np.ascontiguousarray(ggv, dtype=np.float64)
         axm = None if ax_max_machines is None else np.ascontiguousarray(ax_max_machines, dtype=np.float64)
         if (ggv is not None and ggv.shape[0] != bsz) or (axm is not None and axm.shape[0] != bsz):
             raise ValueError("trajectory_batch: ggv / ax_max_machines need one table per variant")
         tr = None if track_of is None else np.ascontiguousarray(track_of, dtype=np.int32)
         with self.scope() as dev:
-            up, new = dev.up, dev.new
+            up, out, get = dev.up, dev.out, dev.get
             d_xy, d_psi, d_k, d_el = up(xy), up(arrs[0]), up(arrs[1]), up(arrs[2])
             d_m, d_vx = up(ms), up(vx)
             d_s = [up(a) for a in scal]
             d_g, d_a, d_t = up(ggv), up(axm), up(tr)
-            d_traj, d_time = new(bsz * mmax * TRAJ_COLS * 8), new(bsz * (mmax + 1) * 8)
-            d_len, d_lim, d_fl = new(bsz * 8), new(bsz * TRAJ_NLIM * 8), new(bsz * 4)
+            d_traj, d_time = out((bsz, mmax, TRAJ_COLS)), out((bsz, mmax + 1))
+            d_len, d_lim, d_fl = out(bsz), out((bsz, TRAJ_NLIM)), out(bsz, np.int32)
             self.trajectory_device(bsz, 0, mmax, d_m, d_t, d_xy, d_psi, d_k, d_el, d_vx, closed, d_s[0], d_s[1], d_s[2], d_g,
                                    ggv.shape[1] if ggv is not None else 0, d_a, axm.shape[1] if axm is not None else 0, curvlim, d_traj,
                                    d_time, d_len, d_lim, d_fl)
-            return dict(traj=self.download(d_traj, (bsz, mmax, TRAJ_COLS), np.float64), t=self.download(d_time, (bsz, mmax + 1), np.float64),
-                        length=self.download(d_len, (bsz,), np.float64), limits=self.download(d_lim, (bsz, TRAJ_NLIM), np.float64),
-                        flags=self.download(d_fl, (bsz,), np.int32))
+            return dict(traj=get(d_traj), t=get(d_time), length=get(d_len), limits=get(d_lim), flags=get(d_fl))
 
     def bound_dists_batch(self, reftracks, normvecs, race, length_veh, width_veh, stepsize_bound=1.0, first_row_only=False):
         """check_traj's first block for a list of tracks (mcq_bound_dists_device) [REF helper_funcs_glob/src/check_traj.py:47-70]: the distance
@@ -1183,18 +1187,16 @@ class Engine:
         mmax = xy.shape[1]
         lens, wids = np.asarray(length_veh, dtype=np.float64), np.asarray(width_veh, dtype=np.float64)
         with self.scope() as dev:
-            up, new = dev.up, dev.new
+            up, out, get = dev.up, dev.out, dev.get
             d_ref, d_nv, d_n, d_xy, d_psi, d_m = up(ref), up(nv), up(ns), up(xy), up(psi), up(ms)
             d_ll = up(np.broadcast_to(lens, (bsz,))) if lens.ndim else None
             d_wl = up(np.broadcast_to(wids, (bsz,))) if wids.ndim else None
-            d_md, d_mn, d_nb, d_bd, d_st = new(bsz * mmax * 8), new(bsz * 8), new(bsz * 8), new(bsz * 2 * nmax * 16), new(bsz * 4)
+            d_md, d_mn, d_nb, d_bd, d_st = out((bsz, mmax)), out(bsz), out((bsz, 2), np.int32), out((bsz, 2, nmax, 2)), out(bsz, np.int32)
             self.bound_dists_device(bsz, nmax, d_n, d_ref, d_nv, mmax, d_m, d_xy, d_psi, 0.0 if lens.ndim else float(lens),
                                     0.0 if wids.ndim else float(wids), d_ll, d_wl, stepsize_bound,
                                     BOUNDS_FIRST_ROW if first_row_only else BOUNDS_ALL, d_md, d_mn, d_nb, d_bd, d_st)
-            bound = self.download(d_bd, (bsz, 2, nmax, 2), np.float64)
-            return dict(min_dists=self.download(d_md, (bsz, mmax), np.float64), min_dist=self.download(d_mn, (bsz,), np.float64),
-                        nb=self.download(d_nb, (bsz, 2), np.int32), bound_r=bound[:, 0].copy(), bound_l=bound[:, 1].copy(),
-                        status=self.download(d_st, (bsz,), np.int32))
+            bound = get(d_bd)
+            return dict(min_dists=get(d_md), min_dist=get(d_mn), nb=get(d_nb), bound_r=bound[:, 0].copy(), bound_l=bound[:, 1].copy(), status=get(d_st))
 
     def export_device(self, tracks, nmax, d_n, d_ref, d_nv, d_alpha, batch, mmax, d_m_of_track, d_track_of, d_traj, d_ltpl, d_idx, d_lengths,
                       d_s_ref, d_total, d_status):
@@ -1240,19 +1242,14 @@ class Engine:
         if ms.shape != (tracks,):
             raise ValueError("export_batch: m must hold one count per track")
         with self.scope() as dev:
-            up, new = dev.up, dev.new
+            up, out = dev.up, dev.out
             d_ref, d_nv, d_al, d_n = up(ref), up(nv), up(al), up(ns)
             d_m, d_t, d_tj = up(ms), up(tr), up(tj)
-            d_tab, d_idx = new(bsz * (nmax + 1) * LTPL_COLS * 8), new(bsz * nmax * 4)
-            d_len, d_s, d_tot, d_st = new(tracks * nmax * 8), new(tracks * (nmax + 1) * 8), new(tracks * 8), new(bsz * 4)
+            d_tab, d_idx = out((bsz, nmax + 1, LTPL_COLS)), out((bsz, nmax), np.int32)
+            d_len, d_s, d_tot, d_st = out((tracks, nmax)), out((tracks, nmax + 1)), out(tracks), out(bsz, np.int32)
             self.export_device(tracks, nmax, d_n, d_ref, d_nv, d_al, bsz, mmax, d_m, d_t, d_tj, d_tab, d_idx, d_len, d_s, d_tot, d_st)
-            tab = self.download(d_tab, (bsz, nmax + 1, LTPL_COLS), np.float64)
-            idx = self.download(d_idx, (bsz, nmax), np.int32)
-            lens = self.download(d_len, (tracks, nmax), np.float64)
-            s_ref = self.download(d_s, (tracks, nmax + 1), np.float64)
-            total = self.download(d_tot, (tracks,), np.float64)
-            status = self.download(d_st, (bsz,), np.int32)
-        return export_result(tab, idx, lens, s_ref, total, status, ns, ms, tr, tj)
+            res = [dev.get(d) for d in (d_tab, d_idx, d_len, d_s, d_tot, d_st)]
+        return export_result(*res, ns, ms, tr, tj)
 
     # ---- friction maps (include/mcq.h "friction maps"; the reference's names on top of these: friction.py) ----------------------------------
     def friction_map(self, cells, mue, bin_side=None):
@@ -1290,11 +1287,10 @@ class Engine:
             res = (np.empty(shape), np.empty(shape, dtype=np.int32), np.empty(shape))
         else:
             with self.scope() as dev:
-                d_xy, d_mu = dev.up(pts), dev.new(count * 8)
-                d_i, d_d = dev.new(count * 4) if want_idx else None, dev.new(count * 8) if want_dist else None
+                d_xy, d_mu = dev.up(pts), dev.out(shape)
+                d_i, d_d = dev.out(shape, np.int32) if want_idx else None, dev.out(shape) if want_dist else None
                 self.friction_query_device(fmap, count, d_xy, d_mu, d_i, d_d)
-                res = (self.download(d_mu, shape, np.float64), self.download(d_i, shape, np.int32) if want_idx else None,
-                       self.download(d_d, shape, np.float64) if want_dist else None)
+                res = (dev.get(d_mu), dev.get(d_i) if want_idx else None, dev.get(d_d) if want_dist else None)
         out = (res[0],) + ((res[1],) if want_idx else ()) + ((res[2],) if want_dist else ())
         return out if len(out) > 1 else out[0]
 
@@ -1348,26 +1344,22 @@ class Engine:
             if jmax >= 1 and 8 * ((2 * n_gauss + 1) * (jmax + 2 * n_gauss + 7) + 384) > 65536:
                 raise ValueError("friction_grid_batch: a row of jmax %d at n_gauss %d does not fit into 64 KB of LDS" % (jmax, n_gauss))
         with self.scope() as dev:
-            up, new = dev.up, dev.new
+            up, out, get = dev.up, dev.out, dev.get
             d_ref, d_nv, d_n, d_wl = up(ref), up(nv), up(ns), up(wl)
-            d_no, d_cnt, d_mu = new(tracks * rows * jmax * 8), new(tracks * rows * 4), new(tracks * 4 * rows * jmax * 8)
-            d_ix = new(tracks * 4 * rows * jmax * 4) if want_idx else None
-            d_w = new(tracks * 4 * rows * 2 * 8) if fit else None
-            d_st = new(tracks * 4)
+            d_no, d_cnt, d_mu = out((tracks, rows, jmax)), out((tracks, rows), np.int32), out((tracks, 4, rows, jmax))
+            d_ix = out((tracks, 4, rows, jmax), np.int32) if want_idx else None
+            d_w = out((tracks, 4, rows, 2)) if fit else None
+            d_st = out(tracks, np.int32)
             self.friction_grid_device(fmap, tracks, nmax, d_n, d_ref, d_nv, w0, d_wl, wheelbase_front, wheelbase_rear, dn, jmax, d_no, d_cnt,
                                       d_mu, d_ix, d_w, d_st)
-            out = dict(n=self.download(d_no, (tracks, rows, jmax), np.float64), cnt=self.download(d_cnt, (tracks, rows), np.int32),
-                       mue=self.download(d_mu, (tracks, 4, rows, jmax), np.float64),
-                       w_mue=self.download(d_w, (tracks, 4, rows, 2), np.float64) if fit else None,
-                       idx=self.download(d_ix, (tracks, 4, rows, jmax), np.int32) if want_idx else None,
-                       status=self.download(d_st, (tracks,), np.int32), rows=ns + 1)
-            if gauss:
-                P = 2 * int(n_gauss) + 2
-                d_wg, d_cd, d_rk, d_sw = new(tracks * 4 * rows * max(P, 1) * 8), new(tracks * rows * 8), new(tracks * rows * 4), new(tracks * rows * 4)
+            res = dict(n=get(d_no), cnt=get(d_cnt), mue=get(d_mu), w_mue=get(d_w) if fit else None, idx=get(d_ix) if want_idx else None,
+                       status=get(d_st), rows=ns + 1)
+            if gauss:       # (n_gauss >= 1: the weights' rows are not empty)
+                d_wg, d_cd = out((tracks, 4, rows, 2 * n_gauss + 2)), out((tracks, rows))
+                d_rk, d_sw = out((tracks, rows), np.int32), out((tracks, rows), np.int32)
                 self.friction_gauss_device(tracks, nmax, jmax, d_no, d_cnt, d_mu, d_st, n_gauss, rcond, d_wg, d_cd, d_rk, d_sw)
-                out.update(w_gauss=self.download(d_wg, (tracks, 4, rows, P), np.float64), center_dist=self.download(d_cd, (tracks, rows), np.float64),
-                           rank=self.download(d_rk, (tracks, rows), np.int32), sweeps=self.download(d_sw, (tracks, rows), np.int32))
-            return out
+                res.update(w_gauss=get(d_wg), center_dist=get(d_cd), rank=get(d_rk), sweeps=get(d_sw))
+            return res
 
     def friction_gauss_device(self, tracks, nmax, jmax, d_n, d_cnt, d_mue, d_status, n_gauss, rcond, d_w_gauss, d_center_dist, d_rank=None,
                               d_sweeps=None):
@@ -1422,10 +1414,10 @@ class Engine:
             if qcnt.shape != (tracks, rows):
                 raise ValueError("friction_model_batch: qcnt must be [tracks, rows]")
         with self.scope() as dev:
-            d_out = dev.new(tracks * 4 * rows * qmax * 8)
+            d_out = dev.out((tracks, 4, rows, qmax))
             self.friction_model_device(tracks, rows - 1, qmax, dev.up(q), dev.up(qcnt), model, dev.up(w), d_out, n_gauss, centres,
                                        dev.up(center_dist), dev.up(n), dev.up(cnt), jmax)
-            return self.download(d_out, (tracks, 4, rows, qmax), np.float64)
+            return dev.get(d_out)
 
     # ---- friction map generation (include/mcq.h "friction map generation"; the reference's names on top of these: friction.py) -------------
     def contains_points_device(self, paths, vmax, d_v, d_verts, d_radius, count, d_xy, d_inside, d_status, d_contour=None, d_contour_count=None):
@@ -1449,17 +1441,17 @@ class Engine:
         pad = np.zeros((k, vmax, 2))
         for i, v in enumerate(verts):
             pad[i, :vs[i]] = v
-        rad = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, dtype=np.float64), (k,)))
+        rad = _per_variant(k, radius)[0]
         with self.scope() as dev:
-            d_in, d_st = dev.new(max(k * count, 1)), dev.new(k * 4)
-            d_c, d_cc = (dev.new(k * vmax * 32), dev.new(k * 4)) if want_contours else (None, None)
+            d_in, d_st = dev.out((k, count), np.uint8, floor=1), dev.out(k, np.int32)
+            d_c, d_cc = (dev.out((k, 2 * vmax, 2)), dev.out(k, np.int32)) if want_contours else (None, None)
             self.contains_points_device(k, vmax, dev.up(vs), dev.up(pad), dev.up(rad), count, dev.up(pts) if count else None, d_in if count else None,
                                         d_st, d_c, d_cc)
-            inside = self.download(d_in, (k, count), np.uint8).astype(bool) if count else np.zeros((k, 0), dtype=bool)
-            status = self.download(d_st, (k,), np.int32)
+            inside = dev.get(d_in).astype(bool) if count else np.zeros((k, 0), dtype=bool)
+            status = dev.get(d_st)
             if not want_contours:
                 return inside, status
-            cc, c = self.download(d_cc, (k,), np.int32), self.download(d_c, (k, 2 * vmax, 2), np.float64)
+            cc, c = dev.get(d_cc), dev.get(d_c)
         return inside, status, [c[i, :cc[i]].copy() for i in range(k)]
 
     def friction_gen_device(self, tracks, nmax, d_n, d_ref, cellwidth, d_inside_right, cmax, d_bound_r, d_bound_l, d_grid, d_count, d_cells, d_status):
@@ -1477,10 +1469,10 @@ class Engine:
         ns, ref = _pad_rows(reftracks, 4, nmin=3)
         tracks, nmax = ref.shape[:2]
         with self.scope() as dev:
-            d_br, d_bl, d_grid, d_st = dev.new(tracks * nmax * 16), dev.new(tracks * nmax * 16), dev.new(tracks * 48), dev.new(tracks * 4)
+            d_br, d_bl, d_grid, d_st = dev.out((tracks, nmax, 2)), dev.out((tracks, nmax, 2)), dev.out((tracks, 6)), dev.out(tracks, np.int32)
             self.friction_gen_device(tracks, nmax, dev.up(ns), dev.up(ref), 1.0, None, 0, d_br, d_bl, d_grid, None, None, d_st)
-            br, bl = self.download(d_br, (tracks, nmax, 2), np.float64), self.download(d_bl, (tracks, nmax, 2), np.float64)
-            status = self.download(d_st, (tracks,), np.int32) & ~FGEN_GRID      # (the grid of the 1 m cell asked for is not the caller's)
+            br, bl = dev.get(d_br), dev.get(d_bl)
+            status = dev.get(d_st) & ~FGEN_GRID      # (the grid of the 1 m cell asked for is not the caller's)
         return [br[t, :ns[t]].copy() for t in range(tracks)], [bl[t, :ns[t]].copy() for t in range(tracks)], status
 
     def friction_gen_batch(self, reftracks, cellwidth_m, inside_trackbound="right", cmax=None):
@@ -1496,18 +1488,16 @@ class Engine:
         tracks, nmax = ref.shape[:2]
         with self.scope() as dev:
             d_ref, d_n, d_side = dev.up(ref), dev.up(ns), dev.up(np.array([s == "right" for s in sides], dtype=np.int32))
-            d_br, d_bl, d_grid = dev.new(tracks * nmax * 16), dev.new(tracks * nmax * 16), dev.new(tracks * 48)
-            d_cnt, d_st = dev.new(tracks * 4), dev.new(tracks * 4)
+            d_br, d_bl, d_grid = dev.out((tracks, nmax, 2)), dev.out((tracks, nmax, 2)), dev.out((tracks, 6))
+            d_cnt, d_st = dev.out(tracks, np.int32), dev.out(tracks, np.int32)
             if cmax is None:
                 self.friction_gen_device(tracks, nmax, d_n, d_ref, cellwidth_m, d_side, 0, None, None, d_grid, d_cnt, None, d_st)
-                cmax = int(self.download(d_cnt, (tracks,), np.int32).max())
+                cmax = int(dev.get(d_cnt).max())
             cmax = int(cmax)
-            d_cells = dev.new(tracks * max(cmax, 1) * 16)
+            d_cells = dev.out((tracks, max(cmax, 1), 2))
             self.friction_gen_device(tracks, nmax, d_n, d_ref, cellwidth_m, d_side, cmax, d_br, d_bl, d_grid, d_cnt, d_cells, d_st)
-            counts, status = self.download(d_cnt, (tracks,), np.int32), self.download(d_st, (tracks,), np.int32)
-            cells = self.download(d_cells, (tracks, max(cmax, 1), 2), np.float64)
-            br, bl = self.download(d_br, (tracks, nmax, 2), np.float64), self.download(d_bl, (tracks, nmax, 2), np.float64)
-            grids = self.download(d_grid, (tracks, 6), np.float64)
+            counts, status, cells = dev.get(d_cnt), dev.get(d_st), dev.get(d_cells)
+            br, bl, grids = dev.get(d_br), dev.get(d_bl), dev.get(d_grid)
         return dict(cells=[cells[t, :min(int(counts[t]), cmax)].copy() for t in range(tracks)], counts=counts, grids=grids,
                     bound_right=[br[t, :ns[t]].copy() for t in range(tracks)], bound_left=[bl[t, :ns[t]].copy() for t in range(tracks)], status=status)
 
@@ -1534,7 +1524,8 @@ class Engine:
 
     # ---- device memory plumbing (mcq_device_alloc & co): numpy in, numpy out, raw device pointers as ints ----------------
     def scope(self):
-        """Context manager owning device allocations: up(array or None) / new(nbytes) give pointers it frees on exit, release(ptr) takes one out."""
+        """Context manager owning device allocations: up(array or None) / out(shape, dtype) / new(nbytes) give pointers it frees on exit, get(ptr)
+        fetches what up or out put there, release(ptr) takes one out."""
         return _Scope(self)
 
     def alloc(self, nbytes):
@@ -1628,31 +1619,19 @@ def les_scalings(A, check=True, closed=True):
     closed=False: `A` is the [4(N-1), 4(N-1)] matrix of calc_splines' OPEN system through N waypoints (mcq_les_scalings_open); returns [N]
     scalings, the inner joints' in entries 0..N-3 and ones in the last two (what solve_batch reads for a chain)."""
     global _LIB_FOR_HOST_HELPERS
-    if not closed:
-        if not (isinstance(A, np.ndarray) and A.dtype == np.float64 and A.ndim == 2 and A.shape[0] == A.shape[1] and A.shape[0] % 4 == 0
-                and A.shape[0] >= 8 and A.flags["C_CONTIGUOUS"]):
-            from .trajectory_planning_helpers import calc_splines as _cs
-            return _cs.scalings_from_open_les_matrix(A, check=check)
-        if _LIB_FOR_HOST_HELPERS is None:
-            _LIB_FOR_HOST_HELPERS = _DEFAULT_ENGINE.lib if _DEFAULT_ENGINE is not None else load_library()
-        n = A.shape[0] // 4 + 1
-        s = np.empty(n)
-        if _LIB_FOR_HOST_HELPERS.mcq_les_scalings_open(A.ctypes.data, n, s.ctypes.data, 1 if check else 0) != 0:
-            raise RuntimeError("Spline equation system matrix A does not have the structure of calc_splines' open-spline system (the MI355X "
-                               "engine derives everything from the spline scalings it encodes): " + _LIB_FOR_HOST_HELPERS.mcq_last_error().decode())
-        return s
     if not (isinstance(A, np.ndarray) and A.dtype == np.float64 and A.ndim == 2 and A.shape[0] == A.shape[1] and A.shape[0] % 4 == 0
-            and A.shape[0] >= 12 and A.flags["C_CONTIGUOUS"]):
+            and A.shape[0] >= (12 if closed else 8) and A.flags["C_CONTIGUOUS"]):
         from .trajectory_planning_helpers import calc_splines as _cs
-        return _cs.scalings_from_les_matrix(A, check=check)
+        return (_cs.scalings_from_les_matrix if closed else _cs.scalings_from_open_les_matrix)(A, check=check)
     if _LIB_FOR_HOST_HELPERS is None:
         _LIB_FOR_HOST_HELPERS = _DEFAULT_ENGINE.lib if _DEFAULT_ENGINE is not None else load_library()
-    n = A.shape[0] // 4
+    lib = _LIB_FOR_HOST_HELPERS
+    n = A.shape[0] // 4 + (0 if closed else 1)
     s = np.empty(n)
-    if _LIB_FOR_HOST_HELPERS.mcq_les_scalings(A.ctypes.data, n, s.ctypes.data, 1 if check else 0) != 0:
-        raise RuntimeError("Spline equation system matrix A does not have the structure of calc_splines' closed-spline "
-                           "system (the MI355X engine derives everything from the N spline scalings it encodes and "
-                           "cannot use an arbitrary matrix): " + _LIB_FOR_HOST_HELPERS.mcq_last_error().decode())
+    if (lib.mcq_les_scalings if closed else lib.mcq_les_scalings_open)(A.ctypes.data, n, s.ctypes.data, 1 if check else 0) != 0:
+        words = ("closed", "N spline scalings it encodes and cannot use an arbitrary matrix") if closed else ("open", "spline scalings it encodes")
+        raise RuntimeError("Spline equation system matrix A does not have the structure of calc_splines' %s-spline system (the MI355X engine derives "
+                           "everything from the %s): " % words + lib.mcq_last_error().decode())
     return s
 
 

@@ -1,9 +1,9 @@
 """The shared bodies of tests/test_emu_helpers.py (SIMT interpreter) and tests/test_gpu_helpers.py (MI355X): the plumbing behind the helper
-entries -- Engine.scope and _pad_rows in engine.py, the ABI table load_library declares, the handle's four grow-only Scratch buffers in
+entries -- Engine.scope and _pad_rows in engine.py, the ABI table load_library declares, the handle's seven grow-only Scratch buffers in
 csrc/mcq_api.hip.  No reference and no tolerance: pointers are counted, results are compared bit for bit with those of a fresh engine.
 
 The shapes are the smallest legal ones (one or two tracks of 8 to 12 waypoints, a 3-row ggv, a 2-row ax_max_machines); the launch that makes a
-scratch grow has 3 tracks of 33 to 40."""
+scratch grow has 3 tracks of 33 to 40.  The friction map has 36 cells, the generated one about sixty; the Gaussian fit has one bump a side."""
 import collections
 import contextlib
 import ctypes
@@ -55,6 +55,15 @@ def race_of(refs):
     return out
 
 
+def traj_of(race):
+    """race_of's rows as trajectory_batch's padded table [rows, mmax, 7] = s, x, y, psi, kappa, vx, ax (NaN behind a row's m)."""
+    tj = np.full(race["xy"].shape[:2] + (engine.TRAJ_COLS,), np.nan)
+    for b, m in enumerate(race["m"]):
+        tj[b, :m, 0] = np.concatenate(([0.0], np.cumsum(race["el_lengths"][b, :m - 1])))
+        tj[b, :m, 1:3], tj[b, :m, 3], tj[b, :m, 4], tj[b, :m, 5], tj[b, :m, 6] = race["xy"][b, :m], race["psi"][b, :m], race["kappa"][b, :m], 20.0, 0.0
+    return tj
+
+
 def vel_tables(bsz):
     return np.tile(GGV, (bsz, 1, 1)), np.tile(AXM, (bsz, 1, 1))
 
@@ -88,8 +97,9 @@ def ledger(eng):
 
 def batch_calls(eng):
     """(name, call, failing call) per method rewritten on Engine.scope, at its smallest shapes.  The failing calls are refused on the host
-    behind the uploads (MCQ_E_ARG from the entry's argument check); prep_batch and normals_crossing_batch have no argument an entry refuses:
-    there the first download raises in the host's place.  Nothing faults on the device."""
+    behind the uploads (MCQ_E_ARG from the entry's argument check); prep_batch, normals_crossing_batch, friction_query_batch,
+    contains_points_batch and track_boundaries_batch have no argument an entry refuses: there the first download raises in the host's place.
+    Nothing faults on the device.  The friction map made here is the engine's to free (Engine.close)."""
     refs, nvs = rings((8, 11))
     tracks, tcks = refs, [tck_of(0), tck_of(1)]
     race = race_of(refs)
@@ -99,6 +109,11 @@ def batch_calls(eng):
     chain = open_ref.seeded_chain(9, 1)
     u_ref, u_nv = [np.stack(a) for a in rings((12, 12))]
     ends = [None, dict(psi_s=chain[3], psi_e=chain[4])]
+    traj = traj_of(race)
+    gx, gy = np.meshgrid(np.linspace(-36.0, 36.0, 6), np.linspace(-24.0, 24.0, 6))
+    fmap = eng.friction_map(np.column_stack((gx.ravel(), gy.ravel())), 0.8 + 0.01 * np.arange(36))
+    fq = np.linspace(-1.0, 1.0, 3) * np.ones((2, 12, 1))
+    fw = np.stack((np.full((2, 4, 12), 0.01), np.full((2, 4, 12), 0.9)), axis=3)
 
     def no_download(call):
         def failing():
@@ -113,6 +128,10 @@ def batch_calls(eng):
     vel = lambda **kw: eng.vel_profile_batch(kap, el, ggv, axm, DRAG, MASS, VMAX, n_of_track=race["m"], **kw)      # noqa: E731
     prep = lambda: eng.prep_batch(refs)      # noqa: E731
     cross = lambda: eng.normals_crossing_batch(refs, nvs)      # noqa: E731
+    query = lambda: eng.friction_query_batch(fmap, refs[0][:, :2], want_idx=True, want_dist=True)      # noqa: E731
+    grid = lambda dn=1.0, **kw: eng.friction_grid_batch(fmap, refs, nvs, 2.0, 1.5, 1.4, dn, jmax=5, **kw)      # noqa: E731
+    inside = lambda: eng.contains_points_batch([r[:, :2] for r in refs], refs[1][:5, :2], radius=0.5, want_contours=True)      # noqa: E731
+    bounds = lambda: eng.track_boundaries_batch(refs)      # noqa: E731
     return [
         ("prep_batch", prep, no_download(prep)),
         ("vel_profile_batch", vel, lambda: vel(dyn_model_exp=0.0)),
@@ -130,6 +149,15 @@ def batch_calls(eng):
         ("bound_dists_batch", lambda: eng.bound_dists_batch(refs, nvs, race, 4.7, 2.0), lambda: eng.bound_dists_batch(refs, nvs, race, 4.7, 2.0, stepsize_bound=0.0)),
         ("solve_uniform_f32", lambda: eng.solve_uniform_f32(u_ref, u_nv, None, 0.5, 2.0),
          lambda: eng.solve_uniform_f32(u_ref, None, None, 0.5, 2.0, objective=engine.OBJ_SHORTEST_PATH)),
+        ("export_batch", lambda: eng.export_batch(refs, nvs, alphas, traj), lambda: eng.export_batch(refs, nvs, alphas, traj[:, :1])),
+        ("spline_fit_batch", lambda: eng.spline_fit_batch(tracks, stepsize_prep=8.0, points=True), lambda: eng.spline_fit_batch(tracks, s=-1.0, stepsize_prep=8.0)),
+        ("friction_query_batch", query, no_download(query)),
+        ("friction_grid_batch", lambda: grid(want_idx=True), lambda: grid(dn=0.0)),
+        ("friction_grid_batch, gauss", lambda: grid(fit="gauss", n_gauss=1), lambda: grid(fit="gauss", n_gauss=1, rcond=float("nan"))),
+        ("friction_model_batch", lambda: eng.friction_model_batch(fq, fw), lambda: eng.friction_model_batch(fq, fw, model=7)),
+        ("contains_points_batch", inside, no_download(inside)),
+        ("track_boundaries_batch", bounds, no_download(bounds)),
+        ("friction_gen_batch", lambda: eng.friction_gen_batch(refs, 4.0), lambda: eng.friction_gen_batch(refs, 0.0)),
         ("parallel.solve_sharded", lambda: parallel.solve_sharded([dict(reftrack=u_ref[0], normvec=u_nv[0], scaling=None, kappa_bound=0.5, w_veh=2.0)], eng),
          None),
     ]
