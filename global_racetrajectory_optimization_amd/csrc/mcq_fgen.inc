@@ -14,8 +14,6 @@
 #define FGEN_EPS 1e-14              /* agg's vertex_dist_epsilon */
 #define FGEN_DEN_EPS 1e-30          /* agg's intersection_epsilon */
 
-__device__ __forceinline__ bool fgen_finite(double a) { return fabs(a) < (double)INFINITY; }      // (false for a NaN)
-
 __device__ __forceinline__ double fgen_dist(double ax, double ay, double bx, double by)
 {
     const double dx = bx - ax, dy = by - ay;
@@ -128,11 +126,11 @@ __global__ void __launch_bounds__(MCQ_NT) mcq_fgen_contour_kernel(McqContour C)
     const bool range = v >= 0 && v <= C.vmax;
     if (range) {
         bool bad = false;
-        for (int i = tid; i < v; i += MCQ_NT) bad = bad || !(fgen_finite(V[2 * (size_t)i]) && fgen_finite(V[2 * (size_t)i + 1]));
+        for (int i = tid; i < v; i += MCQ_NT) bad = bad || !(finite_d(V[2 * (size_t)i]) && finite_d(V[2 * (size_t)i + 1]));
         if (bad) s_bad = 1;
     }
     __syncthreads();
-    const bool nonfinite = range && (s_bad != 0 || !fgen_finite(radius));
+    const bool nonfinite = range && (s_bad != 0 || !finite_d(radius));
     if (C.status && tid == 0) C.status[p] = !range ? MCQ_FGEN_FEW : (nonfinite ? MCQ_FGEN_NONFINITE : 0);
     if (!range || nonfinite || v < 3) {
         if (tid == 0) C.ccount[p] = 0;
@@ -233,7 +231,7 @@ __global__ void __launch_bounds__(MCQ_NT) mcq_fgen_points_kernel(McqContour C, i
     const bool has = q < (size_t)count;
     const double tx = has ? xy[2 * q] : 0.0, ty = has ? xy[2 * q + 1] : 0.0;
     const unsigned par = fgen_parity<1>(C.cont + (size_t)p * C.vmax * 4, C.ccount[p], tx, &ty, s_v);
-    if (has) inside_out[(size_t)p * count + q] = (par != 0 && fgen_finite(tx) && fgen_finite(ty)) ? 1 : 0;
+    if (has) inside_out[(size_t)p * count + q] = (par != 0 && finite_d(tx) && finite_d(ty)) ? 1 : 0;
 }
 
 // A workgroup per track: calc_trackboundaries, the polygons, the grid.  rec[t] = nx, ny -- zero for a refused track.
@@ -257,7 +255,7 @@ __global__ void __launch_bounds__(MCQ_NT) mcq_fgen_bounds_kernel(McqFgen G)
         bool bad = false;
         for (int i = tid; i < n; i += MCQ_NT) {
             const double x = ref[4 * (size_t)i], y = ref[4 * (size_t)i + 1], wr = ref[4 * (size_t)i + 2], wl = ref[4 * (size_t)i + 3];
-            bad = bad || !(fgen_finite(x) && fgen_finite(y) && fgen_finite(wr) && fgen_finite(wl));
+            bad = bad || !(finite_d(x) && finite_d(y) && finite_d(wr) && finite_d(wl));
             minx = fmin(minx, x); maxx = fmax(maxx, x); miny = fmin(miny, y); maxy = fmax(maxy, y); maxr = fmax(maxr, wr); maxl = fmax(maxl, wl);
         }
         if (bad) s_bad = 1;
@@ -292,7 +290,7 @@ __global__ void __launch_bounds__(MCQ_NT) mcq_fgen_bounds_kernel(McqFgen G)
             const double nx = gy * nf, ny = -gx * nf;
             const double x = ref[4 * (size_t)i], y = ref[4 * (size_t)i + 1], wr = ref[4 * (size_t)i + 2], wl = ref[4 * (size_t)i + 3];
             const double rx = x + nx * wr, ry = y + ny * wr, lx = x - nx * wl, ly = y - ny * wl;
-            bad = bad || !(fgen_finite(rx) && fgen_finite(ry) && fgen_finite(lx) && fgen_finite(ly));
+            bad = bad || !(finite_d(rx) && finite_d(ry) && finite_d(lx) && finite_d(ly));
             if (br) { br[2 * (size_t)i] = rx; br[2 * (size_t)i + 1] = ry; }
             if (bl) { bl[2 * (size_t)i] = lx; bl[2 * (size_t)i + 1] = ly; }
             if (!closed) {          // one polygon: the left boundary, then the right one backwards

@@ -722,43 +722,29 @@ __global__ void __launch_bounds__(MCQ_NT) mcq_spline_fit_kernel(McqFit P)
     if (!bad) {
         int b = 0;
         for (int i = tid; i < n; i += MCQ_NT)
-            if (!bd_finite(trk[4 * (size_t)i]) || !bd_finite(trk[4 * (size_t)i + 1])) b = 1;
+            if (!finite_d(trk[4 * (size_t)i]) || !finite_d(trk[4 * (size_t)i + 1])) b = 1;
         if (b) s_bad = 1;
         __syncthreads();
         bad = s_bad != 0;
     }
     if (!bad && P.step > 0.0) {
-        // interp_track's rule (mcq_bound_points_kernel's statements): the closed raw line's running sum, numpy.linspace, numpy.interp
+        // interp_track's rule: the closed raw line's running sum, numpy.linspace, numpy.interp -- mcq_bound_points_kernel's rule, written here
+        // a second time because this file is compiled without contraction and that kernel fuses slope * (x - xp) + fp: one function would
+        // round one of the two differently from what it returns today
         if (tid == 0) cum[0] = 0.0;
         int b = 0;
-        for (int base = 0; base < n; base += MCQ_NT) {
-            const int i = base + tid;
-            if (i < n) {
-                const int j = i + 1 < n ? i + 1 : 0;
-                const double dx = trk[4 * (size_t)j] - trk[4 * (size_t)i], dy = trk[4 * (size_t)j + 1] - trk[4 * (size_t)i + 1];
-                const double e = sqrt(dx * dx + dy * dy);
-                if (!(e > 0.0)) b = 1;
-                s_el[tid] = e;
-            }
-            __syncthreads();
-            if (tid == 0) {
-                double c = s_carry;
-                const int cnt = n - base < MCQ_NT ? n - base : MCQ_NT;
-                for (int k = 0; k < cnt; ++k) {
-                    c += s_el[k];
-                    s_el[k] = c;
-                }
-                s_carry = c;
-            }
-            __syncthreads();
-            if (i < n) cum[(size_t)i + 1] = s_el[tid];
-            __syncthreads();
-        }
+        running_sum<MCQ_NT>(n, s_el, s_carry, cum + 1, [&](int i) {
+            const int j = i + 1 < n ? i + 1 : 0;
+            const double dx = trk[4 * (size_t)j] - trk[4 * (size_t)i], dy = trk[4 * (size_t)j + 1] - trk[4 * (size_t)i + 1];
+            const double e = sqrt(dx * dx + dy * dy);
+            if (!(e > 0.0)) b = 1;
+            return e;
+        });
         if (b) s_bad = 1;
         __syncthreads();
         const double total = s_carry;
         const double cnt = ceil(total / P.step);
-        if (s_bad || !bd_finite(cnt) || !(cnt >= 1.0)) bad = true;
+        if (s_bad || !finite_d(cnt) || !(cnt >= 1.0)) bad = true;
         else if (cnt + 1.0 > (double)P.mimax) {
             bad = true;
             need = cnt < 2147483646.0 ? (int)cnt + 1 : 0;
@@ -808,28 +794,12 @@ __global__ void __launch_bounds__(MCQ_NT) mcq_spline_fit_kernel(McqFit P)
             u[0] = 0.0;
         }
         __syncthreads();
-        for (int base = 0; base < mi - 1; base += MCQ_NT) {
-            const int i = base + tid;
-            if (i < mi - 1) {
-                const double dx = pts[2 * (size_t)(i + 1)] - pts[2 * (size_t)i], dy = pts[2 * (size_t)(i + 1) + 1] - pts[2 * (size_t)i + 1];
-                s_el[tid] = sqrt(dx * dx + dy * dy);
-            }
-            __syncthreads();
-            if (tid == 0) {
-                double c = s_carry;
-                const int cnt = mi - 1 - base < MCQ_NT ? mi - 1 - base : MCQ_NT;
-                for (int k = 0; k < cnt; ++k) {
-                    c += s_el[k];
-                    s_el[k] = c;
-                }
-                s_carry = c;
-            }
-            __syncthreads();
-            if (i < mi - 1) u[(size_t)i + 1] = s_el[tid];
-            __syncthreads();
-        }
+        running_sum<MCQ_NT>(mi - 1, s_el, s_carry, u + 1, [&](int i) {
+            const double dx = pts[2 * (size_t)(i + 1)] - pts[2 * (size_t)i], dy = pts[2 * (size_t)(i + 1) + 1] - pts[2 * (size_t)i + 1];
+            return sqrt(dx * dx + dy * dy);
+        });
         const double last = s_carry;
-        if (!(last > 0.0) || !bd_finite(last)) bad = true;          // (uniform)
+        if (!(last > 0.0) || !finite_d(last)) bad = true;          // (uniform)
         if (!bad) {
             for (int i = tid; i < mi; i += MCQ_NT) u[i] = i == mi - 1 ? 1.0 : u[i] / last;
             __syncthreads();

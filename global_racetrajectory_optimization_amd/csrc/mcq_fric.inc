@@ -16,8 +16,6 @@
 //      that bound (rounding is monotonic), so with the strict comparison none of them can even tie.  Among cells at exactly equal computed squared
 //      distance the lowest original index wins. ----
 
-__device__ __forceinline__ bool fric_finite(double a) { return fabs(a) < (double)INFINITY; }      // (false for a NaN)
-
 // the lower edge of bin k along an axis that starts at o: the same two roundings as the host's (mcq_fmap_create)
 __device__ __forceinline__ double fric_edge(double o, double side, int k) { return o + (double)k * side; }
 
@@ -45,7 +43,7 @@ __device__ __forceinline__ void fric_span(const McqFmap& F, int iy, int ix0, int
 // idx = the nearest cell's original index and d2 its squared distance; -1 and NaN for a query that is not finite
 __device__ __forceinline__ void fric_nearest(const McqFmap& F, double qx, double qy, int& idx, double& d2)
 {
-    if (!(fric_finite(qx) && fric_finite(qy))) { idx = -1; d2 = NAN; return; }
+    if (!(finite_d(qx) && finite_d(qy))) { idx = -1; d2 = NAN; return; }
     const int nbx = F.nbx, nby = F.nby;
     const int bx = fric_bin(qx, F.x0, F.side, nbx), by = fric_bin(qy, F.y0, F.side, nby);
     double best = INFINITY;
@@ -115,12 +113,12 @@ __global__ void __launch_bounds__(MCQ_NT) mcq_friction_grid_kernel(McqFricGrid G
     const double* nv = G.nv + (size_t)t * G.nmax * 2;
     if (tid == 0) { s_bad = 0; s_over = 0; }
     __syncthreads();
-    bool bad = n < 1 || n > G.nmax || !(fric_finite(width) && fric_finite(G.wbf) && fric_finite(G.wbr));
+    bool bad = n < 1 || n > G.nmax || !(finite_d(width) && finite_d(G.wbf) && finite_d(G.wbr));
     if (!bad) {
         bool any_bad = false, any_over = false;
         for (int r = tid; r < n; r += MCQ_NT) {
             const double x = ref[4 * r], y = ref[4 * r + 1], wr = ref[4 * r + 2], wl = ref[4 * r + 3], nx = nv[2 * r], ny = nv[2 * r + 1];
-            if (!(fric_finite(x) && fric_finite(y) && fric_finite(wr) && fric_finite(wl) && fric_finite(nx) && fric_finite(ny))) any_bad = true;
+            if (!(finite_d(x) && finite_d(y) && finite_d(wr) && finite_d(wl) && finite_d(nx) && finite_d(ny))) any_bad = true;
             else if (fric_steps(wr, hw, dn) + fric_steps(wl, hw, dn) + 1 > G.jmax) any_over = true;
         }
         if (any_bad) s_bad = 1;

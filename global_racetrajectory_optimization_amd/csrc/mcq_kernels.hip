@@ -2278,6 +2278,107 @@ __global__ void __launch_bounds__(MCQ_NT, 2) mcq_solve_kernel(McqBatch B)
 }
 
 // =====================================================================================================================
+// Steps the helper kernels below share (and mcq_fit.inc, mcq_fric.inc, mcq_fgen.inc): each rule is stated here, once
+// =====================================================================================================================
+__device__ __forceinline__ bool finite_d(double a) { return fabs(a) < (double)INFINITY; }      // (false for a NaN)
+
+// ---- one segment of a unit-scaling spline, x(t) = ax + bx t + cx t^2 + dx t^3 on [0, 1] (y alike): from the points (the a-coefficients) and
+//      the c-coefficients at its ends s and sp ----
+struct SplSeg { double ax, ay, bx, by, cx, cy, dx, dy; };
+__device__ __forceinline__ SplSeg seg_of(const gdouble* PX, const gdouble* PY, const gdouble* CX, const gdouble* CY, int s, int sp)
+{
+    SplSeg g;
+    g.ax = PX[s]; g.ay = PY[s]; g.cx = CX[s]; g.cy = CY[s];
+    g.bx = (PX[sp] - g.ax) - (2.0 * g.cx + CX[sp]) / 3.0; g.by = (PY[sp] - g.ay) - (2.0 * g.cy + CY[sp]) / 3.0;
+    g.dx = (CX[sp] - g.cx) / 3.0; g.dy = (CY[sp] - g.cy) / 3.0;
+    return g;
+}
+__device__ __forceinline__ void seg_pos(const SplSeg& g, double t, double& x, double& y)
+{
+    x = g.ax + t * (g.bx + t * (g.cx + t * g.dx));
+    y = g.ay + t * (g.by + t * (g.cy + t * g.dy));
+}
+// 15 points, the sum of the 14 chords (tph.calc_spline_lengths; the powers of t written out as there, not Horner's form)
+__device__ __forceinline__ double seg_length(const SplSeg& g)
+{
+    double len = 0.0, x0 = g.ax, y0 = g.ay;
+    for (int k = 1; k < 15; ++k) {
+        const double t = (double)k / 14.0;
+        const double x1 = g.ax + g.bx * t + g.cx * t * t + g.dx * t * t * t;
+        const double y1 = g.ay + g.by * t + g.cy * t * t + g.dy * t * t * t;
+        len += hypot(x1 - x0, y1 - y0);
+        x0 = x1;
+        y0 = y1;
+    }
+    return len;
+}
+// station j of a raceline at t of its segment: position, heading and curvature from the derivatives, analytically (tph.calc_head_curv_an)
+__device__ __forceinline__ void seg_station(const SplSeg& g, double t, int j, gdouble* xy, gdouble* psi, gdouble* kap)
+{
+    const double pi = 3.14159265358979323846;
+    if (xy) {
+        double x, y;
+        seg_pos(g, t, x, y);
+        xy[2 * j] = x;
+        xy[2 * j + 1] = y;
+    }
+    const double xd = g.bx + 2.0 * g.cx * t + 3.0 * g.dx * t * t, yd = g.by + 2.0 * g.cy * t + 3.0 * g.dy * t * t;
+    const double xdd = 2.0 * g.cx + 6.0 * g.dx * t, ydd = 2.0 * g.cy + 6.0 * g.dy * t;
+    if (psi) {                                               // heading, 0 = north, wrapped to [-pi, pi) (tph.normalize_psi)
+        double a = atan2(yd, xd) - 0.5 * pi;
+        if (a >= pi) a -= 2.0 * pi;
+        else if (a < -pi) a += 2.0 * pi;
+        psi[j] = a;
+    }
+    const double v2 = xd * xd + yd * yd;
+    kap[j] = (xd * ydd - yd * xdd) / (v2 * sqrt(v2));
+}
+
+// ---- the segment of arc length q among ns segments with the lengths LEN and their running sum CUM: numpy.searchsorted(CUM, q, side='right'),
+//      clamped to the last segment; t: the local parameter ----
+__device__ __forceinline__ int seg_search(const gdouble* CUM, const gdouble* LEN, int ns, double q, double& t)
+{
+    int lo = 0, hi = ns;                                     // first index with CUM[idx] > q
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (CUM[mid] > q) hi = mid; else lo = mid + 1;
+    }
+    const int s = lo < ns - 1 ? lo : ns - 1;
+    const double start = s > 0 ? CUM[s - 1] : 0.0;
+    t = (q - start) / LEN[s];
+    return s;
+}
+
+// ---- running sum in the summation order of numpy.cumsum: out[i] = el(0) + .. + el(i), i < n, in chunks of CH through LDS (sbuf: CH doubles),
+//      thread 0 adding sequentially from `carry` on -- LDS too, zeroed by the caller's thread 0, the total afterwards.  All threads of the
+//      workgroup call, after a barrier behind whatever el() reads; the last barrier stands behind the last store. ----
+template <int CH, typename EL>
+__device__ __forceinline__ void running_sum(int n, double* sbuf, double& carry, gdouble* out, EL el)
+{
+    const int tid = threadIdx.x;
+    for (int c0 = 0; c0 < n; c0 += CH) {
+        const int cn = n - c0 < CH ? n - c0 : CH;
+        for (int q = tid; q < CH; q += MCQ_NT)
+            if (c0 + q < n) sbuf[q] = el(c0 + q);
+        __syncthreads();
+        if (tid == 0) {
+            double acc = carry;
+            for (int q = 0; q < cn; ++q) { acc += sbuf[q]; sbuf[q] = acc; }
+            carry = acc;
+        }
+        __syncthreads();
+        for (int q = tid; q < CH; q += MCQ_NT)
+            if (c0 + q < n) out[(size_t)c0 + q] = sbuf[q];
+        __syncthreads();
+    }
+}
+
+// (A function rounds as the place where it is WRITTEN does: the functions above contract products into sums, as every kernel that calls them
+//  did.  What the kernels behind `#pragma clang fp contract(off)` further down share with a kernel in front of it -- the chords of a polyline,
+//  the numpy.interp sampling of mcq_bound_points_kernel and mcq_spline_fit_kernel -- is therefore not here: the one fuses
+//  slope * (x - xp) + fp, the other must not, and each keeps its statements.  running_sum's element is the caller's lambda, rounded as the caller.)
+
+// =====================================================================================================================
 // K4: IQP glue -- re-linearisation on the device
 // =====================================================================================================================
 // Closed cubic spline with unit scalings through n points: the c-coefficients solve  circ(1, 4, 1) c = rhs,
@@ -2335,18 +2436,36 @@ __device__ void relin_spline_rhs(const gdouble* PX, const gdouble* PY, int n, gd
     }
 }
 
-// Front half of the glue, shared by mcq_relinearise_kernel and mcq_raceline_kernel: raceline p + a n (and the shifted
+// Lengths of the ns segments of the unit-scaling spline through n points (a ring: ns = n; a chain: ns = n - 1, where no index wraps) and their
+// running sum, 2048 at a time.  Returns no_interp_points of tph.interp_splines at `stepsize` -- a ceil() of the sum's last entry, `total` -- or -1.
+// lds: RELIN_LDS doubles of the caller's LDS (the glue kernels bring their own 16 KB; mcq_iqp_rounds_kernel lends the solver's array).
+#define RELIN_LDS 2050
+__device__ __forceinline__ int spline_lengths(const gdouble* PX, const gdouble* PY, const gdouble* CX, const gdouble* CY, int ns, int n, gdouble* LEN,
+                                              gdouble* CUM, double stepsize, double& total, double* lds)
+{
+    double& s_carry = lds[2048];
+    int& s_cnt = *(int*)(lds + 2049);
+    const int tid = threadIdx.x;
+    for (int i = tid; i < ns; i += MCQ_NT) LEN[i] = seg_length(seg_of(PX, PY, CX, CY, i, cyc1(i + 1, n)));
+    if (tid == 0) s_carry = 0.0;
+    __syncthreads();
+    running_sum<2048>(ns, lds, s_carry, CUM, [LEN](int i) { return LEN[i]; });
+    total = s_carry;
+    if (tid == 0) {
+        const double cnt = ceil(total / stepsize) + 1.0;
+        s_cnt = (cnt >= 2.0 && cnt <= 2.0e9) ? (int)cnt : -1;
+    }
+    __syncthreads();
+    return s_cnt;
+}
+
+// Front half of the glue, shared by mcq_relinearise_kernel and the racelines' ring body: raceline p + a n (and the shifted
 // widths), closed unit-scaling spline through it, spline lengths and their running sum, point count of the re-sampled ring.
 // vec slots: 0/1 raceline points (a-coefficients), 2/3 rhs, 4/5 c-coefficients, 6 lengths, 7 running sum, 8/9 widths.
 // Returns the number of points kept (tph.interp_splines, incl_last_point = False) or -1; `total` = length of the raceline.
-// lds: RELIN_LDS doubles of the caller's LDS (the glue kernels bring their own 16 KB; mcq_iqp_rounds_kernel lends the solver's array).
-#define RELIN_LDS 2050
 __device__ __forceinline__ int relin_front(const gdouble* ref, const gdouble* nv, const gdouble* al, int n, double alpha_scale,
                                            double stepsize, gdouble* vec, size_t nm, double& total, double* lds)
 {
-    double* sbuf = lds;
-    double& s_carry = lds[2048];
-    int& s_m = *(int*)(lds + 2049);
     const int tid = threadIdx.x;
     gdouble* PX = vec + 0 * nm;   gdouble* PY = vec + 1 * nm;    // raceline points (a-coefficients)
     gdouble* RX = vec + 2 * nm;   gdouble* RY = vec + 3 * nm;    // rhs, later the new points
@@ -2367,50 +2486,8 @@ __device__ __forceinline__ int relin_front(const gdouble* ref, const gdouble* nv
     __syncthreads();
     relin_spline_c(RX, RY, n, CX, CY);
     __syncthreads();
-
-    // ---- spline lengths: 15 points per segment, sum of the 14 chords (tph.calc_spline_lengths) --------------------------
-    for (int i = tid; i < n; i += MCQ_NT) {
-        const int ip = i + 1 == n ? 0 : i + 1;
-        const double ax = PX[i], ay = PY[i], cx = CX[i], cy = CY[i];
-        const double dlx = PX[ip] - ax, dly = PY[ip] - ay;
-        const double bx = dlx - (2.0 * cx + CX[ip]) / 3.0, by = dly - (2.0 * cy + CY[ip]) / 3.0;
-        const double dx = (CX[ip] - cx) / 3.0, dy = (CY[ip] - cy) / 3.0;
-        double len = 0.0, x0 = ax, y0 = ay;
-        for (int k = 1; k < 15; ++k) {
-            const double t = (double)k / 14.0;
-            const double x1 = ax + bx * t + cx * t * t + dx * t * t * t;
-            const double y1 = ay + by * t + cy * t * t + dy * t * t * t;
-            len += hypot(x1 - x0, y1 - y0);
-            x0 = x1;
-            y0 = y1;
-        }
-        LEN[i] = len;
-    }
-    __syncthreads();
-    // ---- running sum, in the summation order of numpy.cumsum (the point count below is a ceil() of its last entry):
-    //      2048-entry chunks through LDS, one thread adds sequentially ---------------------------------------------------
-    if (tid == 0) s_carry = 0.0;
-    for (int c0 = 0; c0 < n; c0 += 2048) {
-        const int cn = n - c0 < 2048 ? n - c0 : 2048;
-        __syncthreads();
-        for (int q = tid; q < cn; q += MCQ_NT) sbuf[q] = LEN[c0 + q];
-        __syncthreads();
-        if (tid == 0) {
-            double acc = s_carry;
-            for (int q = 0; q < cn; ++q) { acc += sbuf[q]; sbuf[q] = acc; }
-            s_carry = acc;
-        }
-        __syncthreads();
-        for (int q = tid; q < cn; q += MCQ_NT) CUM[c0 + q] = sbuf[q];
-    }
-    __syncthreads();
-    total = s_carry;
-    if (tid == 0) {
-        const double cnt = ceil(total / stepsize) + 1.0;         // no_interp_points of tph.interp_splines
-        s_m = (cnt >= 2.0 && cnt <= 2.0e9) ? (int)cnt - 1 : -1;  // points kept (incl_last_point = False)
-    }
-    __syncthreads();
-    return s_m;
+    const int cnt = spline_lengths(PX, PY, CX, CY, n, n, LEN, CUM, stepsize, total, lds);
+    return cnt < 0 ? -1 : cnt - 1;
 }
 
 // The glue of one track, by its workgroup: the body of mcq_relinearise_kernel (and of every round of mcq_iqp_rounds_kernel).  IO: the ring
@@ -2455,20 +2532,11 @@ __device__ __forceinline__ void relin_body(const McqRelin& R, const McqRelinIO& 
     const double step = total / (double)m;
     for (int j = tid; j < m; j += MCQ_NT) {
         const double q = (double)j * step;
-        int lo = 0, hi = n;                                      // first index with CUM[idx] > q
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (CUM[mid] > q) hi = mid; else lo = mid + 1;
-        }
-        const int s = lo < n - 1 ? lo : n - 1;
-        const int sp = s + 1 == n ? 0 : s + 1;
-        const double start = s > 0 ? CUM[s - 1] : 0.0;
-        const double t = (q - start) / LEN[s];
-        const double ax = PX[s], ay = PY[s], cx = CX[s], cy = CY[s];
-        const double bx = (PX[sp] - ax) - (2.0 * cx + CX[sp]) / 3.0, by = (PY[sp] - ay) - (2.0 * cy + CY[sp]) / 3.0;
-        const double dx = (CX[sp] - cx) / 3.0, dy = (CY[sp] - cy) / 3.0;
-        QX[j] = ax + t * (bx + t * (cx + t * dx));
-        QY[j] = ay + t * (by + t * (cy + t * dy));
+        double t, x, y;
+        const int s = seg_search(CUM, LEN, n, q, t), sp = cyc1(s + 1, n);
+        seg_pos(seg_of(PX, PY, CX, CY, s, sp), t, x, y);
+        QX[j] = x;
+        QY[j] = y;
         refo[4 * j + 2] = WR[s] + (WR[sp] - WR[s]) * t;
         refo[4 * j + 3] = WL[s] + (WL[sp] - WL[s]) * t;
         if (R.state_out) {      // working set of the pass just solved, carried to the new ring: the nearer end of the segment
@@ -2487,12 +2555,10 @@ __device__ __forceinline__ void relin_body(const McqRelin& R, const McqRelinIO& 
     relin_spline_c(PX, PY, m, CX, CY);
     __syncthreads();
     for (int j = tid; j < m; j += MCQ_NT) {
-        const int jp = j + 1 == m ? 0 : j + 1;
-        const double bx = (QX[jp] - QX[j]) - (2.0 * CX[j] + CX[jp]) / 3.0;
-        const double by = (QY[jp] - QY[j]) - (2.0 * CY[j] + CY[jp]) / 3.0;
-        const double nrm = sqrt(by * by + bx * bx);
-        nvo[2 * j] = by / nrm;
-        nvo[2 * j + 1] = -bx / nrm;
+        const SplSeg g = seg_of(QX, QY, CX, CY, j, cyc1(j + 1, m));
+        const double nrm = sqrt(g.by * g.by + g.bx * g.bx);
+        nvo[2 * j] = g.by / nrm;
+        nvo[2 * j + 1] = -g.bx / nrm;
     }
     if (tid == 0) { *status = MCQ_OK; *n_out = m; }
 }
@@ -2860,75 +2926,8 @@ __global__ void __launch_bounds__(64) mcq_vel_profile_open_locgg_kernel(McqVelFo
 // ---- what main_globaltraj.py does with alpha before the velocity profile [REF main_globaltraj.py:371-387]: tph.create_raceline
 //      (raceline p + alpha n, closed unit-scaling spline, re-sampling at ~stepsize_interp_after_opt) followed by
 //      tph.calc_head_curv_an (heading and curvature from the spline's derivatives, analytically) -- one workgroup per track,
-//      outputs strided by mmax: exactly what mcq_vel_profile_kernel consumes (kappa, el_lengths). ----
-__global__ void __launch_bounds__(MCQ_NT) mcq_raceline_kernel(McqRace Q)
-{
-    const int tid = threadIdx.x, pb = blockIdx.x;
-    const size_t nm = (size_t)Q.nmax, mm = (size_t)Q.mmax;
-    const int n = Q.n_in ? Q.n_in[pb] : Q.nmax;
-    const gdouble* ref = (const gdouble*)(Q.ref + (size_t)pb * nm * 4);
-    const gdouble* nv = (const gdouble*)(Q.nv + (size_t)pb * nm * 2);
-    const gdouble* al = (const gdouble*)(Q.alpha + (size_t)pb * nm);
-    gdouble* vec = (gdouble*)(Q.vec + (size_t)pb * nm * MCQ_NVEC);
-    gdouble* PX = vec + 0 * nm;   gdouble* PY = vec + 1 * nm;
-    gdouble* CX = vec + 4 * nm;   gdouble* CY = vec + 5 * nm;
-    gdouble* LEN = vec + 6 * nm;  gdouble* CUM = vec + 7 * nm;
-    gint* m_out = (gint*)(Q.m_out + pb);
-    gint* status = (gint*)(Q.status + pb);
-    if (n < 3) {
-        if (tid == 0) { *status = MCQ_BAD_INPUT; *m_out = 0; }
-        return;
-    }
-    double total;
-    __shared__ double relin_lds[RELIN_LDS];
-    const int m = relin_front(ref, nv, al, n, 1.0, Q.stepsize, vec, nm, total, relin_lds);
-    if (m < 2 || m > Q.mmax) {
-        if (tid == 0) { *status = MCQ_BAD_INPUT; *m_out = m > 0 ? m : 0; }
-        return;
-    }
-    gdouble* xy = Q.xy_out ? (gdouble*)(Q.xy_out + (size_t)pb * mm * 2) : nullptr;
-    gdouble* psi = Q.psi_out ? (gdouble*)(Q.psi_out + (size_t)pb * mm) : nullptr;
-    gdouble* kap = (gdouble*)(Q.kappa_out + (size_t)pb * mm);
-    gdouble* el = (gdouble*)(Q.el_out + (size_t)pb * mm);
-    const double step = total / (double)m;                       // numpy.linspace(0, total, m + 1): station j = j * step
-    const double pi = 3.14159265358979323846;
-    for (int j = tid; j < m; j += MCQ_NT) {
-        const double q = (double)j * step;
-        int lo = 0, hi = n;                                      // first index with CUM[idx] > q
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (CUM[mid] > q) hi = mid; else lo = mid + 1;
-        }
-        const int s = lo < n - 1 ? lo : n - 1;
-        const int sp = s + 1 == n ? 0 : s + 1;
-        const double start = s > 0 ? CUM[s - 1] : 0.0;
-        const double t = (q - start) / LEN[s];
-        const double ax = PX[s], ay = PY[s], cx = CX[s], cy = CY[s];
-        const double bx = (PX[sp] - ax) - (2.0 * cx + CX[sp]) / 3.0, by = (PY[sp] - ay) - (2.0 * cy + CY[sp]) / 3.0;
-        const double dx = (CX[sp] - cx) / 3.0, dy = (CY[sp] - cy) / 3.0;
-        if (xy) {
-            xy[2 * j] = ax + t * (bx + t * (cx + t * dx));
-            xy[2 * j + 1] = ay + t * (by + t * (cy + t * dy));
-        }
-        const double xd = bx + 2.0 * cx * t + 3.0 * dx * t * t, yd = by + 2.0 * cy * t + 3.0 * dy * t * t;
-        const double xdd = 2.0 * cx + 6.0 * dx * t, ydd = 2.0 * cy + 6.0 * dy * t;
-        if (psi) {                                               // heading, 0 = north, wrapped to [-pi, pi) (tph.normalize_psi)
-            double a = atan2(yd, xd) - 0.5 * pi;
-            if (a >= pi) a -= 2.0 * pi;
-            else if (a < -pi) a += 2.0 * pi;
-            psi[j] = a;
-        }
-        const double v2 = xd * xd + yd * yd;
-        kap[j] = (xd * ydd - yd * xdd) / (v2 * sqrt(v2));
-        el[j] = j + 1 < m ? (double)(j + 1) * step - q : total - q;
-    }
-    if (tid == 0) { *status = MCQ_OK; *m_out = m; }
-}
-
-// ---- mcq_raceline_kernel's body once more, statement for statement, for the launch that mixes rings and chains (mcq_raceline_ends_kernel).
-//      A copy, not a function shared with the kernel above: with the body shared, hipcc placed a handful of that kernel's scalar address
-//      instructions differently, and the existing entry keeps its code object as it is.  Both suites hold the two to the same bits
-//      (tests/race_open_checks.py: mixed launches). ----
+//      outputs strided by mmax: exactly what mcq_vel_profile_kernel consumes (kappa, el_lengths).  The body of mcq_raceline_kernel and of
+//      the rings in a launch that mixes rings and chains (mcq_raceline_ends_kernel); relin_lds: RELIN_LDS doubles. ----
 __device__ __forceinline__ void race_ring_body(const McqRace& Q, double* relin_lds)
 {
     const int tid = threadIdx.x, pb = blockIdx.x;
@@ -2958,38 +2957,20 @@ __device__ __forceinline__ void race_ring_body(const McqRace& Q, double* relin_l
     gdouble* kap = (gdouble*)(Q.kappa_out + (size_t)pb * mm);
     gdouble* el = (gdouble*)(Q.el_out + (size_t)pb * mm);
     const double step = total / (double)m;                       // numpy.linspace(0, total, m + 1): station j = j * step
-    const double pi = 3.14159265358979323846;
     for (int j = tid; j < m; j += MCQ_NT) {
         const double q = (double)j * step;
-        int lo = 0, hi = n;                                      // first index with CUM[idx] > q
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (CUM[mid] > q) hi = mid; else lo = mid + 1;
-        }
-        const int s = lo < n - 1 ? lo : n - 1;
-        const int sp = s + 1 == n ? 0 : s + 1;
-        const double start = s > 0 ? CUM[s - 1] : 0.0;
-        const double t = (q - start) / LEN[s];
-        const double ax = PX[s], ay = PY[s], cx = CX[s], cy = CY[s];
-        const double bx = (PX[sp] - ax) - (2.0 * cx + CX[sp]) / 3.0, by = (PY[sp] - ay) - (2.0 * cy + CY[sp]) / 3.0;
-        const double dx = (CX[sp] - cx) / 3.0, dy = (CY[sp] - cy) / 3.0;
-        if (xy) {
-            xy[2 * j] = ax + t * (bx + t * (cx + t * dx));
-            xy[2 * j + 1] = ay + t * (by + t * (cy + t * dy));
-        }
-        const double xd = bx + 2.0 * cx * t + 3.0 * dx * t * t, yd = by + 2.0 * cy * t + 3.0 * dy * t * t;
-        const double xdd = 2.0 * cx + 6.0 * dx * t, ydd = 2.0 * cy + 6.0 * dy * t;
-        if (psi) {                                               // heading, 0 = north, wrapped to [-pi, pi) (tph.normalize_psi)
-            double a = atan2(yd, xd) - 0.5 * pi;
-            if (a >= pi) a -= 2.0 * pi;
-            else if (a < -pi) a += 2.0 * pi;
-            psi[j] = a;
-        }
-        const double v2 = xd * xd + yd * yd;
-        kap[j] = (xd * ydd - yd * xdd) / (v2 * sqrt(v2));
+        double t;
+        const int s = seg_search(CUM, LEN, n, q, t);
+        seg_station(seg_of(PX, PY, CX, CY, s, cyc1(s + 1, n)), t, j, xy, psi, kap);
         el[j] = j + 1 < m ? (double)(j + 1) * step - q : total - q;
     }
     if (tid == 0) { *status = MCQ_OK; *m_out = m; }
+}
+
+__global__ void __launch_bounds__(MCQ_NT) mcq_raceline_kernel(McqRace Q)
+{
+    __shared__ double relin_lds[RELIN_LDS];
+    race_ring_body(Q, relin_lds);
 }
 
 // ---- the same for an OPEN chain of n >= 2 waypoints (mcq_raceline_device_ends; DESIGN.md "Open chains"): n - 1 splines through
@@ -3048,9 +3029,6 @@ __device__ void chain_spline_c(const gdouble* RX, const gdouble* RY, int n, gdou
 // vec slots as in relin_front (0/1 points, 2/3 rhs, 4/5 c, 6 lengths, 7 running sum); lds: RELIN_LDS doubles.
 __device__ __forceinline__ void race_chain_body(const McqRace& Q, const double* psi_ends, double* lds)
 {
-    double* sbuf = lds;
-    double& s_carry = lds[2048];
-    int& s_m = *(int*)(lds + 2049);
     const int tid = threadIdx.x, pb = blockIdx.x;
     const size_t nm = (size_t)Q.nmax, mm = (size_t)Q.mmax;
     const int n = Q.n_in ? Q.n_in[pb] : Q.nmax;
@@ -3092,45 +3070,8 @@ __device__ __forceinline__ void race_chain_body(const McqRace& Q, const double* 
     __syncthreads();
     chain_spline_c(RX, RY, n, CX, CY);
     __syncthreads();
-    for (int i = tid; i < ns; i += MCQ_NT) {
-        const double ax = PX[i], ay = PY[i], cx = CX[i], cy = CY[i];
-        const double dlx = PX[i + 1] - ax, dly = PY[i + 1] - ay;
-        const double bx = dlx - (2.0 * cx + CX[i + 1]) / 3.0, by = dly - (2.0 * cy + CY[i + 1]) / 3.0;
-        const double dx = (CX[i + 1] - cx) / 3.0, dy = (CY[i + 1] - cy) / 3.0;
-        double len = 0.0, x0 = ax, y0 = ay;
-        for (int k = 1; k < 15; ++k) {
-            const double t = (double)k / 14.0;
-            const double x1 = ax + bx * t + cx * t * t + dx * t * t * t;
-            const double y1 = ay + by * t + cy * t * t + dy * t * t * t;
-            len += hypot(x1 - x0, y1 - y0);
-            x0 = x1;
-            y0 = y1;
-        }
-        LEN[i] = len;
-    }
-    __syncthreads();
-    if (tid == 0) s_carry = 0.0;
-    for (int c0 = 0; c0 < ns; c0 += 2048) {
-        const int cn = ns - c0 < 2048 ? ns - c0 : 2048;
-        __syncthreads();
-        for (int q = tid; q < cn; q += MCQ_NT) sbuf[q] = LEN[c0 + q];
-        __syncthreads();
-        if (tid == 0) {
-            double acc = s_carry;
-            for (int q = 0; q < cn; ++q) { acc += sbuf[q]; sbuf[q] = acc; }
-            s_carry = acc;
-        }
-        __syncthreads();
-        for (int q = tid; q < cn; q += MCQ_NT) CUM[c0 + q] = sbuf[q];
-    }
-    __syncthreads();
-    const double total = s_carry;
-    if (tid == 0) {
-        const double cnt = ceil(total / Q.stepsize) + 1.0;      // no_interp_points of tph.interp_splines, all of them kept
-        s_m = (cnt >= 2.0 && cnt <= 2.0e9) ? (int)cnt : -1;
-    }
-    __syncthreads();
-    const int m = s_m;
+    double total;
+    const int m = spline_lengths(PX, PY, CX, CY, ns, n, LEN, CUM, Q.stepsize, total, lds);      // no_interp_points, all of them kept
     if (m < 2 || m > Q.mmax) {
         if (tid == 0) { *status = MCQ_BAD_INPUT; *m_out = m > 0 ? m : 0; }
         return;
@@ -3140,41 +3081,17 @@ __device__ __forceinline__ void race_chain_body(const McqRace& Q, const double* 
     gdouble* kap = (gdouble*)(Q.kappa_out + (size_t)pb * mm);
     gdouble* el = (gdouble*)(Q.el_out + (size_t)pb * mm);
     const double step = total / (double)(m - 1);                 // numpy.linspace(0, total, m): station j = j * step
-    const double pi = 3.14159265358979323846;
     for (int j = tid; j < m; j += MCQ_NT) {
         int s;
         double t, q = 0.0;
         if (j < m - 1) {
             q = (double)j * step;
-            int lo = 0, hi = ns;                                 // first index with CUM[idx] > q
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (CUM[mid] > q) hi = mid; else lo = mid + 1;
-            }
-            s = lo < ns - 1 ? lo : ns - 1;
-            const double start = s > 0 ? CUM[s - 1] : 0.0;
-            t = (q - start) / LEN[s];
-        } else {                                                 // the last point: the end of the last segment
-            s = ns - 1;
+            s = seg_search(CUM, LEN, ns, q, t);
+        } else {                                                 // the last point: the end of the last segment (a branch of its own, not a
+            s = ns - 1;                                          //  select on the search's result: DESIGN.md section 3, "Open chains")
             t = 1.0;
         }
-        const double ax = PX[s], ay = PY[s], cx = CX[s], cy = CY[s];
-        const double bx = (PX[s + 1] - ax) - (2.0 * cx + CX[s + 1]) / 3.0, by = (PY[s + 1] - ay) - (2.0 * cy + CY[s + 1]) / 3.0;
-        const double dx = (CX[s + 1] - cx) / 3.0, dy = (CY[s + 1] - cy) / 3.0;
-        if (xy) {
-            xy[2 * j] = ax + t * (bx + t * (cx + t * dx));
-            xy[2 * j + 1] = ay + t * (by + t * (cy + t * dy));
-        }
-        const double xd = bx + 2.0 * cx * t + 3.0 * dx * t * t, yd = by + 2.0 * cy * t + 3.0 * dy * t * t;
-        const double xdd = 2.0 * cx + 6.0 * dx * t, ydd = 2.0 * cy + 6.0 * dy * t;
-        if (psi) {                                               // heading, 0 = north, wrapped to [-pi, pi) (tph.normalize_psi)
-            double a = atan2(yd, xd) - 0.5 * pi;
-            if (a >= pi) a -= 2.0 * pi;
-            else if (a < -pi) a += 2.0 * pi;
-            psi[j] = a;
-        }
-        const double v2 = xd * xd + yd * yd;
-        kap[j] = (xd * ydd - yd * xdd) / (v2 * sqrt(v2));
+        seg_station(seg_of(PX, PY, CX, CY, s, s + 1), t, j, xy, psi, kap);
         if (j + 2 < m) el[j] = (double)(j + 1) * step - q;
         else if (j + 2 == m) el[j] = total - q;
         else el[j] = 0.0;                                        // no element after the last point: written, never stale
@@ -3490,7 +3407,6 @@ __global__ void __launch_bounds__(64) mcq_trajectory_kernel(McqTraj T)
 //      nb = ceil(total / step) samples kept of numpy.linspace(0, total, nb + 1); per sample a binary search for its element and numpy.interp's
 //      slope * (x - xp_j) + fp_j in each coordinate. ----
 typedef __attribute__((address_space(1))) d2 gd2;
-__device__ __forceinline__ bool bd_finite(double a) { return fabs(a) < (double)INFINITY; }      // (false for a NaN)
 
 __global__ void __launch_bounds__(MCQ_NT) mcq_bound_points_kernel(McqBound P)
 {
@@ -3529,7 +3445,7 @@ __global__ void __launch_bounds__(MCQ_NT) mcq_bound_points_kernel(McqBound P)
         const double w = ref[4 * (size_t)i + 2 + side];
         const double sw = side ? -w : w;
         const double bx = ref[4 * (size_t)i] + nv[2 * (size_t)i] * sw, by = ref[4 * (size_t)i + 1] + nv[2 * (size_t)i + 1] * sw;
-        if (!bd_finite(bx) || !bd_finite(by)) bad = 1;
+        if (!finite_d(bx) || !finite_d(by)) bad = 1;
         pts[2 * (size_t)i] = bx;
         pts[2 * (size_t)i + 1] = by;
         if (bout) {
@@ -3539,41 +3455,25 @@ __global__ void __launch_bounds__(MCQ_NT) mcq_bound_points_kernel(McqBound P)
     }
     if (bout) for (size_t i = (size_t)n * 2 + tid; i < nm * 2; i += MCQ_NT) bout[i] = NAN;
     for (int i = tid; i < m; i += MCQ_NT)
-        if (!bd_finite(xy[2 * (size_t)i]) || !bd_finite(xy[2 * (size_t)i + 1]) || !bd_finite(psi[i])) bad = 1;
+        if (!finite_d(xy[2 * (size_t)i]) || !finite_d(xy[2 * (size_t)i + 1]) || !finite_d(psi[i])) bad = 1;
     if (tid == 0) {
-        if (P.length_list && !bd_finite(P.length_list[t])) bad = 1;
-        if (P.width_list && !bd_finite(P.width_list[t])) bad = 1;
+        if (P.length_list && !finite_d(P.length_list[t])) bad = 1;
+        if (P.width_list && !finite_d(P.width_list[t])) bad = 1;
         cum[0] = 0.0;
     }
     __syncthreads();        // the boundary points are in the scratch for every thread of the workgroup
-    for (int base = 0; base < n; base += MCQ_NT) {
-        const int i = base + tid;
-        if (i < n) {
-            const int j = i + 1 < n ? i + 1 : 0;
-            const double dx = pts[2 * (size_t)j] - pts[2 * (size_t)i], dy = pts[2 * (size_t)j + 1] - pts[2 * (size_t)i + 1];
-            const double e = sqrt(dx * dx + dy * dy);
-            if (!(e > 0.0)) bad = 1;       // numpy.interp has no answer on an element of length 0
-            s_el[tid] = e;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            double c = s_carry;
-            const int cnt = n - base < MCQ_NT ? n - base : MCQ_NT;
-            for (int k = 0; k < cnt; ++k) {
-                c += s_el[k];
-                s_el[k] = c;
-            }
-            s_carry = c;
-        }
-        __syncthreads();
-        if (i < n) cum[(size_t)i + 1] = s_el[tid];
-        __syncthreads();
-    }
+    running_sum<MCQ_NT>(n, s_el, s_carry, cum + 1, [&](int i) {
+        const int j = i + 1 < n ? i + 1 : 0;
+        const double dx = pts[2 * (size_t)j] - pts[2 * (size_t)i], dy = pts[2 * (size_t)j + 1] - pts[2 * (size_t)i + 1];
+        const double e = sqrt(dx * dx + dy * dy);
+        if (!(e > 0.0)) bad = 1;       // numpy.interp has no answer on an element of length 0
+        return e;
+    });
     if (bad) s_bad = 1;
     __syncthreads();
     const double total = s_carry;
     const double cnt = ceil(total / P.step);
-    if (s_bad || !bd_finite(cnt) || !(cnt >= 1.0) || cnt > (double)P.nbmax) {
+    if (s_bad || !finite_d(cnt) || !(cnt >= 1.0) || cnt > (double)P.nbmax) {
         if (tid == 0) {
             *st = MCQ_BAD_INPUT;
             *nbo = (!s_bad && cnt >= 1.0 && cnt < 2147483647.0) ? (int)cnt : 0;       // the samples a boundary would need
@@ -3582,7 +3482,7 @@ __global__ void __launch_bounds__(MCQ_NT) mcq_bound_points_kernel(McqBound P)
     }
     const int nb = (int)cnt;
     const double dl = total / (double)nb;           // numpy.linspace's step: (stop - start) / (num - 1)
-    for (int j = tid; j < nb; j += MCQ_NT) {
+    for (int j = tid; j < nb; j += MCQ_NT) {        // (mcq_spline_fit_kernel samples by the same rule without contraction: not one function)
         const double x = (double)j * dl;
         int lo = 0, hi = n - 1;                     // the last k in [0, n - 1] with cum[k] <= x
         while (lo < hi) {
@@ -3860,39 +3760,24 @@ __global__ void __launch_bounds__(MCQ_NT) mcq_spline_length_kernel(McqSpline S)
     gdouble* cum = (gdouble*)(S.tguess + (size_t)tr * (nm + 1));
     int bad = 0;
     for (int i = tid; i < 4 * n; i += MCQ_NT)
-        if (!bd_finite(trk[i])) bad = 1;
+        if (!finite_d(trk[i])) bad = 1;
     for (int i = tid; i < nk; i += MCQ_NT) {
-        if (!bd_finite(kt[i])) bad = 1;
+        if (!finite_d(kt[i])) bad = 1;
         if (i > 0 && !(kt[i - 1] <= kt[i])) bad = 1;
-        if (i < nk - K - 1 && (!bd_finite(kc[i]) || !bd_finite(kc[(size_t)S.nkmax + i]))) bad = 1;
+        if (i < nk - K - 1 && (!finite_d(kc[i]) || !finite_d(kc[(size_t)S.nkmax + i]))) bad = 1;
     }
     if (tid == 0) cum[0] = 0.0;
-    for (int base = 0; base < n; base += MCQ_NT) {       // element lengths of the closed raw line, summed in numpy.cumsum's order
-        const int i = base + tid;
-        if (i < n) {
-            const int j = i + 1 < n ? i + 1 : 0;
-            const double dx = trk[4 * (size_t)j] - trk[4 * (size_t)i], dy = trk[4 * (size_t)j + 1] - trk[4 * (size_t)i + 1];
-            s_el[tid] = sqrt(dx * dx + dy * dy);
-        }
-        __syncthreads();
-        if (tid == 0) {
-            double c = s_carry;
-            const int cnt = n - base < MCQ_NT ? n - base : MCQ_NT;
-            for (int k = 0; k < cnt; ++k) {
-                c += s_el[k];
-                s_el[k] = c;
-            }
-            s_carry = c;
-        }
-        __syncthreads();
-        if (i < n) cum[(size_t)i + 1] = s_el[tid];
-        __syncthreads();
-    }
+    // element lengths of the closed raw line, summed in numpy.cumsum's order
+    running_sum<MCQ_NT>(n, s_el, s_carry, cum + 1, [&](int i) {
+        const int j = i + 1 < n ? i + 1 : 0;
+        const double dx = trk[4 * (size_t)j] - trk[4 * (size_t)i], dy = trk[4 * (size_t)j + 1] - trk[4 * (size_t)i + 1];
+        return sqrt(dx * dx + dy * dy);
+    });
     if (bad) s_bad = 1;
     __syncthreads();
     const double total = s_carry;
     const double ct = ceil(total);
-    if (s_bad || !(total > 0.0) || !bd_finite(total) || ct > 4194304.0) {        // (2^22 m: the 4 ceil(total) length samples stay a bounded loop)
+    if (s_bad || !(total > 0.0) || !finite_d(total) || ct > 4194304.0) {        // (2^22 m: the 4 ceil(total) length samples stay a bounded loop)
         if (tid == 0) {
             *st = MCQ_BAD_INPUT;
             *mo = 0;
@@ -3908,7 +3793,7 @@ __global__ void __launch_bounds__(MCQ_NT) mcq_spline_length_kernel(McqSpline S)
     const double len = block_reduce_(acc, 0, s_red);
     const double cnt = ceil(len / S.step) + 1.0;
     if (tid == 0) {
-        if (!bd_finite(cnt) || cnt > 1073741824.0) {
+        if (!finite_d(cnt) || cnt > 1073741824.0) {
             *st = MCQ_BAD_INPUT;
             *mo = 0;
             *np_ = 0;
@@ -4141,8 +4026,6 @@ __global__ void __launch_bounds__(MCQ_NT) mcq_min_width_kernel(int nmax, const i
 //      their running sum are that kernel's bits -- leaves LEN / CUM in the slab's slots 6 / 7, where mcq_export_rows_kernel reads them; the station
 //      count relin_front derives from its stepsize is not used (the constant 1).  A refused track (a non-finite input among its n waypoints, a total
 //      that is not finite) marks itself with a NaN in CUM[n - 1]; a track whose n is out of range is recognised by every reader from n itself. ----
-__device__ __forceinline__ bool ex_finite(double a) { return fabs(a) < (double)INFINITY; }      // (false for a NaN)
-
 __global__ void __launch_bounds__(MCQ_NT) mcq_export_s_kernel(McqExport X)
 {
     __shared__ double relin_lds[RELIN_LDS];
@@ -4164,8 +4047,8 @@ __global__ void __launch_bounds__(MCQ_NT) mcq_export_s_kernel(McqExport X)
     if (range) {
         int bad = 0;
         for (int i = tid; i < n; i += MCQ_NT) {
-            const bool ok = ex_finite(ref[4 * (size_t)i]) && ex_finite(ref[4 * (size_t)i + 1]) && ex_finite(ref[4 * (size_t)i + 2]) &&
-                            ex_finite(ref[4 * (size_t)i + 3]) && ex_finite(nv[2 * (size_t)i]) && ex_finite(nv[2 * (size_t)i + 1]) && ex_finite(al[i]);
+            const bool ok = finite_d(ref[4 * (size_t)i]) && finite_d(ref[4 * (size_t)i + 1]) && finite_d(ref[4 * (size_t)i + 2]) &&
+                            finite_d(ref[4 * (size_t)i + 3]) && finite_d(nv[2 * (size_t)i]) && finite_d(nv[2 * (size_t)i + 1]) && finite_d(al[i]);
             if (!ok) bad = 1;
         }
         if (bad) s_bad = 1;
@@ -4175,7 +4058,7 @@ __global__ void __launch_bounds__(MCQ_NT) mcq_export_s_kernel(McqExport X)
     bool good = range && s_bad == 0;
     if (good) {
         relin_front(ref, nv, al, n, 1.0, 1.0, vec, nm, total, relin_lds);
-        good = ex_finite(total);
+        good = finite_d(total);
     }
     if (!good) {
         if (range && tid == 0) CUM[n - 1] = NAN;
@@ -4225,7 +4108,7 @@ __global__ void __launch_bounds__(MCQ_NT) mcq_export_rows_kernel(McqExport X)
     double total = NAN;
     if (!bad) {
         total = CUM[n - 1];
-        bad = !ex_finite(total);
+        bad = !finite_d(total);
     }
     if (tid == 0) s_bad = 0;
     // this thread's rows (MCQ_EX_RPT of them, MCQ_NT apart) and their queries: s_ref of the row (row n asks for s_ref_0)
