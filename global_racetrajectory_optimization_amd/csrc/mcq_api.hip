@@ -88,6 +88,7 @@ struct mcq_handle {
     Scratch ends;                       // per-problem ring / open-chain records of mcq_solve_batch_ends (device)
     Scratch fgen;                       // mcq_points_in_path_device / mcq_friction_gen_device: polygons, kept vertices, contours, their counts
     Scratch fgen_pts;                   // mcq_friction_gen_device: the grid points' flags and the blocks' counts (sized after the boundaries' launch)
+    Scratch mintime;                    // mcq_mintime_eval_device: the intervals' times and energies [batch][nmax] each, where the caller takes none
     mcq_iqp_round_cb iqp_cb = nullptr;  // mcq_iqp_set_round_callback
     void* iqp_cb_user = nullptr;
     void* comm = nullptr;               // ncclComm_t of mcq_comm_init (RCCL, loaded with dlopen)
@@ -283,7 +284,7 @@ extern "C" void mcq_destroy(mcq_handle* h)
     for (int k = 0; k < 16; ++k) if (h->ev_slice[k]) (void)hipEventDestroy(h->ev_slice[k]);
     if (h->cs_in) (void)hipStreamDestroy(h->cs_in);
     if (h->cs_out) (void)hipStreamDestroy(h->cs_out);
-    for (Scratch* s : {&h->vel, &h->bound, &h->fit, &h->spl, &h->ends, &h->fgen, &h->fgen_pts}) (void)hipFree(s->p);
+    for (Scratch* s : {&h->vel, &h->bound, &h->fit, &h->spl, &h->ends, &h->fgen, &h->fgen_pts, &h->mintime}) (void)hipFree(s->p);
     if (h->pin) (void)hipHostFree(h->pin);
     for (int k = 0; k < 5; ++k) if (h->ev[k]) (void)hipEventDestroy(h->ev[k]);
     for (int k = 0; k < 2; ++k) if (h->ev_span[k]) (void)hipEventDestroy(h->ev_span[k]);
@@ -1535,6 +1536,168 @@ extern "C" int mcq_friction_gen_device(mcq_handle* h, int tracks, int nmax, cons
         hipLaunchKernelGGL(mcq_fgen_scatter_kernel, dim3((unsigned)maxblk, tracks), dim3(256), 0, st, G);
         HIP_TRY(hipGetLastError());
     }
+    return 0;
+}
+
+// ---- the minimum-time NLP as functions of w (include/mcq.h; csrc/mcq_mintime.inc) ----
+// The collocation constants [REF opt_mintime.py:143-176]: Lagrange polynomials through tau = [0, the Gauss-Legendre points of degree 3 on (0, 1)],
+// D their values at 1, C their derivatives at the points, B their integrals over [0, 1].  Computed once, in long double, from the monomial
+// coefficients as numpy.poly1d holds them.
+static const McqMtColl& mintime_coll()
+{
+    static const McqMtColl coll = [] {
+        McqMtColl c;
+        const long double s15 = sqrtl(15.0L) / 10.0L, tau[4] = {0.0L, 0.5L - s15, 0.5L, 0.5L + s15};
+        for (int j = 0; j < 4; ++j) {
+            long double p[4] = {0.0L, 0.0L, 0.0L, 1.0L};       // coefficients, highest power first, of the product so far (degree grows to 3)
+            int deg = 0;
+            for (int r = 0; r < 4; ++r) {
+                if (r == j) continue;
+                long double q[4] = {0.0L, 0.0L, 0.0L, 0.0L};
+                const long double den = tau[j] - tau[r];
+                for (int i = 3 - deg; i < 4; ++i) {
+                    q[i - 1] += p[i] / den;
+                    q[i] += -tau[r] * p[i] / den;
+                }
+                for (int i = 0; i < 4; ++i) p[i] = q[i];
+                ++deg;
+            }
+            c.tau[j] = (double)tau[j];
+            c.D[j] = (double)(p[0] + p[1] + p[2] + p[3]);
+            c.B[j] = (double)(p[0] / 4.0L + p[1] / 3.0L + p[2] / 2.0L + p[3]);
+            for (int r = 0; r < 4; ++r) c.C[j][r] = (double)((3.0L * p[0] * tau[r] + 2.0L * p[1]) * tau[r] + p[2]);
+        }
+        return c;
+    }();
+    return coll;
+}
+
+static int mintime_opts_bad(const mcq_mintime_opts* o)
+{
+    return !o || o->pwr_behavior != 0 || (o->friction != -1 && o->friction != MCQ_FRIC_LINEAR && o->friction != MCQ_FRIC_GAUSS) ||
+           (o->friction == MCQ_FRIC_GAUSS && (o->n_gauss < 1 || o->n_gauss > 15));
+}
+
+extern "C" int mcq_mintime_layout(int N, const mcq_mintime_opts* opts, mcq_mintime_dims* out)
+{
+    if (N < 2 || !out || mintime_opts_bad(opts) || (long long)N * 31 + 64 > 0x7fffffffLL) {
+        g_err = "mcq_mintime_layout: bad argument (N >= 2, no powertrain states, friction -1 / MCQ_FRIC_LINEAR / MCQ_FRIC_GAUSS with n_gauss 1 .. 15)";
+        return MCQ_E_ARG;
+    }
+    const int safe = opts->safe_traj ? 1 : 0, energy = opts->limit_energy ? 1 : 0;
+    memset(out, 0, sizeof(*out));
+    out->nw = 5 + 24 * N;
+    out->ng = mcq_mt_ng(N, safe, energy);
+    out->off_x = 0; out->off_u = 5; out->off_xc = 9; out->stride_w = 24;
+    out->rows_first = 27 + 2 * safe; out->rows_next = 31 + 2 * safe;
+    out->row_colloc = 0; out->row_cont = 15; out->row_power = 20; out->row_kamm = 21; out->row_roll = 25; out->row_pedal = 26; out->row_act = 27;
+    out->row_safe = safe ? 31 : -1;
+    out->row_periodic = mcq_mt_row0(N, safe);
+    out->row_energy = energy ? out->row_periodic + 5 : -1;
+    const McqMtColl& c = mintime_coll();
+    memcpy(out->tau, c.tau, sizeof(c.tau)); memcpy(out->C, c.C, sizeof(c.C)); memcpy(out->D, c.D, sizeof(c.D)); memcpy(out->B, c.B, sizeof(c.B));
+    return 0;
+}
+
+// the checks the four device entries share, and the launch record they fill further
+static int mintime_record(const char* who, mcq_handle* h, const mcq_mintime_data* d, const mcq_mintime_opts* o, bool need_w, McqMintime& M)
+{
+    if (!h || !d || mintime_opts_bad(o) || d->batch <= 0 || d->nmax < 2 || !d->pars || !d->w_tr_right_cl || !d->w_tr_left_cl ||
+        (need_w && (!d->h || !d->kappa_cl || !d->w)) || (need_w && o->friction >= 0 && !d->w_mue) ||
+        (need_w && o->friction == MCQ_FRIC_GAUSS && !d->center_dist)) {
+        g_err = std::string(who) + ": bad argument";
+        return MCQ_E_ARG;
+    }
+    if (d->batch > 65535 || (long long)d->nmax * MCQ_MT_JAC_LANES + 64 * MCQ_MT_JAC_LANES > 0x7fffffffLL) {
+        g_err = std::string(who) + ": more problems or intervals than one launch holds";
+        return MCQ_E_TOO_LARGE;
+    }
+    memset(&M, 0, sizeof(M));
+    M.d = *d;
+    M.o = *o;
+    M.c = mintime_coll();
+    M.P = o->friction < 0 ? 0 : (o->friction == MCQ_FRIC_LINEAR ? 2 : 2 * o->n_gauss + 2);
+    M.nwmax = 5 + 24 * d->nmax;
+    M.ngmax = mcq_mt_ng(d->nmax, o->safe_traj ? 1 : 0, o->limit_energy ? 1 : 0);
+    return 0;
+}
+
+extern "C" int mcq_mintime_bounds_device(mcq_handle* h, const mcq_mintime_data* data, const mcq_mintime_opts* opts, double* w0_out, double* lbw_out,
+                                         double* ubw_out, double* lbg_out, double* ubg_out)
+{
+    McqMintime M;
+    if (int rc = mintime_record("mcq_mintime_bounds_device", h, data, opts, false, M)) return rc;
+    if (!w0_out || !lbw_out || !ubw_out || !lbg_out || !ubg_out) {
+        g_err = "mcq_mintime_bounds_device: bad argument";
+        return MCQ_E_ARG;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    M.w0 = w0_out; M.lbw = lbw_out; M.ubw = ubw_out; M.lbg = lbg_out; M.ubg = ubg_out;
+    hipLaunchKernelGGL(mcq_mintime_bounds_kernel, dim3(data->batch), dim3(256), 0, h->ws[0].stream, M);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int mcq_mintime_eval_device(mcq_handle* h, const mcq_mintime_data* data, const mcq_mintime_opts* opts, double* g_out, double* J_out,
+                                       double* lap_time_out, double* energy_out, double* x_opt_out, double* u_opt_out, double* tf_opt_out,
+                                       double* dt_opt_out, double* ax_opt_out, double* ay_opt_out, double* ec_opt_out, int* status_out)
+{
+    McqMintime M;
+    if (int rc = mintime_record("mcq_mintime_eval_device", h, data, opts, true, M)) return rc;
+    if (!g_out || !J_out || !status_out) {
+        g_err = "mcq_mintime_eval_device: bad argument";
+        return MCQ_E_ARG;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t bn = (size_t)data->batch * data->nmax;
+    M.dt_own = dt_opt_out; M.ec_own = ec_opt_out;
+    if (!dt_opt_out || !ec_opt_out) {
+        if (int rc = grow(h, h->mintime, 2 * bn * sizeof(double))) return rc;
+        if (!dt_opt_out) M.dt_own = (double*)h->mintime.p;
+        if (!ec_opt_out) M.ec_own = (double*)h->mintime.p + bn;
+    }
+    M.g = g_out; M.J = J_out; M.lap = lap_time_out; M.energy = energy_out; M.x_opt = x_opt_out; M.u_opt = u_opt_out; M.tf_opt = tf_opt_out;
+    M.dt_opt = dt_opt_out; M.ax_opt = ax_opt_out; M.ay_opt = ay_opt_out; M.ec_opt = ec_opt_out; M.status = status_out;
+    const unsigned per_wg = 256 / MCQ_MT_EVAL_LANES;
+    hipLaunchKernelGGL(mcq_mintime_eval_kernel, dim3(((unsigned)data->nmax + per_wg - 1) / per_wg, data->batch), dim3(256), 0, h->ws[0].stream, M);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(mcq_mintime_sum_kernel, dim3(data->batch), dim3(256), 0, h->ws[0].stream, M);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int mcq_mintime_jac_device(mcq_handle* h, const mcq_mintime_data* data, const mcq_mintime_opts* opts, double* blocks_out, double* grad_J_out,
+                                      double* grad_energy_out)
+{
+    McqMintime M;
+    if (int rc = mintime_record("mcq_mintime_jac_device", h, data, opts, true, M)) return rc;
+    if (!blocks_out || !grad_J_out) {
+        g_err = "mcq_mintime_jac_device: bad argument";
+        return MCQ_E_ARG;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    M.blocks = blocks_out; M.grad_J = grad_J_out; M.grad_E = grad_energy_out;
+    const size_t lanes = (size_t)data->nmax * MCQ_MT_JAC_LANES;
+    hipLaunchKernelGGL(mcq_mintime_jac_kernel, dim3((unsigned)((lanes + 255) / 256), data->batch), dim3(256), 0, h->ws[0].stream, M);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int mcq_mintime_kkt_device(mcq_handle* h, const mcq_mintime_data* data, const mcq_mintime_opts* opts, const double* g, const double* blocks,
+                                      const double* grad_J, const double* grad_energy, const double* lam_g, const double* lam_x, const double* lbw,
+                                      const double* ubw, const double* lbg, const double* ubg, double* r_out, double* kkt_out)
+{
+    McqMintime M;
+    if (int rc = mintime_record("mcq_mintime_kkt_device", h, data, opts, true, M)) return rc;
+    if (!g || !blocks || !grad_J || (opts->limit_energy && !grad_energy) || !lam_g || !lam_x || !lbw || !ubw || !lbg || !ubg || !r_out || !kkt_out) {
+        g_err = "mcq_mintime_kkt_device: bad argument";
+        return MCQ_E_ARG;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    M.g_in = g; M.blocks_in = blocks; M.grad_J_in = grad_J; M.grad_E_in = grad_energy; M.lam_g = lam_g; M.lam_x = lam_x;
+    M.lbw_in = lbw; M.ubw_in = ubw; M.lbg_in = lbg; M.ubg_in = ubg; M.r = r_out; M.kkt = kkt_out;
+    hipLaunchKernelGGL(mcq_mintime_kkt_kernel, dim3(data->batch), dim3(256), 0, h->ws[0].stream, M);
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 

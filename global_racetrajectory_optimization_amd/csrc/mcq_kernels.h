@@ -525,6 +525,41 @@ struct McqFgen {
     unsigned char* bits;     // [tracks][maxblk * 256]: per item the on-track flags of its MCQ_FGEN_PPT points
     int* bcount;             // [tracks][maxblk]: cells per block of 256 items, then their running sum
 };
+/* ---- the minimum-time NLP as functions of w (mcq_mintime_*_device; csrc/mcq_mintime.inc) [REF opt_mintime_traj/src/opt_mintime.py:143-861].
+ *      Layouts: include/mcq.h.  Lane mappings: the evaluation one lane per (interval, evaluation point) -- 4 per interval, 64 intervals per workgroup;
+ *      the Jacobian one lane per (interval, evaluation point, direction) -- 36 per interval, a one-tangent dual number each. ---- */
+#define MCQ_MT_EVAL_LANES 4
+#define MCQ_MT_JAC_LANES 36
+struct McqMtColl {
+    double tau[4], C[4][4], D[4], B[4];
+};
+struct McqMintime {
+    mcq_mintime_data d;
+    mcq_mintime_opts o;
+    McqMtColl c;
+    int P;                   // doubles per friction row: 0, 2 or 2 n_gauss + 2
+    int nwmax, ngmax;
+    // evaluation
+    double *g, *J, *lap, *energy, *x_opt, *u_opt, *tf_opt, *dt_opt, *ax_opt, *ay_opt, *ec_opt;
+    int* status;
+    double *dt_own;          // [batch][nmax]: dt_opt, or the handle's scratch where the caller takes none (the sums read it)
+    double *ec_own;
+    // bounds
+    double *w0, *lbw, *ubw, *lbg, *ubg;
+    // Jacobian
+    double *blocks, *grad_J, *grad_E;
+    // certificate
+    const double *g_in, *blocks_in, *grad_J_in, *grad_E_in, *lam_g, *lam_x, *lbw_in, *ubw_in, *lbg_in, *ubg_in;
+    double *r, *kkt;
+};
+__host__ __device__ inline int mcq_mt_ng(int N, int safe, int energy) { return N * (27 + 2 * safe) + 4 * (N - 1) + 5 + energy; }
+__host__ __device__ inline int mcq_mt_row0(int k, int safe) { return k * (27 + 2 * safe) + (k > 0 ? 4 * (k - 1) : 0); }
+__global__ void mcq_mintime_bounds_kernel(McqMintime M);
+__global__ void mcq_mintime_eval_kernel(McqMintime M);
+__global__ void mcq_mintime_sum_kernel(McqMintime M);
+__global__ void mcq_mintime_jac_kernel(McqMintime M);
+__global__ void mcq_mintime_kkt_kernel(McqMintime M);
+
 __global__ void mcq_fgen_bounds_kernel(McqFgen G);
 __global__ void mcq_fgen_mask_kernel(McqFgen G);
 __global__ void mcq_fgen_scan_kernel(McqFgen G);

@@ -3995,6 +3995,8 @@ __global__ void __launch_bounds__(MCQ_NT) mcq_spline_finish_kernel(McqSpline S)
 #include "mcq_fric.inc"
 // (and for mcq_fgen.inc: the generation of a friction map's cells)
 #include "mcq_fgen.inc"
+// (and for mcq_mintime.inc: the minimum-time NLP as functions of a decision vector)
+#include "mcq_mintime.inc"
 
 __global__ void __launch_bounds__(MCQ_NT) mcq_min_width_kernel(int nmax, const int* n_list, double* ref_all, double min_width, int* changed_out)
 {

@@ -122,6 +122,31 @@ FRIC_LINEAR, FRIC_GAUSS = 0, 1                      # MCQ_FRIC_*: the model mcq_
 FRIC_CENTRES_FIT, FRIC_CENTRES_MINTIME = 0, 1       # MCQ_FRIC_CENTRES_*: where the Gaussian model's bumps sit
 FGEN_NONFINITE, FGEN_FEW, FGEN_OVERFLOW, FGEN_GRID = 1, 2, 4, 8     # MCQ_FGEN_*: the status bits of the friction-map generation
 
+# ---- the minimum-time NLP (include/mcq.h "the minimum-time optimal-control problem") ----
+MINTIME_PARS = ("mass", "dragcoeff", "g", "v_max",
+                "wheelbase_front", "wheelbase_rear", "track_width_front", "track_width_rear", "cog_z", "I_z", "liftcoeff_front", "liftcoeff_rear",
+                "k_brake_front", "k_drive_front", "k_roll", "t_delta", "t_drive", "t_brake", "power_max", "f_drive_max", "f_brake_max", "delta_max",
+                "c_roll", "f_z0", "B_front", "C_front", "eps_front", "E_front", "B_rear", "C_rear", "eps_rear", "E_rear",
+                "width_opt", "mue", "penalty_F", "penalty_delta", "energy_limit", "ax_pos_safe", "ax_neg_safe", "ay_safe")      # mcq_mintime_pars, in order
+MT_BLOCK = 33           # MCQ_MT_BLOCK: row and column slots of a Jacobian block
+MT_FRICTION = {None: -1, "linear": FRIC_LINEAR, "gauss": FRIC_GAUSS}
+
+
+class McqMintimeOpts(ctypes.Structure):
+    _fields_ = [("friction", ctypes.c_int), ("n_gauss", ctypes.c_int), ("safe_traj", ctypes.c_int), ("limit_energy", ctypes.c_int),
+                ("pwr_behavior", ctypes.c_int)]
+
+
+class McqMintimeDims(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int) for k in ("nw", "ng", "off_x", "off_u", "off_xc", "stride_w", "rows_first", "rows_next", "row_colloc", "row_cont",
+                                            "row_power", "row_kamm", "row_roll", "row_pedal", "row_act", "row_safe", "row_periodic", "row_energy")] + \
+               [("tau", ctypes.c_double * 4), ("C", ctypes.c_double * 16), ("D", ctypes.c_double * 4), ("B", ctypes.c_double * 4)]
+
+
+class McqMintimeData(ctypes.Structure):
+    _fields_ = [("batch", ctypes.c_int), ("nmax", ctypes.c_int)] + \
+               [(k, ctypes.c_void_p) for k in ("n_list", "h", "kappa_cl", "w_tr_right_cl", "w_tr_left_cl", "pars", "w_mue", "center_dist", "w")]
+
 
 IQP_ROUND_CB = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int))
 
@@ -201,6 +226,11 @@ _ABI = {
     "mcq_f32_rows_device": (_ci, [_vp, _ci, _ci, _ci, _vp, _vp, _vp]),
     "mcq_f32_widen_device": (_ci, [_vp, _sz, _vp, _vp]),
     "mcq_f32_narrow_device": (_ci, [_vp, _sz, _vp, _vp]),
+    "mcq_mintime_layout": (_ci, [_ci, _P(McqMintimeOpts), _P(McqMintimeDims)]),
+    "mcq_mintime_bounds_device": (_ci, [_vp, _P(McqMintimeData), _P(McqMintimeOpts), _vp, _vp, _vp, _vp, _vp]),
+    "mcq_mintime_eval_device": (_ci, [_vp, _P(McqMintimeData), _P(McqMintimeOpts), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mcq_mintime_jac_device": (_ci, [_vp, _P(McqMintimeData), _P(McqMintimeOpts), _vp, _vp, _vp]),
+    "mcq_mintime_kkt_device": (_ci, [_vp, _P(McqMintimeData), _P(McqMintimeOpts), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 EXPORTED_SYMBOLS = tuple(_ABI)
 
@@ -1418,6 +1448,168 @@ class Engine:
             self.friction_model_device(tracks, rows - 1, qmax, dev.up(q), dev.up(qcnt), model, dev.up(w), d_out, n_gauss, centres,
                                        dev.up(center_dist), dev.up(n), dev.up(cnt), jmax)
             return dev.get(d_out)
+
+    # ---- the minimum-time NLP as functions of w (include/mcq.h; the reference's names and files on top of these: mintime.py) -----------------
+    @staticmethod
+    def mintime_opts(friction=None, n_gauss=0, safe_traj=False, limit_energy=False, pwr_behavior=False):
+        """mcq_mintime_opts from the reference's words: friction None / "linear" / "gauss" (optim_opts var_friction) or an MCQ_FRIC_* number.
+        pwr_behavior: NotImplementedError -- the 11-state powertrain model is not built."""
+        if pwr_behavior:
+            raise NotImplementedError("mintime: pwr_behavior (the powertrain's six thermal and charge states) is not implemented")
+        if friction in MT_FRICTION:
+            friction = MT_FRICTION[friction]
+        elif isinstance(friction, str):
+            raise ValueError("mintime: var_friction must be None, 'linear' or 'gauss', got %r" % (friction,))
+        return McqMintimeOpts(int(friction), int(n_gauss), int(bool(safe_traj)), int(bool(limit_energy)), 0)
+
+    def mintime_layout(self, N, **opt_kw):
+        """mcq_mintime_layout: nw, ng, the offsets in w and g, and the collocation constants tau [4], C [4, 4], D [4], B [4] as a dict."""
+        o, d = self.mintime_opts(**opt_kw), McqMintimeDims()
+        self._check(self.lib.mcq_mintime_layout(int(N), ctypes.byref(o), ctypes.byref(d)), "mcq_mintime_layout")
+        res = {k: getattr(d, k) for k, t in McqMintimeDims._fields_ if t is ctypes.c_int}
+        res.update(tau=np.array(d.tau), C=np.array(d.C).reshape(4, 4), D=np.array(d.D), B=np.array(d.B))
+        return res
+
+    @staticmethod
+    def mintime_sizes(nmax, opts):
+        """(5 + 24 nmax, ng of nmax): the widths of the w-shaped and g-shaped buffers of a launch."""
+        return 5 + 24 * int(nmax), int(nmax) * (27 + 2 * opts.safe_traj) + 4 * (int(nmax) - 1) + 5 + opts.limit_energy
+
+    @staticmethod
+    def mintime_data(batch, nmax, d_n, d_h, d_kappa, d_w_right, d_w_left, d_pars, d_w=None, d_w_mue=None, d_center_dist=None):
+        """mcq_mintime_data from device pointers (None where an entry does not read the array)."""
+        return McqMintimeData(int(batch), int(nmax), d_n or None, d_h or None, d_kappa or None, d_w_right, d_w_left, d_pars, d_w_mue or None,
+                              d_center_dist or None, d_w or None)
+
+    def mintime_bounds_device(self, data, opts, d_w0, d_lbw, d_ubw, d_lbg, d_ubg):
+        """mcq_mintime_bounds_device on device pointers.  Asynchronous."""
+        self._check(self.lib.mcq_mintime_bounds_device(self.h, ctypes.byref(data), ctypes.byref(opts), d_w0, d_lbw, d_ubw, d_lbg, d_ubg),
+                    "mcq_mintime_bounds_device")
+
+    def mintime_eval_device(self, data, opts, d_g, d_J, d_status, d_lap=None, d_energy=None, d_x=None, d_u=None, d_tf=None, d_dt=None, d_ax=None,
+                            d_ay=None, d_ec=None):
+        """mcq_mintime_eval_device on device pointers; every output but d_g, d_J, d_status may be None.  Asynchronous."""
+        self._check(self.lib.mcq_mintime_eval_device(self.h, ctypes.byref(data), ctypes.byref(opts), d_g, d_J, d_lap or None, d_energy or None,
+                                                     d_x or None, d_u or None, d_tf or None, d_dt or None, d_ax or None, d_ay or None, d_ec or None,
+                                                     d_status), "mcq_mintime_eval_device")
+
+    def mintime_jac_device(self, data, opts, d_blocks, d_grad_J, d_grad_energy=None):
+        """mcq_mintime_jac_device on device pointers: d_blocks [batch][nmax][33][33], d_grad_J and d_grad_energy [batch][5 + 24 nmax].  Asynchronous."""
+        self._check(self.lib.mcq_mintime_jac_device(self.h, ctypes.byref(data), ctypes.byref(opts), d_blocks, d_grad_J, d_grad_energy or None),
+                    "mcq_mintime_jac_device")
+
+    def mintime_kkt_device(self, data, opts, d_g, d_blocks, d_grad_J, d_grad_energy, d_lam_g, d_lam_x, d_lbw, d_ubw, d_lbg, d_ubg, d_r, d_kkt):
+        """mcq_mintime_kkt_device on device pointers: what the three entries above left on the device, and the multipliers.  Asynchronous."""
+        self._check(self.lib.mcq_mintime_kkt_device(self.h, ctypes.byref(data), ctypes.byref(opts), d_g, d_blocks, d_grad_J, d_grad_energy or None,
+                                                    d_lam_g, d_lam_x, d_lbw, d_ubw, d_lbg, d_ubg, d_r, d_kkt), "mcq_mintime_kkt_device")
+
+    def _mintime_up(self, dev, problems, opts, nmax, need_w, resident=None):
+        """The padded device arrays of a list of problems -- dicts of h [N], kappa_cl / w_tr_right_cl / w_tr_left_cl [N + 1], pars (a dict of
+        MINTIME_PARS or their 40 values), w [5 + 24 N], and with a friction model w_mue [4, N + 1, P] (and center_dist [N + 1]).  resident:
+        (d_w_mue, d_center_dist) device pointers in the friction entries' layout for these problems at this nmax, instead of the host arrays."""
+        if not problems:
+            raise ValueError("mintime: no problems")
+        Ns = np.array([np.asarray(q["h"]).shape[0] for q in problems], dtype=np.int32)
+        nmax = int(Ns.max()) if nmax is None else int(nmax)
+        if Ns.min() < 2 or Ns.max() > nmax:
+            raise ValueError("mintime: every problem needs 2 <= N <= nmax intervals (N = %s, nmax = %d)" % (Ns.tolist(), nmax))
+        batch, nwmax = len(problems), 5 + 24 * nmax
+        P = 0 if opts.friction < 0 else (2 if opts.friction == FRIC_LINEAR else 2 * opts.n_gauss + 2)
+        h, w = np.zeros((batch, nmax)), np.zeros((batch, nwmax))
+        closed = np.zeros((3, batch, nmax + 1))
+        pars = np.zeros((batch, len(MINTIME_PARS)))
+        wm, cd = np.zeros((batch, 4, nmax + 1, max(P, 1))), np.zeros((batch, nmax + 1))
+        for b, q in enumerate(problems):
+            N = int(Ns[b])
+            h[b, :N] = np.asarray(q["h"], dtype=np.float64)
+            for a, key in enumerate(("kappa_cl", "w_tr_right_cl", "w_tr_left_cl")):
+                v = np.asarray(q[key], dtype=np.float64)
+                if v.shape != (N + 1,):
+                    raise ValueError("mintime: %s must hold N + 1 = %d values" % (key, N + 1))
+                closed[a, b, :N + 1] = v
+            pars[b] = [q["pars"][k] for k in MINTIME_PARS] if isinstance(q["pars"], dict) else np.asarray(q["pars"], dtype=np.float64)
+            if need_w:
+                v = np.asarray(q["w"], dtype=np.float64)
+                if v.shape != (5 + 24 * N,):
+                    raise ValueError("mintime: w must hold 5 + 24 N = %d values" % (5 + 24 * N))
+                w[b, :5 + 24 * N] = v
+            if P and resident is None:
+                v = np.asarray(q["w_mue"], dtype=np.float64)
+                if v.shape != (4, N + 1, P):
+                    raise ValueError("mintime: w_mue must be [4, N + 1, %d]" % P)
+                wm[b, :, :N + 1] = v
+                if opts.friction == FRIC_GAUSS:
+                    cd[b, :N + 1] = np.asarray(q["center_dist"], dtype=np.float64)
+        d_wm, d_cd = resident if resident is not None else ((dev.up(wm), dev.up(cd)) if P else (None, None))
+        data = self.mintime_data(batch, nmax, dev.up(Ns), dev.up(h), dev.up(closed[0]), dev.up(closed[1]), dev.up(closed[2]), dev.up(pars),
+                                 dev.up(w) if need_w else None, d_wm, d_cd)
+        return data, Ns, nmax
+
+    def mintime_bounds_batch(self, problems, nmax=None, **opt_kw):
+        """w0, lbw, ubw [batch, 5 + 24 nmax], lbg, ubg [batch, ng of nmax] as the reference builds them (NaN past a problem's own sizes)."""
+        opts = self.mintime_opts(**opt_kw)
+        with self.scope() as dev:
+            data, Ns, nmax = self._mintime_up(dev, problems, opts, nmax, False)
+            nw, ng = self.mintime_sizes(nmax, opts)
+            d = [dev.out((len(Ns), nw)) for _ in range(3)] + [dev.out((len(Ns), ng)) for _ in range(2)]
+            self.mintime_bounds_device(data, opts, *d)
+            return dict(zip(("w0", "lbw", "ubw", "lbg", "ubg"), [dev.get(q) for q in d]), N=Ns)
+
+    def mintime_eval_batch(self, problems, nmax=None, resident=None, **opt_kw):
+        """g, J, the lap time, the energy and the reference's f_sol outputs of a list of problems in one launch (mcq_mintime_eval_device): a dict of
+        padded arrays g [batch, ng of nmax], J, lap_time, energy, status [batch], x_opt [batch, nmax + 1, 5], u_opt [batch, nmax, 4], tf_opt
+        [batch, nmax, 12], dt_opt, ax_opt, ay_opt, ec_opt [batch, nmax], N [batch].  resident: see _mintime_up."""
+        opts = self.mintime_opts(**opt_kw)
+        with self.scope() as dev:
+            data, Ns, nmax = self._mintime_up(dev, problems, opts, nmax, True, resident)
+            B, (nw, ng) = len(Ns), self.mintime_sizes(nmax, opts)
+            shapes = dict(g=(B, ng), J=(B,), lap_time=(B,), energy=(B,), x_opt=(B, nmax + 1, 5), u_opt=(B, nmax, 4), tf_opt=(B, nmax, 12),
+                          dt_opt=(B, nmax), ax_opt=(B, nmax), ay_opt=(B, nmax), ec_opt=(B, nmax))
+            d = {k: dev.out(v) for k, v in shapes.items()}
+            d_st = dev.out(B, np.int32)
+            self.mintime_eval_device(data, opts, d["g"], d["J"], d_st, d["lap_time"], d["energy"], d["x_opt"], d["u_opt"], d["tf_opt"], d["dt_opt"],
+                                     d["ax_opt"], d["ay_opt"], d["ec_opt"])
+            res = {k: dev.get(v) for k, v in d.items()}
+            res.update(status=dev.get(d_st), N=Ns)
+            return res
+
+    def mintime_jac_batch(self, problems, nmax=None, **opt_kw):
+        """The Jacobian of g in interval blocks [batch, nmax, 33, 33], grad_J and grad_energy [batch, 5 + 24 nmax] (mcq_mintime_jac_device)."""
+        opts = self.mintime_opts(**opt_kw)
+        with self.scope() as dev:
+            data, Ns, nmax = self._mintime_up(dev, problems, opts, nmax, True)
+            B, (nw, ng) = len(Ns), self.mintime_sizes(nmax, opts)
+            shapes = dict(blocks=(B, nmax, MT_BLOCK, MT_BLOCK), grad_J=(B, nw), grad_energy=(B, nw))
+            d = {k: dev.out(v) for k, v in shapes.items()}
+            self.mintime_jac_device(data, opts, d["blocks"], d["grad_J"], d["grad_energy"])
+            res = {k: dev.get(v) for k, v in d.items()}
+            res.update(N=Ns)
+            return res
+
+    def mintime_kkt_batch(self, problems, lam_g, lam_x, nmax=None, **opt_kw):
+        """The certificate of primal-dual points: bounds, evaluation, Jacobian and mcq_mintime_kkt_device chained on the device.  lam_g [ng_k] and
+        lam_x [nw_k] per problem.  Returns r [batch, 5 + 24 nmax] and kkt [batch, 3] (max |r|, the largest bound violation, the largest
+        complementarity product), with g, J, lap_time, status of the evaluation."""
+        opts = self.mintime_opts(**opt_kw)
+        with self.scope() as dev:
+            data, Ns, nmax = self._mintime_up(dev, problems, opts, nmax, True)
+            B, (nw, ng) = len(Ns), self.mintime_sizes(nmax, opts)
+            lg, lx = np.zeros((B, ng)), np.zeros((B, nw))
+            for b in range(B):
+                vg, vx = np.asarray(lam_g[b], dtype=np.float64), np.asarray(lam_x[b], dtype=np.float64)
+                if vx.shape != (5 + 24 * int(Ns[b]),) or vg.ndim != 1 or vg.shape[0] > ng:
+                    raise ValueError("mintime_kkt_batch: lam_x must hold nw values and lam_g ng values of its problem")
+                lg[b, :vg.shape[0]], lx[b, :vx.shape[0]] = vg, vx
+            bw = [dev.out((B, nw)) for _ in range(3)]
+            bg = [dev.out((B, ng)) for _ in range(2)]
+            d_g, d_J, d_lap, d_st = dev.out((B, ng)), dev.out(B), dev.out(B), dev.out(B, np.int32)
+            d_blk, d_gJ, d_gE = dev.out((B, nmax, MT_BLOCK, MT_BLOCK)), dev.out((B, nw)), dev.out((B, nw))
+            d_r, d_k = dev.out((B, nw)), dev.out((B, 3))
+            self.mintime_bounds_device(data, opts, bw[0], bw[1], bw[2], bg[0], bg[1])
+            self.mintime_eval_device(data, opts, d_g, d_J, d_st, d_lap)
+            self.mintime_jac_device(data, opts, d_blk, d_gJ, d_gE)
+            self.mintime_kkt_device(data, opts, d_g, d_blk, d_gJ, d_gE, dev.up(lg), dev.up(lx), bw[1], bw[2], bg[0], bg[1], d_r, d_k)
+            return dict(r=dev.get(d_r), kkt=dev.get(d_k), g=dev.get(d_g), J=dev.get(d_J), lap_time=dev.get(d_lap), status=dev.get(d_st), N=Ns)
 
     # ---- friction map generation (include/mcq.h "friction map generation"; the reference's names on top of these: friction.py) -------------
     def contains_points_device(self, paths, vmax, d_v, d_verts, d_radius, count, d_xy, d_inside, d_status, d_contour=None, d_contour_count=None):

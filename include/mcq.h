@@ -712,6 +712,103 @@ int mcq_friction_gen_device(mcq_handle* h, int tracks, int nmax, const int* n_li
                             const int* inside_right, int cmax, double* bound_r_out, double* bound_l_out, double* grid_out, int* count_out,
                             double* cells_out, int* status_out);
 
+/* ---- the minimum-time optimal-control problem: evaluate, differentiate, certify [REF opt_mintime_traj/src/opt_mintime.py:143-861] ----
+ * The reference's NLP -- double-track model, nx = 5 states [v, beta, omega_z, n, xi] scaled by [50, 0.5, 1, 5, 1], nu = 4 controls [delta, f_drive,
+ * f_brake, gamma_y] scaled by [0.5, 7500, 20000, 5000], Gauss-Legendre collocation of degree 3 over N intervals of a closed track -- as FUNCTIONS of
+ * a decision vector w: the constraint vector g, the objective J, the reference's f_sol outputs, the Jacobian of g, the gradients of J and of the
+ * energy sum, and the KKT residual of a primal-dual point.  No solver step, no Hessian, no powertrain states (pwr_behavior: MCQ_E_ARG), and not
+ * tph's nonreg_sampling / calc_head_curv_num: curvature and station steps are inputs.
+ *
+ * Layouts (csrc/mcq_mintime.inc; mcq_mintime_layout states them as numbers):
+ *   w  [nw = 5 + 24 N]: X_0 | per interval k: U_k (4), Xc_k,0 Xc_k,1 Xc_k,2 (5 each), X_k+1 (5)  ->  X_k at 24 k, U_k at 24 k + 5, Xc_k,j at 24 k + 9 + 5 j.
+ *   g  [ng = N (27 + 2 safe) + 4 (N - 1) + 5 + energy], per interval k in the reference's order: 15 collocation rows h_k f(Xc_k,j, U_k, kappa_j) - xp_j,
+ *      5 continuity rows, 1 power row, 4 Kamm rows (fl, fr, rl, rr), 1 roll-moment row, 1 pedal row, 4 actuator rows where k > 0, 2 safe-trajectory
+ *      rows where enabled; interval k starts at k (27 + 2 safe) + 4 max(k - 1, 0).  After the last interval: 5 periodicity rows X_0 - X_N, then the
+ *      energy row (sum of v_k f_drive_k dt_k) / 3.6e6 where enabled.
+ *   Curvature at collocation point j of interval k: kappa_cl[k] + tau_j (kappa_cl[k + 1] - kappa_cl[k]) -- CasADi's linear interpolant is NOT pinned bit
+ *      for bit.  The reference's quirks are kept: f_y with the constant mue under every friction model; path rows at X_k+1 with U_k and friction row
+ *      k + 1; actuator rows (U_k - U_k-1) / (h[k - 1] sigma), sigma = (1 - kappa_cl[k] n_k+1) / v_k+1; energy with the interval's START state; the pedal
+ *      row's lower bound -20000 / (7500 * 20000); the cyclic regularisation sum of (p_k - p_k+1)^2 with the last term wrapped to the first.
+ *   Jacobian blocks [batch][nmax][33][33], row-major: block k holds the 33 row slots of interval k in the order above (the 4 actuator and 2 safe slots
+ *      zero where absent) against the 33 column slots [X_k (5), U_k (4), Xc_k,0..2 (15), X_k+1 (5), U_k-1 (4)]: slots 0 .. 28 are w[24 k .. 24 k + 28].  The
+ *      periodicity rows (+1 at X_0, -1 at X_N) are constant and not stored; the energy row is the dense grad_energy.
+ *   Sums (J, lap time, energy) are taken in ONE order that depends on N alone: thread t of 256 adds intervals t, t + 256, .. in rising order, then a
+ *      binary tree over the 256 partial sums -- a problem's bits do not depend on the launch's company, the batch order or the buffers' width.
+ *
+ * mcq_mintime_pars: the entries of veh_params, vehicle_params_mintime, tire_params_mintime and optim_opts the model reads, ONE record per problem
+ *   (a DEVICE array [batch]), so that a sweep over masses or friction levels is one launch.  mcq_mintime_opts: friction -1 (the constant mue),
+ *   MCQ_FRIC_LINEAR or MCQ_FRIC_GAUSS (n_gauss 1 .. 15) for the Kamm rows; safe_traj, limit_energy: the optional rows; pwr_behavior must be 0.
+ * mcq_mintime_data: the DEVICE arrays of a launch, stated once for the four device entries.  n_list [batch] (NULL: all nmax) intervals per problem,
+ *   h [batch][nmax], kappa_cl / w_tr_right_cl / w_tr_left_cl [batch][nmax + 1] (the closed arrays: entry N repeats entry 0), w_mue [batch][4][nmax + 1][P]
+ *   (P = 2: slope, intercept; P = 2 n_gauss + 2) and center_dist [batch][nmax + 1] exactly as mcq_friction_grid_device / mcq_friction_gauss_device
+ *   emit them for tracks of nmax waypoints, w [batch][5 + 24 nmax].
+ *
+ * mcq_mintime_layout: host, pure.  N >= 2 (the reference's difference matrix degenerates at N = 1).  Also the collocation constants tau, C, D, B
+ *   as the kernels use them (computed once on the host; numpy.poly1d's construction to rounding).
+ * mcq_mintime_bounds_device: w0 (the flat guess v = 20 m/s), lbw, ubw [batch][5 + 24 nmax], lbg, ubg [batch][ng of nmax] as the reference builds them; the
+ *   n bounds from the widths and width_opt.  Entries past a problem's own nw / ng: NaN.
+ * mcq_mintime_eval_device: g [batch][ng of nmax], J, lap_time, energy [batch] (energy in kWh, the energy row's value, computed with or without the row),
+ *   x_opt [batch][nmax + 1][5], u_opt [batch][nmax][4], tf_opt [batch][nmax][12] (x, y, z of fl, fr, rl, rr at X_k+1), dt_opt, ax_opt, ay_opt, ec_opt
+ *   [batch][nmax] (ec in Ws), status [batch].  Any output but g, J and status may be NULL.
+ * mcq_mintime_jac_device: blocks, grad_J [batch][5 + 24 nmax], grad_energy (the same; may be NULL).  One lane per (evaluation point, direction): 36 lanes
+ *   per interval, a one-tangent dual number each.
+ * mcq_mintime_kkt_device: r = grad_J + J_g^T lam_g + lam_x [batch][5 + 24 nmax] under CasADi's sign convention L = f + lam_g . g + lam_x . w, from the blocks
+ *   and gradients of mcq_mintime_jac_device and g of mcq_mintime_eval_device; kkt_out [batch][3]: max |r|; the largest violation of lbw <= w <= ubw and
+ *   lbg <= g <= ubg (0 where none); the largest |lam * distance to the bound it belongs to| over FINITE bounds -- a positive multiplier belongs to the
+ *   upper bound, a negative one to the lower.  grad_energy is read with limit_energy only.
+ * Edges: outputs are always overwritten.  A NaN or inf in a problem's w or inputs gives NaN in the rows and outputs computed from it and in that problem's
+ *   sums and maxima (status MCQ_BAD_INPUT on the evaluation), and has no effect on another problem.  Rows, blocks and entries past a problem's own
+ *   N are NaN.  A problem whose n_list entry is below 2 or above nmax: status MCQ_BAD_INPUT, every output of that problem NaN.
+ * MCQ_E_ARG: N < 2 (layout), nmax < 2, batch <= 0, an unknown friction model, n_gauss outside 1 .. 15 with the Gaussian model, friction weights or
+ *   center_dist missing for the model, pwr_behavior != 0, NULL where an array is required; MCQ_E_TOO_LARGE: 5 + 24 nmax or the launch's blocks beyond
+ *   2^31 - 1, more than 65535 problems (they lie along the launches' second axis).  DEVICE pointers; asynchronous on the handle's stream. */
+#define MCQ_MT_NX 5
+#define MCQ_MT_NU 4
+#define MCQ_MT_BLOCK 33
+#define MCQ_MT_NPARS 40
+typedef struct mcq_mintime_pars {
+    double mass, dragcoeff, g, v_max;                                                              /* veh_params */
+    double wheelbase_front, wheelbase_rear, track_width_front, track_width_rear, cog_z, I_z;       /* vehicle_params_mintime */
+    double liftcoeff_front, liftcoeff_rear, k_brake_front, k_drive_front, k_roll, t_delta, t_drive, t_brake;
+    double power_max, f_drive_max, f_brake_max, delta_max;
+    double c_roll, f_z0, B_front, C_front, eps_front, E_front, B_rear, C_rear, eps_rear, E_rear;   /* tire_params_mintime */
+    double width_opt, mue, penalty_F, penalty_delta, energy_limit, ax_pos_safe, ax_neg_safe, ay_safe;   /* optim_opts */
+} mcq_mintime_pars;
+typedef struct mcq_mintime_opts {
+    int friction, n_gauss, safe_traj, limit_energy, pwr_behavior;
+} mcq_mintime_opts;
+typedef struct mcq_mintime_dims {
+    int nw, ng;
+    int off_x, off_u, off_xc, stride_w;            /* X_k at off_x + k stride_w, U_k at off_u + k stride_w, Xc_k,j at off_xc + k stride_w + 5 j */
+    int rows_first, rows_next;                     /* rows of interval 0, of every later interval: interval k >= 1 starts at rows_first + (k - 1) rows_next */
+    int row_colloc, row_cont, row_power, row_kamm, row_roll, row_pedal, row_act, row_safe;   /* within an interval; row_safe for k >= 1 (4 less at k = 0), -1 where absent */
+    int row_periodic, row_energy;                  /* in g; row_energy -1 where absent */
+    double tau[4], C[4][4], D[4], B[4];
+} mcq_mintime_dims;
+typedef struct mcq_mintime_data {
+    int batch, nmax;
+    const int* n_list;
+    const double* h;
+    const double* kappa_cl;
+    const double* w_tr_right_cl;
+    const double* w_tr_left_cl;
+    const mcq_mintime_pars* pars;
+    const double* w_mue;
+    const double* center_dist;
+    const double* w;
+} mcq_mintime_data;
+int mcq_mintime_layout(int N, const mcq_mintime_opts* opts, mcq_mintime_dims* dims_out);
+int mcq_mintime_bounds_device(mcq_handle* h, const mcq_mintime_data* data, const mcq_mintime_opts* opts, double* w0_out, double* lbw_out,
+                              double* ubw_out, double* lbg_out, double* ubg_out);
+int mcq_mintime_eval_device(mcq_handle* h, const mcq_mintime_data* data, const mcq_mintime_opts* opts, double* g_out, double* J_out,
+                            double* lap_time_out, double* energy_out, double* x_opt_out, double* u_opt_out, double* tf_opt_out, double* dt_opt_out,
+                            double* ax_opt_out, double* ay_opt_out, double* ec_opt_out, int* status_out);
+int mcq_mintime_jac_device(mcq_handle* h, const mcq_mintime_data* data, const mcq_mintime_opts* opts, double* blocks_out, double* grad_J_out,
+                           double* grad_energy_out);
+int mcq_mintime_kkt_device(mcq_handle* h, const mcq_mintime_data* data, const mcq_mintime_opts* opts, const double* g, const double* blocks,
+                           const double* grad_J, const double* grad_energy, const double* lam_g, const double* lam_x, const double* lbw,
+                           const double* ubw, const double* lbg, const double* ubg, double* r_out, double* kkt_out);
+
 /* Host-buffer entry for a UNIFORM batch (every track n waypoints): reftrack [batch][n][4], normvec [batch][n][2] or NULL,
  * scaling [batch][n] or NULL in host memory, results to host memory.  One asynchronous copy per array straight from / to the
  * caller's buffers -- no packing pass; buffers from mcq_host_alloc (pinned) are copied at PCIe speed, pageable ones go through
