@@ -1701,6 +1701,39 @@ extern "C" int mcq_mintime_kkt_device(mcq_handle* h, const mcq_mintime_data* dat
     return 0;
 }
 
+extern "C" int mcq_mintime_hess_device(mcq_handle* h, const mcq_mintime_data* data, const mcq_mintime_opts* opts, const double* lam_g,
+                                       const double* sigma, double* hblocks_out)
+{
+    McqMintime M;
+    if (int rc = mintime_record("mcq_mintime_hess_device", h, data, opts, true, M)) return rc;
+    if (!lam_g || !hblocks_out) {
+        g_err = "mcq_mintime_hess_device: bad argument";
+        return MCQ_E_ARG;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    M.lam_g = lam_g; M.sigma = sigma; M.hblocks = hblocks_out;
+    hipLaunchKernelGGL(mcq_mintime_hess_kernel, dim3((unsigned)data->nmax, data->batch), dim3(MCQ_MT_HESS_NT), 0, h->ws[0].stream, M);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// (reads n_list alone of the launch's arrays: h, kappa_cl and w may be NULL)
+extern "C" int mcq_mintime_hessvec_device(mcq_handle* h, const mcq_mintime_data* data, const mcq_mintime_opts* opts, const double* hblocks,
+                                          const double* v, int nvec, double* y_out)
+{
+    McqMintime M;
+    if (int rc = mintime_record("mcq_mintime_hessvec_device", h, data, opts, false, M)) return rc;
+    if (!hblocks || !v || nvec <= 0 || !y_out) {
+        g_err = "mcq_mintime_hessvec_device: bad argument";
+        return MCQ_E_ARG;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    M.hblocks_in = hblocks; M.v = v; M.nvec = nvec; M.y = y_out;
+    hipLaunchKernelGGL(mcq_mintime_hessvec_kernel, dim3(((unsigned)M.nwmax + 255) / 256, data->batch), dim3(256), 0, h->ws[0].stream, M);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // ---- device memory plumbing for callers that keep data resident between calls without a second HIP runtime in the
 //      process (the Python IQP driver): plain allocate / free / copy on the handle's device and stream ------------------
 extern "C" int mcq_device_alloc(mcq_handle* h, size_t bytes, void** out)

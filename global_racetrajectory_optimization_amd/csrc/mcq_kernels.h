@@ -527,9 +527,13 @@ struct McqFgen {
 };
 /* ---- the minimum-time NLP as functions of w (mcq_mintime_*_device; csrc/mcq_mintime.inc) [REF opt_mintime_traj/src/opt_mintime.py:143-861].
  *      Layouts: include/mcq.h.  Lane mappings: the evaluation one lane per (interval, evaluation point) -- 4 per interval, 64 intervals per workgroup;
- *      the Jacobian one lane per (interval, evaluation point, direction) -- 36 per interval, a one-tangent dual number each. ---- */
+ *      the Jacobian one lane per (interval, evaluation point, direction) -- 36 per interval, a one-tangent dual number each; the Hessian of the
+ *      Lagrangian a workgroup of 192 lanes per interval, one lane per (evaluation point, unordered pair of its 9 directions) -- 180 hyper-dual
+ *      evaluations; H v one lane per entry of w. ---- */
 #define MCQ_MT_EVAL_LANES 4
 #define MCQ_MT_JAC_LANES 36
+#define MCQ_MT_HESS_NT 192
+#define MCQ_MT_HESS_PAIRS 45
 struct McqMtColl {
     double tau[4], C[4][4], D[4], B[4];
 };
@@ -551,6 +555,10 @@ struct McqMintime {
     // certificate
     const double *g_in, *blocks_in, *grad_J_in, *grad_E_in, *lam_g, *lam_x, *lbw_in, *ubw_in, *lbg_in, *ubg_in;
     double *r, *kkt;
+    // Hessian of the Lagrangian (lam_g above), H v
+    const double *sigma, *hblocks_in, *v;
+    double *hblocks, *y;
+    int nvec;
 };
 __host__ __device__ inline int mcq_mt_ng(int N, int safe, int energy) { return N * (27 + 2 * safe) + 4 * (N - 1) + 5 + energy; }
 __host__ __device__ inline int mcq_mt_row0(int k, int safe) { return k * (27 + 2 * safe) + (k > 0 ? 4 * (k - 1) : 0); }
@@ -559,6 +567,8 @@ __global__ void mcq_mintime_eval_kernel(McqMintime M);
 __global__ void mcq_mintime_sum_kernel(McqMintime M);
 __global__ void mcq_mintime_jac_kernel(McqMintime M);
 __global__ void mcq_mintime_kkt_kernel(McqMintime M);
+__global__ void mcq_mintime_hess_kernel(McqMintime M);
+__global__ void mcq_mintime_hessvec_kernel(McqMintime M);
 
 __global__ void mcq_fgen_bounds_kernel(McqFgen G);
 __global__ void mcq_fgen_mask_kernel(McqFgen G);

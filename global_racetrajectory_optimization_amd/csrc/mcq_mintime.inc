@@ -2,7 +2,8 @@
 // include/mcq.h) [REF opt_mintime_traj/src/opt_mintime.py:143-861].  Part of the one translation unit (mcq_kernels.hip includes it).
 //
 // THE MODEL, ONCE: mt_model is the reference's double-track model (:284-441) as a function template over a scalar type T, instantiated with double
-// (mcq_mintime_eval_kernel) and with MtDual, a dual number of a value and ONE tangent (mcq_mintime_jac_kernel).  Statement order follows the
+// (mcq_mintime_eval_kernel), with MtDual, a dual number of a value and ONE tangent (mcq_mintime_jac_kernel), and with MtHyper, a hyper-dual number
+// of a value, two tangents and their mixed term (mcq_mintime_hess_kernel).  Statement order follows the
 // reference's expressions from left to right; the compiler may contract a * b + c.
 //
 // LANE MAPPINGS.  Evaluation: one lane per (interval k, evaluation point p): p = 0 .. 2 the collocation points (f_dyn at Xc_k,p with U_k), p = 3 the
@@ -12,6 +13,13 @@
 // intermediate (the model has about 40 of them live at the slip angles: 400 doubles against 512 registers of 32 bits, i.e. 256 doubles); one tangent
 // keeps the live set at twice the scalar model's, and a block's column slots become adjacent lanes' stores.  docs/NOTEBOOK.md "Mintime evaluation"
 // records the registers the compiler reports.
+//
+// Hessian of the Lagrangian (mcq_mintime_hess_kernel): one workgroup of 192 lanes per interval, one lane per (evaluation point p, unordered pair
+// of directions a <= b): 4 x 45 = 180 lanes, each ONE model evaluation with MtHyper, a hyper-dual number (value, two tangents, the mixed term).  Per
+// point only one scalar needs second derivatives -- the multiplier-weighted sum of the point's rows plus its quadrature share -- so a lane reduces
+// its rows' mixed terms to one double in LDS; after a barrier the 192 lanes store the block's 1089 entries in row-major order, each entry a pure
+// function of its unordered slot pair (so (r, c) and (c, r) carry the same bits), one writer each, no zero-fill pass.  docs/NOTEBOOK.md "Mintime
+// Hessian" records the mappings compiled and their registers.
 //
 // CasADi's interpolant is NOT pinned bit for bit: curvature at collocation point j is kappa_cl[k] + tau_j * (kappa_cl[k + 1] - kappa_cl[k]).
 
@@ -55,6 +63,41 @@ __device__ __forceinline__ double mt_val(double x) { return x; }
 __device__ __forceinline__ double mt_val(MtDual x) { return x.v; }
 __device__ __forceinline__ double mt_tan(double) { return 0.0; }
 __device__ __forceinline__ double mt_tan(MtDual x) { return x.d; }
+
+// a hyper-dual number: value, the tangents along two directions a and b, and the mixed second derivative
+struct MtHyper {
+    double v, a, b, ab;
+};
+__device__ __forceinline__ MtHyper mt_hyper(double v, double a, double b, double ab) { MtHyper r; r.v = v; r.a = a; r.b = b; r.ab = ab; return r; }
+__device__ __forceinline__ MtHyper operator+(MtHyper x, MtHyper y) { return mt_hyper(x.v + y.v, x.a + y.a, x.b + y.b, x.ab + y.ab); }
+__device__ __forceinline__ MtHyper operator-(MtHyper x, MtHyper y) { return mt_hyper(x.v - y.v, x.a - y.a, x.b - y.b, x.ab - y.ab); }
+__device__ __forceinline__ MtHyper operator*(MtHyper x, MtHyper y)
+{
+    return mt_hyper(x.v * y.v, x.a * y.v + x.v * y.a, x.b * y.v + x.v * y.b, x.ab * y.v + x.a * y.b + x.b * y.a + x.v * y.ab);
+}
+__device__ __forceinline__ MtHyper operator/(MtHyper x, MtHyper y)
+{
+    const double q = x.v / y.v, qa = (x.a - q * y.a) / y.v, qb = (x.b - q * y.b) / y.v;
+    return mt_hyper(q, qa, qb, (x.ab - qa * y.b - qb * y.a - q * y.ab) / y.v);
+}
+__device__ __forceinline__ MtHyper operator+(MtHyper x, double y) { return mt_hyper(x.v + y, x.a, x.b, x.ab); }
+__device__ __forceinline__ MtHyper operator+(double x, MtHyper y) { return mt_hyper(x + y.v, y.a, y.b, y.ab); }
+__device__ __forceinline__ MtHyper operator-(MtHyper x, double y) { return mt_hyper(x.v - y, x.a, x.b, x.ab); }
+__device__ __forceinline__ MtHyper operator-(double x, MtHyper y) { return mt_hyper(x - y.v, -y.a, -y.b, -y.ab); }
+__device__ __forceinline__ MtHyper operator*(MtHyper x, double y) { return mt_hyper(x.v * y, x.a * y, x.b * y, x.ab * y); }
+__device__ __forceinline__ MtHyper operator*(double x, MtHyper y) { return mt_hyper(x * y.v, x * y.a, x * y.b, x * y.ab); }
+__device__ __forceinline__ MtHyper operator/(MtHyper x, double y) { return mt_hyper(x.v / y, x.a / y, x.b / y, x.ab / y); }
+__device__ __forceinline__ MtHyper operator-(MtHyper x) { return mt_hyper(-x.v, -x.a, -x.b, -x.ab); }
+// f(x) from f, f' and f'' at the value
+__device__ __forceinline__ MtHyper mt_chain(MtHyper x, double f, double f1, double f2) { return mt_hyper(f, f1 * x.a, f1 * x.b, f1 * x.ab + f2 * (x.a * x.b)); }
+__device__ __forceinline__ MtHyper mt_sin(MtHyper x) { const double s = sin(x.v), c = cos(x.v); return mt_chain(x, s, c, -s); }
+__device__ __forceinline__ MtHyper mt_cos(MtHyper x) { const double s = sin(x.v), c = cos(x.v); return mt_chain(x, c, -s, -c); }
+__device__ __forceinline__ MtHyper mt_atan(MtHyper x) { const double r = 1.0 / (1.0 + x.v * x.v); return mt_chain(x, atan(x.v), r, -2.0 * x.v * (r * r)); }
+__device__ __forceinline__ MtHyper mt_exp(MtHyper x) { const double e = exp(x.v); return mt_chain(x, e, e, e); }
+// the second derivative of the branch taken (zero on the other; a NaN stays one)
+__device__ __forceinline__ MtHyper mt_pos(MtHyper x) { const double z = x.v != x.v ? x.v : 0.0; return x.v > 0.0 ? x : mt_hyper(z, z, z, z); }
+__device__ __forceinline__ MtHyper mt_neg(MtHyper x) { const double z = x.v != x.v ? x.v : 0.0; return x.v < 0.0 ? x : mt_hyper(z, z, z, z); }
+__device__ __forceinline__ double mt_val(MtHyper x) { return x.v; }
 
 template <class T>
 struct MtModel {
@@ -610,5 +653,160 @@ __global__ void __launch_bounds__(MCQ_NT) mcq_mintime_kkt_kernel(McqMintime M)
         M.kkt[3 * (size_t)b] = N ? rmax : NAN;
         M.kkt[3 * (size_t)b + 1] = N ? viol : NAN;
         M.kkt[3 * (size_t)b + 2] = N ? comp : NAN;
+    }
+}
+
+// ---- the Hessian of the Lagrangian in interval blocks: a workgroup per interval, one lane per (evaluation point, pair of directions) ----
+// the index of the unordered pair a <= b of 9 directions among the 45
+__device__ __forceinline__ int mt_pair(int a, int b) { return a * 9 - a * (a - 1) / 2 + (b - a); }
+// the regularisation's second derivative between controls i and j of one interval (the same between the two intervals' controls, negated)
+__device__ __forceinline__ double mt_reg2(const mcq_mintime_pars& P, int i, int j)
+{
+    const double cf[4] = {0.0, MT_FDS / 10000.0, MT_FBS / 10000.0, 0.0};
+    return i == 0 && j == 0 ? P.penalty_delta * (2.0 * MT_DELTAS * MT_DELTAS) : P.penalty_F * (2.0 * cf[i] * cf[j]);
+}
+
+__global__ void __launch_bounds__(MCQ_MT_HESS_NT) mcq_mintime_hess_kernel(McqMintime M)
+{
+    __shared__ double s_h[4][MCQ_MT_HESS_PAIRS];   // per point: the weighted scalar's second derivative along every pair of its 9 directions
+    __shared__ double s_dq[3][5], s_q[3];          // per collocation point: the quadrature term's gradient on its state, and the term
+    __shared__ int s_bad;
+    const int b = blockIdx.y, k = blockIdx.x, tid = threadIdx.x, N = mt_intervals(M, b), nmax = M.d.nmax, safe = M.o.safe_traj ? 1 : 0;
+    const int nn = MCQ_MT_BLOCK * MCQ_MT_BLOCK;
+    double* blk = M.hblocks + ((size_t)b * nmax + k) * nn;
+    if (k >= N) {                      // (the whole workgroup)
+        for (int e = tid; e < nn; e += MCQ_MT_HESS_NT) blk[e] = NAN;
+        return;
+    }
+    const size_t n1 = (size_t)nmax + 1;
+    const mcq_mintime_pars P = M.d.pars[b];
+    const double* w = M.d.w + (size_t)b * M.nwmax + 24 * (size_t)k;
+    // slots 29 .. 32: U_k-1, at k = 0 U_N-1 (the regularisation's wrapped term)
+    const double* wu = M.d.w + (size_t)b * M.nwmax + 24 * (size_t)(k > 0 ? k - 1 : N - 1) + 5;
+    const int row0 = mcq_mt_row0(k, safe), at = k > 0 ? 31 : 27;
+    const double* lam = M.lam_g + (size_t)b * M.ngmax + row0;
+    const double sg = M.sigma ? M.sigma[b] : 1.0;
+    const double lam_e = M.o.limit_energy ? M.lam_g[(size_t)b * M.ngmax + mcq_mt_row0(N, safe) + 5] : 0.0;
+    const double hk = M.d.h[(size_t)b * nmax + k], hp = k > 0 ? M.d.h[(size_t)b * nmax + k - 1] : 1.0;
+    const double ka = M.d.kappa_cl[b * n1 + k], kb = M.d.kappa_cl[b * n1 + k + 1];
+    const double ce = lam_e * (MT_VS * MT_FDS / 3600000.0);
+    // every input of the interval is finite, or the whole block is NaN: an input per lane
+    if (tid == 0) s_bad = 0;
+    __syncthreads();
+    double chk = 0.0;
+    if (tid < 29) chk = mt_chk(w[tid]);
+    else if (tid < 33) chk = mt_chk(wu[tid - 29]);
+    else if (tid < 60) chk = mt_chk(lam[tid - 33]);
+    else if (tid < 64) chk = k > 0 ? mt_chk(lam[27 + tid - 60]) : 0.0;
+    else if (tid < 66) chk = safe ? mt_chk(lam[at + tid - 64]) : 0.0;
+    else if (tid == 66) chk = mt_chk(hk) + mt_chk(hp) + mt_chk(ka) + mt_chk(kb) + mt_chk(sg) + mt_chk(lam_e);
+    if (chk != 0.0) s_bad = 1;
+    if (tid < 4 * MCQ_MT_HESS_PAIRS) {
+        const int p = tid / MCQ_MT_HESS_PAIRS, q = tid - MCQ_MT_HESS_PAIRS * p;
+        int da = 0, db = q;
+        while (db >= 9 - da) { db -= 9 - da; ++da; }
+        db += da;
+        // directions 0 .. 4: a state of the point (Xc_k,p, or X_k+1 at the path point), 5 .. 8: a control of U_k
+        const int xo = p < 3 ? 9 + 5 * p : 24, j = p < 3 ? p + 1 : 0;
+        const double kappa = p < 3 ? ka + M.c.tau[j] * (kb - ka) : ka;
+        MtHyper x[5], u[4];
+        for (int i = 0; i < 5; ++i) x[i] = mt_hyper(w[xo + i], da == i ? 1.0 : 0.0, db == i ? 1.0 : 0.0, 0.0);
+        for (int i = 0; i < 4; ++i) u[i] = mt_hyper(w[5 + i], da == 5 + i ? 1.0 : 0.0, db == 5 + i ? 1.0 : 0.0, 0.0);
+        MtModel<MtHyper> m;
+        mt_model(x, u, kappa, P, m);
+        double acc = 0.0;
+        if (p < 3) {
+            // the collocation rows' multipliers, and on the quadrature term sigma (the objective) and the energy row's share at the START state
+            for (int i = 0; i < 5; ++i) acc += lam[5 * p + i] * (hk * m.dx[i].ab);
+            acc += (sg + ce * (w[0] * w[6])) * (M.c.B[j] * m.sf.ab * hk);
+            if (q == 0) s_q[p] = M.c.B[j] * m.sf.v * hk;
+            if (da == db && da < 5) s_dq[p][da] = M.c.B[j] * m.sf.a * hk;
+        } else {
+            double up[4];
+            for (int i = 0; i < 4; ++i) up[i] = k > 0 ? wu[i] : 0.0;
+            MtHyper rows[13];
+            mt_path_rows(M, P, b, k, x, u, up, ka, hp, m, rows);
+            for (int i = 0; i < 7; ++i) acc += lam[20 + i] * rows[i].ab;
+            if (k > 0)
+                for (int i = 0; i < 4; ++i) acc += lam[27 + i] * rows[7 + i].ab;
+            if (safe)
+                for (int i = 0; i < 2; ++i) acc += lam[at + i] * rows[11 + i].ab;
+        }
+        s_h[p][q] = acc;
+    }
+    __syncthreads();
+    const bool bad = s_bad != 0;
+    const double dt = s_q[0] + s_q[1] + s_q[2];
+    // the actuator rows against U_k-1 in closed form: row i is (U_k[i] - U_k-1[i]) G, G = v_k+1 / (h[k - 1] (1 - kappa_cl[k] n_k+1))
+    const double den = 1.0 - ka * (w[27] * MT_NS);
+    const double g0 = MT_VS / (hp * den), g3 = (w[24] * MT_VS) * (ka * MT_NS) / (hp * (den * den));
+    for (int e = tid; e < nn; e += MCQ_MT_HESS_NT) {
+        const int er = e / MCQ_MT_BLOCK, ec = e - MCQ_MT_BLOCK * er, r = er < ec ? er : ec, c = er < ec ? ec : er;
+        // the groups of the slots: 0 X_k, 1 U_k, 2 .. 4 Xc_k,0..2, 5 X_k+1, 6 U_k-1, and the index inside
+        const int gr = r < 5 ? 0 : (r < 9 ? 1 : (r < 24 ? 2 + (r - 9) / 5 : (r < 29 ? 5 : 6)));
+        const int gc = c < 5 ? 0 : (c < 9 ? 1 : (c < 24 ? 2 + (c - 9) / 5 : (c < 29 ? 5 : 6)));
+        const int ir = r - (gr == 0 ? 0 : (gr == 1 ? 5 : (gr < 5 ? 9 + 5 * (gr - 2) : (gr == 5 ? 24 : 29))));
+        const int ic = c - (gc == 0 ? 0 : (gc == 1 ? 5 : (gc < 5 ? 9 + 5 * (gc - 2) : (gc == 5 ? 24 : 29))));
+        double v = 0.0;
+        if (gr == 0) {
+            // the energy's cross terms of the START state's speed: with f_drive, with the quadrature's states
+            if (r == 0 && c == 6) v = ce * dt;
+            else if (r == 0 && gc >= 2 && gc < 5) v = ce * w[6] * s_dq[gc - 2][ic];
+        } else if (gr == 1) {
+            if (gc == 1) {
+                const int pq = mt_pair(5 + ir, 5 + ic);
+                v = s_h[0][pq] + s_h[1][pq] + s_h[2][pq] + s_h[3][pq] + sg * mt_reg2(P, ir, ic);
+            } else if (gc < 5) {
+                v = s_h[gc - 2][mt_pair(ic, 5 + ir)] + (ir == 1 ? ce * w[0] * s_dq[gc - 2][ic] : 0.0);
+            } else if (gc == 5) {
+                v = s_h[3][mt_pair(ic, 5 + ir)];
+            } else {
+                v = -(sg * mt_reg2(P, ir, ic));
+            }
+        } else if (gr < 5) {
+            if (gc == gr) v = s_h[gr - 2][mt_pair(ir, ic)];
+        } else if (gr == 5) {
+            if (gc == 5) v = s_h[3][mt_pair(ir, ic)];
+            else if (k > 0 && ir == 0) v = -(lam[27 + ic] * g0);
+            else if (k > 0 && ir == 3) v = -(lam[27 + ic] * g3);
+        } else {
+            v = sg * mt_reg2(P, ir, ic);
+        }
+        blk[e] = bad ? NAN : v;
+    }
+}
+
+// ---- y = H v from the blocks: a lane per entry of w, the block that holds the entry at 24 k + slot first, then the other, slots rising ----
+__global__ void __launch_bounds__(MCQ_NT) mcq_mintime_hessvec_kernel(McqMintime M)
+{
+    const int b = blockIdx.y, N = mt_intervals(M, b), nmax = M.d.nmax, nw = N ? 5 + 24 * N : 0;
+    const int i = blockIdx.x * MCQ_NT + threadIdx.x;
+    if (i >= M.nwmax) return;
+    const int nn = MCQ_MT_BLOCK * MCQ_MT_BLOCK;
+    const double* blocks = M.hblocks_in + (size_t)b * nmax * nn;
+    int k = i / 24, c = i - 24 * k;
+    // up to two blocks hold the entry: (block, slot)
+    int kb[2] = {-1, -1}, cb[2] = {0, 0};
+    if (i >= nw) {
+        // (past the problem's own entries: nothing is read)
+    } else if (c < 5) {
+        if (k < N) { kb[0] = k; cb[0] = c; }
+        if (k >= 1) { kb[1] = k - 1; cb[1] = 24 + c; }
+    } else {
+        kb[0] = k; cb[0] = c;
+        if (c < 9) { kb[1] = k + 1 < N ? k + 1 : 0; cb[1] = 24 + c; }
+    }
+    for (int t = 0; t < M.nvec; ++t) {
+        const double* v = M.v + ((size_t)b * M.nvec + t) * M.nwmax;
+        double acc = 0.0;
+        for (int s = 0; s < 2; ++s) {
+            if (kb[s] < 0) continue;
+            const double* row = blocks + (size_t)kb[s] * nn + cb[s] * MCQ_MT_BLOCK;       // (a block is symmetric: the slot's row is its column)
+            const double* vk = v + 24 * (size_t)kb[s];
+            const double* vu = v + 24 * (size_t)(kb[s] > 0 ? kb[s] - 1 : N - 1) + 5;
+            for (int a = 0; a < 29; ++a) acc += row[a] * vk[a];
+            for (int a = 0; a < 4; ++a) acc += row[29 + a] * vu[a];
+        }
+        M.y[((size_t)b * M.nvec + t) * M.nwmax + i] = i < nw ? acc : NAN;
     }
 }

@@ -231,6 +231,8 @@ _ABI = {
     "mcq_mintime_eval_device": (_ci, [_vp, _P(McqMintimeData), _P(McqMintimeOpts), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mcq_mintime_jac_device": (_ci, [_vp, _P(McqMintimeData), _P(McqMintimeOpts), _vp, _vp, _vp]),
     "mcq_mintime_kkt_device": (_ci, [_vp, _P(McqMintimeData), _P(McqMintimeOpts), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mcq_mintime_hess_device": (_ci, [_vp, _P(McqMintimeData), _P(McqMintimeOpts), _vp, _vp, _vp]),
+    "mcq_mintime_hessvec_device": (_ci, [_vp, _P(McqMintimeData), _P(McqMintimeOpts), _vp, _vp, _ci, _vp]),
 }
 EXPORTED_SYMBOLS = tuple(_ABI)
 
@@ -1610,6 +1612,62 @@ class Engine:
             self.mintime_jac_device(data, opts, d_blk, d_gJ, d_gE)
             self.mintime_kkt_device(data, opts, d_g, d_blk, d_gJ, d_gE, dev.up(lg), dev.up(lx), bw[1], bw[2], bg[0], bg[1], d_r, d_k)
             return dict(r=dev.get(d_r), kkt=dev.get(d_k), g=dev.get(d_g), J=dev.get(d_J), lap_time=dev.get(d_lap), status=dev.get(d_st), N=Ns)
+
+    def mintime_hess_device(self, data, opts, d_lam_g, d_sigma, d_hblocks):
+        """mcq_mintime_hess_device on device pointers: d_lam_g [batch][ng of nmax], d_sigma [batch] or None (1), d_hblocks [batch][nmax][33][33].
+        Asynchronous."""
+        self._check(self.lib.mcq_mintime_hess_device(self.h, ctypes.byref(data), ctypes.byref(opts), d_lam_g, d_sigma or None, d_hblocks),
+                    "mcq_mintime_hess_device")
+
+    def mintime_hessvec_device(self, data, opts, d_hblocks, d_v, nvec, d_y):
+        """mcq_mintime_hessvec_device on device pointers: d_v and d_y [batch][nvec][5 + 24 nmax].  Asynchronous."""
+        self._check(self.lib.mcq_mintime_hessvec_device(self.h, ctypes.byref(data), ctypes.byref(opts), d_hblocks, d_v, int(nvec), d_y),
+                    "mcq_mintime_hessvec_device")
+
+    @staticmethod
+    def _mintime_lam(Ns, lam_g, sigma, ng):
+        """lam_g (one vector per problem, at most ng values) and sigma (None, or one number per problem) as padded arrays [batch, ng], [batch]"""
+        B = len(Ns)
+        lg = np.zeros((B, ng))
+        for b in range(B):
+            vg = np.asarray(lam_g[b], dtype=np.float64)
+            if vg.ndim != 1 or vg.shape[0] > ng:
+                raise ValueError("mintime: lam_g must hold the ng values of its problem")
+            lg[b, :vg.shape[0]] = vg
+        sg = None if sigma is None else np.ascontiguousarray(np.broadcast_to(np.asarray(sigma, dtype=np.float64), (B,)))
+        return lg, sg
+
+    def mintime_hess_batch(self, problems, lam_g, sigma=None, nmax=None, **opt_kw):
+        """The Hessian of the Lagrangian sigma J + lam_g . g in interval blocks hblocks [batch, nmax, 33, 33] (mcq_mintime_hess_device; the slots and the
+        k = 0 rule: include/mcq.h; mintime.hessian_coo assembles them).  lam_g [ng_k] per problem, sigma None (1) or one number per problem."""
+        opts = self.mintime_opts(**opt_kw)
+        with self.scope() as dev:
+            data, Ns, nmax = self._mintime_up(dev, problems, opts, nmax, True)
+            B, (nw, ng) = len(Ns), self.mintime_sizes(nmax, opts)
+            lg, sg = self._mintime_lam(Ns, lam_g, sigma, ng)
+            d_h = dev.out((B, nmax, MT_BLOCK, MT_BLOCK))
+            self.mintime_hess_device(data, opts, dev.up(lg), None if sg is None else dev.up(sg), d_h)
+            return dict(hblocks=dev.get(d_h), N=Ns)
+
+    def mintime_hessvec_batch(self, problems, lam_g, v, sigma=None, nmax=None, **opt_kw):
+        """y = H v for the vectors v [nvec, nw_k] of every problem (the same nvec for all): the Hessian blocks and mcq_mintime_hessvec_device chained on
+        the device.  Returns y [batch, nvec, 5 + 24 nmax] (NaN past a problem's own nw) and hblocks."""
+        opts = self.mintime_opts(**opt_kw)
+        with self.scope() as dev:
+            data, Ns, nmax = self._mintime_up(dev, problems, opts, nmax, True)
+            B, (nw, ng) = len(Ns), self.mintime_sizes(nmax, opts)
+            lg, sg = self._mintime_lam(Ns, lam_g, sigma, ng)
+            vs = [np.atleast_2d(np.asarray(q, dtype=np.float64)) for q in v]
+            nvec = vs[0].shape[0] if vs else 0
+            vv = np.zeros((B, max(nvec, 1), nw))
+            for b in range(B):
+                if len(vs) != B or vs[b].shape != (nvec, 5 + 24 * int(Ns[b])):
+                    raise ValueError("mintime_hessvec_batch: v must hold [nvec, nw] values per problem, the same nvec for all")
+                vv[b, :, :vs[b].shape[1]] = vs[b]
+            d_h, d_y = dev.out((B, nmax, MT_BLOCK, MT_BLOCK)), dev.out((B, max(nvec, 1), nw))
+            self.mintime_hess_device(data, opts, dev.up(lg), None if sg is None else dev.up(sg), d_h)
+            self.mintime_hessvec_device(data, opts, d_h, dev.up(vv), nvec, d_y)
+            return dict(y=dev.get(d_y), hblocks=dev.get(d_h), N=Ns)
 
     # ---- friction map generation (include/mcq.h "friction map generation"; the reference's names on top of these: friction.py) -------------
     def contains_points_device(self, paths, vmax, d_v, d_verts, d_radius, count, d_xy, d_inside, d_status, d_contour=None, d_contour_count=None):

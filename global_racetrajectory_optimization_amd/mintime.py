@@ -122,6 +122,40 @@ def jacobian_coo(blocks, N, safe_traj=False, grad_energy=None):
     return sp.coo_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=(ng, nw))
 
 
+def hessian_slots(N, k):
+    """the entries of w behind the 33 slots of Hessian block k: slots 0 .. 28 are w[24 k ..], slots 29 .. 32 are U_k-1 -- at k = 0 U_N-1"""
+    return np.concatenate((24 * k + np.arange(29), 24 * ((k - 1) % N) + 5 + np.arange(4)))
+
+
+def hessian_coo(hblocks, N, triangle="full"):
+    """The Hessian blocks [>= N, 33, 33] of one problem (Engine.mintime_hess_batch) -> the Hessian of the Lagrangian as a scipy.sparse COO matrix
+    [nw, nw] in the reference's numbering of w.  The overlaps of neighbouring blocks are added (COO duplicates sum on conversion), slots 29 .. 32 of
+    block 0 go to U_N-1.  triangle "full", or "lower" (CasADi's hess_lag output is a triangle; rows >= columns here)."""
+    import scipy.sparse as sp
+    if triangle not in ("full", "lower"):
+        raise ValueError("hessian_coo: triangle must be 'full' or 'lower'")
+    hblocks = np.asarray(hblocks)[:N]
+    nw = 5 + 24 * N
+    rows, cols, vals = [], [], []
+    for k in range(N):
+        idx = hessian_slots(N, k)
+        r, c = np.nonzero(hblocks[k])
+        if triangle == "lower":
+            keep = idx[r] >= idx[c]
+            r, c = r[keep], c[keep]
+        rows.append(idx[r])
+        cols.append(idx[c])
+        vals.append(hblocks[k][r, c])
+    A = sp.coo_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=(nw, nw))
+    A.sum_duplicates()
+    return A
+
+
+def lagrangian_hessian(out, b=0, triangle="full"):
+    """The Hessian of problem b of Engine.mintime_hess_batch's (or mintime_hessvec_batch's) result as a sparse matrix (hessian_coo)."""
+    return hessian_coo(out["hblocks"][b], int(out["N"][b]), triangle)
+
+
 def certificate(out, b=0):
     """The KKT maxima of problem b of Engine.mintime_kkt_batch's result as a dictionary."""
     k = out["kkt"][b]

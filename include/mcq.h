@@ -716,8 +716,9 @@ int mcq_friction_gen_device(mcq_handle* h, int tracks, int nmax, const int* n_li
  * The reference's NLP -- double-track model, nx = 5 states [v, beta, omega_z, n, xi] scaled by [50, 0.5, 1, 5, 1], nu = 4 controls [delta, f_drive,
  * f_brake, gamma_y] scaled by [0.5, 7500, 20000, 5000], Gauss-Legendre collocation of degree 3 over N intervals of a closed track -- as FUNCTIONS of
  * a decision vector w: the constraint vector g, the objective J, the reference's f_sol outputs, the Jacobian of g, the gradients of J and of the
- * energy sum, and the KKT residual of a primal-dual point.  No solver step, no Hessian, no powertrain states (pwr_behavior: MCQ_E_ARG), and not
- * tph's nonreg_sampling / calc_head_curv_num: curvature and station steps are inputs.
+ * energy sum, the KKT residual of a primal-dual point, the Hessian of the Lagrangian and its products with vectors.  No solver step, no
+ * factorisation, no powertrain states (pwr_behavior: MCQ_E_ARG), and not tph's nonreg_sampling / calc_head_curv_num: curvature and station steps
+ * are inputs.
  *
  * Layouts (csrc/mcq_mintime.inc; mcq_mintime_layout states them as numbers):
  *   w  [nw = 5 + 24 N]: X_0 | per interval k: U_k (4), Xc_k,0 Xc_k,1 Xc_k,2 (5 each), X_k+1 (5)  ->  X_k at 24 k, U_k at 24 k + 5, Xc_k,j at 24 k + 9 + 5 j.
@@ -732,13 +733,24 @@ int mcq_friction_gen_device(mcq_handle* h, int tracks, int nmax, const int* n_li
  *   Jacobian blocks [batch][nmax][33][33], row-major: block k holds the 33 row slots of interval k in the order above (the 4 actuator and 2 safe slots
  *      zero where absent) against the 33 column slots [X_k (5), U_k (4), Xc_k,0..2 (15), X_k+1 (5), U_k-1 (4)]: slots 0 .. 28 are w[24 k .. 24 k + 28].  The
  *      periodicity rows (+1 at X_0, -1 at X_N) are constant and not stored; the energy row is the dense grad_energy.
+ *   Hessian blocks [batch][nmax][33][33], row-major, symmetric bit for bit: H(w, sigma, lam_g) = sigma hess J + sum_i lam_g[i] hess g_i (CasADi's
+ *      hess_lag; the certificate's signs) is the sum over the intervals of S_k^T (hess phi_k) S_k, block k = hess phi_k over the SAME 33 column slots,
+ *        phi_k = sum over the rows r of interval k that exist of lam_g[row0(k) + r] g_k,r
+ *              + sigma (dt_k + penalty_delta (d_k-1 - d_k)^2 + penalty_F (F_k-1 - F_k)^2) + lam_g[row_energy] ec_k / 3.6e6 (with limit_energy only),
+ *      d = 0.5 U[0], F = U[1] 7500 / 10000 + U[2] 20000 / 10000, k - 1 cyclic.  AT k = 0 SLOTS 29 .. 32 STAND FOR U_N-1: they carry the
+ *      regularisation's wrapped term alone (interval 0 has no actuator rows) -- the one place where the slots differ in meaning from the Jacobian's;
+ *      at N = 2 each block then holds one of the two equal terms, as J does.  Continuity and periodicity rows are linear and contribute nothing.
+ *      The overlaps (X_k+1 / the next block's X_k, U_k / the next block's U_k-1 slots) are the consumer's to add, as the certificate reads a column
+ *      from up to two Jacobian blocks.  The reference's quirks stay: the constant mue in f_y, the path rows at X_k+1 with U_k and friction row k + 1,
+ *      sigma of the actuator rows with kappa_cl[k], the energy with the START state (its cross terms between X_k[0], U_k[1] and Xc_k,j); the safe
+ *      rows take the second derivative of the branch of max / min taken.
  *   Sums (J, lap time, energy) are taken in ONE order that depends on N alone: thread t of 256 adds intervals t, t + 256, .. in rising order, then a
  *      binary tree over the 256 partial sums -- a problem's bits do not depend on the launch's company, the batch order or the buffers' width.
  *
  * mcq_mintime_pars: the entries of veh_params, vehicle_params_mintime, tire_params_mintime and optim_opts the model reads, ONE record per problem
  *   (a DEVICE array [batch]), so that a sweep over masses or friction levels is one launch.  mcq_mintime_opts: friction -1 (the constant mue),
  *   MCQ_FRIC_LINEAR or MCQ_FRIC_GAUSS (n_gauss 1 .. 15) for the Kamm rows; safe_traj, limit_energy: the optional rows; pwr_behavior must be 0.
- * mcq_mintime_data: the DEVICE arrays of a launch, stated once for the four device entries.  n_list [batch] (NULL: all nmax) intervals per problem,
+ * mcq_mintime_data: the DEVICE arrays of a launch, stated once for the device entries.  n_list [batch] (NULL: all nmax) intervals per problem,
  *   h [batch][nmax], kappa_cl / w_tr_right_cl / w_tr_left_cl [batch][nmax + 1] (the closed arrays: entry N repeats entry 0), w_mue [batch][4][nmax + 1][P]
  *   (P = 2: slope, intercept; P = 2 n_gauss + 2) and center_dist [batch][nmax + 1] exactly as mcq_friction_grid_device / mcq_friction_gauss_device
  *   emit them for tracks of nmax waypoints, w [batch][5 + 24 nmax].
@@ -756,6 +768,15 @@ int mcq_friction_gen_device(mcq_handle* h, int tracks, int nmax, const int* n_li
  *   and gradients of mcq_mintime_jac_device and g of mcq_mintime_eval_device; kkt_out [batch][3]: max |r|; the largest violation of lbw <= w <= ubw and
  *   lbg <= g <= ubg (0 where none); the largest |lam * distance to the bound it belongs to| over FINITE bounds -- a positive multiplier belongs to the
  *   upper bound, a negative one to the lower.  grad_energy is read with limit_energy only.
+ * mcq_mintime_hess_device: the Hessian blocks from lam_g [batch][ng of nmax] and sigma [batch] (NULL: 1).  A workgroup per interval, one lane per
+ *   (evaluation point, unordered pair of its 9 directions): 180 hyper-dual evaluations; every entry has one writer.  Block k is NaN entirely when an
+ *   input of interval k is not finite -- its 33 slots of w, h[k] (and h[k - 1] where k > 0), kappa_cl[k], kappa_cl[k + 1], the multiplier of one of
+ *   its existing rows, sigma, the energy row's multiplier where enabled -- and no other block is affected.  Multipliers of periodicity rows, of
+ *   absent rows and of a disabled energy row are not read.
+ * mcq_mintime_hessvec_device: y = H v for nvec vectors per problem, v and y [batch][nvec][5 + 24 nmax], from the blocks.  A lane per entry of w in ONE
+ *   order: the products of the block that holds entry 24 k + s at slot s, slots rising, then those of the other block that holds it (block k - 1
+ *   for a state of X_k, block k + 1 -- block 0 after the last -- for a control); X_N lies in block N - 1 alone.  Reads n_list alone of the launch's
+ *   arrays (h, kappa_cl, w may be NULL).  Entries past a problem's own nw: NaN.  nvec <= 0: MCQ_E_ARG.
  * Edges: outputs are always overwritten.  A NaN or inf in a problem's w or inputs gives NaN in the rows and outputs computed from it and in that problem's
  *   sums and maxima (status MCQ_BAD_INPUT on the evaluation), and has no effect on another problem.  Rows, blocks and entries past a problem's own
  *   N are NaN.  A problem whose n_list entry is below 2 or above nmax: status MCQ_BAD_INPUT, every output of that problem NaN.
@@ -808,6 +829,10 @@ int mcq_mintime_jac_device(mcq_handle* h, const mcq_mintime_data* data, const mc
 int mcq_mintime_kkt_device(mcq_handle* h, const mcq_mintime_data* data, const mcq_mintime_opts* opts, const double* g, const double* blocks,
                            const double* grad_J, const double* grad_energy, const double* lam_g, const double* lam_x, const double* lbw,
                            const double* ubw, const double* lbg, const double* ubg, double* r_out, double* kkt_out);
+int mcq_mintime_hess_device(mcq_handle* h, const mcq_mintime_data* data, const mcq_mintime_opts* opts, const double* lam_g, const double* sigma,
+                            double* hblocks_out);
+int mcq_mintime_hessvec_device(mcq_handle* h, const mcq_mintime_data* data, const mcq_mintime_opts* opts, const double* hblocks, const double* v,
+                               int nvec, double* y_out);
 
 /* Host-buffer entry for a UNIFORM batch (every track n waypoints): reftrack [batch][n][4], normvec [batch][n][2] or NULL,
  * scaling [batch][n] or NULL in host memory, results to host memory.  One asynchronous copy per array straight from / to the
