@@ -53,6 +53,19 @@ struct Scratch {
     size_t bytes = 0;
 };
 
+// One sliced mcq_solve_device call -- or several over the very same buffers -- whose slices nothing has joined yet: what each slice writes
+// (alpha, curv_error, status, info: its own rows), what the call reads (reftrack, normvec, scaling: whole), the end of its latest launch per stream.
+struct Range {
+    const char *lo = nullptr, *hi = nullptr;        // [lo, hi); empty where the caller passed no such array
+    bool meets(const Range& o) const { return lo < o.hi && o.lo < hi; }
+    bool operator==(const Range& o) const { return lo == o.lo && hi == o.hi; }
+};
+struct SliceCall {
+    Range wr[2][4], rd[3];
+    hipEvent_t end[2] = {nullptr, nullptr};         // created on first use, kept with the slot
+};
+#define MCQ_SLICE_CALLS 16
+
 struct mcq_handle {
     int device = 0;
     Workspace ws[2];
@@ -108,7 +121,33 @@ struct mcq_handle {
     hipEvent_t ev_up[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr}, ev_down[2] = {nullptr, nullptr};
     hipEvent_t ev_slice[16] = {};      // mcq_solve_host / mcq_solve_batch in slices: upload / kernel done, per slice
     int last_upload_direct = 0;         // the last host-buffer batch went up without the packing pass (mcq_last_upload_was_direct)
+    // mcq_solve_device in two slices (solve_device_sliced): the calls whose two streams have not been joined since
+    int cus = 256;                      // compute units of the device (mcq_create); the MI355X's where the runtime does not say
+    SliceCall sl[MCQ_SLICE_CALLS];
+    int sl_count = 0;
+    int sl_batch = 0, sl_n = 0;         // the shape of the calls in sl[]: the same split and the same workspace rows per slice
+    bool sl_fast_ok = false;            // nothing but sliced calls has been enqueued on the handle since the last full join
+    // (two names for events of sl[], not owned)
+    hipEvent_t sl_last1 = nullptr;      // end of the latest slice on ws[1].stream; != nullptr: ws[0].stream has not waited for it yet
+    hipEvent_t sl_time1 = nullptr;      // != nullptr: the last timed launch was a sliced call, and this is the end of its slice on ws[1].stream
+    hipEvent_t sl_join = nullptr;       // the full join: ws[1].stream behind ws[0].stream
+    hipEvent_t ev_span1 = nullptr;      // mcq_timing_end: the span's end on ws[1].stream
+    bool stream_given = false;          // mcq_stream has handed ws[0].stream out: the caller may enqueue on it what the handle does not see
 };
+
+// ws[0].stream BEHIND EVERYTHING the handle has enqueued: the one stream every entry but the sliced mcq_solve_device works on.  A pending slice
+// on ws[1].stream is waited for first (on the device; nothing pending: no call at all), and the next sliced call joins both ways before it
+// launches, because what the caller of this function enqueues is not in its record.  Only solve_device_sliced, the comm stream's waits,
+// mcq_timing_end and creation / destruction take the raw streams.
+static hipStream_t compute_stream(mcq_handle* h)
+{
+    if (h->sl_last1) {
+        if (hipStreamWaitEvent(h->ws[0].stream, h->sl_last1, 0) != hipSuccess) (void)hipStreamSynchronize(h->ws[1].stream);
+        h->sl_last1 = nullptr;
+    }
+    h->sl_fast_ok = false;
+    return h->ws[0].stream;
+}
 
 // ---- the one error path of the HIP calls ----------------------------------------------------------------------------------------
 // the message callers and tests match on: "<expr> failed: <hip error> (<file>:<line>)"
@@ -145,7 +184,7 @@ static void drain(mcq_handle* h)
 static int grow(mcq_handle* h, Scratch& s, size_t bytes)
 {
     if (bytes <= s.bytes) return 0;
-    HIP_TRY(hipStreamSynchronize(h->ws[0].stream));
+    HIP_TRY(hipStreamSynchronize(compute_stream(h)));
     (void)hipFree(s.p);
     s = Scratch();
     HIP_TRY(hipMalloc(&s.p, bytes));
@@ -215,6 +254,13 @@ extern "C" int mcq_create(int device_id, mcq_handle** out)
         const char* e = getenv("MCQ_POISON");
         h->poison = e && e[0] == '1';
     }
+#ifdef __HIPCC__        // (the tests' interpreter build -- g++, every stream synchronous -- has no device to ask)
+    {
+        int cus = 0;
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_id) == hipSuccess && cus > 0) h->cus = cus;
+        else (void)hipGetLastError();
+    }
+#endif
     hipError_t e = hipStreamCreate(&h->ws[0].stream);
     for (int k = 0; k < 5 && e == hipSuccess; ++k) e = hipEventCreate(&h->ev[k]);
     if (e != hipSuccess) {
@@ -289,6 +335,8 @@ extern "C" void mcq_destroy(mcq_handle* h)
     for (int k = 0; k < 5; ++k) if (h->ev[k]) (void)hipEventDestroy(h->ev[k]);
     for (int k = 0; k < 2; ++k) if (h->ev_span[k]) (void)hipEventDestroy(h->ev_span[k]);
     for (int k = 0; k < 2; ++k) if (h->ev_st[k]) (void)hipEventDestroy(h->ev_st[k]);
+    for (SliceCall& c : h->sl) for (hipEvent_t e : c.end) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : {h->sl_join, h->ev_span1}) if (e) (void)hipEventDestroy(e);
     if (h->ws[0].stream) (void)hipStreamDestroy(h->ws[0].stream);
     delete h;
 }
@@ -345,14 +393,14 @@ static void ensure_gi(mcq_handle* h, size_t batch, size_t nmax)
     const size_t per2 = MCQ_GI_SLOT_DOUBLES(nmax, nmax) * sizeof(double);
     slots = std::max(slots, w.gi_slots);
     slots = (int)std::min<size_t>((size_t)slots, cap_bytes / per2);
-    (void)hipStreamSynchronize(w.stream);
+    (void)hipStreamSynchronize(compute_stream(h));
     (void)hipFree(w.gi);
     w.gi = nullptr;
     w.gi_slots = w.gi_nmax = 0;
     h->gi_bytes = 0;
     slots = alloc_slots(&w.gi, slots, per2);
     if (slots < 1) { h->gi_none_nmax = nmax; return; }
-    if (h->poison) (void)hipMemsetAsync(w.gi, 0xff, (size_t)slots * per2, w.stream);
+    if (h->poison) (void)hipMemsetAsync(w.gi, 0xff, (size_t)slots * per2, compute_stream(h));
     w.gi_slots = slots;
     w.gi_nmax = (int)nmax;
     h->gi_bytes = (long long)((size_t)slots * per2);
@@ -368,14 +416,14 @@ static int ensure_gi_small(mcq_handle* h, size_t batch, size_t nmax)
         const size_t per = MCQ_GI_SLOT_DOUBLES(nmax, gi_small_qcap(nmax)) * sizeof(double);
         const size_t cap_bytes = std::max(gi_byte_cap(), (size_t)8 << 30);
         slots = (int)std::min<size_t>((size_t)slots, cap_bytes / per);
-        (void)hipStreamSynchronize(h->ws[0].stream);
+        (void)hipStreamSynchronize(compute_stream(h));
         (void)hipFree(h->gis);
         h->gis = nullptr;
         h->gis_slots = h->gis_nmax = 0;
         h->gis_bytes = 0;
         slots = alloc_slots(&h->gis, slots, per);
         if (slots >= 1) {
-            if (h->poison) (void)hipMemsetAsync(h->gis, 0xff, (size_t)slots * per, h->ws[0].stream);
+            if (h->poison) (void)hipMemsetAsync(h->gis, 0xff, (size_t)slots * per, compute_stream(h));
             h->gis_slots = slots;
             h->gis_nmax = (int)nmax;
             h->gis_bytes = (long long)((size_t)slots * per);
@@ -398,7 +446,7 @@ static int ensure_workspace(mcq_handle* h, int which, size_t batch, size_t nmax)
         if (which == 0) ensure_gi(h, batch, nmax);
         return 0;
     }
-    HIP_TRY(hipStreamSynchronize(w.stream));
+    HIP_TRY(hipStreamSynchronize(which == 0 ? compute_stream(h) : w.stream));
     free_workspace(h, which);
     const size_t l_bytes = elems * MCQ_LLD * sizeof(double), vec_bytes = elems * MCQ_NVEC * sizeof(double),
                  z_bytes = (elems + batch * (size_t)MCQ_KMAX * MCQ_KMAX) * sizeof(double),
@@ -445,7 +493,7 @@ static int ensure_staging(mcq_handle* h, int which, size_t batch, size_t nmax)
     Staging& s = h->stage[which];
     const size_t elems = batch * nmax;
     if (elems <= s.elems && batch <= s.batch) return 0;
-    HIP_TRY(hipStreamSynchronize(h->ws[0].stream));
+    HIP_TRY(hipStreamSynchronize(compute_stream(h)));
     if (which == 1) {       // (the pipeline's copy streams: ensure_pipe has created them)
         HIP_TRY(hipStreamSynchronize(h->cs_in));
         HIP_TRY(hipStreamSynchronize(h->cs_out));
@@ -464,10 +512,10 @@ static int ensure_staging(mcq_handle* h, int which, size_t batch, size_t nmax)
         HIP_TRY(hipMalloc((void**)&h->d_info, batch * sizeof(mcq_info)));
         HIP_TRY(hipMalloc((void**)&h->d_org, batch * 2 * sizeof(double)));
         if (h->poison) {
-            HIP_TRY(hipMemsetAsync(s.ref, 0xff, elems * 4 * sizeof(double), h->ws[0].stream));
-            HIP_TRY(hipMemsetAsync(s.nv, 0xff, elems * 2 * sizeof(double), h->ws[0].stream));
-            HIP_TRY(hipMemsetAsync(s.sc, 0xff, elems * sizeof(double), h->ws[0].stream));
-            HIP_TRY(hipMemsetAsync(s.alpha, 0xff, elems * sizeof(double), h->ws[0].stream));
+            HIP_TRY(hipMemsetAsync(s.ref, 0xff, elems * 4 * sizeof(double), compute_stream(h)));
+            HIP_TRY(hipMemsetAsync(s.nv, 0xff, elems * 2 * sizeof(double), compute_stream(h)));
+            HIP_TRY(hipMemsetAsync(s.sc, 0xff, elems * sizeof(double), compute_stream(h)));
+            HIP_TRY(hipMemsetAsync(s.alpha, 0xff, elems * sizeof(double), compute_stream(h)));
         }
     }
     s.elems = elems;
@@ -542,7 +590,7 @@ static int fill_batch(mcq_handle* h, McqBatch& B, const mcq_opts& o, Workspace& 
 static int launch(mcq_handle* h, McqBatch& B, const mcq_opts& o, Workspace& w)
 {
     const bool first = &w == &h->ws[0];
-    hipStream_t st = w.stream;
+    hipStream_t st = first ? compute_stream(h) : w.stream;
     if (int rc = fill_batch(h, B, o, w)) return rc;
     // warm start: only the working sets mcq_relinearise_device carried over for exactly this batch layout
     B.warm = (first && o.warm_start > 0 && h->state2_valid && !B.prep_only && h->state2_batch == B.batch && h->state2_nmax == B.nmax)
@@ -568,11 +616,150 @@ static int launch(mcq_handle* h, McqBatch& B, const mcq_opts& o, Workspace& w)
     HIP_TRY(hipGetLastError());
     if (first) HIP_TRY(hipEventRecord(h->ev[3], st));
     if (first) HIP_TRY(hipEventRecord(h->ev[4], st));
-    if (first) h->timing_valid = true;
+    if (first) { h->timing_valid = true; h->sl_time1 = nullptr; }
     if (first && h->span_open && !sp) ++h->span_launches;       // (a shortest-path launch has never been counted: docs/NOTEBOOK.md, "Host API")
     return 0;
 }
 static int launch(mcq_handle* h, McqBatch& B, const mcq_opts& o) { return launch(h, B, o, h->ws[0]); }
+
+// ---- mcq_solve_device in TWO SLICES, ordered slice by slice -----------------------------------------------------------------------------
+// A launch of more workgroups than the device holds at once ends with its slowest slot: 1024 problems on 512 slots take ~10.3 ms for ~9.4 ms of
+// mean load, and the next call's launch, in the same stream, may not start in between (docs/NOTEBOOK.md R6.3).  So problems [0, b) go as one
+// launch on ws[0].stream and [b, batch) as one on ws[1].stream, both over their own rows of workspace 0 (McqBatch.pb0, as mcq_solve_host's
+// slices), and a LATER call's slice j is ordered behind this call's slice j only -- by stream order: while the stragglers of one launch finish,
+// the other stream's launch fills the slots they have left.  Results are bitwise those of the one launch: the problems are independent.
+//
+// What keeps this correct is the record h->sl[] of the sliced calls since the last FULL JOIN (each stream waits for the other's last event).
+// A call may skip the join only if it has the record's shape -- the same split, the same workspace rows per slice -- and, by interval checks
+// on addresses, touches nothing the OTHER stream of a recorded call may still be working on (slice_conflict).  Everything else joins first,
+// which is always correct and merely forfeits the overlap: another shape, an overlap, a full record, anything enqueued through compute_stream()
+// in between.  Calls over the very same buffers share one entry (the later call's events stand for both, by stream order), so a loop over one
+// set of buffers, or over two in turn, never fills the record; entries whose launches have ended make room when a new one is needed.
+static int device_slice_min(const mcq_handle* h)
+{
+    if (const char* e = getenv("MCQ_DEVICE_SLICE_MIN")) return std::max(atoi(e), 2);        // (the tests slice batches of two to eight)
+    // More than one residency round (two workgroups per CU): a batch the device holds at once has no tail to fill, and an isolated call of
+    // exactly 512 problems on 256 CUs takes 5.79 ms as two launches of 256 against 5.46 ms as one (docs/NOTEBOOK.md)
+    return 2 * h->cus + 1;
+}
+
+static Range rows_of(const void* p, size_t r0, size_t r1, size_t row_bytes)
+{
+    Range r;
+    if (p) { r.lo = (const char*)p + r0 * row_bytes; r.hi = (const char*)p + r1 * row_bytes; }
+    return r;
+}
+
+// what the two slices [0, b) and [b, batch) of B write, and what the call reads
+static void slice_ranges(const McqBatch& B, int b, SliceCall& c)
+{
+    const size_t n = (size_t)B.nmax, bt = (size_t)B.batch;
+    for (int j = 0; j < 2; ++j) {
+        const size_t r0 = j ? (size_t)b : 0, r1 = j ? bt : (size_t)b;
+        c.wr[j][0] = rows_of(B.alpha, r0, r1, n * sizeof(double));
+        c.wr[j][1] = rows_of(B.curv_err, r0, r1, sizeof(double));
+        c.wr[j][2] = rows_of(B.status, r0, r1, sizeof(int));
+        c.wr[j][3] = rows_of(B.info, r0, r1, sizeof(mcq_info));
+    }
+    c.rd[0] = rows_of(B.ref, 0, bt, n * 4 * sizeof(double));
+    c.rd[1] = rows_of(B.nv, 0, bt, n * 2 * sizeof(double));
+    c.rd[2] = rows_of(B.sc, 0, bt, n * sizeof(double));
+}
+
+// May slice j of the new call `c` run while slice 1 - j of the recorded call `old` does?  Not if it writes what that one writes, and -- the
+// reads are kept whole, not per slice -- not if either call reads what the other writes.  (Slice j behind `old`'s slice j: stream order.)
+static bool slice_conflict(const SliceCall& c, const SliceCall& old)
+{
+    for (int j = 0; j < 2; ++j)
+        for (const Range& w : c.wr[j]) {
+            for (const Range& ow : old.wr[1 - j]) if (w.meets(ow)) return true;
+            for (const Range& r : old.rd) if (w.meets(r)) return true;
+        }
+    for (const Range& r : c.rd)
+        for (int j = 0; j < 2; ++j)
+            for (const Range& ow : old.wr[j]) if (r.meets(ow)) return true;
+    return false;
+}
+
+static bool same_buffers(const SliceCall& a, const SliceCall& b)
+{
+    for (int j = 0; j < 2; ++j) for (int k = 0; k < 4; ++k) if (!(a.wr[j][k] == b.wr[j][k])) return false;
+    for (int k = 0; k < 3; ++k) if (!(a.rd[k] == b.rd[k])) return false;
+    return true;
+}
+
+// (the tests' interpreter build has no hipEventQuery; its streams are synchronous: whatever was enqueued has ended)
+static bool event_done(hipEvent_t e)
+{
+#ifdef __HIPCC__
+    const hipError_t q = hipEventQuery(e);
+    if (q != hipSuccess) (void)hipGetLastError();       // (hipErrorNotReady is no error of the handle's)
+    return q == hipSuccess;
+#else
+    (void)e;
+    return true;
+#endif
+}
+
+static int solve_device_sliced(mcq_handle* h, McqBatch& B, const mcq_opts& o)
+{
+    if (!h->ws[1].stream) HIP_TRY(hipStreamCreate(&h->ws[1].stream));
+    if (!h->sl_join) HIP_TRY(hipEventCreate(&h->sl_join));
+    if (int rc = fill_batch(h, B, o, h->ws[0])) return rc;
+    B.warm = nullptr;
+    h->state2_valid = false;
+    const int b = (B.batch + 1) / 2;
+    SliceCall c;
+    slice_ranges(B, b, c);
+    bool join = !h->sl_fast_ok || B.batch != h->sl_batch || B.nmax != h->sl_n;
+    for (int k = 0; k < h->sl_count && !join; ++k) join = slice_conflict(c, h->sl[k]);
+    int slot = -1;
+    for (int k = 0; k < h->sl_count && !join && slot < 0; ++k) if (same_buffers(c, h->sl[k])) slot = k;
+    if (!join && slot < 0 && h->sl_count == MCQ_SLICE_CALLS) {
+        // room: the entries whose launches have ended on both streams go (their events stay with their slots)
+        int kept = 0;
+        for (int k = 0; k < h->sl_count; ++k)
+            if (!(event_done(h->sl[k].end[0]) && event_done(h->sl[k].end[1]))) std::swap(h->sl[kept++], h->sl[k]);
+        h->sl_count = kept;
+        join = kept == MCQ_SLICE_CALLS;
+    }
+    hipStream_t s0 = h->ws[0].stream, s1 = h->ws[1].stream;
+    if (join) {
+        // the full join: ws[0].stream behind the last slice on ws[1].stream (compute_stream), ws[1].stream behind ws[0].stream as it is now
+        s0 = compute_stream(h);
+        HIP_TRY(hipEventRecord(h->sl_join, s0));
+        HIP_TRY(hipStreamWaitEvent(s1, h->sl_join, 0));
+        h->sl_count = 0;
+        h->sl_batch = B.batch;
+        h->sl_n = B.nmax;
+        h->sl_fast_ok = true;
+    }
+    if (slot < 0 || join) slot = h->sl_count++;
+    SliceCall& e = h->sl[slot];
+    for (int j = 0; j < 2; ++j) if (!e.end[j]) HIP_TRY(hipEventCreate(&e.end[j]));
+    c.end[0] = e.end[0];
+    c.end[1] = e.end[1];
+    e = c;
+    if (getenv("MCQ_DEVICE_SLICE_TRACE")) fprintf(stderr, "mcq_solve_device: two slices, %s, %d in the record\n", join ? "joined" : "overlapped", h->sl_count);
+    // slice 0 carries the event timing of launch(): mcq_last_timing reads slice 1's end next to it
+    McqBatch S = B;
+    HIP_TRY(hipEventRecord(h->ev[0], s0));
+    HIP_TRY(hipEventRecord(h->ev[1], s0));
+    HIP_TRY(hipEventRecord(h->ev[2], s0));
+    hipLaunchKernelGGL(mcq_solve_kernel, dim3(b), dim3(256), 0, s0, S);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->ev[3], s0));
+    HIP_TRY(hipEventRecord(h->ev[4], s0));
+    HIP_TRY(hipEventRecord(e.end[0], s0));
+    S.pb0 = b;
+    hipLaunchKernelGGL(mcq_solve_kernel, dim3(B.batch - b), dim3(256), 0, s1, S);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(e.end[1], s1));
+    h->sl_last1 = h->sl_time1 = e.end[1];
+    h->timing_valid = true;
+    if (h->span_open) ++h->span_launches;       // one per CALL: span / launches stays the average device time per step
+    return 0;
+}
 
 extern "C" int mcq_solve_device(mcq_handle* h, int batch, int n, const double* reftrack, const double* normvec,
                                 const double* scaling, double kappa_bound, double w_veh, const mcq_opts* opts,
@@ -587,7 +774,18 @@ extern "C" int mcq_solve_device(mcq_handle* h, int batch, int n, const double* r
     int rc = ensure_workspace(h, 0, (size_t)batch, (size_t)n);
     if (rc) return rc;
     McqBatch B = make_batch(batch, n, nullptr, reftrack, normvec, scaling, alpha_out, curv_err_out, status_out, info_out, kappa_bound, w_veh);
-    return launch(h, B, o);
+    // One launch ($MCQ_DEVICE_ONE_LAUNCH=1: always, the A/B knob) for what has no tail to fill or is tied to ws[0].stream: a batch below the
+    // threshold, a warm start that applies (state2), the shortest path (its assembly kernel precedes the solve), MCQ_ALG_GI (its small slots
+    // are sized for one launch's resident workgroups), a handle whose stream the caller holds (mcq_stream).  mcq_solve_device_f32 and
+    // mcq_solve_device_f32_rows stay with the one launch too: their conversions run on ws[0].stream around the solve, and config 5's 8192
+    // problems per GPU -- sixteen residency rounds -- amortise the tail.
+    const bool warm = o.warm_start > 0 && h->state2_valid && h->state2_batch == batch && h->state2_nmax == n;
+    const char* one = getenv("MCQ_DEVICE_ONE_LAUNCH");
+    if (batch < device_slice_min(h) || warm || o.objective != MCQ_OBJ_MIN_CURV || o.algorithm == MCQ_ALG_GI || h->stream_given || (one && one[0] == '1')) {
+        if (getenv("MCQ_DEVICE_SLICE_TRACE")) fprintf(stderr, "mcq_solve_device: one launch\n");
+        return launch(h, B, o);
+    }
+    return solve_device_sliced(h, B, o);
 }
 
 // grid of the streaming conversions: four values per work-item, 4096 workgroups at most
@@ -599,14 +797,14 @@ static dim3 convert_grid(size_t count)
 
 static int widen_launch(mcq_handle* h, const float* src, double* dst, size_t count)
 {
-    hipLaunchKernelGGL(mcq_widen_kernel, convert_grid(count), dim3(256), 0, h->ws[0].stream, src, dst, count);
+    hipLaunchKernelGGL(mcq_widen_kernel, convert_grid(count), dim3(256), 0, compute_stream(h), src, dst, count);
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
 static int narrow_launch(mcq_handle* h, const double* src, float* dst, size_t count)
 {
-    hipLaunchKernelGGL(mcq_narrow_kernel, convert_grid(count), dim3(256), 0, h->ws[0].stream, src, dst, count);
+    hipLaunchKernelGGL(mcq_narrow_kernel, convert_grid(count), dim3(256), 0, compute_stream(h), src, dst, count);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -644,7 +842,7 @@ extern "C" int mcq_solve_device_f32(mcq_handle* h, int batch, int n, const float
 // one wave per track (mcq_widen_rows_kernel): fp64 rows [x, y, w_r, w_l] from float rows in either layout
 static int widen_rows_launch(mcq_handle* h, int batch, int n, int layout, const float* d_rows, const double* d_origin, double* d_out)
 {
-    hipLaunchKernelGGL(mcq_widen_rows_kernel, dim3((unsigned)batch), dim3(64), 0, h->ws[0].stream, d_rows, d_origin, d_out, n, layout);
+    hipLaunchKernelGGL(mcq_widen_rows_kernel, dim3((unsigned)batch), dim3(64), 0, compute_stream(h), d_rows, d_origin, d_out, n, layout);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -778,7 +976,7 @@ extern "C" int mcq_normals_crossing_device(mcq_handle* h, int batch, int nmax, c
         return MCQ_E_ARG;
     }
     HIP_TRY(hipSetDevice(h->device));
-    hipLaunchKernelGGL(mcq_normals_crossing_kernel, dim3(batch), dim3(256), 0, h->ws[0].stream, nmax, n_list, reftrack, normvec,
+    hipLaunchKernelGGL(mcq_normals_crossing_kernel, dim3(batch), dim3(256), 0, compute_stream(h), nmax, n_list, reftrack, normvec,
                        horizon, crossing_out);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -818,7 +1016,7 @@ extern "C" int mcq_relinearise_device(mcq_handle* h, int batch, int nmax, const 
     h->state2_valid = true;
     h->state2_batch = batch;
     h->state2_nmax = nmax;
-    hipLaunchKernelGGL(mcq_relinearise_kernel, dim3(batch), dim3(256), 0, h->ws[0].stream, R);
+    hipLaunchKernelGGL(mcq_relinearise_kernel, dim3(batch), dim3(256), 0, compute_stream(h), R);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -855,10 +1053,10 @@ static int vel_profile_launch(mcq_handle* h, int batch, int n, int nmax, const i
     V.scratch = (double*)h->vel.p; V.vx_out = vx_out; V.lap_time = lap_time_out;
     F.loc_gg = loc_gg; F.v_start = v_start; F.v_end = v_end;
     const dim3 grid((batch + 63) / 64), block(64);
-    if (closed && !loc_gg) hipLaunchKernelGGL(mcq_vel_profile_kernel, grid, block, 0, h->ws[0].stream, V);
-    else if (closed) hipLaunchKernelGGL(mcq_vel_profile_locgg_kernel, grid, block, 0, h->ws[0].stream, F);
-    else if (!loc_gg) hipLaunchKernelGGL(mcq_vel_profile_open_kernel, grid, block, 0, h->ws[0].stream, F);
-    else hipLaunchKernelGGL(mcq_vel_profile_open_locgg_kernel, grid, block, 0, h->ws[0].stream, F);
+    if (closed && !loc_gg) hipLaunchKernelGGL(mcq_vel_profile_kernel, grid, block, 0, compute_stream(h), V);
+    else if (closed) hipLaunchKernelGGL(mcq_vel_profile_locgg_kernel, grid, block, 0, compute_stream(h), F);
+    else if (!loc_gg) hipLaunchKernelGGL(mcq_vel_profile_open_kernel, grid, block, 0, compute_stream(h), F);
+    else hipLaunchKernelGGL(mcq_vel_profile_open_locgg_kernel, grid, block, 0, compute_stream(h), F);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -943,7 +1141,7 @@ extern "C" int mcq_raceline_device(mcq_handle* h, int batch, int nmax, const int
     McqRace Q;
     memset(&Q, 0, sizeof(Q));
     fill_race(Q, h, batch, nmax, n_in, reftrack, normvec, alpha, stepsize, mmax, raceline_out, psi_out, kappa_out, el_lengths_out, m_out, status_out);
-    hipLaunchKernelGGL(mcq_raceline_kernel, dim3(batch), dim3(256), 0, h->ws[0].stream, Q);
+    hipLaunchKernelGGL(mcq_raceline_kernel, dim3(batch), dim3(256), 0, compute_stream(h), Q);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -963,7 +1161,7 @@ extern "C" int mcq_raceline_device_ends(mcq_handle* h, int batch, int nmax, cons
     if (rc) return rc;
     if (!psi) {     // legal for a launch of rings only: the flags are read back (the one blocking path of this entry)
         std::vector<int> flags((size_t)batch);
-        HIP_TRY(hipStreamSynchronize(h->ws[0].stream));
+        HIP_TRY(hipStreamSynchronize(compute_stream(h)));
         HIP_TRY(hipMemcpy(flags.data(), closed, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost));
         for (int k = 0; k < batch; ++k)
             if (flags[k] == 0) {
@@ -975,7 +1173,7 @@ extern "C" int mcq_raceline_device_ends(mcq_handle* h, int batch, int nmax, cons
     memset(&E, 0, sizeof(E));
     fill_race(E.Q, h, batch, nmax, n_in, reftrack, normvec, alpha, stepsize, mmax, raceline_out, psi_out, kappa_out, el_lengths_out, m_out, status_out);
     E.closed = closed; E.psi = psi;
-    hipLaunchKernelGGL(mcq_raceline_ends_kernel, dim3(batch), dim3(256), 0, h->ws[0].stream, E);
+    hipLaunchKernelGGL(mcq_raceline_ends_kernel, dim3(batch), dim3(256), 0, compute_stream(h), E);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1004,7 +1202,7 @@ extern "C" int mcq_trajectory_device(mcq_handle* h, int batch, int m, int mmax, 
     T.ggv = ggv; T.ng = ggv ? n_ggv : 0; T.axm = ax_max_machines; T.nam = ax_max_machines ? n_machines : 0;
     T.curvlim = curvlim;
     T.traj = traj_out; T.t_out = t_out; T.length = length_out; T.limits = limits_out; T.flags = flags_out;
-    hipLaunchKernelGGL(mcq_trajectory_kernel, dim3(batch), dim3(64), 0, h->ws[0].stream, T);
+    hipLaunchKernelGGL(mcq_trajectory_kernel, dim3(batch), dim3(64), 0, compute_stream(h), T);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1059,7 +1257,7 @@ extern "C" int mcq_bound_dists_device(mcq_handle* h, int tracks, int nmax, const
     P.samples = a.at<double>(h->bound.p, 0); P.pts = a.at<double>(h->bound.p, 1); P.cum = a.at<double>(h->bound.p, 2);
     P.side_status = a.at<int>(h->bound.p, 3);
     P.min_dists = min_dists_out; P.min_dist = min_dist_out; P.nb_out = nb_out; P.bound_out = bound_out; P.status = status_out;
-    hipStream_t st = h->ws[0].stream;
+    hipStream_t st = compute_stream(h);
     hipLaunchKernelGGL(mcq_bound_points_kernel, dim3(2 * tracks), dim3(256), 0, st, P);
     HIP_TRY(hipGetLastError());
     const int block = 256 * MCQ_BD_S;
@@ -1106,7 +1304,7 @@ extern "C" int mcq_spline_fit_device(mcq_handle* h, int tracks, int nmax, const 
     P.work_per = fit_work_per(mimax, k, nkmax);
     P.nk_out = nk_out; P.knots_out = knots_out; P.coef_out = coef_out; P.fp_out = fp_out; P.ier_out = ier_out; P.mi_out = mi_out;
     P.pts_out = pts_out; P.status = status_out;
-    hipLaunchKernelGGL(mcq_spline_fit_kernel, dim3(tracks), dim3(256), 0, h->ws[0].stream, P);
+    hipLaunchKernelGGL(mcq_spline_fit_kernel, dim3(tracks), dim3(256), 0, compute_stream(h), P);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1140,7 +1338,7 @@ extern "C" int mcq_spline_approx_device(mcq_handle* h, int tracks, int nmax, con
     S.npts = a.at<int>(h->spl.p, 4);
     S.ref_out = reftrack_out; S.m_out = m_out; S.ct_out = closest_t_out; S.dist_out = dists_out; S.dev_out = dev_out;
     S.nonmono_out = nonmono_out; S.status = status_out;
-    hipStream_t st = h->ws[0].stream;
+    hipStream_t st = compute_stream(h);
     hipLaunchKernelGGL(mcq_spline_length_kernel, dim3(tracks), dim3(256), 0, st, S);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(mcq_spline_search_kernel, dim3((nmax + 1 + 255) / 256, tracks), dim3(256), 0, st, S);
@@ -1158,7 +1356,7 @@ extern "C" int mcq_min_width_device(mcq_handle* h, int batch, int nmax, const in
         return MCQ_E_ARG;
     }
     HIP_TRY(hipSetDevice(h->device));
-    hipLaunchKernelGGL(mcq_min_width_kernel, dim3(batch), dim3(256), 0, h->ws[0].stream, nmax, n_list, reftrack_io, min_width, changed_out);
+    hipLaunchKernelGGL(mcq_min_width_kernel, dim3(batch), dim3(256), 0, compute_stream(h), nmax, n_list, reftrack_io, min_width, changed_out);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1190,7 +1388,7 @@ extern "C" int mcq_export_device(mcq_handle* h, int tracks, int nmax, const int*
     X.vec = h->ws[0].vec;
     X.ltpl = ltpl_out; X.idx = idx_out; X.len_out = spline_lengths_out; X.s_ref_out = s_ref_out; X.total_out = spline_total_out;
     X.status = status_out;
-    hipStream_t st = h->ws[0].stream;
+    hipStream_t st = compute_stream(h);
     hipLaunchKernelGGL(mcq_export_s_kernel, dim3(tracks), dim3(256), 0, st, X);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(mcq_export_rows_kernel, dim3((unsigned)((size_t)batch * nblk)), dim3(256), 0, st, X);
@@ -1304,7 +1502,7 @@ extern "C" int mcq_fmap_destroy(mcq_handle* h, mcq_fmap* fmap)
     if (!h) { g_err = "mcq_fmap_destroy: bad argument"; return MCQ_E_ARG; }
     if (!fmap) return 0;
     HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->ws[0].stream));      // a launch in flight may still read the map
+    HIP_TRY(hipStreamSynchronize(compute_stream(h)));      // a launch in flight may still read the map
     (void)hipFree(fmap->dev);
     delete fmap;
     return 0;
@@ -1330,7 +1528,7 @@ extern "C" int mcq_fmap_query_device(mcq_handle* h, const mcq_fmap* fmap, int co
     }
     if (count == 0) return 0;
     HIP_TRY(hipSetDevice(h->device));
-    hipLaunchKernelGGL(mcq_fmap_query_kernel, dim3((unsigned)(((size_t)count + 255) / 256)), dim3(256), 0, h->ws[0].stream, fmap->F, count, xy,
+    hipLaunchKernelGGL(mcq_fmap_query_kernel, dim3((unsigned)(((size_t)count + 255) / 256)), dim3(256), 0, compute_stream(h), fmap->F, count, xy,
                        mue_out, idx_out, dist_out);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -1359,7 +1557,7 @@ extern "C" int mcq_friction_grid_device(mcq_handle* h, const mcq_fmap* fmap, int
     G.n_list = n_list; G.ref = reftrack; G.nv = normvec;
     G.width = width_opt; G.width_list = width_list; G.wbf = wheelbase_front; G.wbr = wheelbase_rear; G.dn = dn;
     G.n_out = n_out; G.cnt_out = cnt_out; G.mue_out = mue_out; G.idx_out = idx_out; G.w_out = w_mue_out; G.status = status_out;
-    hipLaunchKernelGGL(mcq_friction_grid_kernel, dim3((unsigned)((size_t)tracks * nblk)), dim3(256), 0, h->ws[0].stream, G);
+    hipLaunchKernelGGL(mcq_friction_grid_kernel, dim3((unsigned)((size_t)tracks * nblk)), dim3(256), 0, compute_stream(h), G);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1391,7 +1589,7 @@ extern "C" int mcq_friction_gauss_device(mcq_handle* h, int tracks, int nmax, in
     G.tracks = tracks; G.nmax = nmax; G.jmax = jmax; G.n_gauss = n_gauss; G.N = N; G.rows_wg = rows_wg; G.rcond = rcond;
     G.n = n_out; G.cnt = cnt_out; G.mue = mue_out; G.status = status;
     G.w_out = w_gauss_out; G.cd_out = center_dist_out; G.rank_out = rank_out; G.sweeps_out = sweeps_out;
-    hipLaunchKernelGGL(mcq_friction_gauss_kernel, dim3((unsigned)((size_t)tracks * nblk)), dim3(64 * rows_wg), rows_wg * row_bytes, h->ws[0].stream, G);
+    hipLaunchKernelGGL(mcq_friction_gauss_kernel, dim3((unsigned)((size_t)tracks * nblk)), dim3(64 * rows_wg), rows_wg * row_bytes, compute_stream(h), G);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1418,7 +1616,7 @@ extern "C" int mcq_friction_model_device(mcq_handle* h, int tracks, int nmax, in
     M.tracks = tracks; M.nmax = nmax; M.qmax = qmax; M.jmax = jmax; M.model = model; M.centres = centres; M.n_gauss = n_gauss;
     M.N = gauss ? 2 * n_gauss + 1 : 0;
     M.q = q; M.qcnt = qcnt; M.w = weights; M.cd = center_dist; M.n = n_out; M.cnt = cnt_out; M.mue_out = mue_out;
-    hipLaunchKernelGGL(mcq_friction_model_kernel, dim3((unsigned)nblk), dim3(256), 0, h->ws[0].stream, M);
+    hipLaunchKernelGGL(mcq_friction_model_kernel, dim3((unsigned)nblk), dim3(256), 0, compute_stream(h), M);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1467,7 +1665,7 @@ extern "C" int mcq_points_in_path_device(mcq_handle* h, int paths, int vmax, con
     C.cont = contour_out ? contour_out : a.at<double>(base, 1);
     C.flag = a.at<int>(base, 2);
     C.ccount = contour_count_out ? contour_count_out : a.at<int>(base, 3);
-    hipStream_t st = h->ws[0].stream;
+    hipStream_t st = compute_stream(h);
     hipLaunchKernelGGL(mcq_fgen_contour_kernel, dim3(paths), dim3(256), 0, st, C);
     HIP_TRY(hipGetLastError());
     if (count == 0) return 0;
@@ -1501,7 +1699,7 @@ extern "C" int mcq_friction_gen_device(mcq_handle* h, int tracks, int nmax, cons
     G.bound_r = bound_r_out; G.bound_l = bound_l_out; G.grid = grid_out; G.count = count_out; G.cells = cells_out; G.status = status_out;
     G.poly = a.at<double>(base, 0); G.cont = a.at<double>(base, 2); G.prad = a.at<double>(base, 3);
     G.pcount = a.at<int>(base, 5); G.ccount = a.at<int>(base, 6); G.rec = a.at<int>(base, 7);
-    hipStream_t st = h->ws[0].stream;
+    hipStream_t st = compute_stream(h);
     hipLaunchKernelGGL(mcq_fgen_bounds_kernel, dim3(tracks), dim3(256), 0, st, G);
     HIP_TRY(hipGetLastError());
     if (!count_out) return 0;       // boundaries, grids and status only
@@ -1633,7 +1831,7 @@ extern "C" int mcq_mintime_bounds_device(mcq_handle* h, const mcq_mintime_data* 
     }
     HIP_TRY(hipSetDevice(h->device));
     M.w0 = w0_out; M.lbw = lbw_out; M.ubw = ubw_out; M.lbg = lbg_out; M.ubg = ubg_out;
-    hipLaunchKernelGGL(mcq_mintime_bounds_kernel, dim3(data->batch), dim3(256), 0, h->ws[0].stream, M);
+    hipLaunchKernelGGL(mcq_mintime_bounds_kernel, dim3(data->batch), dim3(256), 0, compute_stream(h), M);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1659,9 +1857,9 @@ extern "C" int mcq_mintime_eval_device(mcq_handle* h, const mcq_mintime_data* da
     M.g = g_out; M.J = J_out; M.lap = lap_time_out; M.energy = energy_out; M.x_opt = x_opt_out; M.u_opt = u_opt_out; M.tf_opt = tf_opt_out;
     M.dt_opt = dt_opt_out; M.ax_opt = ax_opt_out; M.ay_opt = ay_opt_out; M.ec_opt = ec_opt_out; M.status = status_out;
     const unsigned per_wg = 256 / MCQ_MT_EVAL_LANES;
-    hipLaunchKernelGGL(mcq_mintime_eval_kernel, dim3(((unsigned)data->nmax + per_wg - 1) / per_wg, data->batch), dim3(256), 0, h->ws[0].stream, M);
+    hipLaunchKernelGGL(mcq_mintime_eval_kernel, dim3(((unsigned)data->nmax + per_wg - 1) / per_wg, data->batch), dim3(256), 0, compute_stream(h), M);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(mcq_mintime_sum_kernel, dim3(data->batch), dim3(256), 0, h->ws[0].stream, M);
+    hipLaunchKernelGGL(mcq_mintime_sum_kernel, dim3(data->batch), dim3(256), 0, compute_stream(h), M);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1678,7 +1876,7 @@ extern "C" int mcq_mintime_jac_device(mcq_handle* h, const mcq_mintime_data* dat
     HIP_TRY(hipSetDevice(h->device));
     M.blocks = blocks_out; M.grad_J = grad_J_out; M.grad_E = grad_energy_out;
     const size_t lanes = (size_t)data->nmax * MCQ_MT_JAC_LANES;
-    hipLaunchKernelGGL(mcq_mintime_jac_kernel, dim3((unsigned)((lanes + 255) / 256), data->batch), dim3(256), 0, h->ws[0].stream, M);
+    hipLaunchKernelGGL(mcq_mintime_jac_kernel, dim3((unsigned)((lanes + 255) / 256), data->batch), dim3(256), 0, compute_stream(h), M);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1696,7 +1894,7 @@ extern "C" int mcq_mintime_kkt_device(mcq_handle* h, const mcq_mintime_data* dat
     HIP_TRY(hipSetDevice(h->device));
     M.g_in = g; M.blocks_in = blocks; M.grad_J_in = grad_J; M.grad_E_in = grad_energy; M.lam_g = lam_g; M.lam_x = lam_x;
     M.lbw_in = lbw; M.ubw_in = ubw; M.lbg_in = lbg; M.ubg_in = ubg; M.r = r_out; M.kkt = kkt_out;
-    hipLaunchKernelGGL(mcq_mintime_kkt_kernel, dim3(data->batch), dim3(256), 0, h->ws[0].stream, M);
+    hipLaunchKernelGGL(mcq_mintime_kkt_kernel, dim3(data->batch), dim3(256), 0, compute_stream(h), M);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1712,7 +1910,7 @@ extern "C" int mcq_mintime_hess_device(mcq_handle* h, const mcq_mintime_data* da
     }
     HIP_TRY(hipSetDevice(h->device));
     M.lam_g = lam_g; M.sigma = sigma; M.hblocks = hblocks_out;
-    hipLaunchKernelGGL(mcq_mintime_hess_kernel, dim3((unsigned)data->nmax, data->batch), dim3(MCQ_MT_HESS_NT), 0, h->ws[0].stream, M);
+    hipLaunchKernelGGL(mcq_mintime_hess_kernel, dim3((unsigned)data->nmax, data->batch), dim3(MCQ_MT_HESS_NT), 0, compute_stream(h), M);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1729,7 +1927,7 @@ extern "C" int mcq_mintime_hessvec_device(mcq_handle* h, const mcq_mintime_data*
     }
     HIP_TRY(hipSetDevice(h->device));
     M.hblocks_in = hblocks; M.v = v; M.nvec = nvec; M.y = y_out;
-    hipLaunchKernelGGL(mcq_mintime_hessvec_kernel, dim3(((unsigned)M.nwmax + 255) / 256, data->batch), dim3(256), 0, h->ws[0].stream, M);
+    hipLaunchKernelGGL(mcq_mintime_hessvec_kernel, dim3(((unsigned)M.nwmax + 255) / 256, data->batch), dim3(256), 0, compute_stream(h), M);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1741,7 +1939,7 @@ extern "C" int mcq_device_alloc(mcq_handle* h, size_t bytes, void** out)
     if (!h || !out || bytes == 0) { g_err = "mcq_device_alloc: bad argument"; return MCQ_E_ARG; }
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipMalloc(out, bytes));
-    HIP_TRY(hipMemsetAsync(*out, 0, bytes, h->ws[0].stream));
+    HIP_TRY(hipMemsetAsync(*out, 0, bytes, compute_stream(h)));
     return 0;
 }
 
@@ -1750,7 +1948,7 @@ extern "C" int mcq_device_free(mcq_handle* h, void* ptr)
     if (!h) { g_err = "mcq_device_free: NULL handle"; return MCQ_E_ARG; }
     if (!ptr) return 0;
     HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->ws[0].stream));
+    HIP_TRY(hipStreamSynchronize(compute_stream(h)));
     if (h->comm_stream) HIP_TRY(hipStreamSynchronize(h->comm_stream));      // (a gather in flight may read or write the buffer)
     HIP_TRY(hipFree(ptr));
     return 0;
@@ -1760,8 +1958,8 @@ extern "C" int mcq_copy_to_device(mcq_handle* h, void* dst, const void* src, siz
 {
     if (!h || !dst || !src) { g_err = "mcq_copy_to_device: bad argument"; return MCQ_E_ARG; }
     HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->ws[0].stream));
-    HIP_TRY(hipStreamSynchronize(h->ws[0].stream));          // the host buffer may be reused on return
+    HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, compute_stream(h)));
+    HIP_TRY(hipStreamSynchronize(compute_stream(h)));          // the host buffer may be reused on return
     return 0;
 }
 
@@ -1771,9 +1969,9 @@ extern "C" int mcq_copy_to_host(mcq_handle* h, void* dst, const void* src, size_
     HIP_TRY(hipSetDevice(h->device));
     // a gather enqueued before this copy may be writing `src` on the comm stream: the copy is ordered behind the latest one (ADVICE r4:
     // parallel.solve_sharded read its receive buffer before the gather had finished)
-    if (h->comm_stream && h->comm_seq > 0) HIP_TRY(hipStreamWaitEvent(h->ws[0].stream, h->comm_done[(h->comm_seq - 1) & 3u], 0));
-    HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->ws[0].stream));
-    HIP_TRY(hipStreamSynchronize(h->ws[0].stream));
+    if (h->comm_stream && h->comm_seq > 0) HIP_TRY(hipStreamWaitEvent(compute_stream(h), h->comm_done[(h->comm_seq - 1) & 3u], 0));
+    HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, compute_stream(h)));
+    HIP_TRY(hipStreamSynchronize(compute_stream(h)));
     return 0;
 }
 
@@ -1781,13 +1979,19 @@ extern "C" int mcq_sync(mcq_handle* h)
 {
     if (!h) { g_err = "mcq_sync: NULL handle"; return MCQ_E_ARG; }
     HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->ws[0].stream));
+    HIP_TRY(hipStreamSynchronize(compute_stream(h)));
     if (h->comm_stream) HIP_TRY(hipStreamSynchronize(h->comm_stream));      // gathers in flight (mcq_comm_allgather) are work of the handle too
     if (h->ws[1].stream) HIP_TRY(hipStreamSynchronize(h->ws[1].stream));
     return 0;
 }
 
-extern "C" void* mcq_stream(mcq_handle* h) { return h ? (void*)h->ws[0].stream : nullptr; }
+// (From here on the caller may enqueue on the stream what the handle does not see: mcq_solve_device keeps to the one launch on this handle.)
+extern "C" void* mcq_stream(mcq_handle* h)
+{
+    if (!h) return nullptr;
+    h->stream_given = true;
+    return (void*)compute_stream(h);
+}
 
 extern "C" int mcq_last_timing(mcq_handle* h, float ms[5])
 {
@@ -1799,16 +2003,26 @@ extern "C" int mcq_last_timing(mcq_handle* h, float ms[5])
     HIP_TRY(hipEventElapsedTime(&ms[2], h->ev[2], h->ev[3]));
     ms[3] = 0.0f;
     HIP_TRY(hipEventElapsedTime(&ms[4], h->ev[0], h->ev[4]));
+    if (h->sl_time1) {
+        // a sliced mcq_solve_device: from slice 0's start to the later of the two slices' ends (neither stream has waited for the other)
+        float to1 = 0.0f;
+        HIP_TRY(hipEventSynchronize(h->sl_time1));
+        HIP_TRY(hipEventElapsedTime(&to1, h->ev[2], h->sl_time1));
+        ms[2] = std::max(ms[2], to1);
+        HIP_TRY(hipEventElapsedTime(&to1, h->ev[0], h->sl_time1));
+        ms[4] = std::max(ms[4], to1);
+    }
     return 0;
 }
 
-// A span of launches on the handle's compute stream, timed on the device (include/mcq.h)
+// A span of calls on the handle, timed on the device (include/mcq.h).  It begins behind everything enqueued so far, on both compute streams
+// (compute_stream; the first sliced call of the span joins ws[1].stream behind the begin event), and ends with the later of the two streams.
 extern "C" int mcq_timing_begin(mcq_handle* h)
 {
     if (!h) { g_err = "mcq_timing_begin: NULL handle"; return MCQ_E_ARG; }
     HIP_TRY(hipSetDevice(h->device));
     for (int k = 0; k < 2; ++k) if (!h->ev_span[k]) HIP_TRY(hipEventCreate(&h->ev_span[k]));
-    HIP_TRY(hipEventRecord(h->ev_span[0], h->ws[0].stream));
+    HIP_TRY(hipEventRecord(h->ev_span[0], compute_stream(h)));
     h->span_launches = 0;
     h->span_open = true;
     return 0;
@@ -1822,6 +2036,14 @@ extern "C" int mcq_timing_end(mcq_handle* h, float* ms_out, int* launches_out)
     HIP_TRY(hipEventRecord(h->ev_span[1], h->ws[0].stream));
     HIP_TRY(hipEventSynchronize(h->ev_span[1]));
     HIP_TRY(hipEventElapsedTime(ms_out, h->ev_span[0], h->ev_span[1]));
+    if (h->sl_last1) {         // slices pending on ws[1].stream: an end event there as well, neither stream waiting for the other
+        float ms1 = 0.0f;
+        if (!h->ev_span1) HIP_TRY(hipEventCreate(&h->ev_span1));
+        HIP_TRY(hipEventRecord(h->ev_span1, h->ws[1].stream));
+        HIP_TRY(hipEventSynchronize(h->ev_span1));
+        HIP_TRY(hipEventElapsedTime(&ms1, h->ev_span[0], h->ev_span1));
+        *ms_out = std::max(*ms_out, ms1);
+    }
     *launches_out = h->span_launches;
     h->span_open = false;
     return 0;
@@ -1834,7 +2056,7 @@ extern "C" long long mcq_workspace_bytes(mcq_handle* h) { return h ? h->ws[0].by
 static int ensure_pin(mcq_handle* h, size_t bytes)
 {
     if (bytes <= h->pin_bytes) return 0;
-    HIP_TRY(hipStreamSynchronize(h->ws[0].stream));
+    HIP_TRY(hipStreamSynchronize(compute_stream(h)));
     if (h->pin) (void)hipHostFree(h->pin);
     h->pin = nullptr;
     h->pin_bytes = 0;
@@ -1935,7 +2157,7 @@ extern "C" int mcq_host_free(mcq_handle* h, void* ptr)
     if (!h) { g_err = "mcq_host_free: NULL handle"; return MCQ_E_ARG; }
     if (!ptr) return 0;
     HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->ws[0].stream));
+    HIP_TRY(hipStreamSynchronize(compute_stream(h)));
     HIP_TRY(hipHostFree(ptr));
     return 0;
 }
@@ -1963,7 +2185,7 @@ static int ensure_slice_streams(mcq_handle* h)
     if (!h->cs_in) { HIP_TRY(hipStreamCreate(&h->cs_in)); HIP_TRY(hipStreamCreate(&h->cs_out)); }
     if (!h->ws[1].stream) HIP_TRY(hipStreamCreate(&h->ws[1].stream));
     for (int k = 0; k < 16; ++k) if (!h->ev_slice[k]) HIP_TRY(hipEventCreate(&h->ev_slice[k]));
-    HIP_TRY(hipStreamSynchronize(h->ws[0].stream));          // whatever ran before on the handle is done with the staging buffers and the workspace
+    HIP_TRY(hipStreamSynchronize(compute_stream(h)));          // whatever ran before on the handle is done with the staging buffers and the workspace
     HIP_TRY(hipStreamSynchronize(h->ws[1].stream));
     return 0;
 }
@@ -2050,11 +2272,11 @@ extern "C" int mcq_solve_host(mcq_handle* h, int batch, int n, const double* ref
         rc = download_results(h, h->cs_out, batch, nullptr, nullptr, 0, curv_err_out, status_out, info_out);
         if (rc) return rc;
         HIP_TRY(hipStreamSynchronize(h->cs_out));
-        HIP_TRY(hipStreamSynchronize(h->ws[0].stream));
+        HIP_TRY(hipStreamSynchronize(compute_stream(h)));
         HIP_TRY(hipStreamSynchronize(h->ws[1].stream));
         return 0;
     }
-    hipStream_t st = h->ws[0].stream;
+    hipStream_t st = compute_stream(h);
     HIP_TRY_DRAIN(hipMemcpyAsync(s.ref, reftrack, elems * 4 * sizeof(double), hipMemcpyHostToDevice, st));
     if (normvec) HIP_TRY_DRAIN(hipMemcpyAsync(s.nv, normvec, elems * 2 * sizeof(double), hipMemcpyHostToDevice, st));
     if (scaling) HIP_TRY_DRAIN(hipMemcpyAsync(s.sc, scaling, elems * sizeof(double), hipMemcpyHostToDevice, st));
@@ -2086,7 +2308,7 @@ extern "C" int mcq_solve_batch_f32(mcq_handle* h, int batch, int n, int layout, 
     rc = ensure_staging(h, 0, (size_t)batch, (size_t)n);
     if (rc) return rc;
     const size_t elems = (size_t)batch * n;
-    hipStream_t st = h->ws[0].stream;
+    hipStream_t st = compute_stream(h);
     float* d_rows = (float*)h->stage[0].nv;
     float* d_al32 = (float*)h->stage[0].sc;
     HIP_TRY_DRAIN(hipMemcpyAsync(d_rows, reftrack, elems * 4 * sizeof(float), hipMemcpyHostToDevice, st));
@@ -2149,7 +2371,7 @@ extern "C" int mcq_solve_host_pipelined(mcq_handle* h, int steps, int batch, int
     // (one per resident workgroup) belong to the first workspace (the second one's few slots made odd steps run ~32 problems at a time)
     const bool two = steps > 1 && !getenv("MCQ_PIPE_ONE_STREAM") && o.algorithm != MCQ_ALG_GI;
     if (two) { rc = ensure_workspace(h, 1, (size_t)batch, (size_t)n); if (rc) return rc; }
-    HIP_TRY(hipStreamSynchronize(h->ws[0].stream));          // whatever ran before on the handle's stream is done with the staging buffers
+    HIP_TRY(hipStreamSynchronize(compute_stream(h)));          // whatever ran before on the handle's stream is done with the staging buffers
     const size_t elems = (size_t)batch * n;
     // Order of the host's enqueues: upload(0); then per step  kernels(k), upload(k + 1), download(k).  The copies of both directions
     // drain through one in-order copy queue of the runtime (rocprofv3 --memory-copy-trace, round 3: with download(k) enqueued ahead
@@ -2198,7 +2420,7 @@ extern "C" int mcq_solve_host_pipelined(mcq_handle* h, int steps, int batch, int
         HIP_TRY_DRAIN(hipEventRecord(h->ev_down[s], h->cs_out));
     }
     HIP_TRY_DRAIN(hipStreamSynchronize(h->cs_in));
-    HIP_TRY_DRAIN(hipStreamSynchronize(h->ws[0].stream));
+    HIP_TRY_DRAIN(hipStreamSynchronize(compute_stream(h)));
     if (two) HIP_TRY_DRAIN(hipStreamSynchronize(h->ws[1].stream));
     HIP_TRY_DRAIN(hipStreamSynchronize(h->cs_out));
     for (int k = 0; k < steps; ++k) {
@@ -2212,7 +2434,7 @@ extern "C" int mcq_solve_host_pipelined(mcq_handle* h, int steps, int batch, int
 static int ensure_iqp(mcq_handle* h, size_t batch)
 {
     if (batch <= h->iqp_batch) return 0;
-    HIP_TRY(hipStreamSynchronize(h->ws[0].stream));
+    HIP_TRY(hipStreamSynchronize(compute_stream(h)));
     (void)hipFree(h->d_iqp); (void)hipFree(h->d_iqp_curv); (void)hipFree(h->d_trace);
     h->d_iqp = nullptr; h->d_iqp_curv = nullptr; h->d_trace = nullptr; h->iqp_batch = 0;
     HIP_TRY(hipMalloc((void**)&h->d_iqp, (batch * 8 + 16) * sizeof(int)));
@@ -2257,10 +2479,10 @@ extern "C" int mcq_iqp_device(mcq_handle* h, int batch, int nmax, int* n_io, dou
     // every track starts live (a track with n == 0 ends in its first, empty pass: status MCQ_BAD_INPUT, rounds_out 1)
     {
         std::vector<int> ones((size_t)batch, 1);
-        HIP_TRY(hipMemcpyAsync(live, ones.data(), batch * sizeof(int), hipMemcpyHostToDevice, h->ws[0].stream));
-        HIP_TRY(hipMemsetAsync(rounds_out, 0, batch * sizeof(int), h->ws[0].stream));
-        HIP_TRY(hipMemsetAsync(buf_out, 0, batch * sizeof(int), h->ws[0].stream));
-        HIP_TRY(hipStreamSynchronize(h->ws[0].stream));      // `ones` goes out of scope
+        HIP_TRY(hipMemcpyAsync(live, ones.data(), batch * sizeof(int), hipMemcpyHostToDevice, compute_stream(h)));
+        HIP_TRY(hipMemsetAsync(rounds_out, 0, batch * sizeof(int), compute_stream(h)));
+        HIP_TRY(hipMemsetAsync(buf_out, 0, batch * sizeof(int), compute_stream(h)));
+        HIP_TRY(hipStreamSynchronize(compute_stream(h)));      // `ones` goes out of scope
     }
     McqIqpStep S;
     memset(&S, 0, sizeof(S));
@@ -2277,13 +2499,13 @@ extern "C" int mcq_iqp_device(mcq_handle* h, int batch, int nmax, int* n_io, dou
     S.final_rounds = rounds_out;
     S.live_count = live_count;
     S.curv_trace = curv_trace_out;
-    if (curv_trace_out) HIP_TRY(hipMemsetAsync(curv_trace_out, 0, (size_t)batch * MCQ_IQP_TRACE * sizeof(double), h->ws[0].stream));
+    if (curv_trace_out) HIP_TRY(hipMemsetAsync(curv_trace_out, 0, (size_t)batch * MCQ_IQP_TRACE * sizeof(double), compute_stream(h)));
     const dim3 sgrid((unsigned)((batch + 255) / 256)), sblock(256);
     int cur = 0, rounds = 0, n_live = batch;
     long long solves = 0;
     if (stats) { stats->rounds = 0; stats->qp_solves = 0; for (int k = 0; k < 16; ++k) { stats->solver_ms[k] = 0.f; stats->fallbacks[k] = 0; } }
     // the final ring sizes are collected in a scratch array and moved to n_io at the end (n_io doubles as set 0's sizes)
-    HIP_TRY(hipMemsetAsync(d_final_n, 0, batch * sizeof(int), h->ws[0].stream));
+    HIP_TRY(hipMemsetAsync(d_final_n, 0, batch * sizeof(int), compute_stream(h)));
     S.final_n = d_final_n;
     int err = 0;
     int it0 = 1;
@@ -2319,17 +2541,17 @@ extern "C" int mcq_iqp_device(mcq_handle* h, int batch, int nmax, int* n_io, dou
         F.sc = scaling;
         F.warm = warm ? h->state2 : nullptr;
         F.rounds = ra;
-        if (hipMemsetAsync(live_count, 0, sizeof(int), h->ws[0].stream) != hipSuccess) err = MCQ_E_DEVICE;
+        if (hipMemsetAsync(live_count, 0, sizeof(int), compute_stream(h)) != hipSuccess) err = MCQ_E_DEVICE;
         if (!err) {
-            hipLaunchKernelGGL(mcq_iqp_rounds_kernel, dim3((unsigned)batch), dim3(256), 0, h->ws[0].stream, F);
+            hipLaunchKernelGGL(mcq_iqp_rounds_kernel, dim3((unsigned)batch), dim3(256), 0, compute_stream(h), F);
             if (hipGetLastError() != hipSuccess) err = MCQ_E_DEVICE;
         }
         // (the loop below may go on from the working sets the last round's glue carried over)
         h->state2_valid = true;
         h->state2_batch = batch;
         h->state2_nmax = nmax;
-        if (!err && (hipMemcpyAsync(&n_live, live_count, sizeof(int), hipMemcpyDeviceToHost, h->ws[0].stream) != hipSuccess ||
-                     hipStreamSynchronize(h->ws[0].stream) != hipSuccess)) err = MCQ_E_DEVICE;
+        if (!err && (hipMemcpyAsync(&n_live, live_count, sizeof(int), hipMemcpyDeviceToHost, compute_stream(h)) != hipSuccess ||
+                     hipStreamSynchronize(compute_stream(h)) != hipSuccess)) err = MCQ_E_DEVICE;
         cur = ra & 1;
         rounds = ra;
         it0 = ra + 1;
@@ -2346,9 +2568,9 @@ extern "C" int mcq_iqp_device(mcq_handle* h, int batch, int nmax, int* n_io, dou
             if (mcq_last_timing(h, ms) == 0) stats->solver_ms[it - 1] = ms[4];
             std::vector<mcq_info> info((size_t)batch);
             std::vector<int> lv((size_t)batch);
-            if (hipMemcpyAsync(info.data(), h->d_info, batch * sizeof(mcq_info), hipMemcpyDeviceToHost, h->ws[0].stream) == hipSuccess &&
-                hipMemcpyAsync(lv.data(), live, batch * sizeof(int), hipMemcpyDeviceToHost, h->ws[0].stream) == hipSuccess &&
-                hipStreamSynchronize(h->ws[0].stream) == hipSuccess) {
+            if (hipMemcpyAsync(info.data(), h->d_info, batch * sizeof(mcq_info), hipMemcpyDeviceToHost, compute_stream(h)) == hipSuccess &&
+                hipMemcpyAsync(lv.data(), live, batch * sizeof(int), hipMemcpyDeviceToHost, compute_stream(h)) == hipSuccess &&
+                hipStreamSynchronize(compute_stream(h)) == hipSuccess) {
                 int fb = 0;
                 for (int k = 0; k < batch; ++k) if (lv[k] && (info[k].second_attempt & 2)) ++fb;
                 stats->fallbacks[it - 1] = fb;
@@ -2357,33 +2579,33 @@ extern "C" int mcq_iqp_device(mcq_handle* h, int batch, int nmax, int* n_io, dou
         if (h->iqp_cb) {        // print_debug: the pass's curvature errors and who ran it, before the termination test decides
             std::vector<double> cv((size_t)batch);
             std::vector<int> lv((size_t)batch);
-            if (hipMemcpyAsync(cv.data(), pass_curv, batch * sizeof(double), hipMemcpyDeviceToHost, h->ws[0].stream) != hipSuccess ||
-                hipMemcpyAsync(lv.data(), live, batch * sizeof(int), hipMemcpyDeviceToHost, h->ws[0].stream) != hipSuccess ||
-                hipStreamSynchronize(h->ws[0].stream) != hipSuccess) { err = MCQ_E_DEVICE; break; }
+            if (hipMemcpyAsync(cv.data(), pass_curv, batch * sizeof(double), hipMemcpyDeviceToHost, compute_stream(h)) != hipSuccess ||
+                hipMemcpyAsync(lv.data(), live, batch * sizeof(int), hipMemcpyDeviceToHost, compute_stream(h)) != hipSuccess ||
+                hipStreamSynchronize(compute_stream(h)) != hipSuccess) { err = MCQ_E_DEVICE; break; }
             h->iqp_cb(h->iqp_cb_user, it, batch, cv.data(), lv.data());
         }
-        if (hipMemsetAsync(live_count, 0, sizeof(int), h->ws[0].stream) != hipSuccess) { err = MCQ_E_DEVICE; break; }
+        if (hipMemsetAsync(live_count, 0, sizeof(int), compute_stream(h)) != hipSuccess) { err = MCQ_E_DEVICE; break; }
         S.phase = 0;
         S.round = it;
         S.cur = cur;
         S.n_ring = n_set[cur];
         S.n_next = n_set[1 - cur];
-        hipLaunchKernelGGL(mcq_iqp_step_kernel, sgrid, sblock, 0, h->ws[0].stream, S);
+        hipLaunchKernelGGL(mcq_iqp_step_kernel, sgrid, sblock, 0, compute_stream(h), S);
         const double scale = it < iters_min ? (double)it / (double)iters_min : 1.0;
         if ((err = mcq_relinearise_device(h, batch, nmax, n_set[cur], ref_set[cur], nv_set[cur], alpha_out, live, scale,
                                           stepsize_interp, ref_set[1 - cur], nv_set[1 - cur], n_set[1 - cur], rst)) != 0) break;
         S.phase = 1;
-        hipLaunchKernelGGL(mcq_iqp_step_kernel, sgrid, sblock, 0, h->ws[0].stream, S);
+        hipLaunchKernelGGL(mcq_iqp_step_kernel, sgrid, sblock, 0, compute_stream(h), S);
         if (hipGetLastError() != hipSuccess) { err = MCQ_E_DEVICE; break; }
         cur = 1 - cur;
         // the first iters_min - 1 rounds cannot end a healthy track: no need to look
         if (it >= iters_min || it == max_rounds) {
-            if (hipMemcpyAsync(&n_live, live_count, sizeof(int), hipMemcpyDeviceToHost, h->ws[0].stream) != hipSuccess ||
-                hipStreamSynchronize(h->ws[0].stream) != hipSuccess) { err = MCQ_E_DEVICE; break; }
+            if (hipMemcpyAsync(&n_live, live_count, sizeof(int), hipMemcpyDeviceToHost, compute_stream(h)) != hipSuccess ||
+                hipStreamSynchronize(compute_stream(h)) != hipSuccess) { err = MCQ_E_DEVICE; break; }
         }
     }
-    if (!err && hipMemcpyAsync(n_io, d_final_n, batch * sizeof(int), hipMemcpyDeviceToDevice, h->ws[0].stream) != hipSuccess) err = MCQ_E_DEVICE;
-    if (hipStreamSynchronize(h->ws[0].stream) != hipSuccess && !err) err = MCQ_E_DEVICE;
+    if (!err && hipMemcpyAsync(n_io, d_final_n, batch * sizeof(int), hipMemcpyDeviceToDevice, compute_stream(h)) != hipSuccess) err = MCQ_E_DEVICE;
+    if (hipStreamSynchronize(compute_stream(h)) != hipSuccess && !err) err = MCQ_E_DEVICE;
     h->state2_valid = false;        // the working sets belong to this run's last glue call, not to a later solve
     if (err) { if (err == MCQ_E_DEVICE && g_err.empty()) g_err = "mcq_iqp_device: HIP runtime error"; return err; }
     if (stats) {
@@ -2448,7 +2670,7 @@ static int pack_and_upload(mcq_handle* h, const mcq_problem* probs, int batch, s
     P.info = (mcq_info*)(P.wv + batch);
     P.n = (int*)(P.info + batch);
     const Staging& s = h->stage[0];
-    hipStream_t up = force_chunks > 0 ? h->cs_in : h->ws[0].stream;
+    hipStream_t up = force_chunks > 0 ? h->cs_in : compute_stream(h);
     // (the padding behind a track's n waypoints is never read by a kernel: no need to clear it)
     auto pack_range = [&](int b0, int b1) {
         for (int b = b0; b < b1; ++b) {
@@ -2569,16 +2791,16 @@ static int solve_batch_impl(mcq_handle* h, const mcq_problem* probs, const mcq_e
         rc = download_results(h, h->cs_out, batch, nullptr, nullptr, 0, curv_err_out, status_out, P.info);
         if (rc) return rc;
         HIP_TRY_DRAIN(hipStreamSynchronize(h->cs_out));
-        HIP_TRY_DRAIN(hipStreamSynchronize(h->ws[0].stream));
+        HIP_TRY_DRAIN(hipStreamSynchronize(compute_stream(h)));
         HIP_TRY_DRAIN(hipStreamSynchronize(h->ws[1].stream));
     } else {
         rc = pack_and_upload(h, probs, batch, nmax, any_sc, with_nv, 0, P);
         if (rc) return rc;
         rc = launch(h, B, o);
         if (rc) { drain(h); return rc; }
-        rc = download_results(h, h->ws[0].stream, batch, P.alpha, s.alpha, (size_t)batch * nmax * sizeof(double), curv_err_out, status_out, P.info);
+        rc = download_results(h, compute_stream(h), batch, P.alpha, s.alpha, (size_t)batch * nmax * sizeof(double), curv_err_out, status_out, P.info);
         if (rc) return rc;
-        HIP_TRY(hipStreamSynchronize(h->ws[0].stream));
+        HIP_TRY(hipStreamSynchronize(compute_stream(h)));
     }
     // the padded rows of the pinned staging, back to back into the caller's array
     size_t off = 0;
@@ -2615,8 +2837,8 @@ extern "C" int mcq_solve_batch_ends(mcq_handle* h, const mcq_problem* probs, con
     HIP_TRY(hipSetDevice(h->device));
     if (int rc = grow(h, h->ends, (size_t)batch * sizeof(mcq_ends))) return rc;
     // ordered before every launch of the solve (and the copy streams of its slices) by the synchronisation: the caller's array is pageable
-    HIP_TRY(hipMemcpyAsync(h->ends.p, ends, (size_t)batch * sizeof(mcq_ends), hipMemcpyHostToDevice, h->ws[0].stream));
-    HIP_TRY(hipStreamSynchronize(h->ws[0].stream));
+    HIP_TRY(hipMemcpyAsync(h->ends.p, ends, (size_t)batch * sizeof(mcq_ends), hipMemcpyHostToDevice, compute_stream(h)));
+    HIP_TRY(hipStreamSynchronize(compute_stream(h)));
     return solve_batch_impl(h, probs, (const mcq_ends*)h->ends.p, batch, opts, alpha_out, curv_err_out, status_out, info_out);
 }
 
@@ -2640,7 +2862,7 @@ extern "C" int mcq_solve_device_stream(mcq_handle* h, int steps, int batch, int 
     // the second stream starts behind whatever the caller has enqueued on the first (uploads of the inputs, an earlier call)
     if (two) {
         for (int k = 0; k < 2; ++k) if (!h->ev_st[k]) HIP_TRY(hipEventCreate(&h->ev_st[k]));
-        HIP_TRY(hipEventRecord(h->ev_st[0], h->ws[0].stream));
+        HIP_TRY(hipEventRecord(h->ev_st[0], compute_stream(h)));
         HIP_TRY(hipStreamWaitEvent(h->ws[1].stream, h->ev_st[0], 0));
     }
     for (int k = 0; k < steps; ++k) {
@@ -2653,7 +2875,7 @@ extern "C" int mcq_solve_device_stream(mcq_handle* h, int steps, int batch, int 
     // the handle's first stream ends behind the second one: mcq_sync / a later call on the handle sees every step done
     if (two) {
         HIP_TRY(hipEventRecord(h->ev_st[1], h->ws[1].stream));
-        HIP_TRY(hipStreamWaitEvent(h->ws[0].stream, h->ev_st[1], 0));
+        HIP_TRY(hipStreamWaitEvent(compute_stream(h), h->ev_st[1], 0));
     }
     return 0;
 }
@@ -2703,7 +2925,7 @@ extern "C" int mcq_iqp_batch(mcq_handle* h, const mcq_problem* probs, int batch,
     if (rc) return rc;
     const size_t elems = (size_t)batch * nmax;
     if (elems > h->stage2_elems) {
-        HIP_TRY(hipStreamSynchronize(h->ws[0].stream));
+        HIP_TRY(hipStreamSynchronize(compute_stream(h)));
         (void)hipFree(h->d_ref2); (void)hipFree(h->d_nv2);
         h->d_ref2 = h->d_nv2 = nullptr; h->stage2_elems = 0;
         HIP_TRY(hipMalloc((void**)&h->d_ref2, elems * 4 * sizeof(double)));
@@ -2732,13 +2954,13 @@ extern "C" int mcq_iqp_batch(mcq_handle* h, const mcq_problem* probs, int batch,
     }
     if (rc) return rc;
     int* buf_h = P.n;                            // the pinned int block: n | (extra) buf, rounds
-    HIP_TRY_DRAIN(hipMemcpyAsync(n_out, h->d_n, batch * sizeof(int), hipMemcpyDeviceToHost, h->ws[0].stream));
-    HIP_TRY_DRAIN(hipMemcpyAsync(buf_h, d_buf, batch * sizeof(int), hipMemcpyDeviceToHost, h->ws[0].stream));
-    HIP_TRY_DRAIN(hipMemcpyAsync(rounds_out, d_rounds, batch * sizeof(int), hipMemcpyDeviceToHost, h->ws[0].stream));
+    HIP_TRY_DRAIN(hipMemcpyAsync(n_out, h->d_n, batch * sizeof(int), hipMemcpyDeviceToHost, compute_stream(h)));
+    HIP_TRY_DRAIN(hipMemcpyAsync(buf_h, d_buf, batch * sizeof(int), hipMemcpyDeviceToHost, compute_stream(h)));
+    HIP_TRY_DRAIN(hipMemcpyAsync(rounds_out, d_rounds, batch * sizeof(int), hipMemcpyDeviceToHost, compute_stream(h)));
     // alpha straight into the caller's [batch][nmax_out] array (its padding holds whatever the device buffer held)
-    rc = download_results(h, h->ws[0].stream, batch, alpha_out, h->stage[0].alpha, elems * sizeof(double), curv_err_out, status_out, nullptr);
+    rc = download_results(h, compute_stream(h), batch, alpha_out, h->stage[0].alpha, elems * sizeof(double), curv_err_out, status_out, nullptr);
     if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(h->ws[0].stream));
+    HIP_TRY(hipStreamSynchronize(compute_stream(h)));
     stamp("alpha and per-track results down");
     bool use[2] = {false, false};
     for (int b = 0; b < batch; ++b) use[buf_h[b] ? 1 : 0] = true;
@@ -2747,9 +2969,9 @@ extern "C" int mcq_iqp_batch(mcq_handle* h, const mcq_problem* probs, int batch,
     if (use[0] != use[1]) {
         // the usual case (one iters_min for all: every track ends in the same round): the final set goes out in two copies
         const int q = use[1] ? 1 : 0;
-        HIP_TRY_DRAIN(hipMemcpyAsync(reftrack_out, d_ref_set[q], elems * 4 * sizeof(double), hipMemcpyDeviceToHost, h->ws[0].stream));
-        HIP_TRY_DRAIN(hipMemcpyAsync(normvec_out, d_nv_set[q], elems * 2 * sizeof(double), hipMemcpyDeviceToHost, h->ws[0].stream));
-        HIP_TRY(hipStreamSynchronize(h->ws[0].stream));
+        HIP_TRY_DRAIN(hipMemcpyAsync(reftrack_out, d_ref_set[q], elems * 4 * sizeof(double), hipMemcpyDeviceToHost, compute_stream(h)));
+        HIP_TRY_DRAIN(hipMemcpyAsync(normvec_out, d_nv_set[q], elems * 2 * sizeof(double), hipMemcpyDeviceToHost, compute_stream(h)));
+        HIP_TRY(hipStreamSynchronize(compute_stream(h)));
         stamp("rings and normals down");
         return 0;
     }
@@ -2764,10 +2986,10 @@ extern "C" int mcq_iqp_batch(mcq_handle* h, const mcq_problem* probs, int batch,
         nv_h[1] = ref_h[1] + elems * 4;
     }
     for (int q = 0; q < 2; ++q) {
-        HIP_TRY_DRAIN(hipMemcpyAsync(ref_h[q], d_ref_set[q], elems * 4 * sizeof(double), hipMemcpyDeviceToHost, h->ws[0].stream));
-        HIP_TRY_DRAIN(hipMemcpyAsync(nv_h[q], d_nv_set[q], elems * 2 * sizeof(double), hipMemcpyDeviceToHost, h->ws[0].stream));
+        HIP_TRY_DRAIN(hipMemcpyAsync(ref_h[q], d_ref_set[q], elems * 4 * sizeof(double), hipMemcpyDeviceToHost, compute_stream(h)));
+        HIP_TRY_DRAIN(hipMemcpyAsync(nv_h[q], d_nv_set[q], elems * 2 * sizeof(double), hipMemcpyDeviceToHost, compute_stream(h)));
     }
-    HIP_TRY(hipStreamSynchronize(h->ws[0].stream));
+    HIP_TRY(hipStreamSynchronize(compute_stream(h)));
     for (int b = 0; b < batch; ++b) {
         const int q = buf_h[b] ? 1 : 0;
         const size_t n = n_out[b] > 0 ? (size_t)n_out[b] : 0;
@@ -2878,8 +3100,11 @@ extern "C" int mcq_comm_allgather(mcq_handle* h, const void* send, void* recv, s
     HIP_TRY(hipSetDevice(h->device));
     // behind everything enqueued on the handle's stream so far (the solve that filled `send`), on a stream of its own: the handle's
     // stream goes on with the next solve while the gather runs
+    // (ws[0].stream is NOT pulled behind a pending slice on ws[1].stream here -- compute_stream would serialise the next sliced call behind this
+    // one, and a caller gathers after every step: the comm stream waits for both slices' ends instead)
     HIP_TRY(hipEventRecord(h->comm_ready, h->ws[0].stream));
     HIP_TRY(hipStreamWaitEvent(h->comm_stream, h->comm_ready, 0));
+    if (h->sl_last1) HIP_TRY(hipStreamWaitEvent(h->comm_stream, h->sl_last1, 0));
     const unsigned slot = h->comm_seq & 3u;
     HIP_TRY(hipEventRecord(h->comm_t0[slot], h->comm_stream));
     const int nccl_t = dtype == MCQ_DT_F64 ? 8 : dtype == MCQ_DT_F32 ? 7 : 2;
@@ -2916,7 +3141,7 @@ extern "C" int mcq_comm_destroy(mcq_handle* h)
     int ret = 0;
     (void)hipSetDevice(h->device);
     if (h->comm) {
-        if (h->ws[0].stream) (void)hipStreamSynchronize(h->ws[0].stream);
+        if (h->ws[0].stream) (void)hipStreamSynchronize(compute_stream(h));
         if (h->comm_stream) (void)hipStreamSynchronize(h->comm_stream);
         const int r = g_rccl.CommDestroy(h->comm);
         h->comm = nullptr;

@@ -177,7 +177,21 @@ int mcq_solve_batch_ends(mcq_handle* h, const mcq_problem* probs, const mcq_ends
  * shard path).  All pointers are DEVICE pointers on the handle's device; layouts as above with a leading batch axis:
  * reftrack [batch][n][4], normvec [batch][n][2], scaling [batch][n] or NULL, alpha_out [batch][n],
  * curv_err_out [batch], status_out [batch], info_out [batch] or NULL.  Asynchronous on the handle's stream;
- * mcq_sync() waits.  mcq_stream() returns the hipStream_t (as void*) so callers can record events on it. */
+ * mcq_sync() waits.  mcq_stream() returns the hipStream_t (as void*) so callers can record events on it.
+ *
+ * mcq_solve_device runs a batch of MORE than one residency round -- two workgroups per compute unit of the device: from 513 problems on 256
+ * CUs; $MCQ_DEVICE_SLICE_MIN gives the smallest sliced batch instead -- as TWO launches: problems [0, (batch + 1) / 2) on the handle's stream, the others on its second compute stream, both
+ * over their rows of the one workspace.  A later such call's slice is ordered behind this call's slice on the same stream only, so the
+ * slowest problems of one launch finish while the next launch fills the slots they have left: a caller that streams batches through this
+ * entry gets the overlap of mcq_solve_device_stream without listing its steps up front and without a second workspace.  The handle still
+ * behaves like ONE in-order stream: every other entry, mcq_sync, the copies and mcq_stream first order the handle's stream behind a pending
+ * slice, and a sliced call skips the join of its two streams only while it provably touches nothing the other stream of an earlier,
+ * un-joined call may still be working on (same batch and n; its slices' output rows clear of the other slices' of those calls; neither
+ * call reading what the other writes -- interval checks on addresses; a loop over one set of buffers, over two in turn, or over fresh ones
+ * per call stays overlapped).  Results are bitwise those of the one launch.  One launch as before: smaller batches, a warm start that
+ * applies, MCQ_OBJ_SHORTEST_PATH, MCQ_ALG_GI, a handle whose mcq_stream the caller has taken (what it enqueues there the handle cannot see),
+ * and $MCQ_DEVICE_ONE_LAUNCH=1 (A/B knob).  $MCQ_DEVICE_SLICE_TRACE=1: one line per call on stderr saying which path it took.  The ragged
+ * and fp32 entries below keep the one launch. */
 int mcq_solve_device(mcq_handle* h, int batch, int n, const double* reftrack, const double* normvec,
                      const double* scaling, double kappa_bound, double w_veh, const mcq_opts* opts, double* alpha_out,
                      double* curv_err_out, int* status_out, mcq_info* info_out);
@@ -959,17 +973,23 @@ int mcq_copy_to_host(mcq_handle* h, void* dst, const void* src, size_t bytes);
 int mcq_sync(mcq_handle* h);
 void* mcq_stream(mcq_handle* h);
 
-/* Timing of the last mcq_solve_device / mcq_solve_batch call, measured with HIP events on the handle's stream:
+/* Timing of the last mcq_solve_device / mcq_solve_batch call, measured with HIP events on the handle's stream(s):
  * ms[2] the solver kernel (since round 4 the whole QP pass: assembly, solve, post-check -- and, round 5, the Goldfarb-Idnani path of the
  * problems that need it), ms[4] the whole launch sequence; ms[0] the assembly kernel of the shortest-path objective (else ~0);
- * ms[1], ms[3] are 0 (the kernels they timed until round 3 no longer exist; the slots stay for ABI compatibility). */
+ * ms[1], ms[3] are 0 (the kernels they timed until round 3 no longer exist; the slots stay for ABI compatibility).
+ * After a SLICED mcq_solve_device, ms[2] and ms[4] run from the start of the first slice to the later of the two slices' ends, through events on
+ * both compute streams (neither waits for the other): with earlier calls still in flight that includes the time a slice spent queued behind
+ * them -- a launch's own duration only for a call enqueued on an idle handle. */
 int mcq_last_timing(mcq_handle* h, float ms[5]);
 
-/* A SPAN of launches timed on the device: mcq_timing_begin records an event on the handle's compute stream, mcq_timing_end records a second one,
- * waits for it and returns the milliseconds between the two and the number of solver launches the handle enqueued on that stream in between
- * (mcq_solve_device* / the QP passes of the IQP entries; not the second stream of mcq_solve_host_pipelined).  With launches enqueued back to back
- * -- no host synchronisation inside the span -- ms / launches is the average duration of a launch, launch gaps included: what bench.py's
- * `roofline.kernel_ms` is (round 5; until then it synchronised after every step to read mcq_last_timing, and a slow host showed up in `value`). */
+/* A SPAN of launches timed on the device: mcq_timing_begin orders the handle's compute stream behind everything enqueued so far (pending slices of
+ * mcq_solve_device included) and records an event on it; mcq_timing_end records an end event on that stream -- and one on the second compute stream
+ * where slices of mcq_solve_device are pending there --, waits, and returns the milliseconds from the begin event to the LATER end and the number
+ * of solver launches the handle enqueued in between (mcq_solve_device* / the QP passes of the IQP entries; not the second stream of
+ * mcq_solve_host_pipelined).  A sliced mcq_solve_device counts as ONE launch, per call: with calls enqueued back to back -- no host
+ * synchronisation inside the span -- ms / launches is the average device time per step, launch gaps included: what bench.py's
+ * `roofline.kernel_ms` is (round 5; until then it synchronised after every step to read mcq_last_timing, and a slow host showed up in `value`).
+ * With slices of consecutive calls overlapping, that is no longer the duration of any single kernel. */
 int mcq_timing_begin(mcq_handle* h);
 int mcq_timing_end(mcq_handle* h, float* ms_out, int* launches_out);
 
