@@ -14,7 +14,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <functional>
 #include <string>
 #include <thread>
 #include <vector>
@@ -23,12 +22,12 @@
 
 static thread_local std::string g_err;
 
-// A compute stream and the device workspace ("slabs") of the solver launches on it.  The handle has two: [0] serves every entry; [1] is
-// mcq_solve_host_pipelined's and mcq_solve_device_stream's SECOND compute stream with a workspace of its own -- the kernels of consecutive
-// steps run on alternating streams, so the tail of one launch (its slowest problems, on CUs the others have left) overlaps the start of the
-// next (round 5).  What only [0] has stays in the handle: state2 and the warm start, the small Goldfarb-Idnani pool, the event timing.
+// A compute stream and the device workspace ("slabs") of the solver launches on it.  The handle has two: [0] serves every entry; [1] is the
+// SECOND compute stream -- the step entries (mcq_solve_host_pipelined, mcq_solve_device_stream) run their odd steps on it with its own slabs, the
+// sliced entries (mcq_solve_device, mcq_solve_host, mcq_solve_batch) their odd slices over rows of workspace 0: the tail of one launch overlaps the
+// start of the next.  What only [0] has stays in the handle: state2 and the warm start, the small Goldfarb-Idnani pool, the event timing.
 struct Workspace {
-    hipStream_t stream = nullptr;       // [0]: created with the handle; [1]: on first use (ensure_workspace, ensure_slice_streams)
+    hipStream_t stream = nullptr;       // [0]: created with the handle; [1]: on first use (ensure_streams)
     double *L = nullptr, *vec = nullptr, *Z = nullptr;
     signed char* state = nullptr;
     double* kbig = nullptr;             // overflow slots of the curvature-row working set (MCQ_KBIG_SLOTS x MCQ_KBIG_SLOT doubles)
@@ -65,13 +64,30 @@ struct SliceCall {
     hipEvent_t end[2] = {nullptr, nullptr};         // created on first use, kept with the slot
 };
 #define MCQ_SLICE_CALLS 16
+// the sliced mcq_solve_device calls whose two streams have not been joined since (solve_device_sliced)
+struct Slices {
+    SliceCall call[MCQ_SLICE_CALLS];
+    int count = 0;
+    int batch = 0, n = 0;               // the shape of the calls in call[]: the same split and the same workspace rows per slice
+    bool fast_ok = false;               // nothing but sliced calls has been enqueued on the handle since the last full join
+    hipEvent_t last1 = nullptr;         // (two names for events of call[], not owned)  end of the latest slice on ws[1].stream; != nullptr: ws[0].stream has not waited for it yet
+    hipEvent_t time1 = nullptr;         // != nullptr: the last timed launch was a sliced call, and this is the end of its slice on ws[1].stream
+    hipEvent_t join = nullptr;          // fork_second: ws[1].stream behind ws[0].stream
+};
+
+// The copies of the host-buffer entries that run beside the kernels: a stream each way, created on first use (ensure_streams)
+struct CopyPipe {
+    hipStream_t in = nullptr, out = nullptr;
+    hipEvent_t up[2] = {}, done[2] = {}, down[2] = {};      // mcq_solve_host_pipelined: one triple per staging slot
+    hipEvent_t slice[16] = {};          // mcq_solve_host / mcq_solve_batch in slices: upload [k] / kernel [8 + k] done, per slice
+};
 
 struct mcq_handle {
     int device = 0;
     Workspace ws[2];
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};      // launches on ws[0] only, like timing_valid and span_launches
     bool timing_valid = false;
-    hipEvent_t ev_st[2] = {nullptr, nullptr};       // mcq_solve_device_stream: joins the second compute stream to the first and back
+    hipEvent_t ev_back = nullptr;                   // join_second: ws[0].stream behind ws[1].stream
     hipEvent_t ev_span[2] = {nullptr, nullptr};     // mcq_timing_begin / mcq_timing_end: a span of launches on the compute stream
     int span_launches = 0;
     bool span_open = false;
@@ -116,36 +132,26 @@ struct mcq_handle {
     long long gis_bytes = 0;
     double* d_org = nullptr;            // per-track origins of the fp32 row entries, [batch][2]
     double* d_trace = nullptr;          // curvature-error trace of mcq_iqp_batch, [batch][MCQ_IQP_TRACE] (grown with d_iqp)
-    // mcq_solve_host_pipelined: two copy streams, one event triple per staging slot
-    hipStream_t cs_in = nullptr, cs_out = nullptr;
-    hipEvent_t ev_up[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr}, ev_down[2] = {nullptr, nullptr};
-    hipEvent_t ev_slice[16] = {};      // mcq_solve_host / mcq_solve_batch in slices: upload / kernel done, per slice
+    CopyPipe cp;
     int last_upload_direct = 0;         // the last host-buffer batch went up without the packing pass (mcq_last_upload_was_direct)
-    // mcq_solve_device in two slices (solve_device_sliced): the calls whose two streams have not been joined since
     int cus = 256;                      // compute units of the device (mcq_create); the MI355X's where the runtime does not say
-    SliceCall sl[MCQ_SLICE_CALLS];
-    int sl_count = 0;
-    int sl_batch = 0, sl_n = 0;         // the shape of the calls in sl[]: the same split and the same workspace rows per slice
-    bool sl_fast_ok = false;            // nothing but sliced calls has been enqueued on the handle since the last full join
-    // (two names for events of sl[], not owned)
-    hipEvent_t sl_last1 = nullptr;      // end of the latest slice on ws[1].stream; != nullptr: ws[0].stream has not waited for it yet
-    hipEvent_t sl_time1 = nullptr;      // != nullptr: the last timed launch was a sliced call, and this is the end of its slice on ws[1].stream
-    hipEvent_t sl_join = nullptr;       // the full join: ws[1].stream behind ws[0].stream
+    Slices sl;
     hipEvent_t ev_span1 = nullptr;      // mcq_timing_end: the span's end on ws[1].stream
     bool stream_given = false;          // mcq_stream has handed ws[0].stream out: the caller may enqueue on it what the handle does not see
 };
 
 // ws[0].stream BEHIND EVERYTHING the handle has enqueued: the one stream every entry but the sliced mcq_solve_device works on.  A pending slice
 // on ws[1].stream is waited for first (on the device; nothing pending: no call at all), and the next sliced call joins both ways before it
-// launches, because what the caller of this function enqueues is not in its record.  Only solve_device_sliced, the comm stream's waits,
-// mcq_timing_end and creation / destruction take the raw streams.
+// launches, because what the caller of this function enqueues is not in its record.  The step and slice entries, which run on ws[1].stream by
+// design, end with it drained or joined (join_second).  Only solve_device_sliced, join_second, the comm stream's waits, mcq_timing_end and
+// creation / destruction take the raw streams.
 static hipStream_t compute_stream(mcq_handle* h)
 {
-    if (h->sl_last1) {
-        if (hipStreamWaitEvent(h->ws[0].stream, h->sl_last1, 0) != hipSuccess) (void)hipStreamSynchronize(h->ws[1].stream);
-        h->sl_last1 = nullptr;
+    if (h->sl.last1) {
+        if (hipStreamWaitEvent(h->ws[0].stream, h->sl.last1, 0) != hipSuccess) (void)hipStreamSynchronize(h->ws[1].stream);
+        h->sl.last1 = nullptr;
     }
-    h->sl_fast_ok = false;
+    h->sl.fast_ok = false;
     return h->ws[0].stream;
 }
 
@@ -162,7 +168,7 @@ static int hip_failed(const char* expr, hipError_t e, const char* file, int line
 // every stream the handle has created is drained: copies from / into the caller's buffers (or the pinned staging) may still be queued on any of them
 static void drain(mcq_handle* h)
 {
-    for (hipStream_t st : {h->cs_in, h->ws[0].stream, h->ws[1].stream, h->cs_out, h->comm_stream})
+    for (hipStream_t st : {h->cp.in, h->ws[0].stream, h->ws[1].stream, h->cp.out, h->comm_stream})
         if (st) (void)hipStreamSynchronize(st);
 }
 
@@ -178,6 +184,39 @@ static void drain(mcq_handle* h)
         hipError_t e_ = (expr);                                                                   \
         if (e_ != hipSuccess) { drain(h); return hip_failed(#expr, e_, __FILE__, __LINE__); }     \
     } while (0)
+
+// The streams and events beyond ws[0].stream come into being HERE, on the first call that needs them and in this order (the runtime hands
+// out hardware queues at creation; no other order has been measured with the comm stream present).
+enum { COPY_STREAMS = 1, SECOND_STREAM = 2, SLICE_EVENTS = 4, STEP_EVENTS = 8 };
+static int ensure_streams(mcq_handle* h, int what)
+{
+    CopyPipe& c = h->cp;
+    if ((what & COPY_STREAMS) && !c.in) { HIP_TRY(hipStreamCreate(&c.in)); HIP_TRY(hipStreamCreate(&c.out)); }
+    if ((what & SECOND_STREAM) && !h->ws[1].stream) HIP_TRY(hipStreamCreate(&h->ws[1].stream));
+    if (what & SLICE_EVENTS) for (hipEvent_t& e : c.slice) if (!e) HIP_TRY(hipEventCreate(&e));
+    if ((what & STEP_EVENTS) && !c.up[0]) {
+        for (int k = 0; k < 2; ++k) { HIP_TRY(hipEventCreate(&c.up[k])); HIP_TRY(hipEventCreate(&c.done[k])); HIP_TRY(hipEventCreate(&c.down[k])); }
+    }
+    return 0;
+}
+
+// ws[1].stream behind ws[0].stream as it stands now -- and, through compute_stream, ws[0].stream behind the last slice on ws[1].stream
+static int fork_second(mcq_handle* h)
+{
+    if (!h->sl.join) HIP_TRY(hipEventCreate(&h->sl.join));
+    HIP_TRY(hipEventRecord(h->sl.join, compute_stream(h)));
+    HIP_TRY(hipStreamWaitEvent(h->ws[1].stream, h->sl.join, 0));
+    return 0;
+}
+
+// ws[0].stream behind ws[1].stream as it stands now: mcq_sync, a later call on the handle or a caller holding mcq_stream() sees both done
+static int join_second(mcq_handle* h)
+{
+    if (!h->ev_back) HIP_TRY(hipEventCreate(&h->ev_back));
+    HIP_TRY(hipEventRecord(h->ev_back, h->ws[1].stream));
+    HIP_TRY(hipStreamWaitEvent(compute_stream(h), h->ev_back, 0));
+    return 0;
+}
 
 // s holds at least `bytes` afterwards.  A launch in flight on the handle's stream may still read the old buffer: it is waited for before the free.
 // A refused allocation leaves the record empty.
@@ -316,27 +355,22 @@ extern "C" void mcq_destroy(mcq_handle* h)
     if (!h) return;
     (void)hipSetDevice(h->device);
     if (h->ws[0].stream) (void)hipStreamSynchronize(h->ws[0].stream);
-    if (h->cs_in) (void)hipStreamSynchronize(h->cs_in);
-    if (h->cs_out) (void)hipStreamSynchronize(h->cs_out);
+    if (h->cp.in) (void)hipStreamSynchronize(h->cp.in);
+    if (h->cp.out) (void)hipStreamSynchronize(h->cp.out);
     (void)mcq_comm_destroy(h);
     if (h->ws[1].stream) (void)hipStreamSynchronize(h->ws[1].stream);
     for (int k = 0; k < 2; ++k) { free_workspace(h, k); free_staging(h, k); }
     if (h->ws[1].stream) (void)hipStreamDestroy(h->ws[1].stream);
-    for (int k = 0; k < 2; ++k) {
-        if (h->ev_up[k]) (void)hipEventDestroy(h->ev_up[k]);
-        if (h->ev_done[k]) (void)hipEventDestroy(h->ev_done[k]);
-        if (h->ev_down[k]) (void)hipEventDestroy(h->ev_down[k]);
-    }
-    for (int k = 0; k < 16; ++k) if (h->ev_slice[k]) (void)hipEventDestroy(h->ev_slice[k]);
-    if (h->cs_in) (void)hipStreamDestroy(h->cs_in);
-    if (h->cs_out) (void)hipStreamDestroy(h->cs_out);
+    for (hipEvent_t* set : {h->cp.up, h->cp.done, h->cp.down}) for (int k = 0; k < 2; ++k) if (set[k]) (void)hipEventDestroy(set[k]);
+    for (hipEvent_t e : h->cp.slice) if (e) (void)hipEventDestroy(e);
+    if (h->cp.in) (void)hipStreamDestroy(h->cp.in);
+    if (h->cp.out) (void)hipStreamDestroy(h->cp.out);
     for (Scratch* s : {&h->vel, &h->bound, &h->fit, &h->spl, &h->ends, &h->fgen, &h->fgen_pts, &h->mintime}) (void)hipFree(s->p);
     if (h->pin) (void)hipHostFree(h->pin);
     for (int k = 0; k < 5; ++k) if (h->ev[k]) (void)hipEventDestroy(h->ev[k]);
     for (int k = 0; k < 2; ++k) if (h->ev_span[k]) (void)hipEventDestroy(h->ev_span[k]);
-    for (int k = 0; k < 2; ++k) if (h->ev_st[k]) (void)hipEventDestroy(h->ev_st[k]);
-    for (SliceCall& c : h->sl) for (hipEvent_t e : c.end) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : {h->sl_join, h->ev_span1}) if (e) (void)hipEventDestroy(e);
+    for (SliceCall& c : h->sl.call) for (hipEvent_t e : c.end) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : {h->sl.join, h->ev_back, h->ev_span1}) if (e) (void)hipEventDestroy(e);
     if (h->ws[0].stream) (void)hipStreamDestroy(h->ws[0].stream);
     delete h;
 }
@@ -440,7 +474,7 @@ static int ensure_gi_small(mcq_handle* h, size_t batch, size_t nmax)
 static int ensure_workspace(mcq_handle* h, int which, size_t batch, size_t nmax)
 {
     Workspace& w = h->ws[which];
-    if (!w.stream) HIP_TRY(hipStreamCreate(&w.stream));
+    if (int rc = ensure_streams(h, which == 1 ? SECOND_STREAM : 0)) return rc;
     const size_t elems = batch * nmax;
     if (elems <= w.elems && batch <= w.batch && (which == 0 || (size_t)w.gi_nmax >= nmax)) {
         if (which == 0) ensure_gi(h, batch, nmax);
@@ -494,9 +528,9 @@ static int ensure_staging(mcq_handle* h, int which, size_t batch, size_t nmax)
     const size_t elems = batch * nmax;
     if (elems <= s.elems && batch <= s.batch) return 0;
     HIP_TRY(hipStreamSynchronize(compute_stream(h)));
-    if (which == 1) {       // (the pipeline's copy streams: ensure_pipe has created them)
-        HIP_TRY(hipStreamSynchronize(h->cs_in));
-        HIP_TRY(hipStreamSynchronize(h->cs_out));
+    if (which == 1) {       // (the pipeline's copy streams: its entry has created them)
+        HIP_TRY(hipStreamSynchronize(h->cp.in));
+        HIP_TRY(hipStreamSynchronize(h->cp.out));
     }
     free_staging(h, which);
     HIP_TRY(hipMalloc((void**)&s.ref, elems * 4 * sizeof(double)));
@@ -585,39 +619,72 @@ static int fill_batch(mcq_handle* h, McqBatch& B, const mcq_opts& o, Workspace& 
     return 0;
 }
 
-// One solver launch on workspace w and its stream.  The warm start, the event timing and the launch count of a span are workspace 0's: a launch
-// on workspace 1 (mcq_solve_host_pipelined's and mcq_solve_device_stream's odd steps) neither reads nor touches them.
-static int launch(mcq_handle* h, McqBatch& B, const mcq_opts& o, Workspace& w)
+// ---- every solve: prepare, enqueue_solve, note_solve.  The warm start, the event timing and the launch count of a span
+// are workspace 0's: a launch on workspace 1 (mcq_solve_host_pipelined's and mcq_solve_device_stream's odd steps) neither reads nor touches them.
+// A warm start applies only with the working sets mcq_relinearise_device carried over for exactly this batch layout.
+static bool warm_applies(const mcq_handle* h, const mcq_opts& o, int batch, int nmax)
+{
+    return o.warm_start > 0 && h->state2_valid && h->state2_batch == batch && h->state2_nmax == nmax;
+}
+
+static bool shortest_path(const McqBatch& B) { return B.objective == MCQ_OBJ_SHORTEST_PATH && !B.prep_only; }
+
+// B ready for enqueue_solve on workspace w: fill_batch, the warm start (workspace 0's, spent by the solve that may take it), the shortest
+// path's conditions
+static int prepare(mcq_handle* h, McqBatch& B, const mcq_opts& o, Workspace& w)
 {
     const bool first = &w == &h->ws[0];
-    hipStream_t st = first ? compute_stream(h) : w.stream;
     if (int rc = fill_batch(h, B, o, w)) return rc;
-    // warm start: only the working sets mcq_relinearise_device carried over for exactly this batch layout
-    B.warm = (first && o.warm_start > 0 && h->state2_valid && !B.prep_only && h->state2_batch == B.batch && h->state2_nmax == B.nmax)
-                 ? h->state2 : nullptr;
+    B.warm = first && !B.prep_only && warm_applies(h, o, B.batch, B.nmax) ? h->state2 : nullptr;
     if (!B.prep_only && first) h->state2_valid = false;
-    const bool sp = B.objective == MCQ_OBJ_SHORTEST_PATH && !B.prep_only;
-    if (sp && !B.nv) { g_err = "shortest-path objective: normvec is required"; return MCQ_E_ARG; }
-    if (sp) B.check_kappa = 0;
-    if (first) HIP_TRY(hipEventRecord(h->ev[0], st));
+    if (shortest_path(B) && !B.nv) { g_err = "shortest-path objective: normvec is required"; return MCQ_E_ARG; }
+    if (shortest_path(B)) B.check_kappa = 0;
+    return 0;
+}
+
+// THE enqueue of the solver's kernels: problems [b0, b1) of the prepared B on `st`, between the events of mcq_last_timing where `timed`.  The
+// shortest path's assembly and prep_only are launches over the whole batch: such a B goes in one piece.
+static int enqueue_solve(mcq_handle* h, const McqBatch& B, hipStream_t st, int b0, int b1, bool timed)
+{
+    if (b1 == b0) return 0;            // (an empty slice; a grid of 0 workgroups is a launch error)
+    if (timed) HIP_TRY(hipEventRecord(h->ev[0], st));
     if (B.prep_only) {
         hipLaunchKernelGGL(mcq_assemble_kernel, dim3(B.batch), dim3(256), 0, st, B);
         HIP_TRY(hipGetLastError());
         return 0;
     }
     // (minimum curvature has no assembly launch: the solver kernel assembles its problem itself -- assemble_problem() -- since round 4)
-    if (sp) {
+    if (shortest_path(B)) {
         hipLaunchKernelGGL(mcq_assemble_sp_kernel, dim3(B.batch), dim3(256), 0, st, B);
         HIP_TRY(hipGetLastError());
     }
-    if (first) HIP_TRY(hipEventRecord(h->ev[1], st));
-    if (first) HIP_TRY(hipEventRecord(h->ev[2], st));
-    hipLaunchKernelGGL(mcq_solve_kernel, dim3(B.batch), dim3(256), 0, st, B);
+    if (timed) HIP_TRY(hipEventRecord(h->ev[1], st));
+    if (timed) HIP_TRY(hipEventRecord(h->ev[2], st));
+    McqBatch S = B;
+    S.pb0 = b0;
+    hipLaunchKernelGGL(mcq_solve_kernel, dim3(b1 - b0), dim3(256), 0, st, S);
     HIP_TRY(hipGetLastError());
-    if (first) HIP_TRY(hipEventRecord(h->ev[3], st));
-    if (first) HIP_TRY(hipEventRecord(h->ev[4], st));
-    if (first) { h->timing_valid = true; h->sl_time1 = nullptr; }
-    if (first && h->span_open && !sp) ++h->span_launches;       // (a shortest-path launch has never been counted: docs/NOTEBOOK.md, "Host API")
+    if (timed) HIP_TRY(hipEventRecord(h->ev[3], st));
+    if (timed) HIP_TRY(hipEventRecord(h->ev[4], st));
+    return 0;
+}
+
+// What a solve leaves for mcq_last_timing and an open span: once per launch on workspace 0 and once per sliced call, whatever its route.
+// timed: ev[0..4] lie around it; end1: a sliced mcq_solve_device's end on ws[1].stream, which the timing runs to where it is the later one.
+static void note_solve(mcq_handle* h, const McqBatch& B, bool timed, hipEvent_t end1)
+{
+    h->timing_valid = timed;
+    h->sl.time1 = end1;
+    if (h->span_open && !shortest_path(B)) ++h->span_launches;  // (a shortest-path launch has never been counted: docs/NOTEBOOK.md, "Host API")
+}
+
+static int launch(mcq_handle* h, McqBatch& B, const mcq_opts& o, Workspace& w)
+{
+    const bool first = &w == &h->ws[0];
+    hipStream_t st = first ? compute_stream(h) : w.stream;
+    if (int rc = prepare(h, B, o, w)) return rc;
+    if (int rc = enqueue_solve(h, B, st, 0, B.batch, first)) return rc;
+    if (first && !B.prep_only) note_solve(h, B, true, nullptr);
     return 0;
 }
 static int launch(mcq_handle* h, McqBatch& B, const mcq_opts& o) { return launch(h, B, o, h->ws[0]); }
@@ -629,19 +696,36 @@ static int launch(mcq_handle* h, McqBatch& B, const mcq_opts& o) { return launch
 // slices), and a LATER call's slice j is ordered behind this call's slice j only -- by stream order: while the stragglers of one launch finish,
 // the other stream's launch fills the slots they have left.  Results are bitwise those of the one launch: the problems are independent.
 //
-// What keeps this correct is the record h->sl[] of the sliced calls since the last FULL JOIN (each stream waits for the other's last event).
+// What keeps this correct is the record h->sl.call[] of the sliced calls since the last FULL JOIN (each stream waits for the other's last event).
 // A call may skip the join only if it has the record's shape -- the same split, the same workspace rows per slice -- and, by interval checks
 // on addresses, touches nothing the OTHER stream of a recorded call may still be working on (slice_conflict).  Everything else joins first,
 // which is always correct and merely forfeits the overlap: another shape, an overlap, a full record, anything enqueued through compute_stream()
 // in between.  Calls over the very same buffers share one entry (the later call's events stand for both, by stream order), so a loop over one
 // set of buffers, or over two in turn, never fills the record; entries whose launches have ended make room when a new one is needed.
-static int device_slice_min(const mcq_handle* h)
+// THE routing rule (DESIGN.md section 7 has the table and the reasons): the slices a solve of this shape gets from an entry of this kind;
+// 1 = the one launch.  Shared conditions first, then the kind's threshold and knobs.
+enum EntryKind { ENTRY_DEVICE, ENTRY_HOST };
+static int slices_for(const mcq_handle* h, EntryKind kind, int batch, int nmax, const mcq_opts& o)
 {
-    if (const char* e = getenv("MCQ_DEVICE_SLICE_MIN")) return std::max(atoi(e), 2);        // (the tests slice batches of two to eight)
-    // More than one residency round (two workgroups per CU): a batch the device holds at once has no tail to fill, and an isolated call of
-    // exactly 512 problems on 256 CUs takes 5.79 ms as two launches of 256 against 5.46 ms as one (docs/NOTEBOOK.md)
-    return 2 * h->cus + 1;
+    if (o.objective != MCQ_OBJ_MIN_CURV || o.algorithm == MCQ_ALG_GI || warm_applies(h, o, batch, nmax)) return 1;
+    if (kind == ENTRY_DEVICE) {
+        // More than one residency round (two workgroups per CU): a batch the device holds at once has no tail to fill, and an isolated call of
+        // exactly 512 problems on 256 CUs takes 5.79 ms as two launches of 256 against 5.46 ms as one (docs/NOTEBOOK.md)
+        int slice_min = 2 * h->cus + 1;
+        if (const char* e = getenv("MCQ_DEVICE_SLICE_MIN")) slice_min = std::max(atoi(e), 2);      // (the tests slice batches of two to eight)
+        // two slices, split (batch + 1) / 2; not on a handle whose stream the caller holds (mcq_stream).  $MCQ_DEVICE_ONE_LAUNCH=1: the A/B knob
+        const char* one = getenv("MCQ_DEVICE_ONE_LAUNCH");
+        return batch < slice_min || h->stream_given || (one && one[0] == '1') ? 1 : 2;
+    }
+    int slice_min = 512;           // ($MCQ_HOST_SLICE_MIN: the tests slice a batch of eleven)
+    if (const char* e = getenv("MCQ_HOST_SLICE_MIN")) slice_min = std::max(atoi(e), 4);
+    int nsl = 2;                   // (one per compute stream; more make a heavy-tailed batch wait slice by slice: docs/NOTEBOOK.md R6.5)
+    if (const char* e = getenv("MCQ_HOST_SLICES")) nsl = std::min(std::max(atoi(e), 2), 8);
+    nsl = std::min(nsl, batch);        // (a slice per problem at most: eight slices of a batch of four to seven had empty ones)
+    return nsl > 1 && batch >= slice_min && !getenv("MCQ_HOST_ONE_LAUNCH") ? nsl : 1;          // ($MCQ_HOST_ONE_LAUNCH: the A/B knob)
 }
+// the host entries' split: slice or chunk k of `parts` begins at this problem
+static int split_at(int batch, int k, int parts) { return (int)((long long)batch * k / parts); }
 
 static Range rows_of(const void* p, size_t r0, size_t r1, size_t row_bytes)
 {
@@ -703,61 +787,46 @@ static bool event_done(hipEvent_t e)
 
 static int solve_device_sliced(mcq_handle* h, McqBatch& B, const mcq_opts& o)
 {
-    if (!h->ws[1].stream) HIP_TRY(hipStreamCreate(&h->ws[1].stream));
-    if (!h->sl_join) HIP_TRY(hipEventCreate(&h->sl_join));
-    if (int rc = fill_batch(h, B, o, h->ws[0])) return rc;
-    B.warm = nullptr;
-    h->state2_valid = false;
+    if (int rc = ensure_streams(h, SECOND_STREAM)) return rc;
+    if (int rc = prepare(h, B, o, h->ws[0])) return rc;
     const int b = (B.batch + 1) / 2;
     SliceCall c;
     slice_ranges(B, b, c);
-    bool join = !h->sl_fast_ok || B.batch != h->sl_batch || B.nmax != h->sl_n;
-    for (int k = 0; k < h->sl_count && !join; ++k) join = slice_conflict(c, h->sl[k]);
+    bool join = !h->sl.fast_ok || B.batch != h->sl.batch || B.nmax != h->sl.n;
+    for (int k = 0; k < h->sl.count && !join; ++k) join = slice_conflict(c, h->sl.call[k]);
     int slot = -1;
-    for (int k = 0; k < h->sl_count && !join && slot < 0; ++k) if (same_buffers(c, h->sl[k])) slot = k;
-    if (!join && slot < 0 && h->sl_count == MCQ_SLICE_CALLS) {
+    for (int k = 0; k < h->sl.count && !join && slot < 0; ++k) if (same_buffers(c, h->sl.call[k])) slot = k;
+    if (!join && slot < 0 && h->sl.count == MCQ_SLICE_CALLS) {
         // room: the entries whose launches have ended on both streams go (their events stay with their slots)
         int kept = 0;
-        for (int k = 0; k < h->sl_count; ++k)
-            if (!(event_done(h->sl[k].end[0]) && event_done(h->sl[k].end[1]))) std::swap(h->sl[kept++], h->sl[k]);
-        h->sl_count = kept;
+        for (int k = 0; k < h->sl.count; ++k)
+            if (!(event_done(h->sl.call[k].end[0]) && event_done(h->sl.call[k].end[1]))) std::swap(h->sl.call[kept++], h->sl.call[k]);
+        h->sl.count = kept;
         join = kept == MCQ_SLICE_CALLS;
     }
     hipStream_t s0 = h->ws[0].stream, s1 = h->ws[1].stream;
     if (join) {
-        // the full join: ws[0].stream behind the last slice on ws[1].stream (compute_stream), ws[1].stream behind ws[0].stream as it is now
-        s0 = compute_stream(h);
-        HIP_TRY(hipEventRecord(h->sl_join, s0));
-        HIP_TRY(hipStreamWaitEvent(s1, h->sl_join, 0));
-        h->sl_count = 0;
-        h->sl_batch = B.batch;
-        h->sl_n = B.nmax;
-        h->sl_fast_ok = true;
+        // the full join: ws[0].stream behind the last slice on ws[1].stream, ws[1].stream behind ws[0].stream as it is now
+        if (int rc = fork_second(h)) return rc;
+        h->sl.count = 0;
+        h->sl.batch = B.batch;
+        h->sl.n = B.nmax;
+        h->sl.fast_ok = true;
     }
-    if (slot < 0 || join) slot = h->sl_count++;
-    SliceCall& e = h->sl[slot];
+    if (slot < 0 || join) slot = h->sl.count++;
+    SliceCall& e = h->sl.call[slot];
     for (int j = 0; j < 2; ++j) if (!e.end[j]) HIP_TRY(hipEventCreate(&e.end[j]));
     c.end[0] = e.end[0];
     c.end[1] = e.end[1];
     e = c;
-    if (getenv("MCQ_DEVICE_SLICE_TRACE")) fprintf(stderr, "mcq_solve_device: two slices, %s, %d in the record\n", join ? "joined" : "overlapped", h->sl_count);
-    // slice 0 carries the event timing of launch(): mcq_last_timing reads slice 1's end next to it
-    McqBatch S = B;
-    HIP_TRY(hipEventRecord(h->ev[0], s0));
-    HIP_TRY(hipEventRecord(h->ev[1], s0));
-    HIP_TRY(hipEventRecord(h->ev[2], s0));
-    hipLaunchKernelGGL(mcq_solve_kernel, dim3(b), dim3(256), 0, s0, S);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(h->ev[3], s0));
-    HIP_TRY(hipEventRecord(h->ev[4], s0));
+    if (getenv("MCQ_DEVICE_SLICE_TRACE")) fprintf(stderr, "mcq_solve_device: two slices, %s, %d in the record\n", join ? "joined" : "overlapped", h->sl.count);
+    // slice 0 carries the event timing of a launch: mcq_last_timing reads slice 1's end next to it
+    if (int rc = enqueue_solve(h, B, s0, 0, b, true)) return rc;
     HIP_TRY(hipEventRecord(e.end[0], s0));
-    S.pb0 = b;
-    hipLaunchKernelGGL(mcq_solve_kernel, dim3(B.batch - b), dim3(256), 0, s1, S);
-    HIP_TRY(hipGetLastError());
+    if (int rc = enqueue_solve(h, B, s1, b, B.batch, false)) return rc;
     HIP_TRY(hipEventRecord(e.end[1], s1));
-    h->sl_last1 = h->sl_time1 = e.end[1];
-    h->timing_valid = true;
-    if (h->span_open) ++h->span_launches;       // one per CALL: span / launches stays the average device time per step
+    h->sl.last1 = e.end[1];
+    note_solve(h, B, true, e.end[1]);           // one per CALL: span / launches stays the average device time per step
     return 0;
 }
 
@@ -774,14 +843,7 @@ extern "C" int mcq_solve_device(mcq_handle* h, int batch, int n, const double* r
     int rc = ensure_workspace(h, 0, (size_t)batch, (size_t)n);
     if (rc) return rc;
     McqBatch B = make_batch(batch, n, nullptr, reftrack, normvec, scaling, alpha_out, curv_err_out, status_out, info_out, kappa_bound, w_veh);
-    // One launch ($MCQ_DEVICE_ONE_LAUNCH=1: always, the A/B knob) for what has no tail to fill or is tied to ws[0].stream: a batch below the
-    // threshold, a warm start that applies (state2), the shortest path (its assembly kernel precedes the solve), MCQ_ALG_GI (its small slots
-    // are sized for one launch's resident workgroups), a handle whose stream the caller holds (mcq_stream).  mcq_solve_device_f32 and
-    // mcq_solve_device_f32_rows stay with the one launch too: their conversions run on ws[0].stream around the solve, and config 5's 8192
-    // problems per GPU -- sixteen residency rounds -- amortise the tail.
-    const bool warm = o.warm_start > 0 && h->state2_valid && h->state2_batch == batch && h->state2_nmax == n;
-    const char* one = getenv("MCQ_DEVICE_ONE_LAUNCH");
-    if (batch < device_slice_min(h) || warm || o.objective != MCQ_OBJ_MIN_CURV || o.algorithm == MCQ_ALG_GI || h->stream_given || (one && one[0] == '1')) {
+    if (slices_for(h, ENTRY_DEVICE, batch, n, o) == 1) {
         if (getenv("MCQ_DEVICE_SLICE_TRACE")) fprintf(stderr, "mcq_solve_device: one launch\n");
         return launch(h, B, o);
     }
@@ -2003,13 +2065,13 @@ extern "C" int mcq_last_timing(mcq_handle* h, float ms[5])
     HIP_TRY(hipEventElapsedTime(&ms[2], h->ev[2], h->ev[3]));
     ms[3] = 0.0f;
     HIP_TRY(hipEventElapsedTime(&ms[4], h->ev[0], h->ev[4]));
-    if (h->sl_time1) {
+    if (h->sl.time1) {
         // a sliced mcq_solve_device: from slice 0's start to the later of the two slices' ends (neither stream has waited for the other)
         float to1 = 0.0f;
-        HIP_TRY(hipEventSynchronize(h->sl_time1));
-        HIP_TRY(hipEventElapsedTime(&to1, h->ev[2], h->sl_time1));
+        HIP_TRY(hipEventSynchronize(h->sl.time1));
+        HIP_TRY(hipEventElapsedTime(&to1, h->ev[2], h->sl.time1));
         ms[2] = std::max(ms[2], to1);
-        HIP_TRY(hipEventElapsedTime(&to1, h->ev[0], h->sl_time1));
+        HIP_TRY(hipEventElapsedTime(&to1, h->ev[0], h->sl.time1));
         ms[4] = std::max(ms[4], to1);
     }
     return 0;
@@ -2036,7 +2098,7 @@ extern "C" int mcq_timing_end(mcq_handle* h, float* ms_out, int* launches_out)
     HIP_TRY(hipEventRecord(h->ev_span[1], h->ws[0].stream));
     HIP_TRY(hipEventSynchronize(h->ev_span[1]));
     HIP_TRY(hipEventElapsedTime(ms_out, h->ev_span[0], h->ev_span[1]));
-    if (h->sl_last1) {         // slices pending on ws[1].stream: an end event there as well, neither stream waiting for the other
+    if (h->sl.last1) {         // slices pending on ws[1].stream: an end event there as well, neither stream waiting for the other
         float ms1 = 0.0f;
         if (!h->ev_span1) HIP_TRY(hipEventCreate(&h->ev_span1));
         HIP_TRY(hipEventRecord(h->ev_span1, h->ws[1].stream));
@@ -2162,61 +2224,29 @@ extern "C" int mcq_host_free(mcq_handle* h, void* ptr)
     return 0;
 }
 
-// the knobs of the sliced host entries (mcq_solve_host, mcq_solve_batch): slices for this batch / these options, or 1
-static int host_slices(int batch, const mcq_opts& o)
+// rows [row0, row0 + rows) of n waypoints each, from the host arrays ref / nv / sc (whole, [batch][n][*]; nv, sc: or nullptr) into staging set s
+static int upload_rows(mcq_handle* h, const Staging& s, const double* ref, const double* nv, const double* sc, size_t row0, size_t rows, size_t n,
+                       hipStream_t st)
 {
-    int slice_min = 512;           // ($MCQ_HOST_SLICE_MIN: the tests slice a batch of eleven)
-    if (const char* e = getenv("MCQ_HOST_SLICE_MIN")) slice_min = std::max(atoi(e), 4);
-    // TWO slices, one per compute stream: both are in flight as soon as their uploads are, so a batch with a heavy tail -- a sweep over tight
-    // curvature bounds, where single problems take seconds in the Goldfarb-Idnani path -- loses nothing against the one launch.  Four slices
-    // gain 0.3 ms more on uniform batches (11.5 against 11.8 ms for 1024 x N = 2000; one launch: 13.0) but make slice k + 2 wait for the slowest
-    // problem of slice k on its stream: 600 curvature-tight long rings then take 76 s instead of 45 (docs/NOTEBOOK.md R6.5).  $MCQ_HOST_SLICES: 2 .. 8
-    int nsl = 2;
-    if (const char* e = getenv("MCQ_HOST_SLICES")) nsl = std::min(std::max(atoi(e), 2), 8);
-    nsl = std::min(nsl, batch);        // (a slice per problem at most: eight slices of a batch of four to seven had empty ones)
-    return (nsl > 1 && batch >= slice_min && o.objective == MCQ_OBJ_MIN_CURV && o.algorithm != MCQ_ALG_GI && !getenv("MCQ_HOST_ONE_LAUNCH")) ? nsl : 1;
-}
-// the compute stream of slice k: the handle's two, in turn.  (Tried, round 6: a stream per slice -- 14.0 ms where two streams give 11.5 for four
-// slices of 256 problems, and the 600 curvature-tight long rings 105 s where the one launch takes 45: more than two queues of large workgroups
-// cost more in the hardware scheduler than they overlap.)
-static hipStream_t slice_stream(mcq_handle* h, int k) { return h->ws[k & 1].stream; }
-static int ensure_slice_streams(mcq_handle* h)
-{
-    if (!h->cs_in) { HIP_TRY(hipStreamCreate(&h->cs_in)); HIP_TRY(hipStreamCreate(&h->cs_out)); }
-    if (!h->ws[1].stream) HIP_TRY(hipStreamCreate(&h->ws[1].stream));
-    for (int k = 0; k < 16; ++k) if (!h->ev_slice[k]) HIP_TRY(hipEventCreate(&h->ev_slice[k]));
-    HIP_TRY(hipStreamSynchronize(compute_stream(h)));          // whatever ran before on the handle is done with the staging buffers and the workspace
-    HIP_TRY(hipStreamSynchronize(h->ws[1].stream));
+    const size_t off = row0 * n, cnt = rows * n;
+    HIP_TRY_DRAIN(hipMemcpyAsync(s.ref + off * 4, ref + off * 4, cnt * 4 * sizeof(double), hipMemcpyHostToDevice, st));
+    if (nv) HIP_TRY_DRAIN(hipMemcpyAsync(s.nv + off * 2, nv + off * 2, cnt * 2 * sizeof(double), hipMemcpyHostToDevice, st));
+    if (sc) HIP_TRY_DRAIN(hipMemcpyAsync(s.sc + off, sc + off, cnt * sizeof(double), hipMemcpyHostToDevice, st));
     return 0;
 }
 
-// what a sliced entry does where the others call launch(): the streams; workspace 0, options and slots of the batch; no warm start, no event timing
-static int begin_slices(mcq_handle* h, McqBatch& B, const mcq_opts& o)
-{
-    if (int rc = ensure_slice_streams(h)) return rc;
-    if (int rc = fill_batch(h, B, o, h->ws[0])) return rc;
-    B.warm = nullptr;
-    h->state2_valid = false;
-    h->timing_valid = false;
-    return 0;
-}
-
-// Slice k = problems b0 .. b1 - 1 of B, whose uploads have just been queued on h->cs_in: its kernel behind them on the slice's compute stream,
-// its rows of alpha (B.nmax each) behind the kernel on h->cs_out into alpha_host ([batch][nmax], the caller's array or the pinned staging).
+// Slice k = problems b0 .. b1 - 1 of B, whose uploads have just been queued on h->cp.in: its kernel behind them on the slice's compute stream,
+// its rows of alpha (B.nmax each) behind the kernel on h->cp.out into alpha_host ([batch][nmax], the caller's array or the pinned staging).
 static int launch_slice(mcq_handle* h, const McqBatch& B, int k, int b0, int b1, double* alpha_host)
 {
-    if (b1 == b0) return 0;            // (none with nsl <= batch; a grid of 0 workgroups is a launch error)
-    HIP_TRY_DRAIN(hipEventRecord(h->ev_slice[k], h->cs_in));
-    hipStream_t st = slice_stream(h, k);
-    HIP_TRY_DRAIN(hipStreamWaitEvent(st, h->ev_slice[k], 0));
-    McqBatch S = B;
-    S.pb0 = b0;
-    hipLaunchKernelGGL(mcq_solve_kernel, dim3(b1 - b0), dim3(256), 0, st, S);
-    HIP_TRY_DRAIN(hipGetLastError());
-    HIP_TRY_DRAIN(hipEventRecord(h->ev_slice[8 + k], st));
-    HIP_TRY_DRAIN(hipStreamWaitEvent(h->cs_out, h->ev_slice[8 + k], 0));
+    HIP_TRY_DRAIN(hipEventRecord(h->cp.slice[k], h->cp.in));
+    hipStream_t st = h->ws[k & 1].stream;          // the handle's two, in turn (a stream per slice was slower: docs/NOTEBOOK.md R6.5)
+    HIP_TRY_DRAIN(hipStreamWaitEvent(st, h->cp.slice[k], 0));
+    if (int rc = enqueue_solve(h, B, st, b0, b1, false)) { drain(h); return rc; }
+    HIP_TRY_DRAIN(hipEventRecord(h->cp.slice[8 + k], st));
+    HIP_TRY_DRAIN(hipStreamWaitEvent(h->cp.out, h->cp.slice[8 + k], 0));
     const size_t off = (size_t)b0 * B.nmax, cnt = (size_t)(b1 - b0) * B.nmax;
-    HIP_TRY_DRAIN(hipMemcpyAsync(alpha_host + off, B.alpha + off, cnt * sizeof(double), hipMemcpyDeviceToHost, h->cs_out));
+    HIP_TRY_DRAIN(hipMemcpyAsync(alpha_host + off, B.alpha + off, cnt * sizeof(double), hipMemcpyDeviceToHost, h->cp.out));
     return 0;
 }
 
@@ -2229,6 +2259,159 @@ static int download_results(mcq_handle* h, hipStream_t st, int batch, void* alph
     HIP_TRY_DRAIN(hipMemcpyAsync(curv_err_dst, h->stage[0].curv, batch * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY_DRAIN(hipMemcpyAsync(status_dst, h->stage[0].status, batch * sizeof(int), hipMemcpyDeviceToHost, st));
     if (info_dst) HIP_TRY_DRAIN(hipMemcpyAsync(info_dst, h->d_info, batch * sizeof(mcq_info), hipMemcpyDeviceToHost, st));
+    return 0;
+}
+
+// ---- how a host batch goes up: per-problem buffers through the handle's pinned staging ([batch][nmax][*]) or straight from where they lie ----
+// What the entry states, then what plan_upload decides once per call; the loop over chunks [b0, b1) of problems (upload_chunk) is the caller's.
+struct Upload {
+    const mcq_problem* probs;   // nullptr: a UNIFORM batch (mcq_solve_host) -- ref / nv / sc are the caller's arrays, read as they lie, one chunk
+    int batch;
+    size_t nmax;
+    bool any_sc, with_nv;
+    double *ref, *nv, *sc, *alpha, *kb, *wv;       // the pinned block: ref | nv | sc | alpha | kb | wv | info | n   (then the entry's extra bytes)
+    mcq_info* info;
+    int* n;
+    bool direct;                // no packing pass: strided copies from the caller's page-locked arrays
+    int nthreads, nchunks;      // of the packing pass where the entry does not slice (a direct batch: one chunk)
+};
+
+// the per-problem scalars of a ragged host batch, through the pinned block to the device on `up`
+static int upload_scalars(mcq_handle* h, const Upload& U, hipStream_t up)
+{
+    if (!U.probs) return 0;         // (a uniform batch: its scalars are arguments of the launch)
+    for (int b = 0; b < U.batch; ++b) { U.kb[b] = U.probs[b].kappa_bound; U.wv[b] = U.probs[b].w_veh; U.n[b] = U.probs[b].n; }
+    HIP_TRY_DRAIN(hipMemcpyAsync(h->d_kb, U.kb, U.batch * sizeof(double), hipMemcpyHostToDevice, up));
+    HIP_TRY_DRAIN(hipMemcpyAsync(h->d_wv, U.wv, U.batch * sizeof(double), hipMemcpyHostToDevice, up));
+    HIP_TRY_DRAIN(hipMemcpyAsync(h->d_n, U.n, U.batch * sizeof(int), hipMemcpyHostToDevice, up));
+    return 0;
+}
+
+// lays out the pinned block and decides how the batch goes up; enqueues nothing
+static int plan_upload(mcq_handle* h, Upload& U, size_t extra_bytes)
+{
+    const mcq_problem* probs = U.probs;
+    const int batch = U.batch;
+    const bool with_nv = U.with_nv;
+    const size_t elems = (size_t)batch * U.nmax;
+    const size_t bytes = elems * (4 + 2 + 1 + 1) * sizeof(double) + (size_t)batch * (2 * sizeof(double) + sizeof(int) + sizeof(mcq_info)) + 64 + extra_bytes;
+    if (int rc = ensure_pin(h, bytes)) return rc;
+    U.ref = (double*)h->pin;
+    U.nv = U.ref + elems * 4;
+    U.sc = U.nv + elems * 2;
+    U.alpha = U.sc + elems;
+    U.kb = U.alpha + elems;
+    U.wv = U.kb + batch;
+    U.info = (mcq_info*)(U.wv + batch);
+    U.n = (int*)(U.info + batch);
+    // ---- no packing at all (round 6): a UNIFORM batch that lies in the caller's memory as one contiguous, page-locked block per array (what
+    //      engine.py hands over for stacked arrays from mcq_host_alloc) goes to the device straight from there -- one strided copy per array
+    //      (rows of n waypoints into rows of nmax) instead of a 115 MB memcpy into the staging first: that memcpy was 4-6 ms of a 36-42 ms
+    //      mcq_iqp_batch call and the part of it that differs from host to host.  $MCQ_PACK_ALWAYS=1: the packing pass (A/B knob). ----
+    const int n0 = probs[0].n;
+    bool direct = batch >= 2 && n0 > 0 && !getenv("MCQ_PACK_ALWAYS");
+    for (int b = 1; b < batch && direct; ++b) {
+        direct = probs[b].n == n0 && probs[b].reftrack == probs[0].reftrack + (size_t)b * n0 * 4
+                 && (!with_nv || probs[b].normvec == probs[0].normvec + (size_t)b * n0 * 2)
+                 && (probs[0].scaling ? probs[b].scaling == probs[0].scaling + (size_t)b * n0 : probs[b].scaling == nullptr);
+    }
+    auto pinned = [](const void* p) {
+        hipPointerAttribute_t a;
+        if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+        return a.type == hipMemoryTypeHost;
+    };
+    U.direct = direct && pinned(probs[0].reftrack) && (!with_nv || pinned(probs[0].normvec)) && (!probs[0].scaling || pinned(probs[0].scaling));
+    h->last_upload_direct = U.direct ? 1 : 0;
+    // A large batch (the 1024 N = 2000 tracks of the bench: 115 MB) is packed in four chunks of tracks by several host threads, and a
+    // chunk's uploads are queued as soon as it is packed: one thread copies at ~10 GB/s -- 11 ms, a quarter of the whole mcq_iqp_batch
+    // call -- and the DMA of chunk k runs while chunk k + 1 is packed.  $MCQ_PACK_THREADS: threads (default 8 for batches above 8 MB; 1 = the single loop).
+    const size_t row_doubles = 4 + (with_nv ? 2 : 0) + (U.any_sc ? 1 : 0);
+    const size_t payload = elems * row_doubles * sizeof(double);
+    const char* pt = getenv("MCQ_PACK_THREADS");
+    const bool forced = pt && *pt;          // (asked for explicitly: whatever the size of the batch -- the tests pack six small tracks on three threads)
+    int nthreads = forced ? atoi(pt) : (payload > ((size_t)8 << 20) && batch >= 16 ? 8 : 1);
+    const int hw = (int)std::thread::hardware_concurrency();
+    if (hw > 0 && nthreads > hw) nthreads = hw;
+    if (nthreads > batch) nthreads = batch;
+    if (nthreads < 1) nthreads = 1;
+    U.nthreads = nthreads;
+    U.nchunks = U.direct ? 1 : std::min(batch, (forced && nthreads > 1) || (payload > ((size_t)32 << 20) && batch >= 16) ? 4 : 1);
+    return 0;
+}
+
+// problems [b0, b1) of the batch into staging set 0 on `up`: straight from the caller's arrays, or packed into the pinned block (by the plan's
+// threads; the padding behind a track's n waypoints is never read by a kernel: no need to clear it) and copied from there
+static int upload_chunk(mcq_handle* h, const Upload& U, int b0, int b1, hipStream_t up)
+{
+    const Staging& s = h->stage[0];
+    const mcq_problem* probs = U.probs;
+    const size_t nmax = U.nmax;
+    if (U.direct) {
+        const size_t w = (size_t)probs[0].n * sizeof(double), pitch = nmax * sizeof(double), rows = (size_t)(b1 - b0);
+        HIP_TRY_DRAIN(hipMemcpy2DAsync(s.ref + (size_t)b0 * nmax * 4, pitch * 4, probs[b0].reftrack, w * 4, w * 4, rows, hipMemcpyHostToDevice, up));
+        if (U.with_nv) HIP_TRY_DRAIN(hipMemcpy2DAsync(s.nv + (size_t)b0 * nmax * 2, pitch * 2, probs[b0].normvec, w * 2, w * 2, rows, hipMemcpyHostToDevice, up));
+        if (U.any_sc) HIP_TRY_DRAIN(hipMemcpy2DAsync(s.sc + (size_t)b0 * nmax, pitch, probs[b0].scaling, w, w, rows, hipMemcpyHostToDevice, up));
+        return 0;
+    }
+    if (probs) fan_out(b0, b1, U.nthreads, [&](int, int r0, int r1) {
+        for (int b = r0; b < r1; ++b) {
+            const size_t n = (size_t)probs[b].n;
+            memcpy(U.ref + (size_t)b * nmax * 4, probs[b].reftrack, n * 4 * sizeof(double));
+            if (U.with_nv) memcpy(U.nv + (size_t)b * nmax * 2, probs[b].normvec, n * 2 * sizeof(double));
+            if (U.any_sc) {
+                if (probs[b].scaling) memcpy(U.sc + (size_t)b * nmax, probs[b].scaling, n * sizeof(double));
+                else for (size_t q = 0; q < n; ++q) U.sc[(size_t)b * nmax + q] = 1.0;
+            }
+        }
+    });
+    return upload_rows(h, s, U.ref, U.with_nv ? U.nv : nullptr, U.any_sc ? U.sc : nullptr, (size_t)b0, (size_t)(b1 - b0), nmax, up);
+}
+
+// the whole batch on the compute stream, for the one launch behind it (mcq_solve_batch unsliced, mcq_iqp_batch)
+static int upload_batch(mcq_handle* h, const Upload& U)
+{
+    hipStream_t up = compute_stream(h);
+    if (U.direct) { if (int rc = upload_scalars(h, U, up)) return rc; }        // (a direct batch's scalars have always gone first)
+    for (int k = 0; k < U.nchunks; ++k)
+        if (int rc = upload_chunk(h, U, split_at(U.batch, k, U.nchunks), split_at(U.batch, k + 1, U.nchunks), up)) return rc;
+    if (!U.direct) { if (int rc = upload_scalars(h, U, up)) return rc; }       // (a packed batch's follow the rows)
+    return 0;
+}
+
+// A host-buffer batch through staging set 0, in slices or as one launch (slices_for): U says how its rows go up, alpha comes back into
+// alpha_host ([batch][nmax]: the caller's array or the pinned staging), the small arrays into the caller's.  Returns with all of it done.
+// In SLICES the upload (and packing) of slice k + 1 and the download of slice k - 1 run while slice k's kernel does -- a copy stream each way,
+// the kernels on the two compute streams in turn, all on disjoint rows of the ONE workspace (McqBatch.pb0): bitwise the one launch.  No
+// event timing then: no pair of events spans the slices' kernels.
+static int solve_staged(mcq_handle* h, McqBatch& B, const mcq_opts& o, const Upload& U, double* alpha_host, double* curv_out, int* status_out,
+                        mcq_info* info_host)
+{
+    const int batch = B.batch, nsl = slices_for(h, ENTRY_HOST, batch, B.nmax, o);
+    if (nsl == 1) {
+        if (int rc = upload_batch(h, U)) return rc;
+        if (int rc = launch(h, B, o)) { drain(h); return rc; }
+        hipStream_t st = compute_stream(h);
+        if (int rc = download_results(h, st, batch, alpha_host, B.alpha, (size_t)batch * B.nmax * sizeof(double), curv_out, status_out, info_host)) return rc;
+        HIP_TRY(hipStreamSynchronize(st));
+        return 0;
+    }
+    if (int rc = ensure_streams(h, COPY_STREAMS | SECOND_STREAM | SLICE_EVENTS)) return rc;
+    HIP_TRY(hipStreamSynchronize(compute_stream(h)));          // whatever ran before on the handle is done with the staging buffers and the workspace
+    HIP_TRY(hipStreamSynchronize(h->ws[1].stream));
+    if (int rc = prepare(h, B, o, h->ws[0])) return rc;
+    int rc = upload_scalars(h, U, h->cp.in);                   // the slices' kernels read the per-problem scalars: first
+    for (int k = 0; k < nsl && !rc; ++k) {
+        const int b0 = split_at(batch, k, nsl), b1 = split_at(batch, k + 1, nsl);
+        rc = upload_chunk(h, U, b0, b1, h->cp.in);
+        if (!rc) rc = launch_slice(h, B, k, b0, b1, alpha_host);
+    }
+    if (rc) { drain(h); return rc; }
+    // (cp.out is behind every slice's kernel now: the small arrays follow the last slice's alpha)
+    if ((rc = download_results(h, h->cp.out, batch, nullptr, nullptr, 0, curv_out, status_out, info_host))) return rc;
+    HIP_TRY_DRAIN(hipStreamSynchronize(h->cp.out));
+    HIP_TRY_DRAIN(hipStreamSynchronize(compute_stream(h)));
+    HIP_TRY_DRAIN(hipStreamSynchronize(h->ws[1].stream));
+    note_solve(h, B, false, nullptr);
     return 0;
 }
 
@@ -2246,47 +2429,14 @@ extern "C" int mcq_solve_host(mcq_handle* h, int batch, int n, const double* ref
     if (rc) return rc;
     rc = ensure_staging(h, 0, (size_t)batch, (size_t)n);
     if (rc) return rc;
-    const size_t elems = (size_t)batch * n;
     const Staging& s = h->stage[0];
     McqBatch B = make_batch(batch, n, nullptr, s.ref, normvec ? s.nv : nullptr, scaling ? s.sc : nullptr, s.alpha, s.curv, s.status,
                             info_out ? h->d_info : nullptr, kappa_bound, w_veh);
-    // A large batch in (two) SLICES (round 6): the upload of slice k + 1 and the download of slice k - 1 run while slice k's kernel does -- on a
-    // copy stream each way --, and the kernels of consecutive slices go to the handle's two compute streams; all of them work on disjoint rows of
-    // the ONE workspace (McqBatch.pb0).  The blocking single-batch entry had paid its 115 MB of H2D and 16 MB of D2H in full next to the kernel: 13.3 ms
-    // for a 10.4 ms kernel at 1024 x N = 2000.  Results bitwise those of the one launch: the problems are independent.  $MCQ_HOST_ONE_LAUNCH=1:
-    // the one launch (A/B knob).
-    const int nsl = host_slices(batch, o);
-    if (nsl > 1) {
-        rc = begin_slices(h, B, o);
-        if (rc) return rc;
-        for (int k = 0; k < nsl; ++k) {
-            const int b0 = (int)((long long)batch * k / nsl), b1 = (int)((long long)batch * (k + 1) / nsl);
-            const size_t off = (size_t)b0 * n, cnt = (size_t)(b1 - b0) * n;
-            HIP_TRY_DRAIN(hipMemcpyAsync(s.ref + off * 4, reftrack + off * 4, cnt * 4 * sizeof(double), hipMemcpyHostToDevice, h->cs_in));
-            if (normvec) HIP_TRY_DRAIN(hipMemcpyAsync(s.nv + off * 2, normvec + off * 2, cnt * 2 * sizeof(double), hipMemcpyHostToDevice, h->cs_in));
-            if (scaling) HIP_TRY_DRAIN(hipMemcpyAsync(s.sc + off, scaling + off, cnt * sizeof(double), hipMemcpyHostToDevice, h->cs_in));
-            rc = launch_slice(h, B, k, b0, b1, alpha_out);
-            if (rc) return rc;
-        }
-        // (cs_out is behind every slice's kernel now: the small arrays follow the last slice's alpha)
-        rc = download_results(h, h->cs_out, batch, nullptr, nullptr, 0, curv_err_out, status_out, info_out);
-        if (rc) return rc;
-        HIP_TRY(hipStreamSynchronize(h->cs_out));
-        HIP_TRY(hipStreamSynchronize(compute_stream(h)));
-        HIP_TRY(hipStreamSynchronize(h->ws[1].stream));
-        return 0;
-    }
-    hipStream_t st = compute_stream(h);
-    HIP_TRY_DRAIN(hipMemcpyAsync(s.ref, reftrack, elems * 4 * sizeof(double), hipMemcpyHostToDevice, st));
-    if (normvec) HIP_TRY_DRAIN(hipMemcpyAsync(s.nv, normvec, elems * 2 * sizeof(double), hipMemcpyHostToDevice, st));
-    if (scaling) HIP_TRY_DRAIN(hipMemcpyAsync(s.sc, scaling, elems * sizeof(double), hipMemcpyHostToDevice, st));
-    rc = launch(h, B, o);
-    if (rc) { drain(h); return rc; }
-    rc = download_results(h, st, batch, alpha_out, s.alpha, elems * sizeof(double), curv_err_out, status_out, info_out);
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(st));
-    // (MCQ_KAPPA_NO_SLOT never arrives here since round 5: the Goldfarb-Idnani path inside the solver kernel takes such problems)
-    return 0;
+    // uniform: the caller's arrays as they lie, read only (nothing is packed into them), one chunk
+    Upload U = {nullptr, batch, (size_t)n, scaling != nullptr, normvec != nullptr, const_cast<double*>(reftrack), const_cast<double*>(normvec),
+                const_cast<double*>(scaling)};
+    U.nchunks = 1;
+    return solve_staged(h, B, o, U, alpha_out, curv_err_out, status_out, info_out);
 }
 
 // Host-buffer fp32 entry (mcq_solve_batch_f32): float rows in, float alpha out -- half the PCIe bytes of the
@@ -2323,21 +2473,17 @@ extern "C" int mcq_solve_batch_f32(mcq_handle* h, int batch, int n, int layout, 
 }
 
 // ---- a stream of uniform host batches with the PCIe behind the kernels (include/mcq.h) ------------------------------------------
-// two copy streams, one event triple per staging slot, the second slot
-static int ensure_pipe(mcq_handle* h, size_t batch, size_t nmax)
+// What the two step entries (mcq_solve_host_pipelined, mcq_solve_device_stream) share.  Kernels of odd steps on the second compute stream /
+// workspace ($MCQ_PIPE_ONE_STREAM: the A/B knob); MCQ_ALG_GI stays on one stream: its slots (one per resident workgroup) belong to the first
+// workspace (the second one's few slots made odd steps run ~32 problems at a time)
+static bool two_step_streams(int steps, const mcq_opts& o) { return steps > 1 && !getenv("MCQ_PIPE_ONE_STREAM") && o.algorithm != MCQ_ALG_GI; }
+
+static int check_step_list(const char* who, int steps, const double* const* reftrack, double* const* alpha_out, double* const* curv_err_out,
+                           int* const* status_out)
 {
-    if (!h->cs_in) {                    // (mcq_solve_host's slices may have created the two copy streams already)
-        HIP_TRY(hipStreamCreate(&h->cs_in));
-        HIP_TRY(hipStreamCreate(&h->cs_out));
-    }
-    if (!h->ev_up[0]) {
-        for (int k = 0; k < 2; ++k) {
-            HIP_TRY(hipEventCreate(&h->ev_up[k]));
-            HIP_TRY(hipEventCreate(&h->ev_done[k]));
-            HIP_TRY(hipEventCreate(&h->ev_down[k]));
-        }
-    }
-    return ensure_staging(h, 1, batch, nmax);
+    for (int k = 0; k < steps; ++k)
+        if (!reftrack[k] || !alpha_out[k] || !curv_err_out[k] || !status_out[k]) { g_err = std::string(who) + ": NULL buffer in step list"; return MCQ_E_ARG; }
+    return 0;
 }
 
 extern "C" int mcq_solve_host_pipelined(mcq_handle* h, int steps, int batch, int n, const double* const* reftrack,
@@ -2349,16 +2495,16 @@ extern "C" int mcq_solve_host_pipelined(mcq_handle* h, int steps, int batch, int
         g_err = "mcq_solve_host_pipelined: bad argument";
         return MCQ_E_ARG;
     }
-    for (int k = 0; k < steps; ++k) {
-        if (!reftrack[k] || !alpha_out[k] || !curv_err_out[k] || !status_out[k]) { g_err = "mcq_solve_host_pipelined: NULL buffer in step list"; return MCQ_E_ARG; }
-    }
+    if (int rc = check_step_list("mcq_solve_host_pipelined", steps, reftrack, alpha_out, curv_err_out, status_out)) return rc;
     HIP_TRY(hipSetDevice(h->device));
     const mcq_opts o = resolve_opts(opts);
     int rc = ensure_workspace(h, 0, (size_t)batch, (size_t)n);
     if (rc) return rc;
     rc = ensure_staging(h, 0, (size_t)batch, (size_t)n);
     if (rc) return rc;
-    rc = ensure_pipe(h, (size_t)batch, (size_t)n);
+    rc = ensure_streams(h, COPY_STREAMS | STEP_EVENTS);
+    if (rc) return rc;
+    rc = ensure_staging(h, 1, (size_t)batch, (size_t)n);
     if (rc) return rc;
     // curv_error / status of every step land in PINNED memory of the handle and reach the caller's arrays at the end: a device-to-host copy into
     // pageable memory -- what these two small arrays usually are -- blocks the host until the step's kernels have finished, i.e. the host could
@@ -2367,9 +2513,7 @@ extern "C" int mcq_solve_host_pipelined(mcq_handle* h, int steps, int batch, int
     if (rc) return rc;
     double* pin_cu = (double*)h->pin;
     int* pin_st = (int*)(pin_cu + (size_t)steps * batch);
-    // kernels of odd steps on the second compute stream / workspace (the variable: A/B knob); MCQ_ALG_GI stays on one stream: its slots
-    // (one per resident workgroup) belong to the first workspace (the second one's few slots made odd steps run ~32 problems at a time)
-    const bool two = steps > 1 && !getenv("MCQ_PIPE_ONE_STREAM") && o.algorithm != MCQ_ALG_GI;
+    const bool two = two_step_streams(steps, o);
     if (two) { rc = ensure_workspace(h, 1, (size_t)batch, (size_t)n); if (rc) return rc; }
     HIP_TRY(hipStreamSynchronize(compute_stream(h)));          // whatever ran before on the handle's stream is done with the staging buffers
     const size_t elems = (size_t)batch * n;
@@ -2379,15 +2523,11 @@ extern "C" int mcq_solve_host_pipelined(mcq_handle* h, int steps, int batch, int
     // step therefore goes in first -- it only depends on kernels two steps back -- and runs while step k computes.
     auto upload = [&](int k) -> int {
         const int s = k & 1;
-        const Staging& S = h->stage[s];
-        const double* nv_k = normvec ? normvec[k] : nullptr;
-        const double* sc_k = scaling ? scaling[k] : nullptr;
         // the kernels of step k - 2 were the last readers of this slot's rows
-        if (k >= 2) HIP_TRY_DRAIN(hipStreamWaitEvent(h->cs_in, h->ev_done[s], 0));
-        HIP_TRY_DRAIN(hipMemcpyAsync(S.ref, reftrack[k], elems * 4 * sizeof(double), hipMemcpyHostToDevice, h->cs_in));
-        if (nv_k) HIP_TRY_DRAIN(hipMemcpyAsync(S.nv, nv_k, elems * 2 * sizeof(double), hipMemcpyHostToDevice, h->cs_in));
-        if (sc_k) HIP_TRY_DRAIN(hipMemcpyAsync(S.sc, sc_k, elems * sizeof(double), hipMemcpyHostToDevice, h->cs_in));
-        HIP_TRY_DRAIN(hipEventRecord(h->ev_up[s], h->cs_in));
+        if (k >= 2) HIP_TRY_DRAIN(hipStreamWaitEvent(h->cp.in, h->cp.done[s], 0));
+        if (int rc2 = upload_rows(h, h->stage[s], reftrack[k], normvec ? normvec[k] : nullptr, scaling ? scaling[k] : nullptr, 0, (size_t)batch,
+                                  (size_t)n, h->cp.in)) return rc2;
+        HIP_TRY_DRAIN(hipEventRecord(h->cp.up[s], h->cp.in));
         return 0;
     };
     rc = upload(0);
@@ -2404,25 +2544,25 @@ extern "C" int mcq_solve_host_pipelined(mcq_handle* h, int steps, int batch, int
         // kernels of step k: after its upload, and after the download of step k - 2 has left the slot's result buffers
         // (slot s's kernels always run on compute stream s: step k - 2, the last user of this slot's workspace and buffers, precedes in stream order)
         Workspace& w = h->ws[two ? s : 0];
-        HIP_TRY_DRAIN(hipStreamWaitEvent(w.stream, h->ev_up[s], 0));
-        if (k >= 2) HIP_TRY_DRAIN(hipStreamWaitEvent(w.stream, h->ev_down[s], 0));
+        HIP_TRY_DRAIN(hipStreamWaitEvent(w.stream, h->cp.up[s], 0));
+        if (k >= 2) HIP_TRY_DRAIN(hipStreamWaitEvent(w.stream, h->cp.down[s], 0));
         McqBatch B = make_batch(batch, n, nullptr, S.ref, nv_k ? S.nv : nullptr, sc_k ? S.sc : nullptr, S.alpha, S.curv, S.status, nullptr,
                                 kappa_bound, w_veh);
         rc = launch(h, B, o, w);
         if (rc) { drain(h); return rc; }
-        HIP_TRY_DRAIN(hipEventRecord(h->ev_done[s], w.stream));
+        HIP_TRY_DRAIN(hipEventRecord(h->cp.done[s], w.stream));
         if (k + 1 < steps) { rc = upload(k + 1); if (rc) return rc; }
         // download of step k
-        HIP_TRY_DRAIN(hipStreamWaitEvent(h->cs_out, h->ev_done[s], 0));
-        HIP_TRY_DRAIN(hipMemcpyAsync(alpha_out[k], S.alpha, elems * sizeof(double), hipMemcpyDeviceToHost, h->cs_out));
-        HIP_TRY_DRAIN(hipMemcpyAsync(pin_cu + (size_t)k * batch, S.curv, batch * sizeof(double), hipMemcpyDeviceToHost, h->cs_out));
-        HIP_TRY_DRAIN(hipMemcpyAsync(pin_st + (size_t)k * batch, S.status, batch * sizeof(int), hipMemcpyDeviceToHost, h->cs_out));
-        HIP_TRY_DRAIN(hipEventRecord(h->ev_down[s], h->cs_out));
+        HIP_TRY_DRAIN(hipStreamWaitEvent(h->cp.out, h->cp.done[s], 0));
+        HIP_TRY_DRAIN(hipMemcpyAsync(alpha_out[k], S.alpha, elems * sizeof(double), hipMemcpyDeviceToHost, h->cp.out));
+        HIP_TRY_DRAIN(hipMemcpyAsync(pin_cu + (size_t)k * batch, S.curv, batch * sizeof(double), hipMemcpyDeviceToHost, h->cp.out));
+        HIP_TRY_DRAIN(hipMemcpyAsync(pin_st + (size_t)k * batch, S.status, batch * sizeof(int), hipMemcpyDeviceToHost, h->cp.out));
+        HIP_TRY_DRAIN(hipEventRecord(h->cp.down[s], h->cp.out));
     }
-    HIP_TRY_DRAIN(hipStreamSynchronize(h->cs_in));
+    HIP_TRY_DRAIN(hipStreamSynchronize(h->cp.in));
     HIP_TRY_DRAIN(hipStreamSynchronize(compute_stream(h)));
     if (two) HIP_TRY_DRAIN(hipStreamSynchronize(h->ws[1].stream));
-    HIP_TRY_DRAIN(hipStreamSynchronize(h->cs_out));
+    HIP_TRY_DRAIN(hipStreamSynchronize(h->cp.out));
     for (int k = 0; k < steps; ++k) {
         memcpy(curv_err_out[k], pin_cu + (size_t)k * batch, batch * sizeof(double));
         memcpy(status_out[k], pin_st + (size_t)k * batch, batch * sizeof(int));
@@ -2631,122 +2771,6 @@ extern "C" int mcq_iqp_device(mcq_handle* h, int batch, int nmax, int* n_io, dou
     return 0;
 }
 
-// Packs the per-problem host buffers into the handle's pinned staging ([batch][nmax][*], zero padded) and queues the uploads.
-// Layout of the pinned block: ref | nv | sc | kb | wv | n   (then, for the results: alpha | info).
-struct PinLayout {
-    double *ref, *nv, *sc, *kb, *wv, *alpha;
-    int* n;
-    mcq_info* info;
-};
-
-// the per-problem scalars of a ragged host batch, through the pinned block to the device on `up`
-static int upload_scalars(mcq_handle* h, const mcq_problem* probs, int batch, const PinLayout& P, hipStream_t up)
-{
-    for (int b = 0; b < batch; ++b) { P.kb[b] = probs[b].kappa_bound; P.wv[b] = probs[b].w_veh; P.n[b] = probs[b].n; }
-    HIP_TRY_DRAIN(hipMemcpyAsync(h->d_kb, P.kb, batch * sizeof(double), hipMemcpyHostToDevice, up));
-    HIP_TRY_DRAIN(hipMemcpyAsync(h->d_wv, P.wv, batch * sizeof(double), hipMemcpyHostToDevice, up));
-    HIP_TRY_DRAIN(hipMemcpyAsync(h->d_n, P.n, batch * sizeof(int), hipMemcpyHostToDevice, up));
-    return 0;
-}
-
-// after_chunk (round 6, mcq_solve_batch in slices): the uploads go to the handle's copy stream h->cs_in instead of its compute stream, in exactly
-// `force_chunks` chunks of tracks, the per-problem scalars first, and after_chunk(k, b0, b1) is called as soon as chunk k's uploads are queued
-// (it queues that slice's kernel behind them while the next chunk is packed).
-static int pack_and_upload(mcq_handle* h, const mcq_problem* probs, int batch, size_t nmax, bool any_sc, bool with_nv,
-                           size_t extra_bytes, PinLayout& P, int force_chunks = 0,
-                           const std::function<int(int, int, int)>& after_chunk = nullptr)
-{
-    const size_t elems = (size_t)batch * nmax;
-    const size_t bytes = elems * (4 + 2 + 1 + 1) * sizeof(double) + (size_t)batch * (2 * sizeof(double) + sizeof(int) + sizeof(mcq_info)) + 64 + extra_bytes;
-    int rc = ensure_pin(h, bytes);
-    if (rc) return rc;
-    char* base = (char*)h->pin;
-    P.ref = (double*)base;
-    P.nv = P.ref + elems * 4;
-    P.sc = P.nv + elems * 2;
-    P.alpha = P.sc + elems;
-    P.kb = P.alpha + elems;
-    P.wv = P.kb + batch;
-    P.info = (mcq_info*)(P.wv + batch);
-    P.n = (int*)(P.info + batch);
-    const Staging& s = h->stage[0];
-    hipStream_t up = force_chunks > 0 ? h->cs_in : compute_stream(h);
-    // (the padding behind a track's n waypoints is never read by a kernel: no need to clear it)
-    auto pack_range = [&](int b0, int b1) {
-        for (int b = b0; b < b1; ++b) {
-            const size_t n = (size_t)probs[b].n;
-            memcpy(P.ref + (size_t)b * nmax * 4, probs[b].reftrack, n * 4 * sizeof(double));
-            if (with_nv) memcpy(P.nv + (size_t)b * nmax * 2, probs[b].normvec, n * 2 * sizeof(double));
-            if (any_sc) {
-                if (probs[b].scaling) memcpy(P.sc + (size_t)b * nmax, probs[b].scaling, n * sizeof(double));
-                else for (size_t q = 0; q < n; ++q) P.sc[(size_t)b * nmax + q] = 1.0;
-            }
-        }
-    };
-    // ---- no packing at all (round 6): a UNIFORM batch that lies in the caller's memory as one contiguous, page-locked block per array (what
-    //      engine.py hands over for stacked arrays from mcq_host_alloc) goes to the device straight from there -- one strided copy per array
-    //      (rows of n waypoints into rows of nmax) instead of a 115 MB memcpy into the staging first: that memcpy was 4-6 ms of a 36-42 ms
-    //      mcq_iqp_batch call and the part of it that differs from host to host.  $MCQ_PACK_ALWAYS=1: the packing pass (A/B knob). ----
-    {
-        const int n0 = probs[0].n;
-        bool direct = batch >= 2 && n0 > 0 && !getenv("MCQ_PACK_ALWAYS");
-        for (int b = 1; b < batch && direct; ++b) {
-            direct = probs[b].n == n0 && probs[b].reftrack == probs[0].reftrack + (size_t)b * n0 * 4
-                     && (!with_nv || probs[b].normvec == probs[0].normvec + (size_t)b * n0 * 2)
-                     && (probs[0].scaling ? probs[b].scaling == probs[0].scaling + (size_t)b * n0 : probs[b].scaling == nullptr);
-        }
-        auto pinned = [](const void* p) {
-            hipPointerAttribute_t a;
-            if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-            return a.type == hipMemoryTypeHost;
-        };
-        direct = direct && pinned(probs[0].reftrack) && (!with_nv || pinned(probs[0].normvec)) && (!probs[0].scaling || pinned(probs[0].scaling));
-        h->last_upload_direct = direct ? 1 : 0;
-        if (direct) {
-            if (int rc2 = upload_scalars(h, probs, batch, P, up)) return rc2;
-            const size_t w = (size_t)n0 * sizeof(double), pitch = nmax * sizeof(double);
-            const int nck = force_chunks > 0 ? std::min(force_chunks, batch) : 1;
-            for (int ck = 0; ck < nck; ++ck) {
-                const int b0 = (int)((long long)batch * ck / nck), b1 = (int)((long long)batch * (ck + 1) / nck);
-                const size_t rows = (size_t)(b1 - b0);
-                HIP_TRY_DRAIN(hipMemcpy2DAsync(s.ref + (size_t)b0 * nmax * 4, pitch * 4, probs[b0].reftrack, w * 4, w * 4, rows, hipMemcpyHostToDevice, up));
-                if (with_nv) HIP_TRY_DRAIN(hipMemcpy2DAsync(s.nv + (size_t)b0 * nmax * 2, pitch * 2, probs[b0].normvec, w * 2, w * 2, rows, hipMemcpyHostToDevice, up));
-                if (any_sc) HIP_TRY_DRAIN(hipMemcpy2DAsync(s.sc + (size_t)b0 * nmax, pitch, probs[b0].scaling, w, w, rows, hipMemcpyHostToDevice, up));
-                if (after_chunk) { if (int rc2 = after_chunk(ck, b0, b1)) return rc2; }
-            }
-            return 0;
-        }
-    }
-    // A large batch (the 1024 N = 2000 tracks of the bench: 115 MB) is packed in four chunks of tracks by several host threads, and a
-    // chunk's uploads are queued as soon as it is packed: one thread copies at ~10 GB/s -- 11 ms, a quarter of the whole mcq_iqp_batch
-    // call -- and the DMA of chunk k runs while chunk k + 1 is packed.  $MCQ_PACK_THREADS: threads (default 8 for batches above 8 MB; 1 = the single loop).
-    const size_t row_doubles = 4 + (with_nv ? 2 : 0) + (any_sc ? 1 : 0);
-    const size_t payload = elems * row_doubles * sizeof(double);
-    const char* pt = getenv("MCQ_PACK_THREADS");
-    const bool forced = pt && *pt;          // (asked for explicitly: whatever the size of the batch -- the tests pack six small tracks on three threads)
-    int nthreads = forced ? atoi(pt) : (payload > ((size_t)8 << 20) && batch >= 16 ? 8 : 1);
-    const int hw = (int)std::thread::hardware_concurrency();
-    if (hw > 0 && nthreads > hw) nthreads = hw;
-    if (nthreads > batch) nthreads = batch;
-    if (nthreads < 1) nthreads = 1;
-    int nchunks = (forced && nthreads > 1) || (payload > ((size_t)32 << 20) && batch >= 16) ? 4 : 1;
-    if (force_chunks > 0) nchunks = force_chunks;
-    if (nchunks > batch) nchunks = batch;
-    if (force_chunks > 0) {        // the slices' kernels read the per-problem scalars: first
-        if (int rc2 = upload_scalars(h, probs, batch, P, up)) return rc2;
-    }
-    for (int ck = 0; ck < nchunks; ++ck) {
-        const int b0 = (int)((long long)batch * ck / nchunks), b1 = (int)((long long)batch * (ck + 1) / nchunks);
-        fan_out(b0, b1, nthreads, [&](int, int r0, int r1) { pack_range(r0, r1); });
-        const size_t off = (size_t)b0 * nmax, cnt = (size_t)(b1 - b0) * nmax;
-        HIP_TRY_DRAIN(hipMemcpyAsync(s.ref + off * 4, P.ref + off * 4, cnt * 4 * sizeof(double), hipMemcpyHostToDevice, up));
-        if (with_nv) HIP_TRY_DRAIN(hipMemcpyAsync(s.nv + off * 2, P.nv + off * 2, cnt * 2 * sizeof(double), hipMemcpyHostToDevice, up));
-        if (any_sc) HIP_TRY_DRAIN(hipMemcpyAsync(s.sc + off, P.sc + off, cnt * sizeof(double), hipMemcpyHostToDevice, up));
-        if (after_chunk) { if (int rc2 = after_chunk(ck, b0, b1)) return rc2; }
-    }
-    return force_chunks > 0 ? 0 : upload_scalars(h, probs, batch, P, up);      // (one launch: the scalars follow the rows)
-}
-
 // mcq_solve_batch and mcq_solve_batch_ends: d_ends = the device copy of the per-problem mcq_ends records, or nullptr (all rings)
 static int solve_batch_impl(mcq_handle* h, const mcq_problem* probs, const mcq_ends* d_ends, int batch, const mcq_opts* opts,
                             double* alpha_out, double* curv_err_out, int* status_out, mcq_info* info_out)
@@ -2771,37 +2795,18 @@ static int solve_batch_impl(mcq_handle* h, const mcq_problem* probs, const mcq_e
     if (rc) return rc;
     rc = ensure_staging(h, 0, (size_t)batch, nmax);
     if (rc) return rc;
-    PinLayout P;
     const Staging& s = h->stage[0];
     const bool with_nv = probs[0].normvec != nullptr;       // none given: normals (and scalings) are derived on the device
+    Upload P = {probs, batch, nmax, any_sc, with_nv};
     McqBatch B = make_batch(batch, (int)nmax, h->d_n, s.ref, with_nv ? s.nv : nullptr, any_sc ? s.sc : nullptr, s.alpha, s.curv, s.status, h->d_info,
                             0.0, 0.0);
     B.kappa_bound_list = h->d_kb;
     B.w_veh_list = h->d_wv;
     B.ends = d_ends;
-    const int nsl = host_slices(batch, o);
-    if (nsl > 1) {
-        // in slices, as mcq_solve_host (see there): chunk k's kernel is queued behind its uploads while chunk k + 1 is packed; the padded alpha
-        // rows come back slice by slice into the pinned staging
-        rc = begin_slices(h, B, o);
-        if (rc) return rc;
-        rc = pack_and_upload(h, probs, batch, nmax, any_sc, with_nv, 0, P, nsl,
-                             [&](int k, int b0, int b1) -> int { return launch_slice(h, B, k, b0, b1, P.alpha); });
-        if (rc) { drain(h); return rc; }
-        rc = download_results(h, h->cs_out, batch, nullptr, nullptr, 0, curv_err_out, status_out, P.info);
-        if (rc) return rc;
-        HIP_TRY_DRAIN(hipStreamSynchronize(h->cs_out));
-        HIP_TRY_DRAIN(hipStreamSynchronize(compute_stream(h)));
-        HIP_TRY_DRAIN(hipStreamSynchronize(h->ws[1].stream));
-    } else {
-        rc = pack_and_upload(h, probs, batch, nmax, any_sc, with_nv, 0, P);
-        if (rc) return rc;
-        rc = launch(h, B, o);
-        if (rc) { drain(h); return rc; }
-        rc = download_results(h, compute_stream(h), batch, P.alpha, s.alpha, (size_t)batch * nmax * sizeof(double), curv_err_out, status_out, P.info);
-        if (rc) return rc;
-        HIP_TRY(hipStreamSynchronize(compute_stream(h)));
-    }
+    rc = plan_upload(h, P, 0);
+    if (rc) return rc;
+    rc = solve_staged(h, B, o, P, P.alpha, curv_err_out, status_out, P.info);
+    if (rc) return rc;
     // the padded rows of the pinned staging, back to back into the caller's array
     size_t off = 0;
     for (int b = 0; b < batch; ++b) {
@@ -2851,20 +2856,15 @@ extern "C" int mcq_solve_device_stream(mcq_handle* h, int steps, int batch, int 
         g_err = "mcq_solve_device_stream: bad argument";
         return MCQ_E_ARG;
     }
-    for (int k = 0; k < steps; ++k)
-        if (!reftrack[k] || !alpha_out[k] || !curv_err_out[k] || !status_out[k]) { g_err = "mcq_solve_device_stream: NULL buffer in step list"; return MCQ_E_ARG; }
+    if (int rc = check_step_list("mcq_solve_device_stream", steps, reftrack, alpha_out, curv_err_out, status_out)) return rc;
     HIP_TRY(hipSetDevice(h->device));
     const mcq_opts o = resolve_opts(opts);
     int rc = ensure_workspace(h, 0, (size_t)batch, (size_t)n);
     if (rc) return rc;
-    const bool two = steps > 1 && !getenv("MCQ_PIPE_ONE_STREAM") && o.algorithm != MCQ_ALG_GI;
+    const bool two = two_step_streams(steps, o);
     if (two) { rc = ensure_workspace(h, 1, (size_t)batch, (size_t)n); if (rc) return rc; }
     // the second stream starts behind whatever the caller has enqueued on the first (uploads of the inputs, an earlier call)
-    if (two) {
-        for (int k = 0; k < 2; ++k) if (!h->ev_st[k]) HIP_TRY(hipEventCreate(&h->ev_st[k]));
-        HIP_TRY(hipEventRecord(h->ev_st[0], compute_stream(h)));
-        HIP_TRY(hipStreamWaitEvent(h->ws[1].stream, h->ev_st[0], 0));
-    }
+    if (two) { rc = fork_second(h); if (rc) return rc; }
     for (int k = 0; k < steps; ++k) {
         const double* nv_k = normvec ? normvec[k] : nullptr;
         McqBatch B = make_batch(batch, n, nullptr, reftrack[k], nv_k, (scaling && nv_k) ? scaling[k] : nullptr, alpha_out[k], curv_err_out[k],
@@ -2872,12 +2872,9 @@ extern "C" int mcq_solve_device_stream(mcq_handle* h, int steps, int batch, int 
         rc = launch(h, B, o, h->ws[two ? (k & 1) : 0]);
         if (rc) { drain(h); return rc; }
     }
-    // the handle's first stream ends behind the second one: mcq_sync / a later call on the handle sees every step done
-    if (two) {
-        HIP_TRY(hipEventRecord(h->ev_st[1], h->ws[1].stream));
-        HIP_TRY(hipStreamWaitEvent(compute_stream(h), h->ev_st[1], 0));
-    }
-    return 0;
+    // the handle's first stream ends behind the second one, now and not lazily: mcq_sync, a later call on the handle or a caller holding
+    // mcq_stream() sees every step done
+    return two ? join_second(h) : 0;
 }
 
 extern "C" int mcq_iqp_set_round_callback(mcq_handle* h, mcq_iqp_round_cb cb, void* user)
@@ -2932,10 +2929,12 @@ extern "C" int mcq_iqp_batch(mcq_handle* h, const mcq_problem* probs, int batch,
         HIP_TRY(hipMalloc((void**)&h->d_nv2, elems * 2 * sizeof(double)));
         h->stage2_elems = elems;
     }
-    PinLayout P;
+    Upload P = {probs, batch, nmax, any_sc, true};
     // results need room for both buffer sets' ref / nv in the worst case: one extra set
     stamp("checked, buffers ready");
-    rc = pack_and_upload(h, probs, batch, nmax, any_sc, true, elems * 6 * sizeof(double) + (size_t)batch * 3 * sizeof(int), P);
+    rc = plan_upload(h, P, elems * 6 * sizeof(double) + (size_t)batch * 3 * sizeof(int));
+    if (rc) return rc;
+    rc = upload_batch(h, P);
     if (rc) return rc;
     stamp("packed, uploads queued");
     rc = ensure_iqp(h, (size_t)batch);                 // the trace staging lives in the handle (no allocation / hipFree -- an implicit
@@ -3104,7 +3103,7 @@ extern "C" int mcq_comm_allgather(mcq_handle* h, const void* send, void* recv, s
     // one, and a caller gathers after every step: the comm stream waits for both slices' ends instead)
     HIP_TRY(hipEventRecord(h->comm_ready, h->ws[0].stream));
     HIP_TRY(hipStreamWaitEvent(h->comm_stream, h->comm_ready, 0));
-    if (h->sl_last1) HIP_TRY(hipStreamWaitEvent(h->comm_stream, h->sl_last1, 0));
+    if (h->sl.last1) HIP_TRY(hipStreamWaitEvent(h->comm_stream, h->sl.last1, 0));
     const unsigned slot = h->comm_seq & 3u;
     HIP_TRY(hipEventRecord(h->comm_t0[slot], h->comm_stream));
     const int nccl_t = dtype == MCQ_DT_F64 ? 8 : dtype == MCQ_DT_F32 ? 7 : 2;

@@ -107,7 +107,10 @@ typedef struct {
     int warm_start;     /* 1: start from the working sets that the preceding mcq_relinearise_device call on this handle carried
                          * over from the preceding solve of the same batch (IQP passes 2+): the exchange alone, no interior point,
                          * unless it runs out of 12 rounds (then the cold path; mcq_info.second_attempt & 2).  Ignored when no such
-                         * working sets are at hand.  The result is an exact KKT vertex of the same QP either way.  Default 0. */
+                         * working sets are at hand.  The result is an exact KKT vertex of the same QP either way.  Default 0.
+                         * A warm start that applies takes the ONE launch in every entry that would otherwise slice the batch --
+                         * mcq_solve_device, and likewise mcq_solve_host / mcq_solve_batch / mcq_solve_batch_ends, which until then
+                         * sliced a batch of 512 or more and dropped the warm start silently. */
 } mcq_opts;
 #define MCQ_OBJ_MIN_CURV 0
 #define MCQ_OBJ_SHORTEST_PATH 1
@@ -986,7 +989,9 @@ int mcq_last_timing(mcq_handle* h, float ms[5]);
  * mcq_solve_device included) and records an event on it; mcq_timing_end records an end event on that stream -- and one on the second compute stream
  * where slices of mcq_solve_device are pending there --, waits, and returns the milliseconds from the begin event to the LATER end and the number
  * of solver launches the handle enqueued in between (mcq_solve_device* / the QP passes of the IQP entries; not the second stream of
- * mcq_solve_host_pipelined).  A sliced mcq_solve_device counts as ONE launch, per call: with calls enqueued back to back -- no host
+ * mcq_solve_host_pipelined).  A sliced call -- mcq_solve_device, and likewise mcq_solve_host / mcq_solve_batch / mcq_solve_batch_ends, which were
+ * not counted at all before -- counts as ONE launch, per call (mcq_last_timing still refuses after a sliced HOST call: no pair of events spans
+ * its slices).  With calls enqueued back to back -- no host
  * synchronisation inside the span -- ms / launches is the average device time per step, launch gaps included: what bench.py's
  * `roofline.kernel_ms` is (round 5; until then it synchronised after every step to read mcq_last_timing, and a slow host showed up in `value`).
  * With slices of consecutive calls overlapping, that is no longer the duration of any single kernel. */

@@ -180,7 +180,7 @@ HOST_BATCH, HOST_N = sc.HOST_BATCH, sc.HOST_N
 
 def check_solve_host_large_batch(eng, worst):
     """mcq_solve_host with a batch above MCQ_HOST_SLICE_MIN (512): the minimum-curvature objective goes in slices on two streams there, this one
-    stays one launch (host_slices() in csrc/mcq_api.hip) -- and has to come back right: bitwise solve_batch's rows, every row on the reference.
+    stays one launch (slices_for() in csrc/mcq_api.hip) -- and has to come back right: bitwise solve_batch's rows, every row on the reference.
     The rings are the host/<k> entries of the spread table."""
     rings = [sc.case("host/%d" % k) for k in range(HOST_BATCH)]
     refs, nvs = np.stack([r[0] for r in rings]), np.stack([r[1] for r in rings])
