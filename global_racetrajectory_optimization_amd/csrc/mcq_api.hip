@@ -99,12 +99,7 @@ struct mcq_handle {
     double *d_kb = nullptr, *d_wv = nullptr;
     int* d_n = nullptr;
     mcq_info* d_info = nullptr;
-    double *d_ref2 = nullptr, *d_nv2 = nullptr;      // second set of the IQP double buffer (mcq_iqp_batch)
-    size_t stage2_elems = 0;
-    int* d_iqp = nullptr;                             // bookkeeping arrays of mcq_iqp_device, 8 ints per track + 1
-    double* d_iqp_curv = nullptr;
-    size_t iqp_batch = 0;
-    void* pin = nullptr;                              // pinned host staging (packing of the host-buffer entries)
+    void* pin = nullptr;                             // pinned host staging (packing of the host-buffer entries)
     size_t pin_bytes = 0;
     bool poison = false;    // MCQ_POISON=1 (debugging aid): every workspace / staging allocation is filled with 0xFF bytes (NaN as a
                             // double), so that a read of memory nothing has written shows up as a wrong result on every box instead of
@@ -118,6 +113,8 @@ struct mcq_handle {
     Scratch fgen;                       // mcq_points_in_path_device / mcq_friction_gen_device: polygons, kept vertices, contours, their counts
     Scratch fgen_pts;                   // mcq_friction_gen_device: the grid points' flags and the blocks' counts (sized after the boundaries' launch)
     Scratch mintime;                    // mcq_mintime_eval_device: the intervals' times and energies [batch][nmax] each, where the caller takes none
+    Scratch iqp;                        // mcq_iqp_device: its bookkeeping per track; mcq_iqp_batch: its trace, buf and rounds as well (iqp_layout)
+    Scratch iqp_set;                    // mcq_iqp_batch: the second set of the double buffer, ring and normals (iqp_set_layout)
     mcq_iqp_round_cb iqp_cb = nullptr;  // mcq_iqp_set_round_callback
     void* iqp_cb_user = nullptr;
     void* comm = nullptr;               // ncclComm_t of mcq_comm_init (RCCL, loaded with dlopen)
@@ -131,7 +128,6 @@ struct mcq_handle {
     int gis_slots = 0, gis_nmax = 0;
     long long gis_bytes = 0;
     double* d_org = nullptr;            // per-track origins of the fp32 row entries, [batch][2]
-    double* d_trace = nullptr;          // curvature-error trace of mcq_iqp_batch, [batch][MCQ_IQP_TRACE] (grown with d_iqp)
     CopyPipe cp;
     int last_upload_direct = 0;         // the last host-buffer batch went up without the packing pass (mcq_last_upload_was_direct)
     int cus = 256;                      // compute units of the device (mcq_create); the MI355X's where the runtime does not say
@@ -235,7 +231,7 @@ static int grow(mcq_handle* h, Scratch& s, size_t bytes)
 // the buffer to `bytes` and takes the pointers with at(), the regions numbered from 0 in the order of the comment above their layout function.
 // A region's bytes are rounded up to `pad` (8: a double may follow ints).
 struct Arena {
-    size_t off[8], align[8], n = 0, bytes = 0;
+    size_t off[10], align[10], n = 0, bytes = 0;
     template <class T> Arena& add(size_t count, size_t pad = 8)
     {
         off[n] = bytes;
@@ -330,7 +326,7 @@ static void free_workspace(mcq_handle* h, int which)
     }
 }
 
-// stage[0] takes what exists once with it: the per-problem scalars and records, the IQP double buffer and bookkeeping
+// stage[0] takes what exists once with it: the per-problem scalars, records and origins
 static void free_staging(mcq_handle* h, int which)
 {
     Staging& s = h->stage[which];
@@ -341,12 +337,8 @@ static void free_staging(mcq_handle* h, int which)
         h->d_kb = h->d_wv = nullptr;
         h->d_n = nullptr;
         h->d_info = nullptr;
-        (void)hipFree(h->d_ref2); (void)hipFree(h->d_nv2); (void)hipFree(h->d_iqp); (void)hipFree(h->d_iqp_curv);
-        h->d_ref2 = h->d_nv2 = h->d_iqp_curv = nullptr;
-        h->d_iqp = nullptr;
-        h->stage2_elems = h->iqp_batch = 0;
-        (void)hipFree(h->d_org); (void)hipFree(h->d_trace);
-        h->d_org = h->d_trace = nullptr;
+        (void)hipFree(h->d_org);
+        h->d_org = nullptr;
     }
 }
 
@@ -365,7 +357,7 @@ extern "C" void mcq_destroy(mcq_handle* h)
     for (hipEvent_t e : h->cp.slice) if (e) (void)hipEventDestroy(e);
     if (h->cp.in) (void)hipStreamDestroy(h->cp.in);
     if (h->cp.out) (void)hipStreamDestroy(h->cp.out);
-    for (Scratch* s : {&h->vel, &h->bound, &h->fit, &h->spl, &h->ends, &h->fgen, &h->fgen_pts, &h->mintime}) (void)hipFree(s->p);
+    for (Scratch* s : {&h->vel, &h->bound, &h->fit, &h->spl, &h->ends, &h->fgen, &h->fgen_pts, &h->mintime, &h->iqp, &h->iqp_set}) (void)hipFree(s->p);
     if (h->pin) (void)hipHostFree(h->pin);
     for (int k = 0; k < 5; ++k) if (h->ev[k]) (void)hipEventDestroy(h->ev[k]);
     for (int k = 0; k < 2; ++k) if (h->ev_span[k]) (void)hipEventDestroy(h->ev_span[k]);
@@ -2143,6 +2135,21 @@ template <class F> static void fan_out(int lo, int hi, int nthreads, F fn)
     for (auto& t : th) t.join();
 }
 
+// host-side time stamps of one call on stderr, where the environment names `env` ($MCQ_PIPE_TRACE, $MCQ_IQP_TRACE): fmt takes `what`, then
+// the ms since the record was made
+struct Stamps {
+    bool on;
+    struct timespec t0;
+    explicit Stamps(const char* env) : on(getenv(env) != nullptr) { clock_gettime(CLOCK_MONOTONIC, &t0); }
+    template <class T> void at(const char* fmt, T what) const
+    {
+        if (!on) return;
+        struct timespec t1;
+        clock_gettime(CLOCK_MONOTONIC, &t1);
+        fprintf(stderr, fmt, what, (t1.tv_sec - t0.tv_sec) * 1e3 + (t1.tv_nsec - t0.tv_nsec) * 1e-6);
+    }
+};
+
 // ---- the n spline scalings out of the dense matrix the reference passes (include/mcq.h); host code, no GPU ----------------------------------
 // closed: calc_splines' closed system through n waypoints, [4n][4n]; open: its open system, [4(n-1)][4(n-1)] with 12 n - 15 non-zeros, whose
 // last block holds the two heading rows and whose s_out ends in two ones.
@@ -2274,6 +2281,7 @@ struct Upload {
     int* n;
     bool direct;                // no packing pass: strided copies from the caller's page-locked arrays
     int nthreads, nchunks;      // of the packing pass where the entry does not slice (a direct batch: one chunk)
+    void* extra;                // the entry's extra bytes, 8-byte aligned
 };
 
 // the per-problem scalars of a ragged host batch, through the pinned block to the device on `up`
@@ -2304,6 +2312,7 @@ static int plan_upload(mcq_handle* h, Upload& U, size_t extra_bytes)
     U.wv = U.kb + batch;
     U.info = (mcq_info*)(U.wv + batch);
     U.n = (int*)(U.info + batch);
+    U.extra = (char*)h->pin + ((size_t)((char*)(U.n + batch) - (char*)h->pin) + 7) / 8 * 8;       // (within the 64 bytes of slack)
     // ---- no packing at all (round 6): a UNIFORM batch that lies in the caller's memory as one contiguous, page-locked block per array (what
     //      engine.py hands over for stacked arrays from mcq_host_alloc) goes to the device straight from there -- one strided copy per array
     //      (rows of n waypoints into rows of nmax) instead of a 115 MB memcpy into the staging first: that memcpy was 4-6 ms of a 36-42 ms
@@ -2532,13 +2541,11 @@ extern "C" int mcq_solve_host_pipelined(mcq_handle* h, int steps, int batch, int
     };
     rc = upload(0);
     if (rc) return rc;
-    const bool trace = getenv("MCQ_PIPE_TRACE") != nullptr;
-    struct timespec ts0;
-    clock_gettime(CLOCK_MONOTONIC, &ts0);
+    const Stamps ts("MCQ_PIPE_TRACE");
     for (int k = 0; k < steps; ++k) {
         const int s = k & 1;
         const Staging& S = h->stage[s];
-        if (trace) { struct timespec t1; clock_gettime(CLOCK_MONOTONIC, &t1); fprintf(stderr, "pipe: step %d enqueued from %.3f ms\n", k, (t1.tv_sec - ts0.tv_sec) * 1e3 + (t1.tv_nsec - ts0.tv_nsec) * 1e-6); }
+        ts.at("pipe: step %d enqueued from %.3f ms\n", k);
         const double* nv_k = normvec ? normvec[k] : nullptr;
         const double* sc_k = scaling ? scaling[k] : nullptr;
         // kernels of step k: after its upload, and after the download of step k - 2 has left the slot's result buffers
@@ -2566,207 +2573,6 @@ extern "C" int mcq_solve_host_pipelined(mcq_handle* h, int steps, int batch, int
     for (int k = 0; k < steps; ++k) {
         memcpy(curv_err_out[k], pin_cu + (size_t)k * batch, batch * sizeof(double));
         memcpy(status_out[k], pin_st + (size_t)k * batch, batch * sizeof(int));
-    }
-    return 0;
-}
-
-// ---- tph.iqp_handler as one call (include/mcq.h) ---------------------------------------------------------------------------------
-static int ensure_iqp(mcq_handle* h, size_t batch)
-{
-    if (batch <= h->iqp_batch) return 0;
-    HIP_TRY(hipStreamSynchronize(compute_stream(h)));
-    (void)hipFree(h->d_iqp); (void)hipFree(h->d_iqp_curv); (void)hipFree(h->d_trace);
-    h->d_iqp = nullptr; h->d_iqp_curv = nullptr; h->d_trace = nullptr; h->iqp_batch = 0;
-    HIP_TRY(hipMalloc((void**)&h->d_iqp, (batch * 8 + 16) * sizeof(int)));
-    HIP_TRY(hipMalloc((void**)&h->d_iqp_curv, batch * 2 * sizeof(double)));
-    HIP_TRY(hipMalloc((void**)&h->d_trace, batch * MCQ_IQP_TRACE * sizeof(double)));     // mcq_iqp_batch's trace staging
-    h->iqp_batch = batch;
-    return 0;
-}
-
-extern "C" int mcq_iqp_device(mcq_handle* h, int batch, int nmax, int* n_io, double* reftrack_a, double* normvec_a,
-                              double* reftrack_b, double* normvec_b, const double* scaling, double kappa_bound, double w_veh,
-                              double stepsize_interp, int iters_min, double curv_error_allowed, int max_rounds,
-                              const mcq_opts* opts, double* alpha_out, int* buf_out, double* curv_err_out, int* status_out,
-                              int* rounds_out, double* curv_trace_out, mcq_iqp_stats* stats)
-{
-    if (!h || batch <= 0 || nmax <= 0 || !n_io || !reftrack_a || !normvec_a || !reftrack_b || !normvec_b || !alpha_out ||
-        !buf_out || !curv_err_out || !status_out || !rounds_out || !(stepsize_interp > 0.0) || iters_min < 1 || max_rounds < 1 ||
-        reftrack_a == reftrack_b || normvec_a == normvec_b) {
-        g_err = "mcq_iqp_device: bad argument";
-        return MCQ_E_ARG;
-    }
-    HIP_TRY(hipSetDevice(h->device));
-    mcq_opts o = resolve_opts(opts);
-    const bool warm = !(opts && opts->warm_start < 0);        // passes 2+ start from the carried working sets unless switched off
-    int rc = ensure_workspace(h, 0, (size_t)batch, (size_t)nmax);
-    if (rc) return rc;
-    rc = ensure_iqp(h, (size_t)batch);
-    if (rc) return rc;
-    const bool timed = stats && stats->timed;
-    if (timed) { rc = ensure_staging(h, 0, (size_t)batch, (size_t)nmax); if (rc) return rc; }
-    // bookkeeping arrays: live | n of the other set | glue status | pass status | final_n (= n_io on return) ... live count
-    int* live = h->d_iqp;
-    int* n_b = live + batch;
-    int* rst = n_b + batch;
-    int* pass_status = rst + batch;
-    int* d_final_n = pass_status + batch;
-    int* live_count = d_final_n + batch;
-    double* pass_curv = h->d_iqp_curv;
-    int* n_set[2] = {n_io, n_b};
-    double* ref_set[2] = {reftrack_a, reftrack_b};
-    double* nv_set[2] = {normvec_a, normvec_b};
-    // every track starts live (a track with n == 0 ends in its first, empty pass: status MCQ_BAD_INPUT, rounds_out 1)
-    {
-        std::vector<int> ones((size_t)batch, 1);
-        HIP_TRY(hipMemcpyAsync(live, ones.data(), batch * sizeof(int), hipMemcpyHostToDevice, compute_stream(h)));
-        HIP_TRY(hipMemsetAsync(rounds_out, 0, batch * sizeof(int), compute_stream(h)));
-        HIP_TRY(hipMemsetAsync(buf_out, 0, batch * sizeof(int), compute_stream(h)));
-        HIP_TRY(hipStreamSynchronize(compute_stream(h)));      // `ones` goes out of scope
-    }
-    McqIqpStep S;
-    memset(&S, 0, sizeof(S));
-    S.batch = batch;
-    S.iters_min = iters_min;
-    S.curv_allowed = curv_error_allowed;
-    S.curv = pass_curv;
-    S.status = pass_status;
-    S.relin_status = rst;
-    S.live = live;
-    S.final_buf = buf_out;
-    S.final_curv = curv_err_out;
-    S.final_status = status_out;
-    S.final_rounds = rounds_out;
-    S.live_count = live_count;
-    S.curv_trace = curv_trace_out;
-    if (curv_trace_out) HIP_TRY(hipMemsetAsync(curv_trace_out, 0, (size_t)batch * MCQ_IQP_TRACE * sizeof(double), compute_stream(h)));
-    const dim3 sgrid((unsigned)((batch + 255) / 256)), sblock(256);
-    int cur = 0, rounds = 0, n_live = batch;
-    long long solves = 0;
-    if (stats) { stats->rounds = 0; stats->qp_solves = 0; for (int k = 0; k < 16; ++k) { stats->solver_ms[k] = 0.f; stats->fallbacks[k] = 0; } }
-    // the final ring sizes are collected in a scratch array and moved to n_io at the end (n_io doubles as set 0's sizes)
-    HIP_TRY(hipMemsetAsync(d_final_n, 0, batch * sizeof(int), compute_stream(h)));
-    S.final_n = d_final_n;
-    int err = 0;
-    int it0 = 1;
-    // ---- The first iters_min rounds as ONE launch.  A track's rounds depend on nothing but its own previous round, and no track can end before
-    //      round iters_min, so nothing has to come back to the host in between; but launched round by round, every round ends with its slowest
-    //      track -- a warm start that falls back to the cold path takes 8.7 ms where the median track takes 3 -- and the next round's launch
-    //      waits for it with most compute units idle (third pass of the 1024 ovals: 6.5 ms of mean load, 11.5 ms of launch; neither another cap
-    //      of the exchange nor the pass before says which tracks those will be: docs/NOTEBOOK.md R5.7).  In mcq_iqp_rounds_kernel every
-    //      workgroup takes its track through those rounds on its own -- the bodies of the solver, bookkeeping and glue kernels between workgroup
-    //      barriers, the same arrays --: nobody waits for anybody.  Results bitwise those of the round-by-round loop below, which takes over
-    //      after round iters_min (and runs everything when per-round data must reach the host: timed statistics, the print_debug callback;
-    //      $MCQ_IQP_FUSED=0: always). ----
-    const char* fe = getenv("MCQ_IQP_FUSED");
-    const bool fused = !(fe && fe[0] == '0') && !timed && !h->iqp_cb;
-    if (fused) {
-        const int ra = iters_min < max_rounds ? iters_min : max_rounds;
-        McqIqpRounds F;
-        memset(&F, 0, sizeof(F));
-        F.B = make_batch(batch, nmax, nullptr, nullptr, nullptr, nullptr, alpha_out, pass_curv, pass_status, nullptr, kappa_bound, w_veh);
-        if ((err = fill_batch(h, F.B, o, h->ws[0])) != 0) return err;
-        F.R.batch = batch;
-        F.R.nmax = nmax;
-        F.R.alpha = alpha_out;
-        F.R.live = live;
-        F.R.stepsize = stepsize_interp;
-        F.R.status = rst;
-        F.R.vec = h->ws[0].vec;
-        F.R.state_in = h->ws[0].state;
-        F.R.state_out = h->state2;
-        F.S = S;
-        F.S.live_count = live_count;
-        for (int q = 0; q < 2; ++q) { F.n_set[q] = n_set[q]; F.ref_set[q] = ref_set[q]; F.nv_set[q] = nv_set[q]; }
-        F.sc = scaling;
-        F.warm = warm ? h->state2 : nullptr;
-        F.rounds = ra;
-        if (hipMemsetAsync(live_count, 0, sizeof(int), compute_stream(h)) != hipSuccess) err = MCQ_E_DEVICE;
-        if (!err) {
-            hipLaunchKernelGGL(mcq_iqp_rounds_kernel, dim3((unsigned)batch), dim3(256), 0, compute_stream(h), F);
-            if (hipGetLastError() != hipSuccess) err = MCQ_E_DEVICE;
-        }
-        // (the loop below may go on from the working sets the last round's glue carried over)
-        h->state2_valid = true;
-        h->state2_batch = batch;
-        h->state2_nmax = nmax;
-        if (!err && (hipMemcpyAsync(&n_live, live_count, sizeof(int), hipMemcpyDeviceToHost, compute_stream(h)) != hipSuccess ||
-                     hipStreamSynchronize(compute_stream(h)) != hipSuccess)) err = MCQ_E_DEVICE;
-        cur = ra & 1;
-        rounds = ra;
-        it0 = ra + 1;
-    }
-    for (int it = it0; it <= max_rounds && n_live > 0 && !err; ++it) {
-        rounds = it;
-        // (scalings: the re-spline of passes 2+ uses unit ones, as upstream)
-        McqBatch B = make_batch(batch, nmax, n_set[cur], ref_set[cur], nv_set[cur], it == 1 ? scaling : nullptr, alpha_out, pass_curv, pass_status,
-                                timed ? h->d_info : nullptr, kappa_bound, w_veh);
-        o.warm_start = (warm && it > 1) ? 1 : 0;
-        if ((err = launch(h, B, o)) != 0) break;
-        if (timed && it <= 16) {
-            float ms[5];
-            if (mcq_last_timing(h, ms) == 0) stats->solver_ms[it - 1] = ms[4];
-            std::vector<mcq_info> info((size_t)batch);
-            std::vector<int> lv((size_t)batch);
-            if (hipMemcpyAsync(info.data(), h->d_info, batch * sizeof(mcq_info), hipMemcpyDeviceToHost, compute_stream(h)) == hipSuccess &&
-                hipMemcpyAsync(lv.data(), live, batch * sizeof(int), hipMemcpyDeviceToHost, compute_stream(h)) == hipSuccess &&
-                hipStreamSynchronize(compute_stream(h)) == hipSuccess) {
-                int fb = 0;
-                for (int k = 0; k < batch; ++k) if (lv[k] && (info[k].second_attempt & 2)) ++fb;
-                stats->fallbacks[it - 1] = fb;
-            }
-        }
-        if (h->iqp_cb) {        // print_debug: the pass's curvature errors and who ran it, before the termination test decides
-            std::vector<double> cv((size_t)batch);
-            std::vector<int> lv((size_t)batch);
-            if (hipMemcpyAsync(cv.data(), pass_curv, batch * sizeof(double), hipMemcpyDeviceToHost, compute_stream(h)) != hipSuccess ||
-                hipMemcpyAsync(lv.data(), live, batch * sizeof(int), hipMemcpyDeviceToHost, compute_stream(h)) != hipSuccess ||
-                hipStreamSynchronize(compute_stream(h)) != hipSuccess) { err = MCQ_E_DEVICE; break; }
-            h->iqp_cb(h->iqp_cb_user, it, batch, cv.data(), lv.data());
-        }
-        if (hipMemsetAsync(live_count, 0, sizeof(int), compute_stream(h)) != hipSuccess) { err = MCQ_E_DEVICE; break; }
-        S.phase = 0;
-        S.round = it;
-        S.cur = cur;
-        S.n_ring = n_set[cur];
-        S.n_next = n_set[1 - cur];
-        hipLaunchKernelGGL(mcq_iqp_step_kernel, sgrid, sblock, 0, compute_stream(h), S);
-        const double scale = it < iters_min ? (double)it / (double)iters_min : 1.0;
-        if ((err = mcq_relinearise_device(h, batch, nmax, n_set[cur], ref_set[cur], nv_set[cur], alpha_out, live, scale,
-                                          stepsize_interp, ref_set[1 - cur], nv_set[1 - cur], n_set[1 - cur], rst)) != 0) break;
-        S.phase = 1;
-        hipLaunchKernelGGL(mcq_iqp_step_kernel, sgrid, sblock, 0, compute_stream(h), S);
-        if (hipGetLastError() != hipSuccess) { err = MCQ_E_DEVICE; break; }
-        cur = 1 - cur;
-        // the first iters_min - 1 rounds cannot end a healthy track: no need to look
-        if (it >= iters_min || it == max_rounds) {
-            if (hipMemcpyAsync(&n_live, live_count, sizeof(int), hipMemcpyDeviceToHost, compute_stream(h)) != hipSuccess ||
-                hipStreamSynchronize(compute_stream(h)) != hipSuccess) { err = MCQ_E_DEVICE; break; }
-        }
-    }
-    if (!err && hipMemcpyAsync(n_io, d_final_n, batch * sizeof(int), hipMemcpyDeviceToDevice, compute_stream(h)) != hipSuccess) err = MCQ_E_DEVICE;
-    if (hipStreamSynchronize(compute_stream(h)) != hipSuccess && !err) err = MCQ_E_DEVICE;
-    h->state2_valid = false;        // the working sets belong to this run's last glue call, not to a later solve
-    if (err) { if (err == MCQ_E_DEVICE && g_err.empty()) g_err = "mcq_iqp_device: HIP runtime error"; return err; }
-    if (stats) {
-        // QP passes summed over the tracks = sum of the rounds every track ran (the live count is only read back from round
-        // iters_min on: counting launches x live tracks over-counted tracks that failed in an early round)
-        // (a statistic: a failed read-back must not discard the run -- qp_solves = -1 then; tracks that came in empty ran no QP)
-        std::vector<int> rv((size_t)batch), nf((size_t)batch);
-        if (hipMemcpy(rv.data(), rounds_out, batch * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess &&
-            hipMemcpy(nf.data(), n_io, batch * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess) {
-            for (int k = 0; k < batch; ++k) if (nf[k] > 0) solves += rv[k];
-        } else solves = -1;
-        stats->rounds = rounds;
-        stats->qp_solves = (int)solves;
-    }
-    if (n_live > 0) {
-        // tracks still iterating at max_rounds: report them (status MCQ_ITER_CAP), keep their last state
-        std::vector<int> lv((size_t)batch), stv((size_t)batch);
-        HIP_TRY(hipMemcpy(lv.data(), live, batch * sizeof(int), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(stv.data(), status_out, batch * sizeof(int), hipMemcpyDeviceToHost));
-        for (int k = 0; k < batch; ++k) if (lv[k] && stv[k] == MCQ_OK) stv[k] = MCQ_ITER_CAP;
-        HIP_TRY(hipMemcpy(status_out, stv.data(), batch * sizeof(int), hipMemcpyHostToDevice));
     }
     return 0;
 }
@@ -2877,11 +2683,274 @@ extern "C" int mcq_solve_device_stream(mcq_handle* h, int steps, int batch, int 
     return two ? join_second(h) : 0;
 }
 
+// ---- tph.iqp_handler as one call (include/mcq.h) ---------------------------------------------------------------------------------
 extern "C" int mcq_iqp_set_round_callback(mcq_handle* h, mcq_iqp_round_cb cb, void* user)
 {
     if (!h) { g_err = "mcq_iqp_set_round_callback: NULL handle"; return MCQ_E_ARG; }
     h->iqp_cb = cb;
     h->iqp_cb_user = cb ? user : nullptr;
+    return 0;
+}
+
+// h->iqp.  mcq_iqp_device's bookkeeping: live | n of the other set | glue status | pass status | final n (= n_io on return) | live count [1] |
+// the pass's curvature errors; what mcq_iqp_batch hands it as its outputs: trace [batch][MCQ_IQP_TRACE] | buf | rounds.  [batch] each.
+enum { IQP_LIVE, IQP_N_OTHER, IQP_GLUE_STATUS, IQP_PASS_STATUS, IQP_FINAL_N, IQP_LIVE_COUNT, IQP_PASS_CURV, IQP_TRACE, IQP_BUF, IQP_ROUNDS };
+static Arena iqp_layout(size_t batch)
+{
+    Arena a;
+    for (int k = IQP_LIVE; k <= IQP_FINAL_N; ++k) a.add<int>(batch);
+    return a.add<int>(1).add<double>(batch).add<double>(batch * MCQ_IQP_TRACE).add<int>(batch).add<int>(batch);
+}
+
+// h->iqp_set, the second set of mcq_iqp_batch's double buffer: ring [batch][nmax][4] | normals [batch][nmax][2] ...
+static Arena iqp_set_layout(size_t elems) { return Arena().add<double>(elems * 4).add<double>(elems * 2); }
+// ... and the extra bytes of its pinned block: room for that set on the host, then buf [batch] as the host reads it
+static Arena iqp_pin_layout(size_t elems, size_t batch) { return iqp_set_layout(elems).add<int>(batch); }
+
+// One run of mcq_iqp_device: what its pieces share.  The regions of h->iqp the kernels' records take read-only are here once more, writable.
+struct IqpRun {
+    int batch, nmax, iters_min, max_rounds;
+    double kappa_bound, w_veh, stepsize;
+    const double* scaling;              // the first pass's (the re-spline of passes 2+ uses unit ones, as upstream)
+    double* alpha;
+    mcq_opts o;
+    bool warm, timed;                   // warm: passes 2+ start from the carried working sets
+    mcq_iqp_stats* stats;
+    int *glue_status, *pass_status;
+    double* pass_curv;
+    int* n_set[2];                      // the two sets: [0] the caller's a (n_io doubles as its sizes), [1] its b and the arena's sizes
+    double *ref_set[2], *nv_set[2];
+    McqIqpStep S;
+    int cur, rounds, n_live;            // the set the next pass reads; rounds run; tracks still iterating, as last read back
+};
+
+// `count` elements of each of two device arrays into host vectors on the compute stream, waited for.  The vectors are the caller's locals: a
+// failure drains before it returns.
+template <class A, class B> static int fetch(mcq_handle* h, int count, const A* d_a, std::vector<A>& a, const B* d_b, std::vector<B>& b)
+{
+    a.resize((size_t)count);
+    b.resize((size_t)count);
+    HIP_TRY_DRAIN(hipMemcpyAsync(a.data(), d_a, count * sizeof(A), hipMemcpyDeviceToHost, compute_stream(h)));
+    HIP_TRY_DRAIN(hipMemcpyAsync(b.data(), d_b, count * sizeof(B), hipMemcpyDeviceToHost, compute_stream(h)));
+    HIP_TRY_DRAIN(hipStreamSynchronize(compute_stream(h)));
+    return 0;
+}
+
+// the tracks still iterating, as the bookkeeping counted them (into the run record: mcq_iqp_device drains where a piece fails)
+static int iqp_read_live(mcq_handle* h, IqpRun& R)
+{
+    HIP_TRY(hipMemcpyAsync(&R.n_live, R.S.live_count, sizeof(int), hipMemcpyDeviceToHost, compute_stream(h)));
+    HIP_TRY(hipStreamSynchronize(compute_stream(h)));
+    return 0;
+}
+
+// every track starts live (a track with n == 0 ends in its first, empty pass: status MCQ_BAD_INPUT, rounds_out 1), every output cleared
+static int iqp_begin(mcq_handle* h, IqpRun& R)
+{
+    const size_t ints = (size_t)R.batch * sizeof(int);
+    const std::vector<int> ones((size_t)R.batch, 1);
+    HIP_TRY_DRAIN(hipMemcpyAsync(R.S.live, ones.data(), ints, hipMemcpyHostToDevice, compute_stream(h)));
+    HIP_TRY_DRAIN(hipMemsetAsync(R.S.final_rounds, 0, ints, compute_stream(h)));
+    HIP_TRY_DRAIN(hipMemsetAsync(R.S.final_buf, 0, ints, compute_stream(h)));
+    HIP_TRY_DRAIN(hipStreamSynchronize(compute_stream(h)));      // `ones` goes out of scope
+    if (R.S.curv_trace) HIP_TRY(hipMemsetAsync(R.S.curv_trace, 0, (size_t)R.batch * MCQ_IQP_TRACE * sizeof(double), compute_stream(h)));
+    if (R.stats) { R.stats->rounds = 0; R.stats->qp_solves = 0; for (int k = 0; k < 16; ++k) { R.stats->solver_ms[k] = 0.f; R.stats->fallbacks[k] = 0; } }
+    // the final ring sizes are collected in a scratch array and moved to n_io at the end
+    HIP_TRY(hipMemsetAsync(R.S.final_n, 0, ints, compute_stream(h)));
+    return 0;
+}
+
+// ---- The first iters_min rounds as ONE launch.  A track's rounds depend on nothing but its own previous round, and no track can end before
+//      round iters_min, so nothing has to come back to the host in between; but launched round by round, every round ends with its slowest
+//      track -- a warm start that falls back to the cold path takes 8.7 ms where the median track takes 3 -- and the next round's launch
+//      waits for it with most compute units idle (third pass of the 1024 ovals: 6.5 ms of mean load, 11.5 ms of launch; neither another cap
+//      of the exchange nor the pass before says which tracks those will be: docs/NOTEBOOK.md R5.7).  In mcq_iqp_rounds_kernel every
+//      workgroup takes its track through those rounds on its own -- the bodies of the solver, bookkeeping and glue kernels between workgroup
+//      barriers, the same arrays --: nobody waits for anybody.  Results bitwise those of iqp_round, which takes over after round iters_min
+//      (and runs everything when per-round data must reach the host: timed statistics, the print_debug callback; $MCQ_IQP_FUSED=0: always). ----
+static int iqp_fused(mcq_handle* h, IqpRun& R)
+{
+    const int ra = std::min(R.iters_min, R.max_rounds);
+    McqIqpRounds F;
+    memset(&F, 0, sizeof(F));
+    F.B = make_batch(R.batch, R.nmax, nullptr, nullptr, nullptr, nullptr, R.alpha, R.pass_curv, R.pass_status, nullptr, R.kappa_bound, R.w_veh);
+    if (int rc = fill_batch(h, F.B, R.o, h->ws[0])) return rc;
+    F.R.batch = R.batch; F.R.nmax = R.nmax; F.R.alpha = R.alpha; F.R.live = R.S.live; F.R.stepsize = R.stepsize; F.R.status = R.glue_status;
+    F.R.vec = h->ws[0].vec; F.R.state_in = h->ws[0].state; F.R.state_out = h->state2;
+    F.S = R.S;
+    for (int q = 0; q < 2; ++q) { F.n_set[q] = R.n_set[q]; F.ref_set[q] = R.ref_set[q]; F.nv_set[q] = R.nv_set[q]; }
+    F.sc = R.scaling;
+    F.warm = R.warm ? h->state2 : nullptr;
+    F.rounds = ra;
+    HIP_TRY(hipMemsetAsync(R.S.live_count, 0, sizeof(int), compute_stream(h)));
+    hipLaunchKernelGGL(mcq_iqp_rounds_kernel, dim3((unsigned)R.batch), dim3(256), 0, compute_stream(h), F);
+    HIP_TRY(hipGetLastError());
+    // (iqp_round may go on from the working sets the last round's glue carried over)
+    h->state2_valid = true;
+    h->state2_batch = R.batch;
+    h->state2_nmax = R.nmax;
+    R.cur = ra & 1;
+    R.rounds = ra;
+    return iqp_read_live(h, R);
+}
+
+// what reaches the host after a round's QP pass: the timed statistics (a failed read-back leaves the round's count at 0) and print_debug's
+// callback -- the pass's curvature errors and who ran it, before the termination test decides
+static int iqp_report(mcq_handle* h, const IqpRun& R, int it)
+{
+    std::vector<int> lv;
+    if (R.timed && it <= 16) {
+        float ms[5];
+        if (mcq_last_timing(h, ms) == 0) R.stats->solver_ms[it - 1] = ms[4];
+        std::vector<mcq_info> info;
+        if (fetch(h, R.batch, h->d_info, info, R.S.live, lv) == 0)
+            for (int k = 0; k < R.batch; ++k) if (lv[k] && (info[k].second_attempt & 2)) ++R.stats->fallbacks[it - 1];
+    }
+    if (h->iqp_cb) {
+        std::vector<double> cv;
+        if (int rc = fetch(h, R.batch, R.pass_curv, cv, R.S.live, lv)) return rc;
+        h->iqp_cb(h->iqp_cb_user, it, R.batch, cv.data(), lv.data());
+    }
+    return 0;
+}
+
+// round `it` launch by launch: the QP pass, the host's reports, the bookkeeping, the glue for the tracks that go on, the bookkeeping
+static int iqp_round(mcq_handle* h, IqpRun& R, int it)
+{
+    const int cur = R.cur;
+    R.rounds = it;
+    McqBatch B = make_batch(R.batch, R.nmax, R.n_set[cur], R.ref_set[cur], R.nv_set[cur], it == 1 ? R.scaling : nullptr, R.alpha, R.pass_curv,
+                            R.pass_status, R.timed ? h->d_info : nullptr, R.kappa_bound, R.w_veh);
+    R.o.warm_start = (R.warm && it > 1) ? 1 : 0;
+    if (int rc = launch(h, B, R.o)) return rc;
+    if (int rc = iqp_report(h, R, it)) return rc;
+    HIP_TRY(hipMemsetAsync(R.S.live_count, 0, sizeof(int), compute_stream(h)));
+    const dim3 grid((unsigned)((R.batch + 255) / 256)), block(256);
+    R.S.phase = 0; R.S.round = it; R.S.cur = cur; R.S.n_ring = R.n_set[cur]; R.S.n_next = R.n_set[1 - cur];
+    hipLaunchKernelGGL(mcq_iqp_step_kernel, grid, block, 0, compute_stream(h), R.S);
+    HIP_TRY(hipGetLastError());
+    const double scale = it < R.iters_min ? (double)it / (double)R.iters_min : 1.0;
+    if (int rc = mcq_relinearise_device(h, R.batch, R.nmax, R.n_set[cur], R.ref_set[cur], R.nv_set[cur], R.alpha, R.S.live, scale, R.stepsize,
+                                        R.ref_set[1 - cur], R.nv_set[1 - cur], R.n_set[1 - cur], R.glue_status)) return rc;
+    R.S.phase = 1;
+    hipLaunchKernelGGL(mcq_iqp_step_kernel, grid, block, 0, compute_stream(h), R.S);
+    HIP_TRY(hipGetLastError());
+    R.cur = 1 - cur;
+    // the first iters_min - 1 rounds cannot end a healthy track: no need to look
+    return (it >= R.iters_min || it == R.max_rounds) ? iqp_read_live(h, R) : 0;
+}
+
+// the final ring sizes into n_io, the run waited for; then, on the idle stream, the statistics and the statuses of the tracks the cap cut off
+static int iqp_finish(mcq_handle* h, IqpRun& R)
+{
+    HIP_TRY(hipMemcpyAsync(R.n_set[0], R.S.final_n, (size_t)R.batch * sizeof(int), hipMemcpyDeviceToDevice, compute_stream(h)));
+    HIP_TRY(hipStreamSynchronize(compute_stream(h)));
+    std::vector<int> a, b;
+    if (R.stats) {
+        // QP passes summed over the tracks = sum of the rounds every track ran (the live count is only read back from round
+        // iters_min on: counting launches x live tracks over-counted tracks that failed in an early round)
+        // (a statistic: a failed read-back must not discard the run -- qp_solves = -1 then; tracks that came in empty ran no QP)
+        long long solves = 0;
+        if (fetch(h, R.batch, R.S.final_rounds, a, R.n_set[0], b) != 0) solves = -1;
+        else for (int k = 0; k < R.batch; ++k) if (b[k] > 0) solves += a[k];
+        R.stats->rounds = R.rounds;
+        R.stats->qp_solves = (int)solves;
+    }
+    if (R.n_live > 0) {
+        // tracks still iterating at max_rounds: report them (status MCQ_ITER_CAP), keep their last state
+        if (int rc = fetch(h, R.batch, R.S.live, a, R.S.final_status, b)) return rc;
+        for (int k = 0; k < R.batch; ++k) if (a[k] && b[k] == MCQ_OK) b[k] = MCQ_ITER_CAP;
+        HIP_TRY_DRAIN(hipMemcpyAsync(R.S.final_status, b.data(), (size_t)R.batch * sizeof(int), hipMemcpyHostToDevice, compute_stream(h)));
+        HIP_TRY_DRAIN(hipStreamSynchronize(compute_stream(h)));
+    }
+    return 0;
+}
+
+// the pieces in their order: the fused launch where nothing per round has to reach the host, the remaining rounds one by one
+static int iqp_run(mcq_handle* h, IqpRun& R)
+{
+    if (int rc = iqp_begin(h, R)) return rc;
+    int it = 1;
+    const char* fe = getenv("MCQ_IQP_FUSED");
+    if (!(fe && fe[0] == '0') && !R.timed && !h->iqp_cb) {
+        if (int rc = iqp_fused(h, R)) return rc;
+        it = R.rounds + 1;
+    }
+    for (; it <= R.max_rounds && R.n_live > 0; ++it)
+        if (int rc = iqp_round(h, R, it)) return rc;
+    return iqp_finish(h, R);
+}
+
+extern "C" int mcq_iqp_device(mcq_handle* h, int batch, int nmax, int* n_io, double* reftrack_a, double* normvec_a,
+                              double* reftrack_b, double* normvec_b, const double* scaling, double kappa_bound, double w_veh,
+                              double stepsize_interp, int iters_min, double curv_error_allowed, int max_rounds,
+                              const mcq_opts* opts, double* alpha_out, int* buf_out, double* curv_err_out, int* status_out,
+                              int* rounds_out, double* curv_trace_out, mcq_iqp_stats* stats)
+{
+    if (!h || batch <= 0 || nmax <= 0 || !n_io || !reftrack_a || !normvec_a || !reftrack_b || !normvec_b || !alpha_out ||
+        !buf_out || !curv_err_out || !status_out || !rounds_out || !(stepsize_interp > 0.0) || iters_min < 1 || max_rounds < 1 ||
+        reftrack_a == reftrack_b || normvec_a == normvec_b) {
+        g_err = "mcq_iqp_device: bad argument";
+        return MCQ_E_ARG;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    const bool timed = stats && stats->timed;
+    if (int rc = ensure_workspace(h, 0, (size_t)batch, (size_t)nmax)) return rc;
+    const Arena a = iqp_layout((size_t)batch);
+    if (int rc = grow(h, h->iqp, a.bytes)) return rc;
+    if (timed) { if (int rc = ensure_staging(h, 0, (size_t)batch, (size_t)nmax)) return rc; }       // (the info records)
+    void* const p = h->iqp.p;
+    IqpRun R = {batch, nmax, iters_min, max_rounds, kappa_bound, w_veh, stepsize_interp, scaling, alpha_out, resolve_opts(opts),
+                !(opts && opts->warm_start < 0), timed, stats, a.at<int>(p, IQP_GLUE_STATUS), a.at<int>(p, IQP_PASS_STATUS), a.at<double>(p, IQP_PASS_CURV),
+                {n_io, a.at<int>(p, IQP_N_OTHER)}, {reftrack_a, reftrack_b}, {normvec_a, normvec_b}};
+    R.n_live = batch;
+    McqIqpStep& S = R.S;            // (zero so far, like cur and rounds)
+    S.batch = batch; S.iters_min = iters_min; S.curv_allowed = curv_error_allowed;
+    S.curv = R.pass_curv; S.status = R.pass_status; S.relin_status = R.glue_status;
+    S.live = a.at<int>(p, IQP_LIVE); S.final_n = a.at<int>(p, IQP_FINAL_N); S.live_count = a.at<int>(p, IQP_LIVE_COUNT);
+    S.final_buf = buf_out; S.final_curv = curv_err_out; S.final_status = status_out; S.final_rounds = rounds_out;
+    S.curv_trace = curv_trace_out;
+    const int rc = iqp_run(h, R);
+    // What every way out of a run has in common: nothing of it is in flight (iqp_finish has waited; a failure may have left copies into the
+    // record or launches queued), and the working sets belong to its last glue call, not to a later solve.
+    if (rc) drain(h);
+    h->state2_valid = false;
+    return rc;
+}
+
+// The end states' rings and normals into the caller's [batch][nmax][*] arrays, buf_h saying which set holds a track's.  One set holds them all
+// (the usual case: one iters_min for all, every track ends in the same round): it goes out in two copies.  Otherwise both sets go through the
+// pinned block -- set 0 into the now free input block, set 1 into the extra bytes -- and from there track by track.
+static int iqp_rings_down(mcq_handle* h, const Upload& P, const Arena& pin, const Stamps& ts, const double* ref_b, const double* nv_b,
+                          const int* n_out, double* reftrack_out, double* normvec_out)
+{
+    const size_t nmax = P.nmax, elems = (size_t)P.batch * nmax;
+    const int* buf_h = pin.at<int>(P.extra, 2);
+    const double* d_ref[2] = {h->stage[0].ref, ref_b};
+    const double* d_nv[2] = {h->stage[0].nv, nv_b};
+    bool use[2] = {false, false};
+    for (int b = 0; b < P.batch; ++b) use[buf_h[b] ? 1 : 0] = true;
+    if (use[0] != use[1]) {
+        const int q = use[1] ? 1 : 0;
+        HIP_TRY_DRAIN(hipMemcpyAsync(reftrack_out, d_ref[q], elems * 4 * sizeof(double), hipMemcpyDeviceToHost, compute_stream(h)));
+        HIP_TRY_DRAIN(hipMemcpyAsync(normvec_out, d_nv[q], elems * 2 * sizeof(double), hipMemcpyDeviceToHost, compute_stream(h)));
+        HIP_TRY_DRAIN(hipStreamSynchronize(compute_stream(h)));
+        ts.at("iqp_batch: %-28s at %.3f ms\n", "rings and normals down");
+        return 0;
+    }
+    double* ref_h[2] = {P.ref, pin.at<double>(P.extra, 0)};
+    double* nv_h[2] = {P.nv, pin.at<double>(P.extra, 1)};
+    for (int q = 0; q < 2; ++q) {
+        HIP_TRY_DRAIN(hipMemcpyAsync(ref_h[q], d_ref[q], elems * 4 * sizeof(double), hipMemcpyDeviceToHost, compute_stream(h)));
+        HIP_TRY_DRAIN(hipMemcpyAsync(nv_h[q], d_nv[q], elems * 2 * sizeof(double), hipMemcpyDeviceToHost, compute_stream(h)));
+    }
+    HIP_TRY_DRAIN(hipStreamSynchronize(compute_stream(h)));
+    for (int b = 0; b < P.batch; ++b) {
+        const int q = buf_h[b] ? 1 : 0;
+        const size_t n = n_out[b] > 0 ? (size_t)n_out[b] : 0;
+        memcpy(reftrack_out + (size_t)b * nmax * 4, ref_h[q] + (size_t)b * nmax * 4, n * 4 * sizeof(double));
+        memcpy(normvec_out + (size_t)b * nmax * 2, nv_h[q] + (size_t)b * nmax * 2, n * 2 * sizeof(double));
+    }
     return 0;
 }
 
@@ -2896,16 +2965,9 @@ extern "C" int mcq_iqp_batch(mcq_handle* h, const mcq_problem* probs, int batch,
         return MCQ_E_ARG;
     }
     HIP_TRY(hipSetDevice(h->device));
-    const bool trace = getenv("MCQ_IQP_TRACE") != nullptr;          // host-side time stamps of this call on stderr
-    struct timespec ts0;
-    clock_gettime(CLOCK_MONOTONIC, &ts0);
-    auto stamp = [&](const char* what) {
-        if (!trace) return;
-        struct timespec t1;
-        clock_gettime(CLOCK_MONOTONIC, &t1);
-        fprintf(stderr, "iqp_batch: %-28s at %.3f ms\n", what, (t1.tv_sec - ts0.tv_sec) * 1e3 + (t1.tv_nsec - ts0.tv_nsec) * 1e-6);
-    };
-    const size_t nmax = (size_t)nmax_out;
+    const Stamps ts("MCQ_IQP_TRACE");
+    const char* const line = "iqp_batch: %-28s at %.3f ms\n";
+    const size_t nmax = (size_t)nmax_out, elems = (size_t)batch * nmax;
     bool any_sc = false;
     for (int b = 0; b < batch; ++b) {
         if (!probs[b].reftrack || !probs[b].normvec || probs[b].n < 0) { g_err = "mcq_iqp_batch: reftrack and normvec are required"; return MCQ_E_ARG; }
@@ -2916,87 +2978,40 @@ extern "C" int mcq_iqp_batch(mcq_handle* h, const mcq_problem* probs, int batch,
         }
         if (probs[b].scaling) any_sc = true;
     }
-    int rc = ensure_workspace(h, 0, (size_t)batch, nmax);
-    if (rc) return rc;
-    rc = ensure_staging(h, 0, (size_t)batch, nmax);
-    if (rc) return rc;
-    const size_t elems = (size_t)batch * nmax;
-    if (elems > h->stage2_elems) {
-        HIP_TRY(hipStreamSynchronize(compute_stream(h)));
-        (void)hipFree(h->d_ref2); (void)hipFree(h->d_nv2);
-        h->d_ref2 = h->d_nv2 = nullptr; h->stage2_elems = 0;
-        HIP_TRY(hipMalloc((void**)&h->d_ref2, elems * 4 * sizeof(double)));
-        HIP_TRY(hipMalloc((void**)&h->d_nv2, elems * 2 * sizeof(double)));
-        h->stage2_elems = elems;
-    }
+    // buffers: grown here and kept by the handle (no allocation / hipFree -- an implicit device-wide synchronisation -- per call)
+    const Arena set2 = iqp_set_layout(elems), own = iqp_layout((size_t)batch);
+    if (int rc = ensure_workspace(h, 0, (size_t)batch, nmax)) return rc;
+    if (int rc = ensure_staging(h, 0, (size_t)batch, nmax)) return rc;
+    if (int rc = grow(h, h->iqp_set, set2.bytes)) return rc;
+    if (int rc = grow(h, h->iqp, own.bytes)) return rc;
+    const Staging& s = h->stage[0];
+    double *ref_b = set2.at<double>(h->iqp_set.p, 0), *nv_b = set2.at<double>(h->iqp_set.p, 1);
+    double* trace_d = curv_trace_out ? own.at<double>(h->iqp.p, IQP_TRACE) : nullptr;
+    int *d_buf = own.at<int>(h->iqp.p, IQP_BUF), *d_rounds = own.at<int>(h->iqp.p, IQP_ROUNDS);
+    ts.at(line, "checked, buffers ready");
+    // plan and upload; the pinned block's extra bytes take the end states of the second set and buf
     Upload P = {probs, batch, nmax, any_sc, true};
-    // results need room for both buffer sets' ref / nv in the worst case: one extra set
-    stamp("checked, buffers ready");
-    rc = plan_upload(h, P, elems * 6 * sizeof(double) + (size_t)batch * 3 * sizeof(int));
+    const Arena pin = iqp_pin_layout(elems, (size_t)batch);
+    if (int rc = plan_upload(h, P, pin.bytes)) return rc;
+    int* buf_h = pin.at<int>(P.extra, 2);
+    if (int rc = upload_batch(h, P)) return rc;
+    ts.at(line, "packed, uploads queued");
+    int rc = mcq_iqp_device(h, batch, (int)nmax, h->d_n, s.ref, s.nv, ref_b, nv_b, any_sc ? s.sc : nullptr, probs[0].kappa_bound, probs[0].w_veh,
+                            stepsize_interp, iters_min, curv_error_allowed, max_rounds, opts, s.alpha, d_buf, s.curv, s.status, d_rounds, trace_d, stats);
+    ts.at(line, "rounds done");
     if (rc) return rc;
-    rc = upload_batch(h, P);
-    if (rc) return rc;
-    stamp("packed, uploads queued");
-    rc = ensure_iqp(h, (size_t)batch);                 // the trace staging lives in the handle (no allocation / hipFree -- an implicit
-    if (rc) return rc;                                 // device-wide synchronisation -- per call)
-    double* d_trace = curv_trace_out ? h->d_trace : nullptr;
-    // d_kb / d_wv staging doubles as the per-track outputs of the loop: curvature error (double), buffer index / rounds (ints)
-    int* d_buf = (int*)h->d_kb;                 // batch doubles >= 2 * batch ints
-    int* d_rounds = d_buf + batch;
-    rc = mcq_iqp_device(h, batch, (int)nmax, h->d_n, h->stage[0].ref, h->stage[0].nv, h->d_ref2, h->d_nv2, any_sc ? h->stage[0].sc : nullptr,
-                        probs[0].kappa_bound, probs[0].w_veh, stepsize_interp, iters_min, curv_error_allowed, max_rounds, opts,
-                        h->stage[0].alpha, d_buf, h->stage[0].curv, h->stage[0].status, d_rounds, d_trace, stats);
-    stamp("rounds done");
-    if (!rc && d_trace && hipMemcpy(curv_trace_out, d_trace, (size_t)batch * MCQ_IQP_TRACE * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) {
-        g_err = "mcq_iqp_batch: read-back of the curvature-error trace failed";
-        rc = MCQ_E_DEVICE;
-    }
-    if (rc) return rc;
-    int* buf_h = P.n;                            // the pinned int block: n | (extra) buf, rounds
+    // results down: alpha straight into the caller's [batch][nmax_out] array (its padding holds whatever the device buffer held)
+    if (trace_d) HIP_TRY(hipMemcpy(curv_trace_out, trace_d, (size_t)batch * MCQ_IQP_TRACE * sizeof(double), hipMemcpyDeviceToHost));
     HIP_TRY_DRAIN(hipMemcpyAsync(n_out, h->d_n, batch * sizeof(int), hipMemcpyDeviceToHost, compute_stream(h)));
     HIP_TRY_DRAIN(hipMemcpyAsync(buf_h, d_buf, batch * sizeof(int), hipMemcpyDeviceToHost, compute_stream(h)));
     HIP_TRY_DRAIN(hipMemcpyAsync(rounds_out, d_rounds, batch * sizeof(int), hipMemcpyDeviceToHost, compute_stream(h)));
-    // alpha straight into the caller's [batch][nmax_out] array (its padding holds whatever the device buffer held)
-    rc = download_results(h, compute_stream(h), batch, alpha_out, h->stage[0].alpha, elems * sizeof(double), curv_err_out, status_out, nullptr);
+    rc = download_results(h, compute_stream(h), batch, alpha_out, s.alpha, elems * sizeof(double), curv_err_out, status_out, nullptr);
     if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(compute_stream(h)));
-    stamp("alpha and per-track results down");
-    bool use[2] = {false, false};
-    for (int b = 0; b < batch; ++b) use[buf_h[b] ? 1 : 0] = true;
-    const double* d_ref_set[2] = {h->stage[0].ref, h->d_ref2};
-    const double* d_nv_set[2] = {h->stage[0].nv, h->d_nv2};
-    if (use[0] != use[1]) {
-        // the usual case (one iters_min for all: every track ends in the same round): the final set goes out in two copies
-        const int q = use[1] ? 1 : 0;
-        HIP_TRY_DRAIN(hipMemcpyAsync(reftrack_out, d_ref_set[q], elems * 4 * sizeof(double), hipMemcpyDeviceToHost, compute_stream(h)));
-        HIP_TRY_DRAIN(hipMemcpyAsync(normvec_out, d_nv_set[q], elems * 2 * sizeof(double), hipMemcpyDeviceToHost, compute_stream(h)));
-        HIP_TRY(hipStreamSynchronize(compute_stream(h)));
-        stamp("rings and normals down");
-        return 0;
-    }
-    // tracks ended in different rounds: both sets through the pinned staging (set 0 into the now free input block, set 1 into
-    // the extra block behind it), then track by track
-    double* ref_h[2] = {P.ref, nullptr};
-    double* nv_h[2] = {P.nv, nullptr};
-    {
-        size_t addr = (size_t)(P.n + batch + 16);
-        addr = (addr + 7) & ~(size_t)7;                 // keep the extra block 8-byte aligned
-        ref_h[1] = (double*)addr;
-        nv_h[1] = ref_h[1] + elems * 4;
-    }
-    for (int q = 0; q < 2; ++q) {
-        HIP_TRY_DRAIN(hipMemcpyAsync(ref_h[q], d_ref_set[q], elems * 4 * sizeof(double), hipMemcpyDeviceToHost, compute_stream(h)));
-        HIP_TRY_DRAIN(hipMemcpyAsync(nv_h[q], d_nv_set[q], elems * 2 * sizeof(double), hipMemcpyDeviceToHost, compute_stream(h)));
-    }
-    HIP_TRY(hipStreamSynchronize(compute_stream(h)));
-    for (int b = 0; b < batch; ++b) {
-        const int q = buf_h[b] ? 1 : 0;
-        const size_t n = n_out[b] > 0 ? (size_t)n_out[b] : 0;
-        memcpy(reftrack_out + (size_t)b * nmax * 4, ref_h[q] + (size_t)b * nmax * 4, n * 4 * sizeof(double));
-        memcpy(normvec_out + (size_t)b * nmax * 2, nv_h[q] + (size_t)b * nmax * 2, n * 2 * sizeof(double));
-    }
-    return 0;
+    HIP_TRY_DRAIN(hipStreamSynchronize(compute_stream(h)));
+    ts.at(line, "alpha and per-track results down");
+    return iqp_rings_down(h, P, pin, ts, ref_b, nv_b, n_out, reftrack_out, normvec_out);
 }
+
 
 
 // =====================================================================================================================

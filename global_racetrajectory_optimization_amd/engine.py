@@ -765,13 +765,31 @@ class Engine:
                                     n_o.ctypes.data_as(_ip), _as_dp(curv), status.ctypes.data_as(_ip),
                                     rounds.ctypes.data_as(_ip), _as_dp(trace), ctypes.byref(st))
         self._check(rc, "mcq_iqp_batch")
+        return dict(alpha=[alpha[k, :n_o[k]] for k in range(bsz)], reftrack=[ref_o[k, :n_o[k]] for k in range(bsz)],
+                    normvectors=[nv_o[k, :n_o[k]] for k in range(bsz)], n=n_o, curv_err=curv, status=status, rounds=rounds,
+                    curv_trace=trace, stats=self._iqp_stats(st, nmax, timed))
+
+    @staticmethod
+    def _iqp_stats(st, nmax, timed):
         stats = dict(rounds=int(st.rounds), qp_solves=int(st.qp_solves), nmax=int(nmax))
         if timed:
             stats["solver_ms"] = [float(st.solver_ms[k]) for k in range(min(st.rounds, 16))]
             stats["fallbacks"] = [int(st.fallbacks[k]) for k in range(min(st.rounds, 16))]
-        return dict(alpha=[alpha[k, :n_o[k]] for k in range(bsz)], reftrack=[ref_o[k, :n_o[k]] for k in range(bsz)],
-                    normvectors=[nv_o[k, :n_o[k]] for k in range(bsz)], n=n_o, curv_err=curv, status=status, rounds=rounds,
-                    curv_trace=trace, stats=stats)
+        return stats
+
+    def iqp_device(self, batch, nmax, d_n, d_ref_a, d_nv_a, d_ref_b, d_nv_b, d_scaling, kappa_bound, w_veh, stepsize_interp, iters_min,
+                   curv_error_allowed, max_rounds, d_alpha, d_buf, d_curv, d_status, d_rounds, d_trace=None, timed=False, **opt_kw):
+        """tph.iqp_handler for a RESIDENT batch (mcq_iqp_device in include/mcq.h): the tracks in set a, [batch][nmax][*], d_n [batch] their
+        waypoint counts on entry and those of the end states on return; d_buf says which set holds a track's end state.  Blocking.  Returns
+        the stats of iqp_batch."""
+        st = McqIqpStats()
+        st.timed = 1 if timed else 0
+        opts = self._opts(**opt_kw)
+        rc = self.lib.mcq_iqp_device(self.h, int(batch), int(nmax), d_n, d_ref_a, d_nv_a, d_ref_b, d_nv_b, d_scaling or None, float(kappa_bound),
+                                     float(w_veh), float(stepsize_interp), int(iters_min), float(curv_error_allowed), int(max_rounds),
+                                     ctypes.byref(opts), d_alpha, d_buf, d_curv, d_status, d_rounds, d_trace or None, ctypes.byref(st))
+        self._check(rc, "mcq_iqp_device")
+        return self._iqp_stats(st, nmax, timed)
 
     def solve_uniform_f32(self, reftrack, normvec, scaling, kappa_bound, w_veh, **opt_kw):
         """Host convenience around solve_device_f32 for a uniform-n batch: reftrack [B,n,4] (cast to float32), normvec

@@ -914,7 +914,8 @@ int mcq_solve_device_stream(mcq_handle* h, int steps, int batch, int n, const do
  * [batch][MCQ_IQP_TRACE] (optional) = curv_error_max of every round of a track (what iqp_handler prints with print_debug;
  * rounds beyond MCQ_IQP_TRACE are not recorded: rounds_out tells when the trace is truncated).  A track with n_io == 0 on entry is
  * not a track: it never runs (status MCQ_BAD_INPUT from its first, empty pass, rounds_out 1).  stats (optional, host): see mcq_iqp_stats.  Blocking (the loop needs the
- * live count). */
+ * live count).  A call of either entry that fails in the HIP runtime returns MCQ_E_DEVICE with nothing of it left in flight, and
+ * mcq_last_error names the HIP call that failed ("<call> failed: <hip error> (<file>:<line>)"), whatever the thread reported before. */
 #define MCQ_IQP_TRACE 16
 typedef struct {
     int rounds;             /* rounds run (the slowest track) */

@@ -1,8 +1,8 @@
 """The bodies of tests/test_emu_iqp.py (SIMT interpreter) and tests/test_gpu_iqp.py (MI355X): mcq_iqp_batch -- iqp_step_track, mcq_iqp_step_kernel,
 mcq_iqp_rounds_kernel, the host's round loop, round cap and two-buffer download -- on the cases of tests/iqp_cases.py against tests/iqp_ref.py under
 the guards of tests/iqp_guard.py.  Round counts, waypoint counts and statuses are compared exactly; alpha, ring rows, normals and curvature errors
-within their guards; the routes of one call (fused launch or round by round, timed, callback, caller's buffers, a batch's order and neighbours)
-bit for bit.  Every function takes the engine; those that compare with the reference take a ring_guard.Worst that collects the worst deviation
+within their guards; the routes of one call (fused launch or round by round, timed, callback, caller's buffers, a batch's order and neighbours,
+the resident entry mcq_iqp_device on buffers of the test's own, a handle whose buffers grew in between) bit for bit.  Every function takes the engine; those that compare with the reference take a ring_guard.Worst that collects the worst deviation
 per family and quantity next to its guard."""
 import contextlib
 import os
@@ -169,6 +169,83 @@ def check_same_round_batch(eng, worst):
     assert set(out["rounds"]) == {3}
     for k in range(len(E)):
         assert same_track(out, k, _batch_call(eng, [E[k]]), 0)
+
+
+def _resident_call(eng, entries):
+    """The batch through Engine.iqp_device on buffers of the test's own -- two ring sets padded to [batch][BATCH_NMAX][*], buf, rounds, trace --
+    as an iqp_batch result: ring and normals of a track are the first n rows of set buf[k].  Also buf, and n_io as it came back."""
+    tracks = [ic.batch_track(kind, trk) for kind, trk in entries]
+    bsz, nmax = len(tracks), ic.BATCH_NMAX
+    ns = np.array([t["reftrack"].shape[0] for t in tracks], dtype=np.int32)
+    ref, nv, sc = np.zeros((bsz, nmax, 4)), np.zeros((bsz, nmax, 2)), np.ones((bsz, nmax))
+    for k, t in enumerate(tracks):
+        ref[k, :ns[k]], nv[k, :ns[k]] = t["reftrack"], t["normvectors"]
+        if t["scaling"] is not None:
+            sc[k, :ns[k]] = t["scaling"]
+    with eng.scope() as dev:
+        d_n, d_sc = dev.up(ns), dev.up(sc)
+        d_sets = ((dev.up(ref), dev.up(nv)), (dev.out((bsz, nmax, 4)), dev.out((bsz, nmax, 2))))
+        d_alpha, d_curv, d_status = dev.out((bsz, nmax)), dev.out(bsz), dev.out(bsz, np.int32)
+        d_buf, d_rounds, d_trace = dev.out(bsz, np.int32), dev.out(bsz, np.int32), dev.out((bsz, TRACE))
+        stats = eng.iqp_device(bsz, nmax, d_n, d_sets[0][0], d_sets[0][1], d_sets[1][0], d_sets[1][1], d_sc, ic.KAPPA, ic.W_VEH, ic.BATCH_STEP,
+                               ic.BATCH_ITERS_MIN, ic.BATCH_ALLOWED, ic.MAX_ROUNDS, d_alpha, d_buf, d_curv, d_status, d_rounds, d_trace)
+        n, buf, alpha = dev.get(d_n), dev.get(d_buf), dev.get(d_alpha)
+        sets = [(dev.get(d_r), dev.get(d_v)) for d_r, d_v in d_sets]
+        out = dict(n=n, buf=buf, curv_err=dev.get(d_curv), status=dev.get(d_status), rounds=dev.get(d_rounds), curv_trace=dev.get(d_trace), stats=stats)
+    assert set(buf) <= {0, 1} and np.all((n >= 0) & (n <= nmax))
+    out.update(alpha=[alpha[k, :n[k]] for k in range(bsz)], reftrack=[sets[buf[k]][0][k, :n[k]] for k in range(bsz)],
+               normvectors=[sets[buf[k]][1][k, :n[k]] for k in range(bsz)])
+    return out
+
+
+def check_resident_entry(eng):
+    """mcq_iqp_device on a caller's own buffers (everywhere else it runs inside mcq_iqp_batch, over the handle's): per track the bits of
+    mcq_iqp_batch for the same entries -- status, rounds and n exactly (n is n_io as it came back), alpha, the ring and normals of set buf[k],
+    curvature error and trace bit for bit (same_track's rule for tracks without state) -- and buf the set the track's last round read
+    (mcq_iqp_batch hands no buf back; its rounds say which set that is).  Fused and round by round."""
+    for what, E in (("same_round", ic.SAME_ROUND), ("mixed", ic.MIXED)):
+        base = _batch_call(eng, E)
+        for fused in ("1", "0"):
+            with _env("MCQ_IQP_FUSED", fused):
+                res = _resident_call(eng, E)
+            check_same_batch("resident %s, MCQ_IQP_FUSED=%s" % (what, fused), E, res, base)
+            assert np.array_equal(res["buf"], (base["rounds"] - 1) & 1), (what, fused, res["buf"], base["rounds"])
+            assert res["stats"]["rounds"] == base["stats"]["rounds"] and res["stats"]["qp_solves"] == base["stats"]["qp_solves"]
+
+
+def check_buffer_growth(eng_factory):
+    """One handle through IQP calls of growing and shrinking batches with a regrowth of staging set 0 in between (a solve_batch of more
+    problems than any call before it): every IQP result is bitwise that of a fresh handle that runs only that call, and the two mixed
+    batches are bitwise each other's."""
+    E = ic.MIXED
+    probs = [dict(reftrack=t["reftrack"], normvec=t["normvectors"], scaling=t["scaling"], kappa_bound=ic.KAPPA, w_veh=ic.W_VEH)
+             for t in (ic.batch_track(kind, trk) for kind, trk in ic.SAME_ROUND * 4)]
+    assert len(probs) == 16 > len(E)
+    used = eng_factory()
+    try:
+        cap1 = run_case(used, ic.CAP_CASE)
+        mixed1 = _batch_call(used, E)
+        assert np.all(used.solve_batch(probs)[2] == OK)
+        mixed2 = _batch_call(used, E)
+        cap2 = run_case(used, ic.CAP_CASE)
+    finally:
+        used.close()
+    fresh = eng_factory()
+    try:
+        cap = run_case(fresh, ic.CAP_CASE)
+    finally:
+        fresh.close()
+    fresh = eng_factory()
+    try:
+        mixed = _batch_call(fresh, E)
+    finally:
+        fresh.close()
+    assert cap["rounds"][0] == ic.CAP_ROUNDS and {int(mixed["rounds"][k]) for k, (kind, _) in enumerate(E) if kind == "ok"} == {3, 4, 5}
+    assert same_track(cap1, 0, cap, 0), "the first IQP call of a handle is not a fresh handle's"
+    assert same_track(cap2, 0, cap, 0), "an IQP call after larger batches and a regrowth of the staging is not a fresh handle's"
+    check_same_batch("mixed after a smaller IQP call", E, mixed1, mixed)
+    check_same_batch("mixed after a regrowth of the staging", E, mixed2, mixed)
+    check_same_batch("mixed, before and after the regrowth", E, mixed1, mixed2)
 
 
 @contextlib.contextmanager

@@ -1,7 +1,8 @@
 // TEST INFRASTRUCTURE ONLY (tests/test_host_layout.py builds and runs it; no GPU, no kernel launch, nothing loaded into an interpreter).
 // csrc/mcq_api.hip is compiled INTO this program against the SIMT interpreter's headers, so that its static host functions can be called:
-//   1. the six scratch layouts (*_layout) against the formulas the entries carried before the arena -- written out below as they stood, the
-//      record of the layout the kernels were validated with: total bytes, every region's offset, every region's alignment;
+//   1. the scratch layouts (*_layout) against the formulas the entries carried before the arena -- written out below as they stood, the
+//      record of the layout the kernels were validated with: total bytes, every region's offset, every region's alignment (the IQP driver's
+//      buffers were allocations of their own before: the regions the driver indexes, back to back on 8-byte boundaries);
 //   2. the structural scan behind mcq_les_scalings / mcq_les_scalings_open on small systems with one corrupted entry, on 1 and on 3 threads:
 //      return code and mcq_last_error text.
 // -DSCAN_ONLY leaves part 1 out (the scan alone also compiles against sources that have no layout functions).
@@ -78,6 +79,16 @@ static void check_layouts()
         for (size_t maxblk : {(size_t)0, (size_t)1, (size_t)3, (size_t)1000, (size_t)1 << 21}) {
             const size_t b_bits = old_up8(tracks * maxblk * 256);
             expect_layout("fgen_pts", fgen_pts_layout(tracks, maxblk), b_bits + tracks * std::max<size_t>(maxblk, 1) * I, {0, b_bits}, {alignof(unsigned char), AI});
+        }
+    }
+    // mcq_iqp_device / mcq_iqp_batch (allocations of their own before the arena): [batch] per region, the live count [1], each on an 8-byte boundary
+    for (size_t batch : {1, 2, 3, 4, 11, 1024, 4097}) {
+        const size_t bi = old_up8(batch * I), lc = 5 * bi, pc = lc + 8, tr = pc + batch * D, buf = tr + batch * MCQ_IQP_TRACE * D;
+        expect_layout("iqp", iqp_layout(batch), buf + 2 * bi, {0, bi, 2 * bi, 3 * bi, 4 * bi, lc, pc, tr, buf, buf + bi}, {AI, AI, AI, AI, AI, AI, AD, AD, AI, AI});
+        for (size_t nmax : {3, 7, 128, 2128}) {
+            const size_t e = batch * nmax;
+            expect_layout("iqp_set", iqp_set_layout(e), e * 6 * D, {0, e * 4 * D}, {AD, AD});
+            expect_layout("iqp_pin", iqp_pin_layout(e, batch), e * 6 * D + bi, {0, e * 4 * D, e * 6 * D}, {AD, AD, AI});
         }
     }
     // mcq_points_in_path_device

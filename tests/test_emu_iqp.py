@@ -63,6 +63,14 @@ def test_handle_history(emu_lib):
     ck.check_handle_history(lambda: engine.Engine(0, lib_path=emu_lib))
 
 
+def test_resident_entry_on_own_buffers(emu):
+    ck.check_resident_entry(emu)
+
+
+def test_buffer_growth(emu_lib):
+    ck.check_buffer_growth(lambda: engine.Engine(0, lib_path=emu_lib))
+
+
 def test_report(emu):
     """The worst deviation per family and quantity next to its guard (what the interpreter achieves; the GPU file prints its own)."""
     print(WORST.report("IQP loop on the interpreter", "deviation"))

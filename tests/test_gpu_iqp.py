@@ -59,6 +59,14 @@ def test_handle_history():
     ck.check_handle_history(lambda: engine.Engine(0))
 
 
+def test_resident_entry_on_own_buffers(gpu_engine):
+    ck.check_resident_entry(gpu_engine)
+
+
+def test_buffer_growth():
+    ck.check_buffer_growth(lambda: engine.Engine(0))
+
+
 def test_report(gpu_engine, request):
     """Last in the file: the worst deviation per family and quantity next to the guard it was held to, past pytest's capture into the log."""
     assert WORST.w, "no comparison has run"

@@ -1,5 +1,5 @@
 """The host side of csrc/mcq_api.hip without a GPU and without an interpreter process: tests/layout_check.cpp compiles the translation unit into a
-stand-alone program under AddressSanitizer and UBSan and holds the scratch layouts (the Arena and the six *_layout functions) to the formulas the
+stand-alone program under AddressSanitizer and UBSan and holds the scratch layouts (the Arena and the *_layout functions) to the formulas the
 entries carried before, and the structural scan of mcq_les_scalings / mcq_les_scalings_open to its return codes and messages on 1 and 3 threads.
 The kernels the translation unit names are taken from the SIMT interpreter's library; none is launched."""
 import os
