@@ -113,6 +113,7 @@ struct mcq_handle {
     Scratch fgen;                       // mcq_points_in_path_device / mcq_friction_gen_device: polygons, kept vertices, contours, their counts
     Scratch fgen_pts;                   // mcq_friction_gen_device: the grid points' flags and the blocks' counts (sized after the boundaries' launch)
     Scratch mintime;                    // mcq_mintime_eval_device: the intervals' times and energies [batch][nmax] each, where the caller takes none
+    Scratch mtstep;                     // mcq_mintime_step_device: the factor and the residual vectors (mcq_mintime_step_bytes per problem)
     Scratch iqp;                        // mcq_iqp_device: its bookkeeping per track; mcq_iqp_batch: its trace, buf and rounds as well (iqp_layout)
     Scratch iqp_set;                    // mcq_iqp_batch: the second set of the double buffer, ring and normals (iqp_set_layout)
     mcq_iqp_round_cb iqp_cb = nullptr;  // mcq_iqp_set_round_callback
@@ -357,7 +358,7 @@ extern "C" void mcq_destroy(mcq_handle* h)
     for (hipEvent_t e : h->cp.slice) if (e) (void)hipEventDestroy(e);
     if (h->cp.in) (void)hipStreamDestroy(h->cp.in);
     if (h->cp.out) (void)hipStreamDestroy(h->cp.out);
-    for (Scratch* s : {&h->vel, &h->bound, &h->fit, &h->spl, &h->ends, &h->fgen, &h->fgen_pts, &h->mintime, &h->iqp, &h->iqp_set}) (void)hipFree(s->p);
+    for (Scratch* s : {&h->vel, &h->bound, &h->fit, &h->spl, &h->ends, &h->fgen, &h->fgen_pts, &h->mintime, &h->mtstep, &h->iqp, &h->iqp_set}) (void)hipFree(s->p);
     if (h->pin) (void)hipHostFree(h->pin);
     for (int k = 0; k < 5; ++k) if (h->ev[k]) (void)hipEventDestroy(h->ev[k]);
     for (int k = 0; k < 2; ++k) if (h->ev_span[k]) (void)hipEventDestroy(h->ev_span[k]);
@@ -1982,6 +1983,51 @@ extern "C" int mcq_mintime_hessvec_device(mcq_handle* h, const mcq_mintime_data*
     HIP_TRY(hipSetDevice(h->device));
     M.hblocks_in = hblocks; M.v = v; M.nvec = nvec; M.y = y_out;
     hipLaunchKernelGGL(mcq_mintime_hessvec_kernel, dim3(((unsigned)M.nwmax + 255) / 256, data->batch), dim3(256), 0, compute_stream(h), M);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---- the regularised primal-dual Newton step from the resident blocks (include/mcq.h; csrc/mcq_mtstep.inc) ----
+extern "C" int mcq_mintime_step_bytes(int nmax, const mcq_mintime_opts* opts, int nvec, size_t* bytes_per_problem)
+{
+    if (nmax < 2 || nvec <= 0 || !bytes_per_problem || mintime_opts_bad(opts) || (long long)nmax * 64 + 64 > 0x7fffffffLL) {
+        g_err = "mcq_mintime_step_bytes: bad argument";
+        return MCQ_E_ARG;
+    }
+    const int nw = 5 + 24 * nmax, ng = mcq_mt_ng(nmax, opts->safe_traj ? 1 : 0, opts->limit_energy ? 1 : 0);
+    *bytes_per_problem = mcq_mts_work(nmax, nvec, nw, ng) * sizeof(double);
+    return 0;
+}
+
+extern "C" long long mcq_mintime_step_workspace(mcq_handle* h) { return h ? (long long)h->mtstep.bytes : 0; }
+
+// (reads n_list alone of the launch's arrays, as mcq_mintime_hessvec_device does)
+extern "C" int mcq_mintime_step_device(mcq_handle* h, const mcq_mintime_data* data, const mcq_mintime_opts* opts, const double* hblocks,
+                                       const double* blocks, const double* grad_energy, const double* dw, const double* dg, const double* rhs,
+                                       int nvec, int refine, double* sol_out, double* res_out, int* inertia_out, int* status_out)
+{
+    McqMintime M;
+    if (int rc = mintime_record("mcq_mintime_step_device", h, data, opts, false, M)) return rc;
+    if (!hblocks || !blocks || (opts->limit_energy && !grad_energy) || !dw || !dg || !rhs || nvec <= 0 || refine < 0 || !sol_out || !res_out ||
+        !inertia_out || !status_out) {
+        g_err = "mcq_mintime_step_device: bad argument";
+        return MCQ_E_ARG;
+    }
+    if ((long long)nvec * ((long long)M.nwmax + M.ngmax) > 0x7fffffffLL) {
+        g_err = "mcq_mintime_step_device: more right-hand sides than one launch holds";
+        return MCQ_E_TOO_LARGE;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    McqMtStep S;
+    memset(&S, 0, sizeof(S));
+    S.batch = data->batch; S.nmax = data->nmax; S.n_list = data->n_list;
+    S.safe = opts->safe_traj ? 1 : 0; S.energy = opts->limit_energy ? 1 : 0; S.nwmax = M.nwmax; S.ngmax = M.ngmax; S.nvec = nvec; S.refine = refine;
+    S.hblocks = hblocks; S.blocks = blocks; S.grad_energy = grad_energy; S.dw = dw; S.dg = dg; S.rhs = rhs;
+    S.sol = sol_out; S.res = res_out; S.inertia = inertia_out; S.status = status_out;
+    S.work_per = mcq_mts_work(S.nmax, nvec, S.nwmax, S.ngmax);
+    if (int rc = grow(h, h->mtstep, (size_t)data->batch * S.work_per * sizeof(double))) return rc;
+    S.work = (double*)h->mtstep.p;
+    hipLaunchKernelGGL(mcq_mintime_step_kernel, dim3(data->batch), dim3(256), 0, compute_stream(h), S);
     HIP_TRY(hipGetLastError());
     return 0;
 }

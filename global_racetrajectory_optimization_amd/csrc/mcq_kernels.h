@@ -569,6 +569,26 @@ __global__ void mcq_mintime_jac_kernel(McqMintime M);
 __global__ void mcq_mintime_kkt_kernel(McqMintime M);
 __global__ void mcq_mintime_hess_kernel(McqMintime M);
 __global__ void mcq_mintime_hessvec_kernel(McqMintime M);
+/* ---- the regularised primal-dual Newton step from the resident blocks (mcq_mintime_step_device; csrc/mcq_mtstep.inc): a workgroup per problem,
+ *      a front of 94 per interval -- 57 pivots, a Schur complement of 37 passed on -- in LDS; the factor kept per interval is the front's 94 x 57
+ *      panel, and once per problem the last 37 x 37; behind them one residual vector per right-hand side. ---- */
+#define MCQ_MTS_PANEL (94 * 57)
+#define MCQ_MTS_LAST (37 * 37)
+struct McqMtStep {
+    int batch, nmax;
+    const int* n_list;
+    int safe, energy, nwmax, ngmax, nvec, refine;
+    const double *hblocks, *blocks, *grad_energy, *dw, *dg, *rhs;
+    double *sol, *res;
+    int *inertia, *status;
+    double* work;            // [batch][work_per]
+    size_t work_per;         // doubles per problem: nmax MCQ_MTS_PANEL + MCQ_MTS_LAST + nvec (nwmax + ngmax)
+};
+__host__ __device__ inline size_t mcq_mts_work(int nmax, int nvec, int nwmax, int ngmax)
+{
+    return (size_t)nmax * MCQ_MTS_PANEL + MCQ_MTS_LAST + (size_t)nvec * ((size_t)nwmax + ngmax);
+}
+__global__ void mcq_mintime_step_kernel(McqMtStep S);
 
 __global__ void mcq_fgen_bounds_kernel(McqFgen G);
 __global__ void mcq_fgen_mask_kernel(McqFgen G);

@@ -3997,6 +3997,8 @@ __global__ void __launch_bounds__(MCQ_NT) mcq_spline_finish_kernel(McqSpline S)
 #include "mcq_fgen.inc"
 // (and for mcq_mintime.inc: the minimum-time NLP as functions of a decision vector)
 #include "mcq_mintime.inc"
+// (and for mcq_mtstep.inc: the primal-dual Newton step from the blocks those entries leave resident)
+#include "mcq_mtstep.inc"
 
 __global__ void __launch_bounds__(MCQ_NT) mcq_min_width_kernel(int nmax, const int* n_list, double* ref_all, double min_width, int* changed_out)
 {

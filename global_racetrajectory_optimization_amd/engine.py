@@ -19,7 +19,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB = os.path.join(_HERE, "csrc", "libmcq.so")
 
 STATUS_OK, STATUS_INFEASIBLE, STATUS_NOT_PD, STATUS_ITER_CAP, STATUS_BAD_INPUT, STATUS_KAPPA_INFEASIBLE, \
-    STATUS_KAPPA_ACTIVE, STATUS_RING_OVERFLOW, STATUS_KAPPA_NO_SLOT = range(9)
+    STATUS_KAPPA_ACTIVE, STATUS_RING_OVERFLOW, STATUS_KAPPA_NO_SLOT, STATUS_SINGULAR = range(10)
 
 _dp = ctypes.POINTER(ctypes.c_double)
 _ip = ctypes.POINTER(ctypes.c_int)
@@ -233,6 +233,9 @@ _ABI = {
     "mcq_mintime_kkt_device": (_ci, [_vp, _P(McqMintimeData), _P(McqMintimeOpts), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mcq_mintime_hess_device": (_ci, [_vp, _P(McqMintimeData), _P(McqMintimeOpts), _vp, _vp, _vp]),
     "mcq_mintime_hessvec_device": (_ci, [_vp, _P(McqMintimeData), _P(McqMintimeOpts), _vp, _vp, _ci, _vp]),
+    "mcq_mintime_step_bytes": (_ci, [_ci, _P(McqMintimeOpts), _ci, _P(_sz)]),
+    "mcq_mintime_step_workspace": (ctypes.c_longlong, [_vp]),
+    "mcq_mintime_step_device": (_ci, [_vp, _P(McqMintimeData), _P(McqMintimeOpts), _vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _vp]),
 }
 EXPORTED_SYMBOLS = tuple(_ABI)
 
@@ -1686,6 +1689,65 @@ class Engine:
             self.mintime_hess_device(data, opts, dev.up(lg), None if sg is None else dev.up(sg), d_h)
             self.mintime_hessvec_device(data, opts, d_h, dev.up(vv), nvec, d_y)
             return dict(y=dev.get(d_y), hblocks=dev.get(d_h), N=Ns)
+
+    # ---- the regularised primal-dual Newton step from the resident blocks (include/mcq.h; mintime.kkt_matrix assembles the same matrix) ----
+    def mintime_step_bytes(self, nmax, nvec=1, **opt_kw):
+        """mcq_mintime_step_bytes: the workspace of mcq_mintime_step_device per problem, in bytes."""
+        out = ctypes.c_size_t(0)
+        self._check(self.lib.mcq_mintime_step_bytes(int(nmax), ctypes.byref(self.mintime_opts(**opt_kw)), int(nvec), ctypes.byref(out)),
+                    "mcq_mintime_step_bytes")
+        return int(out.value)
+
+    def mintime_step_workspace(self):
+        """The bytes the handle holds for mcq_mintime_step_device now (it grows, never shrinks)."""
+        return int(self.lib.mcq_mintime_step_workspace(self.h))
+
+    def mintime_step_device(self, data, opts, d_hblocks, d_blocks, d_grad_energy, d_dw, d_dg, d_rhs, nvec, refine, d_sol, d_res, d_inertia, d_status):
+        """mcq_mintime_step_device on device pointers: d_hblocks, d_blocks [batch][nmax][33][33], d_grad_energy [batch][5 + 24 nmax] or None (read
+        with limit_energy only), d_dw [batch][5 + 24 nmax], d_dg [batch][ng of nmax], d_rhs and d_sol [batch][nvec][nw + ng of nmax], d_res
+        [batch][nvec], d_inertia [batch][3] and d_status [batch] int32.  Asynchronous."""
+        self._check(self.lib.mcq_mintime_step_device(self.h, ctypes.byref(data), ctypes.byref(opts), d_hblocks, d_blocks, d_grad_energy or None, d_dw,
+                                                     d_dg, d_rhs, int(nvec), int(refine), d_sol, d_res, d_inertia, d_status),
+                    "mcq_mintime_step_device")
+
+    @staticmethod
+    def _mintime_step_pad(Ns, ngs, nw, ng, dw, dg, rhs):
+        """the diagonals and right-hand sides of every problem (dw [nw_k], dg [ng_k], rhs [nvec, nw_k + ng_k]: w part, then multiplier part) as
+        padded arrays [batch, nw], [batch, ng], [batch, nvec, nw + ng] with the multiplier part at nw"""
+        B = len(Ns)
+        rs = [np.atleast_2d(np.asarray(q, dtype=np.float64)) for q in rhs]
+        nvec = rs[0].shape[0] if rs else 0
+        pw, pg, pr = np.zeros((B, nw)), np.zeros((B, ng)), np.zeros((B, max(nvec, 1), nw + ng))
+        if len(rs) != B or len(dw) != B or len(dg) != B:
+            raise ValueError("mintime_step_batch: dw, dg and rhs must hold one entry per problem")
+        for b in range(B):
+            nwb, ngb = 5 + 24 * int(Ns[b]), int(ngs[b])
+            a, c = np.asarray(dw[b], dtype=np.float64), np.asarray(dg[b], dtype=np.float64)
+            if a.shape != (nwb,) or c.shape != (ngb,) or rs[b].shape != (nvec, nwb + ngb):
+                raise ValueError("mintime_step_batch: dw must hold nw, dg ng and rhs [nvec, nw + ng] values of its problem, the same nvec for all")
+            pw[b, :nwb], pg[b, :ngb] = a, c
+            pr[b, :, :nwb], pr[b, :, nw:nw + ngb] = rs[b][:, :nwb], rs[b][:, nwb:]
+        return pw, pg, pr, nvec
+
+    def mintime_step_batch(self, problems, lam_g, dw, dg, rhs, sigma=None, refine=2, nmax=None, **opt_kw):
+        """The Newton step of every problem at its w and lam_g: Jacobian -> Hessian -> mcq_mintime_step_device chained on resident blocks.  dw [nw_k],
+        dg [ng_k] and rhs [nvec, nw_k + ng_k] per problem (the same nvec for all).  Returns sol [batch, nvec, nw + ng of nmax] (the multiplier part
+        at nw_max; mintime.step_of splits it), res [batch, nvec], inertia [batch, 3], status [batch], and the blocks, hblocks and grad_energy used."""
+        opts = self.mintime_opts(**opt_kw)
+        with self.scope() as dev:
+            data, Ns, nmax = self._mintime_up(dev, problems, opts, nmax, True)
+            B, (nw, ng) = len(Ns), self.mintime_sizes(nmax, opts)
+            ngs = np.array([self.mintime_sizes(int(n), opts)[1] for n in Ns])
+            lg, sg = self._mintime_lam(Ns, lam_g, sigma, ng)
+            pw, pg, pr, nvec = self._mintime_step_pad(Ns, ngs, nw, ng, dw, dg, rhs)
+            d_blk, d_gJ, d_gE, d_h = dev.out((B, nmax, MT_BLOCK, MT_BLOCK)), dev.out((B, nw)), dev.out((B, nw)), dev.out((B, nmax, MT_BLOCK, MT_BLOCK))
+            d_sol, d_res = dev.out((B, max(nvec, 1), nw + ng)), dev.out((B, max(nvec, 1)))
+            d_in, d_st = dev.out((B, 3), np.int32), dev.out(B, np.int32)
+            self.mintime_jac_device(data, opts, d_blk, d_gJ, d_gE)
+            self.mintime_hess_device(data, opts, dev.up(lg), None if sg is None else dev.up(sg), d_h)
+            self.mintime_step_device(data, opts, d_h, d_blk, d_gE, dev.up(pw), dev.up(pg), dev.up(pr), nvec, refine, d_sol, d_res, d_in, d_st)
+            return dict(sol=dev.get(d_sol), res=dev.get(d_res), inertia=dev.get(d_in), status=dev.get(d_st), blocks=dev.get(d_blk),
+                        hblocks=dev.get(d_h), grad_energy=dev.get(d_gE), N=Ns, ng=ngs, nw_max=nw)
 
     # ---- friction map generation (include/mcq.h "friction map generation"; the reference's names on top of these: friction.py) -------------
     def contains_points_device(self, paths, vmax, d_v, d_verts, d_radius, count, d_xy, d_inside, d_status, d_contour=None, d_contour_count=None):

@@ -156,6 +156,29 @@ def lagrangian_hessian(out, b=0, triangle="full"):
     return hessian_coo(out["hblocks"][b], int(out["N"][b]), triangle)
 
 
+def kkt_matrix(hblocks, blocks, N, dw, dg, safe_traj=False, grad_energy=None):
+    """The regularised primal-dual matrix of one problem as a scipy.sparse CSC matrix [nw + ng, nw + ng] in the (w, lam_g) numbering that
+    Engine.mintime_step_batch solves with: [[H + diag(dw), J^T], [J, -diag(dg)]], H from hessian_coo, J from jacobian_coo (with grad_energy [>= nw]
+    the energy row is its last row), dw [>= nw] and dg [>= ng] the caller's diagonals."""
+    import scipy.sparse as sp
+    H = hessian_coo(hblocks, N)
+    J = jacobian_coo(blocks, N, safe_traj, grad_energy)
+    ng, nw = J.shape
+    dw, dg = np.asarray(dw, dtype=np.float64)[:nw], np.asarray(dg, dtype=np.float64)[:ng]
+    if dw.shape != (nw,) or dg.shape != (ng,):
+        raise ValueError("kkt_matrix: dw must hold nw = %d entries and dg ng = %d" % (nw, ng))
+    return sp.bmat([[H + sp.diags(dw), J.T], [J, -sp.diags(dg)]], format="csc")
+
+
+def step_of(out, b=0, t=0):
+    """Right-hand side t of problem b of Engine.mintime_step_batch's result as (x_w [nw], x_lam [ng]): the solution without its NaN tails."""
+    N = int(out["N"][b])
+    nw, ng = 5 + 24 * N, int(out["ng"][b])
+    sol = out["sol"][b, t]
+    off = int(out["nw_max"])
+    return sol[:nw].copy(), sol[off:off + ng].copy()
+
+
 def certificate(out, b=0):
     """The KKT maxima of problem b of Engine.mintime_kkt_batch's result as a dictionary."""
     k = out["kkt"][b]

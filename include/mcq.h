@@ -56,9 +56,10 @@ enum {
                                * check_kappa < 0 and the returned point violates a curvature row. */
     MCQ_RING_OVERFLOW = 7,    /* mcq_iqp_device / mcq_iqp_batch only: the re-sampled raceline of an IQP round needs more waypoints than
                                * the buffers hold (nmax / nmax_out) -- not an input error of the QP (that stays MCQ_BAD_INPUT) */
-    MCQ_KAPPA_NO_SLOT = 8     /* returned only on a handle WITHOUT Goldfarb-Idnani slots (rings beyond the byte cap): more than eight problems of
+    MCQ_KAPPA_NO_SLOT = 8,    /* returned only on a handle WITHOUT Goldfarb-Idnani slots (rings beyond the byte cap): more than eight problems of
                                * one launch with more than 120 active curvature rows each.  Everywhere else such problems are solved by the
                                * Goldfarb-Idnani path inside the same kernel, on every entry point */
+    MCQ_SINGULAR = 9          /* mcq_mintime_step_device only: a pivot of the primal-dual matrix's LDL^T is zero or not finite */
 };
 
 /* library-level error codes (negative return values) */
@@ -733,8 +734,8 @@ int mcq_friction_gen_device(mcq_handle* h, int tracks, int nmax, const int* n_li
  * The reference's NLP -- double-track model, nx = 5 states [v, beta, omega_z, n, xi] scaled by [50, 0.5, 1, 5, 1], nu = 4 controls [delta, f_drive,
  * f_brake, gamma_y] scaled by [0.5, 7500, 20000, 5000], Gauss-Legendre collocation of degree 3 over N intervals of a closed track -- as FUNCTIONS of
  * a decision vector w: the constraint vector g, the objective J, the reference's f_sol outputs, the Jacobian of g, the gradients of J and of the
- * energy sum, the KKT residual of a primal-dual point, the Hessian of the Lagrangian and its products with vectors.  No solver step, no
- * factorisation, no powertrain states (pwr_behavior: MCQ_E_ARG), and not tph's nonreg_sampling / calc_head_curv_num: curvature and station steps
+ * energy sum, the KKT residual of a primal-dual point, the Hessian of the Lagrangian and its products with vectors; the Newton step built from
+ * them follows below.  No NLP loop, no powertrain states (pwr_behavior: MCQ_E_ARG), and not tph's nonreg_sampling / calc_head_curv_num: curvature and station steps
  * are inputs.
  *
  * Layouts (csrc/mcq_mintime.inc; mcq_mintime_layout states them as numbers):
@@ -850,6 +851,36 @@ int mcq_mintime_hess_device(mcq_handle* h, const mcq_mintime_data* data, const m
                             double* hblocks_out);
 int mcq_mintime_hessvec_device(mcq_handle* h, const mcq_mintime_data* data, const mcq_mintime_opts* opts, const double* hblocks, const double* v,
                                int nvec, double* y_out);
+
+/* ---- the minimum-time problem: the regularised primal-dual Newton step from the resident blocks (csrc/mcq_mtstep.inc) ----
+ * One linear-algebra entry over the layouts above, what an interior-point or SQP iteration needs per iteration: the solution of
+ *     K [x_w; x_lam] = rhs,    K = [ H + diag(dw)   J^T ; J   -diag(dg) ]
+ * and K's inertia.  H is the sum of the Hessian blocks (overlaps added, block 0's slots 29 .. 32 on U_N-1; the blocks are read as SYMMETRIC, as
+ * mcq_mintime_hess_device emits them), J the Jacobian blocks' existing row slots, the constant periodicity rows (+1 at X_0, -1 at X_N) and, with
+ * limit_energy, the dense row grad_energy -- the matrix mintime.kkt_matrix assembles.  dw [batch][5 + 24 nmax] and dg [batch][ng of nmax] are the
+ * caller's diagonals (barrier and slack terms plus regularisation); any finite value of either sign is taken, the inertia says what came of it.
+ * Signs are the certificate's (L = f + lam_g . g).  It is not an NLP loop: no step length, no barrier update, no inertia correction.
+ *   hblocks, blocks [batch][nmax][33][33]; grad_energy [batch][5 + 24 nmax], read with limit_energy only (NULL otherwise); rhs and sol_out
+ *   [batch][nvec][(5 + 24 nmax) + (ng of nmax)]: the w part at 0, the multiplier part at 5 + 24 nmax.  Of `data` only batch, nmax and n_list are read.
+ * Method: a multifrontal LDL^T WITHOUT pivoting in one static order, a front per interval: front k eliminates U_k-1, X_k, Xc_k, the path rows of
+ *   interval k - 1 and the collocation and continuity rows of interval k -- no row before the variables it reads -- and passes a Schur complement of
+ *   37 on; the lap closes through a border of X_0, U_N-1, the periodicity rows and the energy row, eliminated last.  refine >= 0 steps of
+ *   iterative refinement follow, each the float64 residual of K from the blocks and the factor's correction.  res_out [batch][nvec]: the max-norm
+ *   of the final residual as computed.  inertia_out [batch][3]: positive, negative and zero pivots.
+ * status_out [batch]: MCQ_OK where every pivot is finite and non-zero; MCQ_SINGULAR where one is not -- that problem's solution and residual NaN,
+ *   its inertia counted up to that pivot, which is the one zero; MCQ_BAD_INPUT for an n_list entry outside 2 .. nmax or a non-finite entry of an
+ *   input inside the problem's own extent (its N blocks, nw, ng entries) -- solution and residual NaN, inertia -1.  No other problem is affected.
+ *   Outputs are always overwritten; entries past a problem's own nw / ng are NaN; inputs past them are not read.  A problem's bits depend on
+ *   its own N and data alone -- not on the launch's company, the batch order, nmax, nvec or the buffers' width.
+ * mcq_mintime_step_bytes (host, pure): the workspace per problem -- per interval the front's 94 x 57 panel of the factor, once the last 37 x 37,
+ *   and one residual vector per right-hand side; the handle keeps batch times that between calls (mcq_mintime_step_workspace: what it holds now).
+ * MCQ_E_ARG: nvec <= 0, refine < 0, NULL where an array is required, and the option refusals above; MCQ_E_TOO_LARGE: as the entries above, or
+ *   nvec times the vector's length beyond 2^31 - 1.  DEVICE pointers; asynchronous on the handle's stream. */
+int mcq_mintime_step_bytes(int nmax, const mcq_mintime_opts* opts, int nvec, size_t* bytes_per_problem);
+long long mcq_mintime_step_workspace(mcq_handle* h);
+int mcq_mintime_step_device(mcq_handle* h, const mcq_mintime_data* data, const mcq_mintime_opts* opts, const double* hblocks, const double* blocks,
+                            const double* grad_energy, const double* dw, const double* dg, const double* rhs, int nvec, int refine,
+                            double* sol_out, double* res_out, int* inertia_out, int* status_out);
 
 /* Host-buffer entry for a UNIFORM batch (every track n waypoints): reftrack [batch][n][4], normvec [batch][n][2] or NULL,
  * scaling [batch][n] or NULL in host memory, results to host memory.  One asynchronous copy per array straight from / to the
