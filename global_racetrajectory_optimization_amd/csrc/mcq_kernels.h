@@ -562,6 +562,68 @@ struct McqMintime {
 };
 __host__ __device__ inline int mcq_mt_ng(int N, int safe, int energy) { return N * (27 + 2 * safe) + 4 * (N - 1) + 5 + energy; }
 __host__ __device__ inline int mcq_mt_row0(int k, int safe) { return k * (27 + 2 * safe) + (k > 0 ? 4 * (k - 1) : 0); }
+/* THE NLP'S MAPS, ONCE (tests/layout_check.cpp holds them to a brute-force statement).  An interval has 33 ROW SLOTS: 0 .. 26 always, 27 .. 30 (the
+ * actuator rows) from k = 1 on, 31 and 32 (the safe pair) with safe_traj alone; the rows of g are the present slots in rising order, interval after
+ * interval from mcq_mt_row0.  A block has 33 COLUMN SLOTS: 0 .. 28 are w[24 k ..], 29 .. 32 are U_k-1. */
+#define MCQ_MT_ROWS_ALWAYS 27   // the slots below exist in every interval, each at its own number behind mcq_mt_row0: a hot loop takes them without asking
+// row slot -> its offset behind mcq_mt_row0(k, safe), or -1 where the slot is absent (below slot 31 a present slot's offset is the slot itself)
+__host__ __device__ inline int mcq_mt_row_off(int k, int safe, int slot)
+{
+    if (slot < MCQ_MT_ROWS_ALWAYS) return slot;
+    if (slot < 31) return k > 0 ? slot : -1;
+    return safe ? (k > 0 ? slot : slot - 4) : -1;
+}
+__host__ __device__ inline int mcq_mt_row_of(int k, int safe, int slot)
+{
+    const int off = mcq_mt_row_off(k, safe, slot);
+    return off < 0 ? -1 : mcq_mt_row0(k, safe) + off;
+}
+// row i < mcq_mt_row0(N, safe) of g -> its interval and row slot: interval 0 has 27 + 2 safe rows, every later one 4 more
+__host__ __device__ inline void mcq_mt_slot_of(int i, int safe, int* k, int* slot)
+{
+    const int first = 27 + 2 * safe;
+    *k = i < first ? 0 : 1 + (i - first) / (first + 4);
+    const int off = i - mcq_mt_row0(*k, safe);
+    *slot = *k == 0 && off >= 27 ? off + 4 : off;
+}
+// entry i of w -> the (at most two) blocks kb and column slots cb that hold it, the block at 24 k + slot first; -1 where there is none.  X_k is also
+// in block k - 1 at 24 + c.  U_k is also in the next block at 24 + c: the Jacobian's (wrap false) has a next block for k + 1 < N alone, the
+// Hessian's (wrap true) is block 0 behind the last (the regularisation's cyclic term).  Nothing holds an entry past nw.
+__host__ __device__ inline void mcq_mt_holders(int N, int i, bool wrap, int kb[2], int cb[2])
+{
+    const int k = i / 24, c = i - 24 * k;
+    kb[0] = kb[1] = cb[0] = cb[1] = -1;
+    if (N == 0 || i >= 5 + 24 * N) return;
+    if (c < 5) {
+        if (k < N) { kb[0] = k; cb[0] = c; }
+        if (k >= 1) { kb[1] = k - 1; cb[1] = 24 + c; }
+    } else {
+        kb[0] = k; cb[0] = c;
+        if (c < 9 && (wrap || k + 1 < N)) { kb[1] = k + 1 < N ? k + 1 : 0; cb[1] = 24 + c; }
+    }
+}
+// the entry of w behind column slot `slot` of Hessian block k (slots 29 .. 32 of block 0: U_N-1; the Jacobian's block 0 has none there)
+__host__ __device__ inline int mcq_mt_slot_entry(int N, int k, int slot) { return slot < 29 ? 24 * k + slot : 24 * (k > 0 ? k - 1 : N - 1) + 5 + (slot - 29); }
+// a problem's own sizes: N from n_list (nmax without one), 0 -- and then nw = ng = per = 0 -- outside 2 .. nmax; per is the first periodicity row
+struct McqMtSizes {
+    int N, safe, energy, nw, ng, per;
+};
+__host__ __device__ inline int mcq_mt_intervals(const int* n_list, int nmax, int b)
+{
+    const int n = n_list ? n_list[b] : nmax;
+    return n < 2 || n > nmax ? 0 : n;
+}
+__host__ __device__ inline McqMtSizes mcq_mt_sizes(const int* n_list, int nmax, int b, int safe, int energy)
+{
+    McqMtSizes Z;
+    Z.N = mcq_mt_intervals(n_list, nmax, b);
+    Z.safe = safe ? 1 : 0;
+    Z.energy = energy ? 1 : 0;
+    Z.nw = Z.N ? 5 + 24 * Z.N : 0;
+    Z.ng = Z.N ? mcq_mt_ng(Z.N, Z.safe, Z.energy) : 0;
+    Z.per = Z.N ? mcq_mt_row0(Z.N, Z.safe) : 0;
+    return Z;
+}
 __global__ void mcq_mintime_bounds_kernel(McqMintime M);
 __global__ void mcq_mintime_eval_kernel(McqMintime M);
 __global__ void mcq_mintime_sum_kernel(McqMintime M);

@@ -21,6 +21,14 @@
 // function of its unordered slot pair (so (r, c) and (c, r) carry the same bits), one writer each, no zero-fill pass.  docs/NOTEBOOK.md "Mintime
 // Hessian" records the mappings compiled and their registers.
 //
+// THE STRUCTURE, ONCE: which row of g a row slot of an interval is (and back), which blocks and column slots hold an entry of w, which entry is behind
+// a column slot, and a problem's own sizes are mcq_kernels.h's mcq_mt_row_off / mcq_mt_row_of, mcq_mt_slot_of, mcq_mt_holders, mcq_mt_slot_entry and
+// mcq_mt_sizes (mt_sizes here; mt_intervals for N alone).  A walk over an interval's rows takes the slots in rising order and skips the absent ones
+// (evaluation); the certificate takes the MCQ_MT_ROWS_ALWAYS slots every interval has in a loop of their own and asks the map once per group behind
+// them, which is what keeps it at 128 VGPRs (docs/NOTEBOOK.md "Mintime kernels: the NLP's row, slot and block maps").  The Jacobian and Hessian
+// kernels sit at the end of the register file: they take N from mt_intervals and keep their bodies; the Hessian kernel's k > 0 / safe tests stay by
+// hand.  The kernels share these indices, not their sums: every dot product stays where it is, spelled as it is (acc += a * b here).
+//
 // CasADi's interpolant is NOT pinned bit for bit: curvature at collocation point j is kappa_cl[k] + tau_j * (kappa_cl[k + 1] - kappa_cl[k]).
 
 #define MT_VS 50.0
@@ -221,11 +229,8 @@ __device__ __forceinline__ void mt_path_rows(const McqMintime& M, const mcq_mint
     }
 }
 
-__device__ __forceinline__ int mt_intervals(const McqMintime& M, int b)
-{
-    const int N = M.d.n_list ? M.d.n_list[b] : M.d.nmax;
-    return N < 2 || N > M.d.nmax ? 0 : N;
-}
+__device__ __forceinline__ int mt_intervals(const McqMintime& M, int b) { return mcq_mt_intervals(M.d.n_list, M.d.nmax, b); }
+__device__ __forceinline__ McqMtSizes mt_sizes(const McqMintime& M, int b) { return mcq_mt_sizes(M.d.n_list, M.d.nmax, b, M.o.safe_traj, M.o.limit_energy); }
 
 // x - x: 0 for a finite x, NaN for every other
 __device__ __forceinline__ double mt_chk(double x) { return x - x; }
@@ -233,7 +238,8 @@ __device__ __forceinline__ double mt_chk(double x) { return x - x; }
 // ---- bounds and the flat guess (:482-507, :563-819): a workgroup per problem ----
 __global__ void __launch_bounds__(MCQ_NT) mcq_mintime_bounds_kernel(McqMintime M)
 {
-    const int b = blockIdx.x, tid = threadIdx.x, N = mt_intervals(M, b), safe = M.o.safe_traj ? 1 : 0;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const McqMtSizes Z = mt_sizes(M, b);
     const mcq_mintime_pars P = M.d.pars[b];
     const size_t n1 = (size_t)M.d.nmax + 1;
     double* w0 = M.w0 + (size_t)b * M.nwmax;
@@ -241,13 +247,12 @@ __global__ void __launch_bounds__(MCQ_NT) mcq_mintime_bounds_kernel(McqMintime M
     double* ubw = M.ubw + (size_t)b * M.nwmax;
     double* lbg = M.lbg + (size_t)b * M.ngmax;
     double* ubg = M.ubg + (size_t)b * M.ngmax;
-    const int nw = N ? 5 + 24 * N : 0, ng = N ? mcq_mt_ng(N, safe, M.o.limit_energy ? 1 : 0) : 0;
     const double half_pi = 0.5 * 3.141592653589793, inf = INFINITY;
     const double delta_min = -P.delta_max / MT_DELTAS, delta_max = P.delta_max / MT_DELTAS, f_drive_max = P.f_drive_max / MT_FDS,
                  f_brake_min = -P.f_brake_max / MT_FBS;
     for (int i = tid; i < M.nwmax; i += MCQ_NT) {
         double g0 = NAN, lo = NAN, hi = NAN;
-        if (i < nw) {
+        if (i < Z.nw) {
             const int k = i / 24, c = i - 24 * k;
             if (c < 5) {
                 const double wr = M.d.w_tr_right_cl[b * n1 + k], wl = M.d.w_tr_left_cl[b * n1 + k];
@@ -266,18 +271,15 @@ __global__ void __launch_bounds__(MCQ_NT) mcq_mintime_bounds_kernel(McqMintime M
         }
         w0[i] = g0; lbw[i] = lo; ubw[i] = hi;
     }
-    const int per = N ? mcq_mt_row0(N, safe) : 0;
     for (int i = tid; i < M.ngmax; i += MCQ_NT) {
         double lo = NAN, hi = NAN;
-        if (i < ng) {
+        if (i < Z.ng) {
             lo = 0.0; hi = 0.0;       // collocation, continuity, roll moment, periodicity
-            if (i >= per) {
-                if (i == per + 5) hi = P.energy_limit;
+            if (i >= Z.per) {
+                if (i == Z.per + 5) hi = P.energy_limit;
             } else {
-                // interval k from the row: interval 0 has 27 + 2 safe rows, every later one 4 more
-                const int first = 27 + 2 * safe, k = i < first ? 0 : 1 + (i - first) / (first + 4);
-                int r = i - mcq_mt_row0(k, safe);
-                if (k == 0 && r >= 27) r += 4;
+                int k, r;
+                mcq_mt_slot_of(i, Z.safe, &k, &r);
                 if (r == 20) { lo = -inf; hi = P.power_max / (MT_FDS * MT_VS); }
                 else if (r >= 21 && r < 25) hi = 1.0;
                 else if (r == 26) lo = -20000.0 / (MT_FDS * MT_FBS);
@@ -349,15 +351,9 @@ __global__ void __launch_bounds__(MCQ_NT) mcq_mintime_eval_kernel(McqMintime M)
         if (!live) return;
         const bool ok = chk == 0.0;
         for (int i = 0; i < 5; ++i) g[15 + i] = ok ? xe[i] - x1[i] : NAN;
-        for (int i = 0; i < 7; ++i) g[20 + i] = ok ? rows[i] : NAN;
-        int at = 27;
-        if (kk > 0) {
-            for (int i = 0; i < 4; ++i) g[27 + i] = ok ? rows[7 + i] : NAN;
-            at = 31;
-        }
-        if (safe) {
-            g[at] = ok ? rows[11] : NAN;
-            g[at + 1] = ok ? rows[12] : NAN;
+        for (int i = 0; i < 13; ++i) {
+            const int off = mcq_mt_row_off(kk, safe, 20 + i);
+            if (off >= 0) g[off] = ok ? rows[i] : NAN;
         }
         const size_t bk = (size_t)b * M.d.nmax + kk;
         const double xs[5] = {MT_VS, MT_BETAS, 1.0, MT_NS, 1.0}, us[4] = {MT_DELTAS, MT_FDS, MT_FBS, MT_GYS};
@@ -384,30 +380,19 @@ __global__ void __launch_bounds__(MCQ_NT) mcq_mintime_eval_kernel(McqMintime M)
     }
 }
 
-// a sum over the workgroup's 256 partial sums in one fixed order: a binary tree in LDS
-__device__ double mt_tree_sum(double v, double* s)
-{
-    const int tid = threadIdx.x;
-    __syncthreads();
-    s[tid] = v;
-    __syncthreads();
-    for (int half = MCQ_NT / 2; half > 0; half >>= 1) {
-        if (tid < half) s[tid] = s[tid] + s[tid + half];
-        __syncthreads();
-    }
-    return s[0];
-}
-
+__device__ __forceinline__ double mt_add(double a, double b) { return a + b; }
 // a maximum that keeps a NaN
 __device__ __forceinline__ double mt_nanmax(double a, double b) { return (a != a || b != b) ? NAN : fmax(a, b); }
-__device__ double mt_tree_max(double v, double* s)
+// the workgroup's 256 partial values combined by OP (mt_add, mt_nanmax) in one fixed order: a binary tree in LDS
+template <double (*OP)(double, double)>
+__device__ double mt_tree(double v, double* s)
 {
     const int tid = threadIdx.x;
     __syncthreads();
     s[tid] = v;
     __syncthreads();
     for (int half = MCQ_NT / 2; half > 0; half >>= 1) {
-        if (tid < half) s[tid] = mt_nanmax(s[tid], s[tid + half]);
+        if (tid < half) s[tid] = OP(s[tid], s[tid + half]);
         __syncthreads();
     }
     return s[0];
@@ -417,14 +402,15 @@ __device__ double mt_tree_max(double v, double* s)
 __global__ void __launch_bounds__(MCQ_NT) mcq_mintime_sum_kernel(McqMintime M)
 {
     __shared__ double s_red[MCQ_NT];
-    const int b = blockIdx.x, tid = threadIdx.x, N = mt_intervals(M, b), safe = M.o.safe_traj ? 1 : 0, nmax = M.d.nmax;
+    const int b = blockIdx.x, tid = threadIdx.x, nmax = M.d.nmax;
+    const McqMtSizes Z = mt_sizes(M, b);
+    const int N = Z.N, ng = Z.ng, per = Z.per;
     const size_t n1 = (size_t)nmax + 1;
     const mcq_mintime_pars P = M.d.pars[b];
     const double* w = M.d.w + (size_t)b * M.nwmax;
     double* g = M.g + (size_t)b * M.ngmax;
     double* dt = M.dt_own + (size_t)b * nmax;
     double* ec = M.ec_own + (size_t)b * nmax;
-    const int ng = N ? mcq_mt_ng(N, safe, M.o.limit_energy ? 1 : 0) : 0, per = N ? mcq_mt_row0(N, safe) : 0;
     double lap = 0.0, en = 0.0, rd = 0.0, rf = 0.0, chk = 0.0;
     for (int k = tid; k < N; k += MCQ_NT) {
         const int kn = k + 1 < N ? k + 1 : 0;
@@ -441,11 +427,11 @@ __global__ void __launch_bounds__(MCQ_NT) mcq_mintime_sum_kernel(McqMintime M)
     }
     if (tid < 5 && N) chk += mt_chk(w[24 * (size_t)N + tid]);
     if (tid == 5 && N) chk += mt_chk(M.d.kappa_cl[b * n1 + N]);
-    lap = mt_tree_sum(lap, s_red);
-    en = mt_tree_sum(en, s_red);
-    rd = mt_tree_sum(rd, s_red);
-    rf = mt_tree_sum(rf, s_red);
-    chk = mt_tree_sum(chk, s_red);
+    lap = mt_tree<mt_add>(lap, s_red);
+    en = mt_tree<mt_add>(en, s_red);
+    rd = mt_tree<mt_add>(rd, s_red);
+    rf = mt_tree<mt_add>(rf, s_red);
+    chk = mt_tree<mt_add>(chk, s_red);
     const bool ok = N && chk == 0.0;
     if (tid == 0) {
         M.J[b] = ok ? lap + P.penalty_F * rf + P.penalty_delta * rd : NAN;
@@ -593,43 +579,35 @@ __global__ void __launch_bounds__(MCQ_NT) mcq_mintime_jac_kernel(McqMintime M)
 __global__ void __launch_bounds__(MCQ_NT) mcq_mintime_kkt_kernel(McqMintime M)
 {
     __shared__ double s_red[MCQ_NT];
-    const int b = blockIdx.x, tid = threadIdx.x, N = mt_intervals(M, b), safe = M.o.safe_traj ? 1 : 0, nmax = M.d.nmax;
-    const int nw = N ? 5 + 24 * N : 0, energy = M.o.limit_energy ? 1 : 0, ng = N ? mcq_mt_ng(N, safe, energy) : 0, per = N ? mcq_mt_row0(N, safe) : 0;
+    const int b = blockIdx.x, tid = threadIdx.x, nmax = M.d.nmax;
+    const McqMtSizes Z = mt_sizes(M, b);
+    const int N = Z.N, per = Z.per;
     const size_t ow = (size_t)b * M.nwmax, og = (size_t)b * M.ngmax;
     const double* blocks = M.blocks_in + (size_t)b * nmax * (MCQ_MT_BLOCK * MCQ_MT_BLOCK);
     const double* lam_g = M.lam_g + og;
     double rmax = 0.0, viol = 0.0, comp = 0.0;
     for (int i = tid; i < M.nwmax; i += MCQ_NT) {
-        if (i >= nw) { M.r[ow + i] = NAN; continue; }
-        int k = i / 24, c = i - 24 * k;
+        if (i >= Z.nw) { M.r[ow + i] = NAN; continue; }
+        const int k = i / 24, c = i - 24 * k;
         double acc = 0.0;
-        // up to two blocks hold the entry: (block, column slot)
-        int kb[2] = {-1, -1}, cb[2] = {0, 0};
-        if (c < 5) {
-            if (k < N) { kb[0] = k; cb[0] = c; }
-            if (k >= 1) { kb[1] = k - 1; cb[1] = 24 + c; }
-        } else if (c < 9) {
-            kb[0] = k; cb[0] = c;
-            if (k + 1 < N) { kb[1] = k + 1; cb[1] = 24 + c; }
-        } else {
-            kb[0] = k; cb[0] = c;
-        }
+        int kb[2], cb[2];
+        mcq_mt_holders(N, i, false, kb, cb);
         for (int t = 0; t < 2; ++t) {
             if (kb[t] < 0) continue;
             const double* blk = blocks + (size_t)kb[t] * (MCQ_MT_BLOCK * MCQ_MT_BLOCK) + cb[t];
-            const int row0 = mcq_mt_row0(kb[t], safe);
-            for (int r = 0; r < 27; ++r) acc += blk[r * MCQ_MT_BLOCK] * lam_g[row0 + r];
-            int at = 27;
-            if (kb[t] > 0) {
-                for (int r = 27; r < 31; ++r) acc += blk[r * MCQ_MT_BLOCK] * lam_g[row0 + r];
-                at = 31;
-            }
-            if (safe)
-                for (int r = 0; r < 2; ++r) acc += blk[(31 + r) * MCQ_MT_BLOCK] * lam_g[row0 + at + r];
+            const double* lk = lam_g + mcq_mt_row0(kb[t], Z.safe);
+            for (int r = 0; r < MCQ_MT_ROWS_ALWAYS; ++r) acc += blk[r * MCQ_MT_BLOCK] * lk[r];
+            // (the actuator rows 27 .. 30 are there together or not at all, the safe pair 31, 32 is adjacent: asked once per group -- one loop over
+            // the six slots compiles to 132 VGPRs and 3 waves per SIMD, this to the 128 and 4 it had)
+            if (mcq_mt_row_off(kb[t], Z.safe, 27) >= 0)
+                for (int r = 27; r < 31; ++r) acc += blk[r * MCQ_MT_BLOCK] * lk[r];
+            const int pair = mcq_mt_row_off(kb[t], Z.safe, 31);
+            if (pair >= 0)
+                for (int r = 0; r < 2; ++r) acc += blk[(31 + r) * MCQ_MT_BLOCK] * lk[pair + r];
         }
         if (c < 5 && k == 0) acc += lam_g[per + c];
         if (c < 5 && k == N) acc -= lam_g[per + c];
-        if (energy) acc += M.grad_E_in[ow + i] * lam_g[per + 5];
+        if (Z.energy) acc += M.grad_E_in[ow + i] * lam_g[per + 5];
         const double lx = M.lam_x[ow + i], wi = M.d.w[ow + i], lo = M.lbw_in[ow + i], hi = M.ubw_in[ow + i];
         const double r = M.grad_J_in[ow + i] + acc + lx;
         M.r[ow + i] = r;
@@ -639,16 +617,16 @@ __global__ void __launch_bounds__(MCQ_NT) mcq_mintime_kkt_kernel(McqMintime M)
         if (lx < 0.0 && lo > -INFINITY) comp = mt_nanmax(comp, fabs(lx * (wi - lo)));
         if (lx != lx) comp = NAN;
     }
-    for (int i = tid; i < ng; i += MCQ_NT) {
+    for (int i = tid; i < Z.ng; i += MCQ_NT) {
         const double lg = lam_g[i], gi = M.g_in[og + i], lo = M.lbg_in[og + i], hi = M.ubg_in[og + i];
         viol = mt_nanmax(viol, mt_nanmax(lo - gi, gi - hi));
         if (lg > 0.0 && hi < INFINITY) comp = mt_nanmax(comp, fabs(lg * (hi - gi)));
         if (lg < 0.0 && lo > -INFINITY) comp = mt_nanmax(comp, fabs(lg * (gi - lo)));
         if (lg != lg) comp = NAN;
     }
-    rmax = mt_tree_max(rmax, s_red);
-    viol = mt_tree_max(viol, s_red);
-    comp = mt_tree_max(comp, s_red);
+    rmax = mt_tree<mt_nanmax>(rmax, s_red);
+    viol = mt_tree<mt_nanmax>(viol, s_red);
+    comp = mt_tree<mt_nanmax>(comp, s_red);
     if (tid == 0) {
         M.kkt[3 * (size_t)b] = N ? rmax : NAN;
         M.kkt[3 * (size_t)b + 1] = N ? viol : NAN;
@@ -683,7 +661,8 @@ __global__ void __launch_bounds__(MCQ_MT_HESS_NT) mcq_mintime_hess_kernel(McqMin
     const double* w = M.d.w + (size_t)b * M.nwmax + 24 * (size_t)k;
     // slots 29 .. 32: U_k-1, at k = 0 U_N-1 (the regularisation's wrapped term)
     const double* wu = M.d.w + (size_t)b * M.nwmax + 24 * (size_t)(k > 0 ? k - 1 : N - 1) + 5;
-    const int row0 = mcq_mt_row0(k, safe), at = k > 0 ? 31 : 27;
+    // (this kernel's register allocation is at its limit: its walks over the row slots stay as they were measured, the safe pair's offset from the map)
+    const int row0 = mcq_mt_row0(k, safe), at = mcq_mt_row_off(k, 1, 31);
     const double* lam = M.lam_g + (size_t)b * M.ngmax + row0;
     const double sg = M.sigma ? M.sigma[b] : 1.0;
     const double lam_e = M.o.limit_energy ? M.lam_g[(size_t)b * M.ngmax + mcq_mt_row0(N, safe) + 5] : 0.0;
@@ -779,34 +758,25 @@ __global__ void __launch_bounds__(MCQ_MT_HESS_NT) mcq_mintime_hess_kernel(McqMin
 // ---- y = H v from the blocks: a lane per entry of w, the block that holds the entry at 24 k + slot first, then the other, slots rising ----
 __global__ void __launch_bounds__(MCQ_NT) mcq_mintime_hessvec_kernel(McqMintime M)
 {
-    const int b = blockIdx.y, N = mt_intervals(M, b), nmax = M.d.nmax, nw = N ? 5 + 24 * N : 0;
+    const int b = blockIdx.y, nmax = M.d.nmax;
+    const McqMtSizes Z = mt_sizes(M, b);
     const int i = blockIdx.x * MCQ_NT + threadIdx.x;
     if (i >= M.nwmax) return;
     const int nn = MCQ_MT_BLOCK * MCQ_MT_BLOCK;
     const double* blocks = M.hblocks_in + (size_t)b * nmax * nn;
-    int k = i / 24, c = i - 24 * k;
-    // up to two blocks hold the entry: (block, slot)
-    int kb[2] = {-1, -1}, cb[2] = {0, 0};
-    if (i >= nw) {
-        // (past the problem's own entries: nothing is read)
-    } else if (c < 5) {
-        if (k < N) { kb[0] = k; cb[0] = c; }
-        if (k >= 1) { kb[1] = k - 1; cb[1] = 24 + c; }
-    } else {
-        kb[0] = k; cb[0] = c;
-        if (c < 9) { kb[1] = k + 1 < N ? k + 1 : 0; cb[1] = 24 + c; }
-    }
+    int kb[2], cb[2];
+    mcq_mt_holders(Z.N, i, true, kb, cb);       // (past the problem's own entries: none, nothing is read)
     for (int t = 0; t < M.nvec; ++t) {
         const double* v = M.v + ((size_t)b * M.nvec + t) * M.nwmax;
         double acc = 0.0;
         for (int s = 0; s < 2; ++s) {
             if (kb[s] < 0) continue;
             const double* row = blocks + (size_t)kb[s] * nn + cb[s] * MCQ_MT_BLOCK;       // (a block is symmetric: the slot's row is its column)
-            const double* vk = v + 24 * (size_t)kb[s];
-            const double* vu = v + 24 * (size_t)(kb[s] > 0 ? kb[s] - 1 : N - 1) + 5;
+            const double* vk = v + mcq_mt_slot_entry(Z.N, kb[s], 0);
+            const double* vu = v + mcq_mt_slot_entry(Z.N, kb[s], 29);
             for (int a = 0; a < 29; ++a) acc += row[a] * vk[a];
             for (int a = 0; a < 4; ++a) acc += row[29 + a] * vu[a];
         }
-        M.y[((size_t)b * M.nvec + t) * M.nwmax + i] = i < nw ? acc : NAN;
+        M.y[((size_t)b * M.nvec + t) * M.nwmax + i] = i < Z.nw ? acc : NAN;
     }
 }

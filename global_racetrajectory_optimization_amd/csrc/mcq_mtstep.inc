@@ -22,6 +22,8 @@
 // entries `lane` and `64 + lane` of the front's vector, the pivots' values travel by __shfl), so up to four right-hand sides share a sweep.
 // REFINEMENT: r = rhs - K x in float64 from the blocks, a lane per unknown in one fixed order (fused multiply-adds), the dense energy row by a tree.
 // Every sum's order depends on the problem's own N alone.
+// THE NLP'S STRUCTURE is mcq_kernels.h's (mcq_mt_row_of, mcq_mt_slot_of, mcq_mt_holders, mcq_mt_slot_entry, mcq_mt_sizes): what is stated here is the
+// front alone -- the positions (mts_var_pos, mts_row_pos), the unknowns behind them (mts_own_unknown, mts_fin_unknown), the diagonals (mts_diag).
 
 #define MTS_OWN 57
 #define MTS_F 94
@@ -29,18 +31,33 @@
 #define MTS_TRI (MTS_F * (MTS_F + 1) / 2)
 #define MTS_ELEMS ((MTS_TRI + MCQ_NT - 1) / MCQ_NT)
 
-struct MtsDims {
-    int N, safe, energy, nw, ng, per, nwmax;
+// the problem's sizes, and where the multiplier part of this launch's [nwmax + ngmax] vectors begins
+struct MtsDims : McqMtSizes {
+    int nwmax;
 };
+// f(i) for every entry i of such a vector that is the problem's own: the w part, then the multiplier part, each spread over the lanes from 0
+template <class F>
+__device__ __forceinline__ void mts_each_own(const MtsDims& D, F f)
+{
+    for (int i = threadIdx.x; i < D.nw; i += MCQ_NT) f(i);
+    for (int i = threadIdx.x; i < D.ng; i += MCQ_NT) f(D.nwmax + i);
+}
 
 __device__ __forceinline__ int mts_tri(int i) { return i * (i + 1) / 2; }
-
-// the entry of the solution vector behind row slot r (20 .. 32) of interval k, or -1 where the slot is absent
-__device__ __forceinline__ int mts_path_row(const MtsDims& D, int k, int r)
+// the row of entry e of a packed lower triangle
+__device__ __forceinline__ int mts_tri_row(int e)
 {
-    if (r < 27) return D.nwmax + mcq_mt_row0(k, D.safe) + r;
-    if (r < 31) return k > 0 ? D.nwmax + mcq_mt_row0(k, D.safe) + r : -1;
-    return D.safe ? D.nwmax + mcq_mt_row0(k, D.safe) + (k > 0 ? 31 : 27) + (r - 31) : -1;
+    int i = (int)((sqrt(8.0 * e + 1.0) - 1.0) * 0.5);
+    while (mts_tri(i + 1) <= e) ++i;
+    while (mts_tri(i) > e) --i;
+    return i;
+}
+
+// the entry of the solution vector behind row slot r of interval k, or -1 where the slot is absent
+__device__ __forceinline__ int mts_row_unknown(const MtsDims& D, int k, int r)
+{
+    const int row = mcq_mt_row_of(k, D.safe, r);
+    return row < 0 ? -1 : D.nwmax + row;
 }
 // the entry behind pivot p (0 .. 56) of front k, or -1 for a placeholder
 __device__ __forceinline__ int mts_own_unknown(const MtsDims& D, int k, int p)
@@ -48,7 +65,7 @@ __device__ __forceinline__ int mts_own_unknown(const MtsDims& D, int k, int p)
     if (p < 4) return k > 0 ? 24 * (k - 1) + 5 + p : -1;
     if (p < 9) return k > 0 ? 24 * k + (p - 4) : -1;
     if (p < 24) return 24 * k + p;
-    if (p < 37) return k > 0 ? mts_path_row(D, k - 1, 20 + (p - 24)) : -1;
+    if (p < 37) return k > 0 ? mts_row_unknown(D, k - 1, 20 + (p - 24)) : -1;
     return D.nwmax + mcq_mt_row0(k, D.safe) + (p - 37);
 }
 // the entry behind position p (57 .. 93) of the LAST front, or -1 for a placeholder
@@ -56,7 +73,7 @@ __device__ __forceinline__ int mts_fin_unknown(const MtsDims& D, int p)
 {
     if (p < 61) return -1;
     if (p < 66) return 24 * D.N + (p - 61);
-    if (p < 79) return mts_path_row(D, D.N - 1, 20 + (p - 66));
+    if (p < 79) return mts_row_unknown(D, D.N - 1, 20 + (p - 66));
     if (p < 84) return p - 79;
     if (p < 88) return 24 * (D.N - 1) + 5 + (p - 84);
     if (p < 93) return D.nwmax + D.per + (p - 88);
@@ -72,7 +89,6 @@ __device__ __forceinline__ int mts_var_pos(const MtsDims& D, int k, int s)
     return k > 0 ? s - 29 : 84 + (s - 29);
 }
 __device__ __forceinline__ int mts_row_pos(int r) { return r < 20 ? 37 + r : 66 + (r - 20); }
-__device__ __forceinline__ bool mts_row_present(const MtsDims& D, int k, int r) { return r < 27 || (r < 31 ? k > 0 : D.safe != 0); }
 
 // what front k adds on the diagonal at position p beside the blocks' entries and what it inherits
 __device__ __forceinline__ double mts_diag(const MtsDims& D, int k, int p, const double* dw, const double* dg)
@@ -81,7 +97,7 @@ __device__ __forceinline__ double mts_diag(const MtsDims& D, int k, int p, const
     if (p < 24) { const int u = mts_own_unknown(D, k, p); return u < 0 ? 1.0 : dw[u]; }
     if (p < 37) return k == 0 ? 1.0 : 0.0;
     if (p < 57) return -dg[mcq_mt_row0(k, D.safe) + (p - 37)];
-    if (p >= 66 && p < 79) { const int u = mts_path_row(D, k, 20 + (p - 66)); return u < 0 ? 1.0 : -dg[u - D.nwmax]; }
+    if (p >= 66 && p < 79) { const int u = mts_row_unknown(D, k, 20 + (p - 66)); return u < 0 ? 1.0 : -dg[u - D.nwmax]; }
     if (!last) return 0.0;
     const int u = mts_fin_unknown(D, p);
     return u < 0 ? 1.0 : (u < D.nwmax ? dw[u] : -dg[u - D.nwmax]);
@@ -106,7 +122,7 @@ __device__ bool mts_eliminate(double* F, const MtsLane& L, const MtsDims& D, int
     for (int j = j0; j < j1; ++j) {
         const double d = F[mts_tri(j) + j];
         if (!(d - d == 0.0) || d == 0.0) return false;
-        const bool placeholder = j < MTS_OWN ? (j < 24 || j >= 37 ? mts_own_unknown(D, k, j) < 0 : (k == 0 || mts_path_row(D, k - 1, 20 + (j - 24)) < 0))
+        const bool placeholder = j < MTS_OWN ? (j < 24 || j >= 37 ? mts_own_unknown(D, k, j) < 0 : (k == 0 || mts_row_unknown(D, k - 1, 20 + (j - 24)) < 0))
                                              : mts_fin_unknown(D, j) < 0;
         if (!placeholder) inertia[d > 0.0 ? 0 : 1] += 1;
         const double rinv = 1.0 / d;
@@ -234,23 +250,15 @@ __device__ void mts_residual(const McqMtStep& S, const MtsDims& D, int b, const 
         for (int i = tid; i < D.nw; i += MCQ_NT) {
             const int k = i / 24, c = i - 24 * k;
             // up to two blocks hold the entry: (block of H, slot), (block of J, slot)
-            int hk[2] = {-1, -1}, hs[2] = {0, 0}, jk[2] = {-1, -1}, js[2] = {0, 0};
-            if (c < 5) {
-                if (k < N) { hk[0] = jk[0] = k; hs[0] = js[0] = c; }
-                if (k >= 1) { hk[1] = jk[1] = k - 1; hs[1] = js[1] = 24 + c; }
-            } else {
-                hk[0] = jk[0] = k; hs[0] = js[0] = c;
-                if (c < 9) {
-                    hk[1] = k + 1 < N ? k + 1 : 0; hs[1] = 24 + c;
-                    if (k + 1 < N) { jk[1] = k + 1; js[1] = 24 + c; }
-                }
-            }
+            int hk[2], hs[2], jk[2], js[2];
+            mcq_mt_holders(N, i, true, hk, hs);
+            mcq_mt_holders(N, i, false, jk, js);
             double acc = dw[i] * xv[i];
             for (int s = 0; s < 2; ++s) {
                 if (hk[s] < 0) continue;
                 const double* row = hb + (size_t)hk[s] * nn + hs[s] * MCQ_MT_BLOCK;
-                const double* vk = xv + 24 * (size_t)hk[s];
-                const double* vu = xv + 24 * (size_t)(hk[s] > 0 ? hk[s] - 1 : N - 1) + 5;
+                const double* vk = xv + mcq_mt_slot_entry(N, hk[s], 0);
+                const double* vu = xv + mcq_mt_slot_entry(N, hk[s], 29);
                 for (int a = 0; a < 29; ++a) acc = fma(row[a], vk[a], acc);
                 for (int a = 0; a < 4; ++a) acc = fma(row[29 + a], vu[a], acc);
             }
@@ -258,14 +266,11 @@ __device__ void mts_residual(const McqMtStep& S, const MtsDims& D, int b, const 
                 if (jk[s] < 0) continue;
                 const double* col = jb + (size_t)jk[s] * nn + js[s];
                 const double* lk = lam + mcq_mt_row0(jk[s], D.safe);
-                for (int rr = 0; rr < 27; ++rr) acc = fma(col[rr * MCQ_MT_BLOCK], lk[rr], acc);
-                int at = 27;
-                if (jk[s] > 0) {
-                    for (int rr = 27; rr < 31; ++rr) acc = fma(col[rr * MCQ_MT_BLOCK], lk[rr], acc);
-                    at = 31;
+                for (int rr = 0; rr < MCQ_MT_ROWS_ALWAYS; ++rr) acc = fma(col[rr * MCQ_MT_BLOCK], lk[rr], acc);
+                for (int rr = MCQ_MT_ROWS_ALWAYS; rr < MCQ_MT_BLOCK; ++rr) {
+                    const int off = mcq_mt_row_off(jk[s], D.safe, rr);
+                    if (off >= 0) acc = fma(col[rr * MCQ_MT_BLOCK], lk[off], acc);
                 }
-                if (D.safe)
-                    for (int rr = 0; rr < 2; ++rr) acc = fma(col[(31 + rr) * MCQ_MT_BLOCK], lk[at + rr], acc);
             }
             if (c < 5 && k == 0) acc += lam[D.per + c];
             if (c < 5 && k == N) acc -= lam[D.per + c];
@@ -277,20 +282,19 @@ __device__ void mts_residual(const McqMtStep& S, const MtsDims& D, int b, const 
             if (rv) rv[i] = ri;
             rmax = mt_nanmax(rmax, fabs(ri));
         }
-        const int first = 27 + 2 * D.safe;
         for (int i = tid; i < D.per + 5; i += MCQ_NT) {
             double acc = -(dg[i] * lam[i]);
             if (i >= D.per) {
                 acc += xv[i - D.per] - xv[24 * (size_t)N + (i - D.per)];
             } else {
-                const int k = i < first ? 0 : 1 + (i - first) / (first + 4);
-                int s = i - mcq_mt_row0(k, D.safe);
-                if (k == 0 && s >= 27) s += 4;
+                int k, s;
+                mcq_mt_slot_of(i, D.safe, &k, &s);
                 const double* row = jb + (size_t)k * nn + s * MCQ_MT_BLOCK;
-                const double* vk = xv + 24 * (size_t)k;
+                const double* vk = xv + mcq_mt_slot_entry(N, k, 0);
+                const double* vu = xv + mcq_mt_slot_entry(N, k, 29);
                 for (int a = 0; a < 29; ++a) acc = fma(row[a], vk[a], acc);
-                if (k > 0)
-                    for (int a = 0; a < 4; ++a) acc = fma(row[29 + a], vk[a + 5 - 24], acc);
+                if (k > 0)      // (the Jacobian's block 0 has no slots 29 .. 32)
+                    for (int a = 0; a < 4; ++a) acc = fma(row[29 + a], vu[a], acc);
             }
             const double ri = bv[D.nwmax + i] - acc;
             if (rv) rv[D.nwmax + i] = ri;
@@ -298,7 +302,7 @@ __device__ void mts_residual(const McqMtStep& S, const MtsDims& D, int b, const 
         }
         if (ge) {
             // the dense row: lane t adds its entries in rising order, then the tree
-            const double e = mt_tree_sum(esum, s_red);
+            const double e = mt_tree<mt_add>(esum, s_red);
             if (tid == 0) {
                 const int i = D.per + 5;
                 const double ri = bv[D.nwmax + i] - (e - dg[i] * lam[i]);
@@ -306,10 +310,17 @@ __device__ void mts_residual(const McqMtStep& S, const MtsDims& D, int b, const 
                 rmax = mt_nanmax(rmax, fabs(ri));
             }
         }
-        rmax = mt_tree_max(rmax, s_red);
+        rmax = mt_tree<mt_nanmax>(rmax, s_red);
         if (tid == 0) res[t] = rmax;
     }
     __syncthreads();
+}
+
+// this problem gets no solution (refused, or a pivot failed): NaN in all of its sol and res
+__device__ void mts_no_solution(const McqMtStep& S, double* sol, double* res, size_t stride)
+{
+    for (size_t e = threadIdx.x; e < S.nvec * stride; e += MCQ_NT) sol[e] = NAN;
+    for (int t = threadIdx.x; t < S.nvec; t += MCQ_NT) res[t] = NAN;
 }
 
 // ---- a workgroup per problem: check, factor, solve, refine ----
@@ -319,12 +330,8 @@ __global__ void __launch_bounds__(MCQ_NT) mcq_mintime_step_kernel(McqMtStep S)
     __shared__ double s_aux[MTS_TAIL * MTS_TAIL];  // the Schur complement passed on (703 packed), the last 37 x 37 while solving
     __shared__ double s_red[MCQ_NT];
     const int b = blockIdx.x, tid = threadIdx.x, nmax = S.nmax, nn = MCQ_MT_BLOCK * MCQ_MT_BLOCK;
-    const int Nin = S.n_list ? S.n_list[b] : nmax, N = Nin < 2 || Nin > nmax ? 0 : Nin;
-    MtsDims D;
-    D.N = N; D.safe = S.safe; D.energy = S.energy; D.nwmax = S.nwmax;
-    D.nw = N ? 5 + 24 * N : 0;
-    D.ng = N ? mcq_mt_ng(N, S.safe, S.energy) : 0;
-    D.per = N ? mcq_mt_row0(N, S.safe) : 0;
+    const MtsDims D = {mcq_mt_sizes(S.n_list, nmax, b, S.safe, S.energy), S.nwmax};
+    const int N = D.N;
     const size_t stride = (size_t)S.nwmax + S.ngmax;
     const double* hb = S.hblocks + (size_t)b * nmax * nn;
     const double* jb = S.blocks + (size_t)b * nmax * nn;
@@ -341,33 +348,23 @@ __global__ void __launch_bounds__(MCQ_NT) mcq_mintime_step_kernel(McqMtStep S)
     for (size_t e = tid; e < (size_t)N * nn; e += MCQ_NT) chk += mt_chk(hb[e]) + mt_chk(jb[e]);
     for (int i = tid; i < D.nw; i += MCQ_NT) chk += mt_chk(dw[i]) + (ge ? mt_chk(ge[i]) : 0.0);
     for (int i = tid; i < D.ng; i += MCQ_NT) chk += mt_chk(dg[i]);
-    for (int t = 0; t < S.nvec; ++t) {
-        for (int i = tid; i < D.nw; i += MCQ_NT) chk += mt_chk(rhs[t * stride + i]);
-        for (int i = tid; i < D.ng; i += MCQ_NT) chk += mt_chk(rhs[t * stride + S.nwmax + i]);
-    }
-    chk = mt_tree_sum(chk, s_red);
+    for (int t = 0; t < S.nvec; ++t) mts_each_own(D, [&](int i) { chk += mt_chk(rhs[t * stride + i]); });
+    chk = mt_tree<mt_add>(chk, s_red);
     const bool ok = N && chk == 0.0;
-    // the solution starts as the right-hand side; NaN past the problem's own entries (everywhere for a refused problem)
-    for (int t = 0; t < S.nvec; ++t)
-        for (size_t i = tid; i < stride; i += MCQ_NT) {
-            const bool own = ok && (i < (size_t)D.nw || (i >= (size_t)S.nwmax && i < (size_t)S.nwmax + D.ng));
-            sol[t * stride + i] = own ? rhs[t * stride + i] : NAN;
-        }
+    // NaN past the problem's own entries (everywhere for a refused problem); inside them the solution starts as the right-hand side
+    mts_no_solution(S, sol, res, stride);
     if (!ok) {
-        for (int t = tid; t < S.nvec; t += MCQ_NT) res[t] = NAN;
         if (tid < 3) S.inertia[3 * (size_t)b + tid] = -1;
         if (tid == 0) S.status[b] = MCQ_BAD_INPUT;
         return;
     }
+    __syncthreads();
+    for (int t = 0; t < S.nvec; ++t) mts_each_own(D, [&](int i) { sol[t * stride + i] = rhs[t * stride + i]; });
     // ---- the factorisation ----
     MtsLane L;
 #pragma unroll
     for (int q = 0; q < MTS_ELEMS; ++q) {
-        const int e = tid + MCQ_NT * q;
-        int i = (int)((sqrt(8.0 * e + 1.0) - 1.0) * 0.5);
-        while (mts_tri(i + 1) <= e) ++i;
-        while (mts_tri(i) > e) --i;
-        const int c = e - mts_tri(i);
+        const int e = tid + MCQ_NT * q, i = mts_tri_row(e), c = e - mts_tri(i);
         L.at[q] = e < MTS_TRI ? (mts_tri(i) | (c << 16)) : -1;
         L.tc[q] = mts_tri(c);
     }
@@ -377,10 +374,7 @@ __global__ void __launch_bounds__(MCQ_NT) mcq_mintime_step_kernel(McqMtStep S)
         const bool last = k == N - 1;
         // what the front inherits, its diagonals, the energy row's columns, the periodicity rows' constants
         for (int e = tid; e < MTS_TRI; e += MCQ_NT) {
-            int i = (int)((sqrt(8.0 * e + 1.0) - 1.0) * 0.5);
-            while (mts_tri(i + 1) <= e) ++i;
-            while (mts_tri(i) > e) --i;
-            const int c = e - mts_tri(i);
+            const int i = mts_tri_row(e), c = e - mts_tri(i);
             const int qi = i < 9 ? i : (i >= 24 && i < 37 ? 9 + (i - 24) : (i >= 79 ? 22 + (i - 79) : -1));
             const int qc = c < 9 ? c : (c >= 24 && c < 37 ? 9 + (c - 24) : (c >= 79 ? 22 + (c - 79) : -1));
             double v = k > 0 && qi >= 0 && qc >= 0 ? s_aux[mts_tri(qi) + qc] : 0.0;
@@ -399,7 +393,7 @@ __global__ void __launch_bounds__(MCQ_NT) mcq_mintime_step_kernel(McqMtStep S)
         // block k of J: the row slots that exist against the column slots that exist
         for (int e = tid; e < nn; e += MCQ_NT) {
             const int r = e / MCQ_MT_BLOCK, c = e - MCQ_MT_BLOCK * r;
-            if (!mts_row_present(D, k, r) || (k == 0 && c >= 29)) continue;
+            if (mcq_mt_row_off(k, D.safe, r) < 0 || (k == 0 && c >= 29)) continue;
             const int pr = mts_row_pos(r), pc = mts_var_pos(D, k, c), hi = pr > pc ? pr : pc, lo = pr > pc ? pc : pr;
             s_buf[mts_tri(hi) + lo] += jb[(size_t)k * nn + e];
         }
@@ -420,9 +414,7 @@ __global__ void __launch_bounds__(MCQ_NT) mcq_mintime_step_kernel(McqMtStep S)
             }
         } else {
             for (int e = tid; e < MTS_TAIL * (MTS_TAIL + 1) / 2; e += MCQ_NT) {
-                int i = (int)((sqrt(8.0 * e + 1.0) - 1.0) * 0.5);
-                while (mts_tri(i + 1) <= e) ++i;
-                while (mts_tri(i) > e) --i;
+                const int i = mts_tri_row(e);
                 s_aux[e] = s_buf[mts_tri(MTS_OWN + i) + MTS_OWN + (e - mts_tri(i))];
             }
         }
@@ -436,11 +428,7 @@ __global__ void __launch_bounds__(MCQ_NT) mcq_mintime_step_kernel(McqMtStep S)
     }
     if (!regular) {
         __syncthreads();
-        for (int t = 0; t < S.nvec; ++t) {
-            for (int i = tid; i < D.nw; i += MCQ_NT) sol[t * stride + i] = NAN;
-            for (int i = tid; i < D.ng; i += MCQ_NT) sol[t * stride + S.nwmax + i] = NAN;
-        }
-        for (int t = tid; t < S.nvec; t += MCQ_NT) res[t] = NAN;
+        mts_no_solution(S, sol, res, stride);
         return;
     }
     // ---- solve, refine ----
@@ -448,10 +436,7 @@ __global__ void __launch_bounds__(MCQ_NT) mcq_mintime_step_kernel(McqMtStep S)
     for (int it = 0; it < S.refine; ++it) {
         mts_residual(S, D, b, sol, rhs, rbuf, stride, res, s_red);
         mts_solve(S, D, work, rbuf, stride, s_buf, s_aux);
-        for (int t = 0; t < S.nvec; ++t) {
-            for (int i = tid; i < D.nw; i += MCQ_NT) sol[t * stride + i] += rbuf[t * stride + i];
-            for (int i = tid; i < D.ng; i += MCQ_NT) sol[t * stride + S.nwmax + i] += rbuf[t * stride + S.nwmax + i];
-        }
+        for (int t = 0; t < S.nvec; ++t) mts_each_own(D, [&](int i) { sol[t * stride + i] += rbuf[t * stride + i]; });
         __syncthreads();
     }
     mts_residual(S, D, b, sol, rhs, nullptr, stride, res, s_red);

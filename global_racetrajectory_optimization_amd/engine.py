@@ -310,6 +310,14 @@ def _pad_like(rows, ns, tail=(), nmin=0):
     return out
 
 
+def _pad_last(rows, width, lead=()):
+    """A ragged list of float64 arrays lead + [n_k] as [B] + lead + [width], zeros behind each n_k <= width."""
+    out = np.zeros((len(rows),) + lead + (width,))
+    for k, r in enumerate(rows):
+        out[k, ..., :r.shape[-1]] = r
+    return out
+
+
 def _closed_length(xy):
     """The length of the closed polygon through the rows of xy [n, 2]."""
     return float(np.sum(np.hypot(*np.diff(np.vstack((xy, xy[:1])), axis=0).T)))
@@ -1496,7 +1504,8 @@ class Engine:
     @staticmethod
     def mintime_sizes(nmax, opts):
         """(5 + 24 nmax, ng of nmax): the widths of the w-shaped and g-shaped buffers of a launch."""
-        return 5 + 24 * int(nmax), int(nmax) * (27 + 2 * opts.safe_traj) + 4 * (int(nmax) - 1) + 5 + opts.limit_energy
+        from . import mintime
+        return 5 + 24 * int(nmax), mintime.g_rows(nmax, opts.safe_traj, opts.limit_energy)[1]
 
     @staticmethod
     def mintime_data(batch, nmax, d_n, d_h, d_kappa, d_w_right, d_w_left, d_pars, d_w=None, d_w_mue=None, d_center_dist=None):
@@ -1617,12 +1626,11 @@ class Engine:
         with self.scope() as dev:
             data, Ns, nmax = self._mintime_up(dev, problems, opts, nmax, True)
             B, (nw, ng) = len(Ns), self.mintime_sizes(nmax, opts)
-            lg, lx = np.zeros((B, ng)), np.zeros((B, nw))
-            for b in range(B):
-                vg, vx = np.asarray(lam_g[b], dtype=np.float64), np.asarray(lam_x[b], dtype=np.float64)
-                if vx.shape != (5 + 24 * int(Ns[b]),) or vg.ndim != 1 or vg.shape[0] > ng:
-                    raise ValueError("mintime_kkt_batch: lam_x must hold nw values and lam_g ng values of its problem")
-                lg[b, :vg.shape[0]], lx[b, :vx.shape[0]] = vg, vx
+            bad = "mintime_kkt_batch: lam_x must hold nw values and lam_g ng values of its problem"
+            vx = [np.asarray(lam_x[b], dtype=np.float64) for b in range(B)]
+            if any(q.shape != (5 + 24 * int(n),) for q, n in zip(vx, Ns)):
+                raise ValueError(bad)
+            lg, lx = self._mintime_lam(Ns, lam_g, None, ng, bad)[0], _pad_last(vx, nw)
             bw = [dev.out((B, nw)) for _ in range(3)]
             bg = [dev.out((B, ng)) for _ in range(2)]
             d_g, d_J, d_lap, d_st = dev.out((B, ng)), dev.out(B), dev.out(B), dev.out(B, np.int32)
@@ -1646,17 +1654,14 @@ class Engine:
                     "mcq_mintime_hessvec_device")
 
     @staticmethod
-    def _mintime_lam(Ns, lam_g, sigma, ng):
+    def _mintime_lam(Ns, lam_g, sigma, ng, bad="mintime: lam_g must hold the ng values of its problem"):
         """lam_g (one vector per problem, at most ng values) and sigma (None, or one number per problem) as padded arrays [batch, ng], [batch]"""
         B = len(Ns)
-        lg = np.zeros((B, ng))
-        for b in range(B):
-            vg = np.asarray(lam_g[b], dtype=np.float64)
-            if vg.ndim != 1 or vg.shape[0] > ng:
-                raise ValueError("mintime: lam_g must hold the ng values of its problem")
-            lg[b, :vg.shape[0]] = vg
+        vg = [np.asarray(lam_g[b], dtype=np.float64) for b in range(B)]
+        if any(q.ndim != 1 or q.shape[0] > ng for q in vg):
+            raise ValueError(bad)
         sg = None if sigma is None else np.ascontiguousarray(np.broadcast_to(np.asarray(sigma, dtype=np.float64), (B,)))
-        return lg, sg
+        return _pad_last(vg, ng), sg
 
     def mintime_hess_batch(self, problems, lam_g, sigma=None, nmax=None, **opt_kw):
         """The Hessian of the Lagrangian sigma J + lam_g . g in interval blocks hblocks [batch, nmax, 33, 33] (mcq_mintime_hess_device; the slots and the
@@ -1680,11 +1685,9 @@ class Engine:
             lg, sg = self._mintime_lam(Ns, lam_g, sigma, ng)
             vs = [np.atleast_2d(np.asarray(q, dtype=np.float64)) for q in v]
             nvec = vs[0].shape[0] if vs else 0
-            vv = np.zeros((B, max(nvec, 1), nw))
-            for b in range(B):
-                if len(vs) != B or vs[b].shape != (nvec, 5 + 24 * int(Ns[b])):
-                    raise ValueError("mintime_hessvec_batch: v must hold [nvec, nw] values per problem, the same nvec for all")
-                vv[b, :, :vs[b].shape[1]] = vs[b]
+            if len(vs) != B or any(q.shape != (nvec, 5 + 24 * int(n)) for q, n in zip(vs, Ns)):
+                raise ValueError("mintime_hessvec_batch: v must hold [nvec, nw] values per problem, the same nvec for all")
+            vv = _pad_last(vs, nw, (max(nvec, 1),))
             d_h, d_y = dev.out((B, nmax, MT_BLOCK, MT_BLOCK)), dev.out((B, max(nvec, 1), nw))
             self.mintime_hess_device(data, opts, dev.up(lg), None if sg is None else dev.up(sg), d_h)
             self.mintime_hessvec_device(data, opts, d_h, dev.up(vv), nvec, d_y)
@@ -1717,17 +1720,15 @@ class Engine:
         B = len(Ns)
         rs = [np.atleast_2d(np.asarray(q, dtype=np.float64)) for q in rhs]
         nvec = rs[0].shape[0] if rs else 0
-        pw, pg, pr = np.zeros((B, nw)), np.zeros((B, ng)), np.zeros((B, max(nvec, 1), nw + ng))
         if len(rs) != B or len(dw) != B or len(dg) != B:
             raise ValueError("mintime_step_batch: dw, dg and rhs must hold one entry per problem")
-        for b in range(B):
-            nwb, ngb = 5 + 24 * int(Ns[b]), int(ngs[b])
-            a, c = np.asarray(dw[b], dtype=np.float64), np.asarray(dg[b], dtype=np.float64)
-            if a.shape != (nwb,) or c.shape != (ngb,) or rs[b].shape != (nvec, nwb + ngb):
-                raise ValueError("mintime_step_batch: dw must hold nw, dg ng and rhs [nvec, nw + ng] values of its problem, the same nvec for all")
-            pw[b, :nwb], pg[b, :ngb] = a, c
-            pr[b, :, :nwb], pr[b, :, nw:nw + ngb] = rs[b][:, :nwb], rs[b][:, nwb:]
-        return pw, pg, pr, nvec
+        nws = [5 + 24 * int(n) for n in Ns]
+        a, c = [np.asarray(q, dtype=np.float64) for q in dw], [np.asarray(q, dtype=np.float64) for q in dg]
+        if any(a[b].shape != (nws[b],) or c[b].shape != (ngs[b],) or rs[b].shape != (nvec, nws[b] + ngs[b]) for b in range(B)):
+            raise ValueError("mintime_step_batch: dw must hold nw, dg ng and rhs [nvec, nw + ng] values of its problem, the same nvec for all")
+        lead = (max(nvec, 1),)
+        pr = np.concatenate((_pad_last([r[:, :n] for r, n in zip(rs, nws)], nw, lead), _pad_last([r[:, n:] for r, n in zip(rs, nws)], ng, lead)), axis=2)
+        return _pad_last(a, nw), _pad_last(c, ng), pr, nvec
 
     def mintime_step_batch(self, problems, lam_g, dw, dg, rhs, sigma=None, refine=2, nmax=None, **opt_kw):
         """The Newton step of every problem at its w and lam_g: Jacobian -> Hessian -> mcq_mintime_step_device chained on resident blocks.  dw [nw_k],

@@ -90,24 +90,31 @@ def export_mintime_solution(file_path, pars, s, t, x, u, tf, ax, ay, atot, w0, l
         np.savetxt(os.path.join(file_path, name), vec, delimiter=";")
 
 
+def g_rows(N, safe_traj=False, limit_energy=False):
+    """The rows of g of a problem of N intervals as (row0, ng, slots): row0 [N + 1] the first row of every interval and, at N, of the periodicity
+    rows; slots[k] the row slots of block k that exist, in the order of their rows -- 0 .. 26, the actuator rows 27 .. 30 from interval 1 on, the
+    pair 31, 32 with safe_traj alone."""
+    safe, k = int(bool(safe_traj)), np.arange(int(N) + 1)
+    row0 = k * (27 + 2 * safe) + 4 * np.maximum(k - 1, 0)
+    slots = [list(range(27)) + (list(range(27, 31)) if j > 0 else []) + ([31, 32] if safe else []) for j in range(int(N))]
+    return row0, int(row0[-1]) + 5 + int(bool(limit_energy)), slots
+
+
 def jacobian_coo(blocks, N, safe_traj=False, grad_energy=None):
     """The interval blocks [>= N, 33, 33] of one problem -> the Jacobian of g as a scipy.sparse COO matrix [ng, nw] in the reference's row and column
     numbering: the blocks' present row slots, the constant periodicity rows (+1 at X_0, -1 at X_N), and with grad_energy [>= nw] the energy row."""
     import scipy.sparse as sp
     blocks = np.asarray(blocks)[:N]
-    safe = int(bool(safe_traj))
     nw = 5 + 24 * N
-    per = N * (27 + 2 * safe) + 4 * (N - 1)
-    ng = per + 5 + (grad_energy is not None)
+    row0, ng, slots = g_rows(N, safe_traj, grad_energy is not None)
+    per = int(row0[N])
     rows, cols, vals = [], [], []
     for k in range(N):
-        start = k * (27 + 2 * safe) + 4 * max(k - 1, 0)
-        slots = list(range(27)) + (list(range(27, 31)) if k > 0 else []) + ([31, 32] if safe else [])
         colmap = np.concatenate((24 * k + np.arange(29), 24 * (k - 1) + 5 + np.arange(4)))
         ncol = 33 if k > 0 else 29
-        sub = blocks[k][slots][:, :ncol]
+        sub = blocks[k][slots[k]][:, :ncol]
         r, c = np.nonzero(sub)
-        rows.append(start + r)
+        rows.append(row0[k] + r)
         cols.append(colmap[c])
         vals.append(sub[r, c])
     rows += [per + np.arange(5), per + np.arange(5)]

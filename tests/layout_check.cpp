@@ -199,10 +199,73 @@ static void check_scan()
     }
 }
 
+#ifndef SCAN_ONLY
+// the minimum-time NLP's maps (csrc/mcq_kernels.h: mcq_mt_row_of, mcq_mt_slot_of, mcq_mt_holders, mcq_mt_slot_entry, mcq_mt_sizes) against a
+// brute-force statement of the structure: every row slot and every column slot of every block visited
+static void check_mintime_maps()
+{
+    const int nmax = 6;
+    for (int N = 2; N <= nmax; ++N) for (int safe = 0; safe < 2; ++safe) for (int energy = 0; energy < 2; ++energy) {
+        const int nw = 5 + 24 * N, per = mcq_mt_row0(N, safe);
+        // (a) the present row slots in order are the rows 0 .. per - 1; (b) mcq_mt_slot_of inverts
+        int next = 0;
+        for (int k = 0; k < N; ++k)
+            for (int s = 0; s < MCQ_MT_BLOCK; ++s) {
+                const int row = mcq_mt_row_of(k, safe, s);
+                const bool absent = (s >= 27 && s < 31 && k == 0) || (s >= 31 && !safe);
+                EXPECT((row < 0) == absent, "N %d safe %d: slot %d of interval %d gives row %d", N, safe, s, k, row);
+                if (row < 0) continue;
+                EXPECT(row == next, "N %d safe %d: slot %d of interval %d is row %d, not %d", N, safe, s, k, row, next);
+                EXPECT(row == mcq_mt_row0(k, safe) + mcq_mt_row_off(k, safe, s), "N %d safe %d: offset of slot %d of interval %d", N, safe, s, k);
+                // what the kernels' group-wise walks rely on: slots 0 .. 30 at their own number, the actuator rows together, the safe pair adjacent
+                EXPECT(s >= 31 || mcq_mt_row_off(k, safe, s) == s, "N %d safe %d: slot %d of interval %d is not at its own number", N, safe, s, k);
+                EXPECT(s < MCQ_MT_ROWS_ALWAYS || s >= 31 || mcq_mt_row_off(k, safe, 27) >= 0, "N %d safe %d: actuator slot %d without slot 27", N, safe, s);
+                EXPECT(s != 32 || mcq_mt_row_off(k, safe, 31) == mcq_mt_row_off(k, safe, 32) - 1, "N %d safe %d: the safe pair of interval %d", N, safe, k);
+                ++next;
+                int k2 = -1, s2 = -1;
+                mcq_mt_slot_of(row, safe, &k2, &s2);
+                EXPECT(k2 == k && s2 == s, "N %d safe %d: row %d is (%d, %d), not (%d, %d)", N, safe, row, k, s, k2, s2);
+            }
+        EXPECT(next == per && mcq_mt_ng(N, safe, energy) == per + 5 + energy, "N %d safe %d energy %d: %d rows in the intervals, row0(N) = %d", N, safe, energy, next, per);
+        // (c) the holders of every entry of w, by a scan over all (block, slot) with the slot-to-entry map written out here
+        for (int wrap = 0; wrap < 2; ++wrap)
+            for (int i = 0; i < 5 + 24 * nmax; ++i) {
+                int want_k[2] = {-1, -1}, want_c[2] = {-1, -1}, found = 0;
+                for (int k = 0; k < N && i < nw; ++k)
+                    for (int s = 0; s < (wrap || k > 0 ? 33 : 29); ++s) {
+                        const int entry = s < 29 ? 24 * k + s : 24 * ((k - 1 + N) % N) + 5 + (s - 29);
+                        if (entry != i) continue;
+                        const int t = k == i / 24 && s == i % 24 ? 0 : 1;      // the block at i = 24 k + slot first
+                        EXPECT(want_k[t] < 0, "N %d: entry %d is twice in place %d", N, i, t);
+                        want_k[t] = k; want_c[t] = s; ++found;
+                        if (wrap) EXPECT(mcq_mt_slot_entry(N, k, s) == i, "N %d: slot %d of block %d is entry %d, not %d", N, s, k, mcq_mt_slot_entry(N, k, s), i);
+                    }
+                int kb[2] = {7, 7}, cb[2] = {7, 7};
+                mcq_mt_holders(N, i, wrap != 0, kb, cb);
+                EXPECT(found <= 2 && (i >= nw) == (found == 0), "N %d wrap %d: entry %d has %d holders", N, wrap, i, found);
+                for (int t = 0; t < 2; ++t)
+                    EXPECT(kb[t] == want_k[t] && cb[t] == want_c[t], "N %d wrap %d: entry %d holder %d is (%d, %d), not (%d, %d)", N, wrap, i, t, kb[t], cb[t],
+                           want_k[t], want_c[t]);
+            }
+        // (d) the sizes: from the list or from nmax, nothing for an N out of range
+        const int list[5] = {N, 1, nmax + 1, 0, -3};
+        for (int b = 0; b < 5; ++b) {
+            const McqMtSizes Z = mcq_mt_sizes(list, nmax, b, safe, energy);
+            const bool in = b == 0;
+            EXPECT(Z.N == (in ? N : 0) && Z.nw == (in ? nw : 0) && Z.ng == (in ? per + 5 + energy : 0) && Z.per == (in ? per : 0) && Z.safe == safe &&
+                       Z.energy == energy, "sizes of N = %d: N %d nw %d ng %d per %d", list[b], Z.N, Z.nw, Z.ng, Z.per);
+        }
+        const McqMtSizes Z = mcq_mt_sizes(nullptr, N, 3, safe, energy);
+        EXPECT(Z.N == N && Z.nw == nw && Z.per == per, "sizes without a list: N %d nw %d per %d", Z.N, Z.nw, Z.per);
+    }
+}
+#endif
+
 int main()
 {
 #ifndef SCAN_ONLY
     check_layouts();
+    check_mintime_maps();
 #endif
     check_scan();
     printf(failures ? "%d checks FAILED\n" : "layout_check: all checks passed\n", failures);
